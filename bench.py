@@ -17,7 +17,12 @@ weight-checksum all-reduce, barriers, the timing reduction and one gather of per
 (the protocol is `self_forcing_amd/distributed.py`, the code the world-size-2 gloo tests run; `--dist-selftest` runs
 it on CPU without any GPU work).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the `--steps` steps and prints the contract fields
+(`value` in decoded frames/s, `ms_per_step` = wall milliseconds of one timed step) with the FLOP and host-load figures of
+the timed region; the inputs of every step are seeded by its index, so runs with the same arguments compute the same
+latents, and `--dump-outputs DIR` writes what the last timed step returned (video, latents) as DIR/<name>.npy.
+Everything else runs with `--full` only: the board's power during the timed region, one prompt alone on the GPU
+(`value_one_stream`), and
   roofline     -- the dominant kernel (self-attention over the KV cache) AT THE BATCH THE TIMED REGION RUNS: algorithmic
                   FLOPs per launch / its average launch duration, measured here with events on the launch stream,
                   against the 2.5 PFLOP/s dense bf16 MFMA peak and against the peak MEASURED on this box
@@ -26,7 +31,9 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                   timed on this host's cores on a bounded sample (N = 1 only);
   vae_decode   -- SURVEY 8f-1, reported beside the metric (whose timed region is the DiT rollout,
                   SURVEY 8d): the Wan VAE decode of one clip's latents to 81 frames of 480x832 pixels,
-                  and the literal rate of rollout + decode with the pixels left in HBM.
+                  and the literal rate of rollout + decode with the pixels left in HBM;
+  gemm, hbm_bound, streaming, cfg_sampler -- the FFN / QKV GEMMs and the HBM-bound kernels of a forward, chunk-at-a-time
+                  generation, and the 50-step CFG sampler.
 """
 import argparse
 import json
@@ -448,6 +455,24 @@ def cpu_baseline_leg(shape, sd, frames_sample, nfpb, n_steps, total_frames):
                                 "forward_seconds": dt}}
 
 
+def dump_outputs(out_dir, arrays, budget_bytes=64 * 10**6):
+    """{name: tensor} -> out_dir/<name>.npy in float32.  When the arrays together exceed `budget_bytes` as float32, each
+    one is written as a fixed sample of its flattened elements instead: an equal share of the budget, at indices drawn
+    by a CPU generator seeded with 0 and sorted -- the same indices in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    per_file = budget_bytes // len(arrays) - 1024              # (1 KiB per file for the .npy header)
+    fits = sum(4 * t.numel() + 1024 for t in arrays.values()) <= budget_bytes
+    for name, t in arrays.items():
+        x = t.detach().float().cpu()
+        if not fits:
+            k = min(x.numel(), per_file // 4)
+            idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), x.numpy())
+        log(f"outputs: {name} {tuple(t.shape)} -> {out_dir}/{name}.npy" + ("" if fits else f" (seeded sample of {x.numel()} elements)"))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -482,6 +507,14 @@ def parse_args(argv=None):
                          "next chunk's first denoising pass -- same latents bit for bit, twice the rows per GEMM)")
     ap.add_argument("--max-inflight", type=int, default=None,
                     help="host pacing: passes a wrapper keeps enqueued before its thread sleeps (default: the wrapper's 2; 0 = unpaced)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: board power during the timed region, the one-prompt rate, "
+                         "measured ceilings + roofline + HBM-bound kernels, VAE decode, streaming, CFG sampler, CPU baseline "
+                         "(the --no-* options and --rollout-only then select among them); without it a run only sets up, "
+                         "warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (video, latents) as DIR/<name>.npy in "
+                         "float32 (at most 64 MB in all: larger outputs as a fixed seeded sample)")
     return ap.parse_args(argv)
 
 
@@ -512,7 +545,9 @@ def main():
             emit(rep)
         return
     LAT_H, LAT_W = a.latent_height, a.latent_width
-    if a.rollout_only:
+    # a plain run measures the headline figure only; every other leg runs with --full
+    legs = a.full and not a.rollout_only
+    if not legs:
         a.no_roofline = a.no_vae = a.no_cpu_baseline = True
         a.cfg_frames = 0
 
@@ -549,18 +584,23 @@ def main():
     prompts = [f"synthetic MovieGenVideoBench prompt #{i}" for i in idx]
     for i in range(total):
         enc(prompts[B * i:B * i + B])                           # embeddings resident in HBM before timing
-    for p in prompts[:total]:
-        enc([p])                                                # (the single-prompt legs)
+    if legs:
+        for p in prompts[:total]:
+            enc([p])                                            # (the single-prompt legs)
     torch.manual_seed(0 + rank)                                 # set_seed(seed + rank), inference.py:45
 
     def one_step(pipe, i):
-        noise = torch.randn([B, a.frames, 16, LAT_H, LAT_W], device=dev, dtype=torch.bfloat16)
-        return pipe.inference(noise, prompts[B * i:B * i + B], return_latents=True, profile=a.profile and rank == 0)[1]
+        # step i draws its noise and its re-noise from a generator of its own, seeded by (rank, i): the same inputs in
+        # every run with the same arguments, whichever stream runs the step and however the streams' draws interleave
+        g = torch.Generator(device=dev).manual_seed(1_000_003 * rank + i)
+        pipe.noise_source = lambda t: torch.randn(t.shape, generator=g, device=t.device, dtype=t.dtype)
+        noise = torch.randn([B, a.frames, 16, LAT_H, LAT_W], generator=g, device=dev, dtype=torch.bfloat16)
+        return pipe.inference(noise, prompts[B * i:B * i + B], return_latents=True, profile=a.profile and rank == 0)
 
     log(f"model resident ({gen.model.param_bytes() / 1e9:.2f} GB); warmup x{a.warmup}, {a.streams} stream(s)")
     # the board sampler starts a rocm-smi process every 0.5 s: inside the timed region only when this is the one rank
     # of the job; with several ranks it watches the warm-up instead (same kernels, no effect on the timed region)
-    board = BoardSampler(dev.index or 0) if rank == 0 else None
+    board = BoardSampler(dev.index or 0) if rank == 0 and a.full else None
     tw = time.perf_counter()
     if board is not None and world > 1:
         board.__enter__()
@@ -577,7 +617,7 @@ def main():
     if board is not None and world == 1:
         board.__enter__()
     cpu0, thr0 = time.process_time(), thread_cpu_seconds()
-    elapsed, local_elapsed, lats = grp.timed(lambda: pool.run(list(range(a.warmup, total)), one_step))
+    elapsed, local_elapsed, results = grp.timed(lambda: pool.run(list(range(a.warmup, total)), one_step))
     proc_cpu = time.process_time() - cpu0                       # CPU seconds of ALL threads of this rank (incl. the sampler's)
     thr1 = thread_cpu_seconds()
     by_thread = sorted(((thr1[t][1] - thr0.get(t, (None, 0.0))[1], thr1[t][0]) for t in thr1), reverse=True)
@@ -585,21 +625,25 @@ def main():
         board.__exit__()
     fw_calls, fw_secs, fw_cpu, fw_threads = host_enqueue_stats()
     log(f"timed {a.steps} steps in {local_elapsed:.2f} s (max over ranks {elapsed:.2f} s)")
-    lat = lats[-1]
+    for pipe in pool.pipes:
+        pipe.noise_source = None                                # (the legs below re-noise from the global RNG, as before)
+    video, lat = results[-1]                                    # what the last timed step returned
     assert torch.isfinite(lat.float()).all(), "non-finite latents"
-    lat = lat[:1]                                               # the legs below work on ONE prompt's latents
     decoded = DECODED_PER_LATENT(a.frames)                      # per prompt
     per_rank = grp.gather([a.steps * B * decoded, local_elapsed, fw_calls, fw_cpu, proc_cpu])
     grp.finish()                                                # last collective; rank 0's legs below run alone
     if rank != 0:
         return
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"video": video, "latents": lat})
+    lat = lat[:1]                                               # the legs below work on ONE prompt's latents
 
     fps = world * a.steps * B * decoded / elapsed
     flops = B * rollout_flops(shape, a.frames, nfpb, len(step_list), fs, window)
     flops_exec = B * rollout_flops(shape, a.frames, nfpb, len(step_list), fs, window, executed=True)
     # one rollout ALONE on the GPU (one stream): the same step, nothing in flight beside it
     one = None
-    if (a.streams > 1 or B > 1) and not a.rollout_only:
+    if (a.streams > 1 or B > 1) and legs:
         def single(i):
             noise = torch.randn([1, a.frames, 16, LAT_H, LAT_W], device=dev, dtype=torch.bfloat16)
             return pool.pipes[0].inference(noise, [prompts[i]], return_latents=True)[1]

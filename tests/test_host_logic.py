@@ -510,3 +510,30 @@ def test_bench_reads_counter_traffic_only_at_the_profiled_shape():
     # algorithmic FLOPs of the S1 rollout (990 TFLOP) and what the context passes skip
     full = bench.rollout_flops(sfa.WAN_1_3B, 21, 3, 4, 1560)
     assert abs(full / 1e12 - 990.3) < 1.0 and bench.rollout_flops(sfa.WAN_1_3B, 21, 3, 4, 1560, executed=True) < full
+
+
+def test_bench_dump_outputs_whole_or_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, whole when they fit the budget, else the same seeded sample of each
+    array in every run; a plain run leaves the other legs to --full."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse_args(["--steps", "3", "--dump-outputs", "out"])
+    assert a.steps == 3 and a.dump_outputs == "out" and not a.full and bench.parse_args(["--full"]).full
+    g = torch.Generator().manual_seed(0)
+    lat = torch.randn(2, 3, 16, 6, 10, generator=g).to(torch.bfloat16)
+    arrays = {"video": (lat * 0.5 + 0.5).clamp(0, 1), "latents": lat}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for name, t in arrays.items():
+        x = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert x.dtype == np.float32 and np.array_equal(x, t.float().numpy())
+    budget = 16 * 1024
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), arrays, budget_bytes=budget)
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= budget
+    for name, t in arrays.items():
+        x = np.load(tmp_path / "s1" / f"{name}.npy")
+        assert x.dtype == np.float32 and 0 < x.size < t.numel() and np.array_equal(x, np.load(tmp_path / "s2" / f"{name}.npy"))
+        assert np.isin(x, t.float().numpy().ravel()).all()

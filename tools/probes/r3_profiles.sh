@@ -4,7 +4,7 @@ set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 WHAT=${1:-all}
-python $R/bench.py --steps 3 --warmup 1 --no-vae --cfg-frames 0 --no-cpu-baseline > $O/bench4.json 2> $O/bench4.err
+python $R/bench.py --full --steps 3 --warmup 1 --no-vae --cfg-frames 0 --no-cpu-baseline > $O/bench4.json 2> $O/bench4.err
 echo bench done
 if [ "$WHAT" = all ] || [ "$WHAT" = trace ]; then
 rm -rf $O/prof_1x2
