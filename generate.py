@@ -12,13 +12,21 @@ seed = `--seed + rank`, noise `[num_samples, num_output_frames, 16, 60, 104]` bf
 one barrier after set-up.  It writes LATENTS (`<idx>-<sample>.pt`) and, when a VAE is given
 (`--vae_path Wan2.1_VAE.pth`, loaded with weights_only=True, or `--vae_random_init_seed N`), the decoded
 video as a uint8 tensor [T, H, W, 3] (`<idx>-<sample>.video.pt`: what the reference hands to
-`write_video`, inference.py:186-196; there is no video encoder in this image).  The umT5 encoder is
+`write_video`, inference.py:186-196; no video-file writer is used here).  The umT5 encoder is
 outside this path, so embeddings are synthetic unless `--prompt_embeds` (a .pt dict prompt -> [L, 4096]
 tensor) is given.  A config WITHOUT `denoising_step_list` selects the multi-step classifier-free-guidance sampler
 (`CausalDiffusionInferencePipeline`), as inference.py:62-67 does; it needs `num_train_timestep`, `timestep_shift`,
 `guidance_scale` and `negative_prompt`.
+
+`--i2v` (inference.py:83-90, 136-149) reads `--data_path` as a TextImagePairDataset directory -- one
+`target_crop_info_<ratio>.json` listing `file_name` / `caption` entries, images under `<ratio>/` --, encodes each
+image with the VAE encoder (so it needs a VAE with encoder weights: `--vae_path`, or `--vae_random_init_seed`) as the
+first latent frame and draws noise for the `num_output_frames - 1` frames after it.  Single process only, as in the
+reference.
 """
 import argparse
+import glob
+import json
 import os
 import sys
 
@@ -47,6 +55,32 @@ class TableTextEncoder:
         return {"prompt_embeds": out.to(self.device)}
 
 
+def read_image_pairs(data_dir: str, eval_first_n: int = 0):
+    """TextImagePairDataset's layout (utils/dataset.py:199-250): [(image path, caption)]."""
+    metas = glob.glob(os.path.join(data_dir, "target_crop_info_*.json"))
+    if len(metas) != 1:
+        raise SystemExit(f"{data_dir}: expected exactly one target_crop_info_*.json, found {len(metas)}")
+    ratio = os.path.splitext(os.path.basename(metas[0]))[0].split("_")[-1]
+    with open(metas[0]) as f:
+        items = json.load(f)
+    if eval_first_n > 0:
+        items = items[:eval_first_n]
+    pairs = [(os.path.join(data_dir, ratio, it["file_name"]), it["caption"]) for it in items]
+    for path, _ in pairs:
+        if not os.path.exists(path):
+            raise SystemExit(f"image not found: {path}")
+    return pairs
+
+
+def load_image(path: str, height: int, width: int) -> torch.Tensor:
+    """Resize((height, width)) bilinear, ToTensor, Normalize([0.5], [0.5]) (inference.py:84-88) -> [3, H, W] in [-1, 1]."""
+    import numpy as np
+    from PIL import Image
+    img = Image.open(path).convert("RGB").resize((width, height), Image.BILINEAR)
+    x = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).permute(2, 0, 1).float() / 255.0
+    return (x - 0.5) / 0.5
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_path", required=True)
@@ -54,7 +88,8 @@ def main():
     ap.add_argument("--checkpoint_path", default=None, help=".pt with 'generator' / 'generator_ema' state dicts, or a .safetensors file")
     ap.add_argument("--use_ema", action="store_true")
     ap.add_argument("--random_init_seed", type=int, default=None, help="seeded random weights instead of a checkpoint")
-    ap.add_argument("--data_path", required=True, help="one prompt per line")
+    ap.add_argument("--data_path", required=True, help="one prompt per line; with --i2v a TextImagePairDataset directory")
+    ap.add_argument("--i2v", action="store_true", help="image-to-video: encode each image as the first latent frame")
     ap.add_argument("--eval_first_n", type=int, default=0)
     ap.add_argument("--prompt_embeds", default=None)
     ap.add_argument("--output_folder", required=True)
@@ -65,12 +100,18 @@ def main():
     ap.add_argument("--latent_width", type=int, default=104)
     ap.add_argument("--vae_path", default=None, help="Wan2.1_VAE.pth: decode the latents to pixels")
     ap.add_argument("--sampling_steps", type=int, default=0, help="multi-step sampler only: override its 50 steps")
-    ap.add_argument("--vae_random_init_seed", type=int, default=None, help="seeded random VAE decoder weights instead")
+    ap.add_argument("--vae_random_init_seed", type=int, default=None,
+                    help="seeded random VAE weights instead (decoder; with --i2v the encoder too)")
     a = ap.parse_args()
 
     # inference.py:39-45: one process per GPU under torch.distributed.run, RCCL for the start / end barriers only
     from self_forcing_amd.distributed import RankGroup, env_rank_world
     rank, local_rank, world = env_rank_world()
+    if a.i2v:
+        if world > 1:
+            raise SystemExit("I2V does not support distributed inference yet (inference.py:83)")
+        if not a.vae_path and a.vae_random_init_seed is None:
+            raise SystemExit("--i2v needs a VAE with encoder weights: --vae_path or --vae_random_init_seed")
     torch.cuda.set_device(local_rank)
     grp = RankGroup(backend="nccl", device=torch.device(f"cuda:{local_rank}"))
     device = torch.device(f"cuda:{local_rank}")
@@ -90,7 +131,11 @@ def main():
     else:
         gen = sfa.WanDiffusionWrapper(**kwargs, is_causal=True, random_init_seed=a.random_init_seed, device=device)
     shape = gen.model.shape
-    prompts = read_prompts(a.data_path, a.eval_first_n)
+    if a.i2v:
+        pairs = read_image_pairs(a.data_path, a.eval_first_n)
+        prompts = [c for _, c in pairs]
+    else:
+        prompts = read_prompts(a.data_path, a.eval_first_n)
     if a.prompt_embeds:
         enc = TableTextEncoder(torch.load(a.prompt_embeds, map_location="cpu", weights_only=True), shape.text_len, shape.text_dim, device)
     else:
@@ -99,7 +144,7 @@ def main():
     if a.vae_path:
         vae = sfa.WanVAEWrapper(torch.load(a.vae_path, map_location="cpu", weights_only=True), device=device)
     elif a.vae_random_init_seed is not None:
-        vae = sfa.WanVAEWrapper(sfa.synth_vae_state_dict(sfa.WAN_VAE, seed=a.vae_random_init_seed), device=device)
+        vae = sfa.WanVAEWrapper(sfa.synth_vae_state_dict(sfa.WAN_VAE, seed=a.vae_random_init_seed, encoder=a.i2v), device=device)
     decode = not isinstance(vae, sfa.IdentityVAE)
     few_step = is_few_step(cfg)        # inference.py:62-67: few-step rollout iff the config has denoising_step_list
     if few_step:
@@ -117,12 +162,21 @@ def main():
     grp.barrier()
 
     for idx in shard_indices(len(prompts), rank, world):
-        noise = torch.randn([a.num_samples, a.num_output_frames, 16, a.latent_height, a.latent_width], device=device,
-                            dtype=torch.bfloat16)
+        initial = None
+        if a.i2v:   # inference.py:136-149: the encoded image is the first latent frame of every sample
+            image = load_image(pairs[idx][0], 8 * a.latent_height, 8 * a.latent_width)
+            image = image[None, :, None].to(device=device, dtype=torch.bfloat16)              # [1, 3, 1, H, W]
+            initial = vae.encode_to_latent(image).to(device=device, dtype=torch.bfloat16)
+            initial = initial.repeat(a.num_samples, 1, 1, 1, 1)
+            torch.save(initial[0].cpu(), os.path.join(a.output_folder, f"{idx}.initial_latent.pt"))
+        n_noise = a.num_output_frames - (1 if a.i2v else 0)
+        noise = torch.randn([a.num_samples, n_noise, 16, a.latent_height, a.latent_width], device=device, dtype=torch.bfloat16)
         if few_step:
-            video, latents = pipe.inference(noise=noise, text_prompts=[prompts[idx]] * a.num_samples, return_latents=True)
+            video, latents = pipe.inference(noise=noise, text_prompts=[prompts[idx]] * a.num_samples, initial_latent=initial,
+                                            return_latents=True)
         else:
-            video, latents = pipe.inference(noise, [prompts[idx]] * a.num_samples, None, None, None, return_latents=True)
+            video, latents = pipe.inference(noise, [prompts[idx]] * a.num_samples, None, None, None, initial_latent=initial,
+                                            return_latents=True)
         for s in range(a.num_samples):
             torch.save(latents[s].cpu(), os.path.join(a.output_folder, f"{idx}-{s}.pt"))
             if decode:   # [T, 3, H, W] in [0, 1] -> [T, H, W, 3] uint8 (inference.py:186-187)

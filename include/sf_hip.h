@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_HIP_ABI_VERSION 8
+#define SF_HIP_ABI_VERSION 9
 
 int sf_abi_version(void);
 const char* sf_last_error(void);
@@ -301,6 +301,12 @@ typedef struct sf_conv_args {
   void* norm_out;
   const void* norm_gamma; /* [Cout] */
   int32_t norm_ld, norm_frame_offset;
+  /* Strided input gathers of the encoder's downsampling (Resample 'downsample2d/3d', vae.py:87-97, :143-160); 0 = 1 = none.
+   * stride_hw = 2: ZeroPad2d((0,1,0,1)) + 3x3 stride 2 (kh = kw = 3, no upsample): output (h, w) reads input
+   *                (2h + dh, 2w + dw), zero past the right / bottom edge; H = Hin / 2, W = Win / 2 (floor).
+   * stride_t = 2:  output frame t reads input frames 2t + dt + t_in_offset (the (3,1,1) time convolution, no padding).
+   * The halo structure takes neither (AUTO falls back to the implicit GEMM). */
+  int32_t stride_hw, stride_t;
 } sf_conv_args;
 
 enum sf_conv_structure { SF_CONV_AUTO = 0, SF_CONV_IGEMM = 1 /* A tile gathered per tap (every shape) */,
@@ -387,6 +393,63 @@ int sf_vae_reset(const sf_vae_model* model, void* state, size_t state_bytes, int
 int sf_vae_decode_frames(const sf_vae_model* model, void* state, size_t state_bytes, void* scratch,
                          size_t scratch_bytes, const void* latent_frames, int lat_h, int lat_w, int window_frames,
                          int frame_index, int n_frames, int window, int history_at, float* pixels_out, void* stream);
+
+/* ==========================================================================================
+ * Wan VAE encode (pixels -> latents): WanVAEWrapper.encode_to_latent -> WanVAE_.encode -> Encoder3d.forward with
+ * feat_cache (utils/wan_wrapper.py:78-92, wan/modules/vae.py:517-543, :265-367).  Same volumes and history model as
+ * the decoder: every causal convolution keeps two history frames physically in front of its new frames; the (3,1,1)
+ * stride-2 time convolution of 'downsample3d' reads the last of them (its one-frame cache, vae.py:143-160).
+ * ========================================================================================== */
+
+/* One sample's pixel frames, channels-first [3][T][H][W] (bf16, or float32 when is_f32; pixel (c, t, y, x) at
+ * pixels[c * c_stride + (t * H + y) * W + x]) -> channels-last bf16 [T][H][W][c_pad], channels 3..c_pad-1 zero
+ * (the input of encoder.conv1, vae.py:324-336). */
+int sf_vae_prepare_pixels(const void* pixels, int is_f32, int64_t c_stride, void* out, int T, int H, int W, int c_pad,
+                          void* stream);
+
+/* Head output [T][h][w][ld_in] bf16 -> the 1x1x1 conv1 rows 0..z-1 (mu, vae.py:538; fp32 accumulation), then
+ * (mu - mean[c]) * (1 / std[c]) (vae.py:539-542) -> float32 [T][z][h][w].  conv1_w [z][ld_w] bf16 (the first z rows
+ * of the 2z x 2z weight, ld_w >= cin), conv1_b [z]. */
+int sf_vae_finish_latent(const void* head_out, int ld_in, int cin, const void* conv1_w, int ld_w, const void* conv1_b,
+                         const float* mean, const float* std, float* out, int T, int z, int h, int w, void* stream);
+
+typedef struct sf_vae_encoder {           /* Encoder3d + conv1, vae.py:265-367, :502 */
+  int32_t z_dim;                          /* latent channels (mu) = 16; the head writes 2 z_dim                       */
+  int32_t n_stages;                       /* len(dim_mult) = 4                                                         */
+  int32_t res_per_stage;                  /* num_res_blocks = 2                                                        */
+  int32_t temporal_down[SF_VAE_MAX_STAGES]; /* stage i ends with downsample3d (1) / downsample2d (0); last stage: none */
+  const float* latent_mean;               /* float32 [z_dim] */
+  const float* latent_std;                /* float32 [z_dim] */
+  const void *conv1_w, *conv1_b;          /* WanVAE_.conv1 rows [0, z_dim): [z_dim][2 z_dim], [z_dim]   */
+  sf_vae_conv in_conv;                    /* encoder.conv1 (3 -> dims[0]), cin padded to 32              */
+  const sf_vae_resblock* res_host;        /* HOST array [n_stages * res_per_stage]: encoder.downsamples  */
+  sf_vae_conv down_conv[SF_VAE_MAX_STAGES];   /* Resample.resample[1] (Conv2d 3x3 stride 2)              */
+  sf_vae_conv time_conv[SF_VAE_MAX_STAGES];   /* (3,1,1) stride 2; w = NULL where absent                 */
+  sf_vae_resblock mid0, mid2;             /* encoder.middle.0 / .2 */
+  const void* attn_gamma;                 /* middle.1.norm.gamma [C]            */
+  const void *attn_qk_w, *attn_qk_b;      /* to_qkv rows [0, 2C): [2C][C], [2C] */
+  const void *attn_v_w, *attn_v_b;        /* to_qkv rows [2C, 3C)               */
+  const void *attn_proj_w, *attn_proj_b;  /* [C][C], [C] */
+  const void* head_gamma;                 /* encoder.head.0.gamma */
+  sf_vae_conv head_conv;                  /* encoder.head.2 (cout = 2 z_dim) */
+} sf_vae_encoder;
+
+/* State / scratch as for the decoder, for pixel frames of H x W (multiples of 2^(n_stages-1)); `window_frames` (2..64):
+ * a call encodes up to window_frames - 1 chunks of 4 pixel frames. */
+size_t sf_vae_encode_state_bytes(const sf_vae_encoder* enc, int H, int W, int window_frames);
+size_t sf_vae_encode_scratch_bytes(const sf_vae_encoder* enc, int H, int W, int window_frames);
+/* WanVAE_.clear_cache (vae.py:610-617) of the encoder's histories. */
+int sf_vae_encode_reset(const sf_vae_encoder* enc, void* state, size_t state_bytes, int H, int W, int window_frames,
+                        void* stream);
+/* n_chunks iterations of the chunk loop of WanVAE_.encode (vae.py:525-537) in one call: chunk_index = chunks encoded
+ * into `state` since its reset; chunk 0 is ONE pixel frame encoded alone (n_chunks = 1), every later chunk 4 frames.
+ * pixels: the call's frames, [3][T][H][W] with channel stride c_stride (elements; bf16, or float32 when is_f32),
+ * T = 1 (chunk 0) or 4 n_chunks.  latents_out: float32 [n_chunks][z_dim][H/8][W/8], normalised mu.  `window` /
+ * `history_at` place the sliding history windows exactly as for sf_vae_decode_frames.  Bit-identical to n_chunks
+ * single-chunk calls. */
+int sf_vae_encode_frames(const sf_vae_encoder* enc, void* state, size_t state_bytes, void* scratch, size_t scratch_bytes,
+                         const void* pixels, int is_f32, int64_t c_stride, int H, int W, int window_frames,
+                         int chunk_index, int n_chunks, int window, int history_at, float* latents_out, void* stream);
 
 /* ==========================================================================================
  * umT5 text encoder (prompt token ids -> prompt embeddings): WanTextEncoder.forward after its tokenizer

@@ -15,8 +15,9 @@ from .wan_wrapper import WanDiffusionWrapper  # noqa: F401
 from .pipeline import CausalInferencePipeline  # noqa: F401
 from .harness import SyntheticTextEncoder, FixedTextEncoder, IdentityVAE  # noqa: F401
 from .concurrent import RolloutPool  # noqa: F401
-from .vae_weights import VaeShape, WAN_VAE, VAE_REDUCED, synth_vae_state_dict, vae_param_shapes  # noqa: F401
-from .vae import WanVAEWrapper, WanVAEDecoder, repack_conv  # noqa: F401
+from .vae_weights import (VaeShape, WAN_VAE, VAE_REDUCED, synth_vae_state_dict, vae_param_shapes,  # noqa: F401
+                          encoder_param_shapes, vae_encode_flops)
+from .vae import WanVAEWrapper, WanVAEDecoder, WanVAEEncoder, repack_conv  # noqa: F401
 from .t5_weights import T5Shape, UMT5_XXL, T5_REDUCED, synth_t5_state_dict, t5_param_shapes  # noqa: F401
 from .text_encoder import WanTextEncoder, UMT5Encoder, relative_position_buckets  # noqa: F401
 from . import unipc  # noqa: F401

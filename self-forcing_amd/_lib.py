@@ -21,7 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("SF_HIP_LIB") or os.path.join(CSRC, "libsf_hip.so")   # SF_HIP_LIB: alternate builds (kernel ablation timing)
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # epilogue codes (enum sf_epilogue)
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_GATE_RESID, EPI_F32 = 0, 1, 2, 3, 4
@@ -97,6 +97,7 @@ class ConvArgs(C.Structure):
         + [(n, C.c_int32) for n in ("Tout", "H", "W", "Hin", "Win", "Cin", "Cout", "kt", "kh", "kw", "upsample",
                                     "t_in_offset", "ldw", "ldo", "ldr", "out_frame_offset", "interleave_c", "epilogue", "structure")]
         + [("norm_out", C.c_void_p), ("norm_gamma", C.c_void_p), ("norm_ld", C.c_int32), ("norm_frame_offset", C.c_int32)]
+        + [("stride_hw", C.c_int32), ("stride_t", C.c_int32)]
     )
 
 
@@ -118,6 +119,20 @@ class VaeModel(C.Structure):
         ("attn_v_w", C.c_void_p), ("attn_v_b", C.c_void_p), ("attn_proj_w", C.c_void_p), ("attn_proj_b", C.c_void_p),
         ("res_host", C.POINTER(VaeResBlock)),
         ("time_conv", VaeConv * VAE_MAX_STAGES), ("up_conv", VaeConv * VAE_MAX_STAGES),
+        ("head_gamma", C.c_void_p), ("head_conv", VaeConv),
+    ]
+
+
+class VaeEncoder(C.Structure):
+    _fields_ = [
+        ("z_dim", C.c_int32), ("n_stages", C.c_int32), ("res_per_stage", C.c_int32),
+        ("temporal_down", C.c_int32 * VAE_MAX_STAGES),
+        ("latent_mean", C.c_void_p), ("latent_std", C.c_void_p), ("conv1_w", C.c_void_p), ("conv1_b", C.c_void_p),
+        ("in_conv", VaeConv), ("res_host", C.POINTER(VaeResBlock)),
+        ("down_conv", VaeConv * VAE_MAX_STAGES), ("time_conv", VaeConv * VAE_MAX_STAGES),
+        ("mid0", VaeResBlock), ("mid2", VaeResBlock),
+        ("attn_gamma", C.c_void_p), ("attn_qk_w", C.c_void_p), ("attn_qk_b", C.c_void_p),
+        ("attn_v_w", C.c_void_p), ("attn_v_b", C.c_void_p), ("attn_proj_w", C.c_void_p), ("attn_proj_b", C.c_void_p),
         ("head_gamma", C.c_void_p), ("head_conv", VaeConv),
     ]
 
@@ -164,6 +179,13 @@ SIGNATURES = {
     "sf_vae_scratch_bytes": (C.c_size_t, [C.POINTER(VaeModel), _i, _i, _i]),
     "sf_vae_reset": (C.c_int, [C.POINTER(VaeModel), _vp, _sz, _i, _i, _i, _vp]),
     "sf_vae_decode_frames": (C.c_int, [C.POINTER(VaeModel), _vp, _sz, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sf_vae_prepare_pixels": (C.c_int, [_vp, _i, _i64, _vp, _i, _i, _i, _i, _vp]),
+    "sf_vae_finish_latent": (C.c_int, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "sf_vae_encode_state_bytes": (C.c_size_t, [C.POINTER(VaeEncoder), _i, _i, _i]),
+    "sf_vae_encode_scratch_bytes": (C.c_size_t, [C.POINTER(VaeEncoder), _i, _i, _i]),
+    "sf_vae_encode_reset": (C.c_int, [C.POINTER(VaeEncoder), _vp, _sz, _i, _i, _i, _vp]),
+    "sf_vae_encode_frames": (C.c_int, [C.POINTER(VaeEncoder), _vp, _sz, _vp, _sz, _vp, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _vp,
+                                       _vp]),
     "sf_embedding_gather": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_t5_softmax_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_mul_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),

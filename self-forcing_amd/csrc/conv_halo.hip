@@ -394,6 +394,7 @@ int launch_halo_head(const HaloP& p, int tiles, hipStream_t s) {   // NT = 1: 32
 // output that is an error the caller reports), 0 after a launch, negative on error.  Domain: 3 x 3 spatial taps (kt 1 or 3), Cin % 32 == 0, Cout a multiple of 96 or of 192, bf16
 // output with bias / bias + residual, no channel -> frame interleave.
 __attribute__((visibility("hidden"))) int sf_conv_halo_launch(const sf_conv_args* a, void* stream) {
+  if (a->stride_hw > 1 || a->stride_t > 1) return 1;   // strided gathers (the encoder's downsampling): implicit GEMM only
   if (!(a->kh == 3 && a->kw == 3) || a->interleave_c != 0 || a->Cin % 32 != 0) return 1;
   if (a->H < 16 || a->W < 16) return 1;
   const bool head = a->epilogue == SF_CONV_BIAS_CLAMP_F32 && a->Cout <= 4 && a->out_f32 && !a->norm_out;

@@ -9,6 +9,11 @@
 //   out[(t,h,w)][n] = bias[n] + sum over taps (dt,dh,dw), ci of
 //                     x[t + dt + t_off][(h + dh - kh/2) >> up][(w + dw - kw/2) >> up][ci] * wk[n][tap*Cin + ci]
 //
+// or, with the strided gathers of the VAE encoder's downsampling (Resample 'downsample2d/3d', vae.py:87-97, :143-160:
+// ZeroPad2d((0,1,0,1)) + Conv2d 3x3 stride 2, and the (3,1,1) time convolution with temporal stride 2),
+//                     x[st t + dt + t_off][2h + dh][2w + dw][ci]   (spatial stride 2: no left / top padding; taps past
+//                                                                   the right / bottom edge read zero)
+//
 // i.e. a GEMM with M = Tout*H*W output positions, N = Cout, K = taps*Cin whose A operand is GATHERED:
 // K is walked in 32-channel slices (Cin % 32 == 0), two slices per 64-deep k-step, every slice lies
 // inside one tap, and a lane's 16-byte piece of an A row comes from the tap-shifted position or -- for
@@ -40,6 +45,8 @@ struct ConvP {
   float* out_f32;
   int M, HW, H, W;
   int Hin, Win, up;
+  int Hv, Wv;         // bounds of the tap coordinates: the output frame with the upsampling, else the input frame
+  int sh, st;         // spatial / temporal input stride (1 or 2)
   int Cin, Cout, cpt, ntaps, khw, kw, ph, pw;
   int t_off, nk, ldw, ldo, ldr, out_frame0, inter_c, Tout;
   int tiles_m, tiles_n;
@@ -87,13 +94,13 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_igemm_kernel(ConvP p) {
     const int mm = min(m, p.M - 1);
     const int t = mm / p.HW, hw = mm - t * p.HW;
     const int h = hw / p.W;
-    const int hh0 = h - p.ph, ww0 = hw - h * p.W - p.pw;
-    abase[i] = (unsigned)(((((long)(t + p.t_off) * p.Hin + (hh0 >> p.up)) * p.Win + (ww0 >> p.up)) * p.Cin + (c & 3) * 8) * 2);
+    const int hh0 = h * p.sh - p.ph, ww0 = (hw - h * p.W) * p.sh - p.pw;
+    abase[i] = (unsigned)(((((long)(t * p.st + p.t_off) * p.Hin + (hh0 >> p.up)) * p.Win + (ww0 >> p.up)) * p.Cin + (c & 3) * 8) * 2);
     unsigned vm = 0;
     const int kk = p.khw == 9 ? 3 : 1;
     for (int dh = 0; dh < kk; ++dh)
       for (int dw = 0; dw < kk; ++dw)
-        if (valid && (unsigned)(hh0 + dh) < (unsigned)p.H && (unsigned)(ww0 + dw) < (unsigned)p.W) vm |= 1u << (dh * 3 + dw);
+        if (valid && (unsigned)(hh0 + dh) < (unsigned)p.Hv && (unsigned)(ww0 + dw) < (unsigned)p.Wv) vm |= 1u << (dh * 3 + dw);
     vmask[i] = vm;
     parh[i] = (unsigned)hh0 & 1u;
     parw[i] = (unsigned)ww0 & 1u;
@@ -400,13 +407,22 @@ extern "C" int sf_conv_igemm(const sf_conv_args* a, void* stream) {
   SF_CHECK(a->structure >= SF_CONV_AUTO && a->structure <= SF_CONV_HALO, "sf_conv_igemm: unknown structure %d", a->structure);
   SF_CHECK(a->x && a->w && a->bias, "sf_conv_igemm: null tensor");
   SF_CHECK(!a->norm_out || a->structure != SF_CONV_IGEMM, "sf_conv_igemm: the fused norm output exists in the halo kernel only");
+  SF_CHECK(a->structure != SF_CONV_HALO || (a->stride_hw <= 1 && a->stride_t <= 1), "sf_conv_igemm: the halo structure takes no strided input");
   SF_CHECK(a->Tout > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, "sf_conv_igemm: empty problem");
   SF_CHECK(a->Cin % 32 == 0, "sf_conv_igemm: Cin=%d must be a multiple of 32 (pad the channels)", a->Cin);
   SF_CHECK((a->kh == 3 && a->kw == 3) || (a->kh == 1 && a->kw == 1), "sf_conv_igemm: spatial taps must be 3x3 or 1x1");
   SF_CHECK(a->kt == 1 || a->kt == 3, "sf_conv_igemm: kt must be 1 or 3");
   SF_CHECK(a->upsample == 0 || a->upsample == 1, "sf_conv_igemm: upsample must be 0 or 1");
-  SF_CHECK(a->Hin == (a->upsample ? a->H / 2 : a->H) && a->Win == (a->upsample ? a->W / 2 : a->W) &&
-           (!a->upsample || (a->H % 2 == 0 && a->W % 2 == 0)), "sf_conv_igemm: input size %dx%d does not match output %dx%d", a->Hin, a->Win, a->H, a->W);
+  SF_CHECK(a->stride_hw >= 0 && a->stride_hw <= 2 && a->stride_t >= 0 && a->stride_t <= 2, "sf_conv_igemm: strides %d / %d (0 or 1: none, 2: stride 2)",
+           a->stride_hw, a->stride_t);
+  const int sh = a->stride_hw == 2 ? 2 : 1, st = a->stride_t == 2 ? 2 : 1;
+  SF_CHECK(sh == 1 || (!a->upsample && a->kh == 3 && a->kw == 3), "sf_conv_igemm: spatial stride 2 is a 3x3 convolution without upsampling");
+  if (sh == 2) {   // ZeroPad2d((0,1,0,1)) + stride 2: H = floor(Hin / 2)
+    SF_CHECK(a->Hin / 2 == a->H && a->Win / 2 == a->W, "sf_conv_igemm: stride-2 input size %dx%d does not match output %dx%d", a->Hin, a->Win, a->H, a->W);
+  } else {
+    SF_CHECK(a->Hin == (a->upsample ? a->H / 2 : a->H) && a->Win == (a->upsample ? a->W / 2 : a->W) &&
+             (!a->upsample || (a->H % 2 == 0 && a->W % 2 == 0)), "sf_conv_igemm: input size %dx%d does not match output %dx%d", a->Hin, a->Win, a->H, a->W);
+  }
   const int taps = a->kt * a->kh * a->kw;
   const int slices = taps * (a->Cin / 32);
   const int nk = (slices + 1) / 2;
@@ -442,12 +458,13 @@ extern "C" int sf_conv_igemm(const sf_conv_args* a, void* stream) {
   p.out = (bf16_t*)a->out; p.resid = (const bf16_t*)a->resid; p.out_f32 = a->out_f32;
   p.HW = a->H * a->W; p.M = a->Tout * p.HW; p.H = a->H; p.W = a->W; p.Tout = a->Tout;
   p.Hin = a->Hin; p.Win = a->Win; p.up = a->upsample;
+  p.Hv = a->upsample ? a->H : a->Hin; p.Wv = a->upsample ? a->W : a->Win; p.sh = sh; p.st = st;
   p.Cin = a->Cin; p.Cout = a->Cout; p.cpt = a->Cin / 32; p.ntaps = taps; p.khw = a->kh * a->kw; p.kw = a->kw;
-  p.ph = a->kh / 2; p.pw = a->kw / 2;
+  p.ph = sh == 2 ? 0 : a->kh / 2; p.pw = sh == 2 ? 0 : a->kw / 2;
   p.t_off = a->t_in_offset; p.nk = nk; p.ldw = a->ldw; p.ldo = a->ldo; p.ldr = a->ldr;
   p.out_frame0 = a->out_frame_offset; p.inter_c = a->interleave_c;
-  {   // frames [0, t_in_offset + Tout + kt - 1) of the input volume can be gathered from
-    const long xb = (long)(a->t_in_offset + a->Tout + a->kt - 1) * a->Hin * a->Win * a->Cin * 2;
+  {   // frames [0, t_in_offset + st (Tout - 1) + kt) of the input volume can be gathered from
+    const long xb = (long)(a->t_in_offset + (long)st * (a->Tout - 1) + a->kt) * a->Hin * a->Win * a->Cin * 2;
     SF_CHECK(xb < 0xFFFFFF00L, "sf_conv_igemm: input volume of %ld bytes exceeds the 4 GiB the gather's 32-bit offsets cover", xb);
     p.x_bytes = (unsigned)xb;
   }

@@ -20,24 +20,11 @@
 // quirks of Resample's bookkeeping (vae.py:104-132) are kept: the first chunk after a reset skips the
 // time convolution (one output frame), and its features never enter that convolution's history.
 #include <cmath>
-#include <cstring>
-#include "sf_common.h"
-#include "../../include/sf_hip.h"
+#include "vae_common.h"
 
 namespace {
 
-struct Carve {
-  char* base;
-  size_t off;
-  explicit Carve(void* p) : base((char*)p), off(0) {}
-  char* take(size_t bytes) {
-    char* r = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return r;
-  }
-};
-
-struct BlockBufs { char *a1, *a2; };
+using namespace sfvae;
 
 struct Plan {
   int n_stages, rps, K;
@@ -51,43 +38,10 @@ struct Plan {
   size_t state_total;
   // scratch
   char *xi[SF_VAE_MAX_STAGES], *x[SF_VAE_MAX_STAGES], *ty[SF_VAE_MAX_STAGES];
-  char *y1, *sc;
-  char *att_xn, *att_qk, *att_vt, *att_s, *att_p, *att_o;
-  int att_npad;
+  ResScratch rs;
+  AttnScratch at;
   size_t scratch_total;
 };
-
-inline size_t vol(int T, int H, int W, int C) { return (size_t)T * H * W * C * 2; }
-
-// Sliding history window of a cached convolution's input volume (capacity 2 + K * Tmax frames, K latent frames).
-// A lap = the calls between two restarts at slot 0; slot q of a lap holds the frames of the lap's q-th latent frame.
-// The lap that begins at the reset is special: its slot 0 is the first chunk, which has ONE frame at every stage
-// (vae.py:109-111) and never enters a time convolution's volume (the quirk of vae.py:104-132).
-inline int hist_frames(int K, int Tmax) { return 2 + K * Tmax; }
-inline int vol_off(int lap_start, int slot, int Tmax, bool time_conv) {   // first history frame of the window that starts at `slot`
-  if (lap_start != 0 || slot == 0) return slot * Tmax;
-  return time_conv ? (slot - 1) * Tmax : 1 + (slot - 1) * Tmax;
-}
-
-struct Call {                 // one sf_vae_decode_frames call
-  int n, F, window, history_at;
-  hipStream_t s;
-  bool first_chunk() const { return n == 0; }
-  int off(int Tmax, bool tc = false) const { return vol_off(n - window, window, Tmax, tc); }
-};
-
-// the two history frames of a volume are where the previous call left them (slot `history_at` of ITS lap); a call that
-// restarts the window copies them to the front first (frame by frame: the ranges may overlap by one frame)
-int place_history(const Call& c, char* buf, int Tmax, size_t frame_bytes, bool tc = false) {
-  if (c.history_at == c.window) return 0;
-  if (tc && c.n - c.history_at == 0 && c.history_at <= 1) return 0;   // only the first chunk so far: this volume is still all zero
-  const int src = vol_off(c.n - c.history_at, c.history_at, Tmax, tc), dst = c.off(Tmax, tc);
-  for (int k = 0; k < 2; ++k) {
-    hipError_t e = hipMemcpyAsync(buf + (size_t)(dst + k) * frame_bytes, buf + (size_t)(src + k) * frame_bytes, frame_bytes, hipMemcpyDeviceToDevice, c.s);
-    SF_CHECK(e == hipSuccess, "sf_vae: history copy failed: %s", hipGetErrorString(e));
-  }
-  return 0;
-}
 
 const sf_vae_resblock& res_at(const sf_vae_model* m, int stage, int j) { return m->res_host[stage * m->res_per_stage + j]; }
 
@@ -137,16 +91,16 @@ Plan make_plan(const sf_vae_model* m, void* state, void* scratch, int h, int w, 
       if (r.shortcut.w && v > sc_max) sc_max = v;
     }
   }
-  p.y1 = sc.take(y1_max);
-  p.sc = sc.take(sc_max);
+  p.rs.y1 = sc.take(y1_max);
+  p.rs.sc = sc.take(sc_max);
   const int n = h * w;
-  p.att_npad = (n + 63) & ~63;
-  p.att_xn = sc.take((size_t)n * C0 * 2);
-  p.att_qk = sc.take((size_t)n * 2 * C0 * 2);
-  p.att_vt = sc.take((size_t)C0 * p.att_npad * 2);
-  p.att_s = sc.take((size_t)n * p.att_npad * 4);
-  p.att_p = sc.take((size_t)n * p.att_npad * 2);
-  p.att_o = sc.take((size_t)n * C0 * 2);
+  p.at.att_npad = (n + 63) & ~63;
+  p.at.att_xn = sc.take((size_t)n * C0 * 2);
+  p.at.att_qk = sc.take((size_t)n * 2 * C0 * 2);
+  p.at.att_vt = sc.take((size_t)C0 * p.at.att_npad * 2);
+  p.at.att_s = sc.take((size_t)n * p.at.att_npad * 4);
+  p.at.att_p = sc.take((size_t)n * p.at.att_npad * 2);
+  p.at.att_o = sc.take((size_t)n * C0 * 2);
   p.scratch_total = sc.off;
   return p;
 }
@@ -182,86 +136,6 @@ int for_each_volume(const sf_vae_model* m, const Plan& p, int h, int w, Fn fn) {
     if (p.tc[i] && (rc = fn(p.tc[i], p.Tmax[i], vol(1, p.H[i], p.W[i], m->time_conv[i].cin), true)) != 0) return rc;
   }
   return fn(p.head_in, p.Tmax[L], vol(1, p.H[L], p.W[L], m->head_conv.cin), false);
-}
-
-#define SF_TRY(expr)            \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
-
-// RMS_norm + SiLU of a convolution's output can ride in its epilogue (second output of the halo kernel) when the
-// convolution is 3 x 3 spatial with 96 or 192 output channels at a resolution the halo kernel takes
-struct NormOut { void* dst; const void* gamma; int ld; int frame_off; };   // dst: base of the consumer's input volume; its new frames start at frame_off
-
-bool can_fuse_norm(const sf_vae_conv& c, int H, int W) { return c.kh == 3 && c.kw == 3 && (c.cout == 96 || c.cout == 192) && H >= 16 && W >= 16; }
-
-int conv(const sf_vae_conv& c, const void* x, int Tout, int H, int W, int upsample, int t_off, void* out, int ldo, int out_frame0,
-         int interleave_c, int epi, const void* resid, int ldr, float* out_f32, void* stream, const NormOut* norm = nullptr) {
-  sf_conv_args a;
-  memset(&a, 0, sizeof(a));
-  if (norm) { a.norm_out = norm->dst; a.norm_gamma = norm->gamma; a.norm_ld = norm->ld; a.norm_frame_offset = norm->frame_off; }
-  a.x = x; a.w = c.w; a.bias = c.bias; a.out = out; a.resid = resid; a.out_f32 = out_f32;
-  a.Tout = Tout; a.H = H; a.W = W; a.Hin = upsample ? H / 2 : H; a.Win = upsample ? W / 2 : W;
-  a.Cin = c.cin; a.Cout = c.cout; a.kt = c.kt; a.kh = c.kh; a.kw = c.kw; a.upsample = upsample; a.t_in_offset = t_off;
-  a.ldw = c.ldw; a.ldo = ldo; a.ldr = ldr; a.out_frame_offset = out_frame0; a.interleave_c = interleave_c; a.epilogue = epi;
-  return sf_conv_igemm(&a, stream);
-}
-
-int gemm(const void* a, int lda, const void* w, int ldw, const void* bias, void* out, int ldo, int M, int N, int K, int epi,
-         const void* resid, int ldr, void* stream) {
-  sf_gemm_args g;
-  memset(&g, 0, sizeof(g));
-  g.a = a; g.w = w; g.bias = bias; g.out = out; g.resid = resid; g.rows_per_group = 1;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldo = ldo; g.ldr = ldr; g.epilogue = epi;
-  return sf_gemm_bf16(&g, stream);
-}
-
-// ResidualBlock.forward (vae.py:202-221) on T frames of H x W.  `in_normed`: the producer of x_in already wrote
-// SiLU(RMS_norm(x_in)) into conv1's input volume (fused epilogue); `next`: where (and with which gamma) this block's
-// output should ALSO be written normalised -- the next block's conv1 input or the head's --, if its conv2 can do that.
-// Returns through *out_normed whether it did.
-int resblock(const sf_vae_resblock& r, const BlockBufs& b, const Plan& p, const char* x_in, char* out, const Call& cl, int T, int Tmax, int H, int W,
-             void* stream, bool in_normed = false, const NormOut* next = nullptr, bool* out_normed = nullptr) {
-  const long rows = (long)T * H * W;
-  const int cin = r.conv1.cin, cout = r.conv1.cout;
-  const size_t f1 = vol(1, H, W, cin), f2 = vol(1, H, W, cout);
-  const int c = cl.off(Tmax);                         // both volumes of the block slide alike
-  if (!in_normed) SF_TRY(sf_rmsnorm_silu_cl(x_in, r.gamma1, b.a1 + (size_t)(c + 2) * f1, rows, cin, 1, stream));
-  if (can_fuse_norm(r.conv1, H, W)) {   // conv1's raw output is only ever read by the norm in front of conv2
-    const NormOut n2 = {b.a2, r.gamma2, cout, c + 2};
-    SF_TRY(conv(r.conv1, b.a1, T, H, W, 0, c, nullptr, cout, 0, 0, SF_CONV_BIAS, nullptr, 0, nullptr, stream, &n2));
-  } else {
-    SF_TRY(conv(r.conv1, b.a1, T, H, W, 0, c, p.y1, cout, 0, 0, SF_CONV_BIAS, nullptr, 0, nullptr, stream));
-    SF_TRY(sf_rmsnorm_silu_cl(p.y1, r.gamma2, b.a2 + (size_t)(c + 2) * f2, rows, cout, 1, stream));
-  }
-  const char* resid = x_in;
-  if (r.shortcut.w) {
-    SF_TRY(conv(r.shortcut, x_in, T, H, W, 0, 0, p.sc, cout, 0, 0, SF_CONV_BIAS, nullptr, 0, nullptr, stream));
-    resid = p.sc;
-  }
-  const bool fuse_next = next && next->ld == r.conv2.cout && can_fuse_norm(r.conv2, H, W);
-  SF_TRY(conv(r.conv2, b.a2, T, H, W, 0, c, out, cout, 0, 0, SF_CONV_BIAS_RESID, resid, cout, nullptr, stream, fuse_next ? next : nullptr));
-  if (out_normed) *out_normed = fuse_next;
-  return 0;
-}
-
-// AttentionBlock.forward (vae.py:241-264) on one frame of n = h*w positions, in place on x [n][C]
-int attention_block(const sf_vae_model* m, const Plan& p, char* x, int n, int C, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int np = p.att_npad;
-  SF_TRY(sf_rmsnorm_silu_cl(x, m->attn_gamma, p.att_xn, n, C, 0, stream));
-  SF_TRY(gemm(p.att_xn, C, m->attn_qk_w, C, m->attn_qk_b, p.att_qk, 2 * C, n, 2 * C, C, SF_EPI_BIAS, nullptr, 0, stream));
-  // V^T [C][np] = Wv . xn^T straight from the projection (no transpose pass); its bias is added after
-  // the P.V product instead (softmax rows sum to one), the padded key columns stay zero
-  hipError_t e = hipMemsetAsync(p.att_vt, 0, (size_t)C * np * 2, s);
-  SF_CHECK(e == hipSuccess, "sf_vae: memset failed: %s", hipGetErrorString(e));
-  SF_TRY(gemm(m->attn_v_w, C, p.att_xn, C, nullptr, p.att_vt, np, C, n, C, SF_EPI_BIAS, nullptr, 0, stream));
-  SF_TRY(gemm(p.att_qk, 2 * C, p.att_qk + (size_t)C * 2, 2 * C, nullptr, p.att_s, np, n, n, C, SF_EPI_F32, nullptr, 0, stream));
-  SF_TRY(sf_softmax_rows((const float*)p.att_s, np, p.att_p, np, n, n, np, 1.0f / sqrtf((float)C), stream));
-  SF_TRY(gemm(p.att_p, np, p.att_vt, np, m->attn_v_b, p.att_o, C, n, C, np, SF_EPI_BIAS, nullptr, 0, stream));
-  SF_TRY(gemm(p.att_o, C, m->attn_proj_w, C, m->attn_proj_b, x, C, n, C, C, SF_EPI_BIAS_RESID, x, C, stream));
-  return 0;
 }
 
 }  // namespace
@@ -326,10 +200,11 @@ extern "C" int sf_vae_decode_frames(const sf_vae_model* m, void* state, size_t s
   SF_TRY(conv(m->conv1, p.c1_in, F, h, w, 0, c1, p.xi[0], C0, 0, 0, SF_CONV_BIAS, nullptr, 0, nullptr, stream));
 
   // middle (vae.py:441-445): res, attention (per frame), res -- on the latent-rate frames
+  const AttnWeights aw = {m->attn_gamma, m->attn_qk_w, m->attn_qk_b, m->attn_v_w, m->attn_v_b, m->attn_proj_w, m->attn_proj_b};
   SF_CHECK(res_at(m, 0, 0).conv1.cin == C0 && res_at(m, 0, 0).conv1.cout == C0, "sf_vae_decode_frames: stage 0 must keep the decoder width");
-  SF_TRY(resblock(m->mid0, p.mid0, p, p.xi[0], p.x[0], cl, F, 1, h, w, stream));
-  for (int f = 0; f < F; ++f) SF_TRY(attention_block(m, p, p.x[0] + (size_t)f * vol(1, h, w, C0), h * w, C0, stream));
-  SF_TRY(resblock(m->mid2, p.mid2, p, p.x[0], p.x[0], cl, F, 1, h, w, stream));
+  SF_TRY(resblock(m->mid0, p.mid0, p.rs, p.xi[0], p.x[0], cl, F, 1, h, w, stream));
+  for (int f = 0; f < F; ++f) SF_TRY(attention_block(aw, p.at, p.x[0] + (size_t)f * vol(1, h, w, C0), h * w, C0, stream));
+  SF_TRY(resblock(m->mid2, p.mid2, p.rs, p.x[0], p.x[0], cl, F, 1, h, w, stream));
 
   // upsample stages (vae.py:448-452).  `normed`: the next consumer's input volume already holds SiLU(RMS_norm(cur))
   int T = F;
@@ -355,7 +230,7 @@ extern "C" int sf_vae_decode_frames(const sf_vae_model* m, void* state, size_t s
         next = {p.head_in, m->head_gamma, Ch, c_st + 2};
       }
       bool out_normed = false;
-      SF_TRY(resblock(r, p.blk[i * m->res_per_stage + j], p, cur, out, cl, T, Tmax, H, W, stream, normed, next.dst ? &next : nullptr, &out_normed));
+      SF_TRY(resblock(r, p.blk[i * m->res_per_stage + j], p.rs, cur, out, cl, T, Tmax, H, W, stream, normed, next.dst ? &next : nullptr, &out_normed));
       normed = out_normed;
       cur = out;
     }

@@ -1,5 +1,5 @@
-// HBM-bound kernels of the VAE decode path (gfx950): channel RMS-norm (+SiLU), the row softmax of the
-// single-head attention block, and the latent-frame preparation.  Channels-last bf16 rows throughout.
+// HBM-bound kernels of the VAE decode and encode paths (gfx950): channel RMS-norm (+SiLU), the row softmax of the
+// single-head attention block, the latent-frame preparation, and the encoder's pixel input / latent output conversions.  Channels-last bf16 rows throughout.
 #include "sf_common.h"
 #include "../../include/sf_hip.h"
 
@@ -76,6 +76,40 @@ __global__ __launch_bounds__(256) void prepare_latent_kernel(const bf16_t* __res
   for (int n = z; n < c_pad; ++n) o[n] = (bf16_t)0.f;
 }
 
+// one thread per pixel position: the 3 channels of [3][T][H][W] -> one channels-last row of c_pad (c_pad % 8 == 0)
+template <typename T>
+__global__ __launch_bounds__(256) void prepare_pixels_kernel(const T* __restrict__ px, long c_stride, bf16_t* __restrict__ out, long n,
+                                                             int c_pad) {
+  const long pos = (long)blockIdx.x * 256 + threadIdx.x;
+  if (pos >= n) return;
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = (bf16_t)0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = (bf16_t)(float)px[c * c_stride + pos];
+  bf16x8* o = reinterpret_cast<bf16x8*>(out + pos * c_pad);
+  o[0] = v;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) v[j] = (bf16_t)0.f;
+  for (int k = 1; k < c_pad / 8; ++k) o[k] = v;
+}
+
+// one thread per latent position: mu[n] = b[n] + sum_c w[n][c] x[c] in fp32 (n < z), then (mu - mean) * (1 / std), planar out
+__global__ __launch_bounds__(256) void finish_latent_kernel(const bf16_t* __restrict__ x, int ld_in, int cin, const bf16_t* __restrict__ w,
+                                                            int ld_w, const bf16_t* __restrict__ b, const float* __restrict__ mean,
+                                                            const float* __restrict__ stdv, float* __restrict__ out, long n, int hw, int z) {
+  const long pos = (long)blockIdx.x * 256 + threadIdx.x;
+  if (pos >= n) return;
+  const long t = pos / hw, q = pos - t * hw;
+  float u[64];
+  for (int c = 0; c < cin; ++c) u[c] = (float)x[pos * ld_in + c];
+  for (int k = 0; k < z; ++k) {
+    float acc = (float)b[k];
+    for (int c = 0; c < cin; ++c) acc += (float)w[k * ld_w + c] * u[c];
+    out[(t * z + k) * hw + q] = (acc - mean[k]) * (1.0f / stdv[k]);
+  }
+}
+
 }  // namespace
 
 extern "C" int sf_rmsnorm_silu_cl(const void* x, const void* gamma, void* out, int64_t rows, int C, int silu, void* stream) {
@@ -118,5 +152,33 @@ extern "C" int sf_vae_prepare_latent(const void* latent, const float* mean, cons
   hipLaunchKernelGGL(prepare_latent_kernel, dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)latent, mean, stdv,
                      (const bf16_t*)conv2_w, (const bf16_t*)conv2_b, (bf16_t*)out, z, hw, c_pad);
   SF_HIP_LAUNCH_CHECK("sf_vae_prepare_latent");
+  return 0;
+}
+
+extern "C" int sf_vae_prepare_pixels(const void* pixels, int is_f32, int64_t c_stride, void* out, int T, int H, int W, int c_pad, void* stream) {
+  SF_CHECK(pixels && out, "sf_vae_prepare_pixels: null tensor");
+  SF_CHECK(T > 0 && H > 0 && W > 0 && c_pad >= 8 && c_pad % 8 == 0, "sf_vae_prepare_pixels: bad shape T=%d H=%d W=%d c_pad=%d (c_pad %% 8 == 0, >= 8)", T, H, W, c_pad);
+  const long n = (long)T * H * W;
+  SF_CHECK(c_stride >= n, "sf_vae_prepare_pixels: channel stride %lld < T*H*W = %ld", (long long)c_stride, n);
+  SF_CHECK((uintptr_t)out % 16 == 0, "sf_vae_prepare_pixels: misaligned output");
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (is_f32)
+    hipLaunchKernelGGL(prepare_pixels_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)pixels, (long)c_stride, (bf16_t*)out, n, c_pad);
+  else
+    hipLaunchKernelGGL(prepare_pixels_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)pixels, (long)c_stride, (bf16_t*)out, n, c_pad);
+  SF_HIP_LAUNCH_CHECK("sf_vae_prepare_pixels");
+  return 0;
+}
+
+extern "C" int sf_vae_finish_latent(const void* head_out, int ld_in, int cin, const void* conv1_w, int ld_w, const void* conv1_b,
+                                    const float* mean, const float* stdv, float* out, int T, int z, int h, int w, void* stream) {
+  SF_CHECK(head_out && conv1_w && conv1_b && mean && stdv && out, "sf_vae_finish_latent: null tensor");
+  SF_CHECK(cin > 0 && cin <= 64 && ld_in >= cin && ld_w >= cin && z > 0 && z <= cin, "sf_vae_finish_latent: bad channels cin=%d ld_in=%d ld_w=%d z=%d (cin <= 64)",
+           cin, ld_in, ld_w, z);
+  SF_CHECK(T > 0 && h > 0 && w > 0, "sf_vae_finish_latent: bad shape T=%d h=%d w=%d", T, h, w);
+  const long n = (long)T * h * w;
+  hipLaunchKernelGGL(finish_latent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)head_out, ld_in, cin,
+                     (const bf16_t*)conv1_w, ld_w, (const bf16_t*)conv1_b, mean, stdv, out, n, h * w, z);
+  SF_HIP_LAUNCH_CHECK("sf_vae_finish_latent");
   return 0;
 }

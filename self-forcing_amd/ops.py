@@ -200,18 +200,21 @@ def lincomb(tensors, coefs, out: Optional[Tensor] = None) -> Tensor:
 # VAE decode kernels (channels-last bf16 volumes)
 def conv_igemm(x: Tensor, w_packed: Tensor, bias: Tensor, kernel, t_out: int, upsample: bool = False,
                t_in_offset: int = 0, resid: Optional[Tensor] = None, interleave: bool = False,
-               clamp_f32: bool = False, cin: Optional[int] = None, structure: str = "auto") -> Tensor:
+               clamp_f32: bool = False, cin: Optional[int] = None, structure: str = "auto", stride=(1, 1)) -> Tensor:
     """Implicit-GEMM convolution (sf_conv_igemm).  x [Tin, Hin, Win, Cin] channels-last with the history
     frames in front; w_packed from `vae.repack_conv`; kernel = (kt, kh, kw).  Returns [Tout, H, W, Cout]
-    bf16 -- [2 Tout, H, W, Cout/2] with `interleave` -- or float32 [Tout, Cout, H, W] with `clamp_f32`."""
+    bf16 -- [2 Tout, H, W, Cout/2] with `interleave` -- or float32 [Tout, Cout, H, W] with `clamp_f32`.
+    stride = (temporal, spatial), each 1 or 2: the encoder's downsampling gathers (spatial 2: ZeroPad2d((0,1,0,1)) +
+    3x3 stride 2, H = Hin // 2; temporal 2: output frame t reads 2t + dt + t_in_offset)."""
     _bf16(x, "x"), _bf16(w_packed, "w_packed"), _bf16(bias, "bias")
     if x.dim() != 4 or not x.is_contiguous():
         raise ValueError("conv_igemm: x must be a contiguous [T, H, W, C] volume")
     tin, hin, win, c = x.shape
     kt, kh, kw = kernel
     cout = w_packed.shape[0]
-    H, W = (2 * hin, 2 * win) if upsample else (hin, win)
-    if t_out + (kt - 1) + t_in_offset > tin:
+    st, sh = stride
+    H, W = (2 * hin, 2 * win) if upsample else (hin // 2, win // 2) if sh == 2 else (hin, win)
+    if st * (t_out - 1) + kt + t_in_offset > tin:
         raise ValueError(f"conv_igemm: {tin} input frames do not cover {t_out} output frames (kt={kt}, offset={t_in_offset})")
     a = ConvArgs()
     a.x, a.w, a.bias = x.data_ptr(), w_packed.data_ptr(), bias.data_ptr()
@@ -219,6 +222,7 @@ def conv_igemm(x: Tensor, w_packed: Tensor, bias: Tensor, kernel, t_out: int, up
     a.Cin, a.Cout, a.kt, a.kh, a.kw = cin or c, cout, kt, kh, kw
     a.upsample, a.t_in_offset, a.ldw = int(upsample), t_in_offset, w_packed.stride(0)
     a.structure = _lib.CONV_STRUCTURES[structure]
+    a.stride_t, a.stride_hw = st, sh
     if clamp_f32:
         out = torch.empty(t_out, cout, H, W, dtype=torch.float32, device=x.device)
         a.out_f32, a.epilogue = out.data_ptr(), CONV_BIAS_CLAMP_F32

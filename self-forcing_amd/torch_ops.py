@@ -18,6 +18,7 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::dit_forward_pair(model, ctx_noisy, ctx_timestep, noisy, timestep, caches![]..., workspace!, evict_scratch!?, ctx_plan[7],
                              plan[7], kv_index!?, global_end) -> (flow, x0)        (context pass of chunk k + first pass of chunk k + 1)
     sf_hip::vae_decode_frames(model, state!, scratch!, z, out!, h, w, window_frames, frame_index, window, history_at) -> ()
+    sf_hip::vae_encode_frames(model, state!, scratch!, pixels, out!, H, W, window_frames, chunk_index, window, history_at) -> ()
     sf_hip::t5_encode(model, ids, mask, buckets, workspace!) -> out
 
 Models (weights + C descriptors) are Python objects that own device memory; operators take an integer HANDLE from
@@ -416,6 +417,46 @@ def vae_decode_frames(model: int, state: Tensor, scratch: Tensor, z: Tensor, out
                "sf_vae_decode_frames")
 
 
+@custom_op(f"{NAMESPACE}::vae_encode_frames", mutates_args=("state", "scratch", "out"))
+def vae_encode_frames(model: int, state: Tensor, scratch: Tensor, pixels: Tensor, out: Tensor, H: int, W: int, window_frames: int,
+                      chunk_index: int, window: int, history_at: int) -> None:
+    """Consecutive chunks of pixel frames [3, T, H, W] (bf16 or float32; T = 1 for chunk_index 0, else 4 per chunk; any
+    channel stride, frames contiguous) -> float32 normalised latents written to `out` [n_chunks, z_dim, H/8, W/8];
+    `state` carries every convolution's history between calls (sf_vae_encode_frames in include/sf_hip.h;
+    `WanVAEEncoder.encode` does the bookkeeping)."""
+    m = _model(model)
+    _need_gpu(pixels, "pixels", None)
+    _need_gpu(out, "out", torch.float32)
+    if pixels.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"vae_encode_frames: pixels must be bf16 or float32, got {pixels.dtype}")
+    if pixels.dim() != 4 or pixels.shape[0] != 3 or tuple(pixels.shape[2:]) != (H, W) or not pixels[0].is_contiguous():
+        raise ValueError(f"vae_encode_frames: pixels must be [3, T, {H}, {W}] with contiguous frames, got {tuple(pixels.shape)}")
+    for name, t in (("state", state), ("scratch", scratch)):       # their element counts are passed on as BYTE counts
+        if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError(f"vae_encode_frames: {name} must be a contiguous CUDA uint8 tensor")
+    T = pixels.shape[1]
+    if chunk_index == 0:
+        if T != 1:
+            raise ValueError("vae_encode_frames: the chunk that follows a reset (chunk_index 0) is one pixel frame")
+        n = 1
+    else:
+        if T % 4 or T == 0:
+            raise ValueError(f"vae_encode_frames: {T} pixel frames is not a whole number of 4-frame chunks")
+        n = T // 4
+    sf_ = m.shape.spatial_factor
+    if tuple(out.shape) != (n, m.shape.z_dim, H // sf_, W // sf_) or not out.is_contiguous():
+        raise ValueError(f"vae_encode_frames: out must be contiguous [{n}, {m.shape.z_dim}, {H // sf_}, {W // sf_}], got {tuple(out.shape)}")
+    _lib.check(_lib.lib().sf_vae_encode_frames(C.byref(m.cmodel), state.data_ptr(), state.numel(), scratch.data_ptr(), scratch.numel(),
+                                               pixels.data_ptr(), int(pixels.dtype == torch.float32), pixels.stride(0), H, W, window_frames,
+                                               chunk_index, n, window, history_at, out.data_ptr(), _stream(pixels)),
+               "sf_vae_encode_frames")
+
+
+@vae_encode_frames.register_fake
+def _(model, state, scratch, pixels, out, H, W, window_frames, chunk_index, window, history_at):
+    return None   # writes only its mutated arguments
+
+
 @custom_op(f"{NAMESPACE}::t5_encode", mutates_args=("workspace",))
 def t5_encode(model: int, ids: Tensor, mask: Tensor, buckets: Tensor, workspace: Tensor) -> Tensor:
     """umT5 encoder pass: ids, mask int64 [B, L] -> bf16 [B, L, dim], rows past each prompt's length zeroed (sf_t5_encode)."""
@@ -435,4 +476,4 @@ def _(model, ids, mask, buckets, workspace):
     return ids.new_empty((ids.shape[0], ids.shape[1], _model(model).shape.dim), dtype=torch.bfloat16)
 
 
-OPS = ("attention", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "t5_encode")
+OPS = ("attention", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "vae_encode_frames", "t5_encode")

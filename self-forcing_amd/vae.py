@@ -1,14 +1,15 @@
-"""Wan VAE decode on the GPU behind the reference's `WanVAEWrapper` surface.
+"""Wan VAE decode and encode on the GPU behind the reference's `WanVAEWrapper` surface.
 
-Mirrors `utils/wan_wrapper.py:56-117` for the decode direction only:
+Mirrors `utils/wan_wrapper.py:56-117`:
 
     vae = WanVAEWrapper(state_dict=..., device="cuda")
     video = vae.decode_to_pixel(latent, use_cache=False)      # [B, F, 16, h, w] -> [B, 1+4(F-1), 3, 8h, 8w]
     vae.model.clear_cache()                                    # inference.py:183
+    latent = vae.encode_to_latent(pixel)                       # [B, 3, T, H, W] -> float32 [B, 1+(T-1)//4, 16, H/8, W/8]
 
-Every kernel is in csrc/ (conv_igemm.hip, vae_elementwise.hip, gemm_bf16.hip) and one latent frame is ONE
-C call (`sf_vae_decode_frames`).  There is no eager/CPU fallback.  `encode_to_latent` (used only by
-`--i2v`, inference.py:145) is not on this path and raises.
+Every kernel is in csrc/ (conv_igemm.hip, vae_elementwise.hip, gemm_bf16.hip); a group of latent frames is ONE C call
+(`sf_vae_decode_frames`), a group of 4-frame chunks likewise (`sf_vae_encode_frames`).  There is no eager/CPU
+fallback.  The encoder (image-to-video, inference.py:145) needs the checkpoint's `encoder.*` / `conv1.*` tensors.
 """
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ import torch
 
 from . import _lib, torch_ops
 from .vae_weights import (LATENT_MEAN, LATENT_STD, ResBlockSpec, ResampleSpec, VaeShape, WAN_VAE, decoder_layout,
-                          vae_param_shapes)
+                          encode_chunks, encoder_dims, encoder_layout, encoder_param_shapes, vae_param_shapes)
 
 Tensor = torch.Tensor
 
@@ -221,6 +222,120 @@ class WanVAEDecoder:
         return out
 
 
+class WanVAEEncoder(WanVAEDecoder):
+    """Device-resident encoder: repacked bf16 weights of `Encoder3d` + `conv1` and the C descriptor; per-(H, W) state
+    (the convolution histories) and scratch allocated on first use.  Counterpart of `WanVAE_.encode`
+    (wan/modules/vae.py:517-543).  Shares the decoder's weight repacking (`_conv`, `_res`)."""
+
+    def __init__(self, shape: VaeShape, state_dict: Dict[str, Tensor], device, frames_per_call: int = 4):
+        if not 1 <= frames_per_call <= 63:
+            raise ValueError("frames_per_call must be in 1..63")
+        self.shape = shape
+        self.device = torch.device(device)
+        self.frames_per_call = frames_per_call          # 4-frame chunks handed to one C call (any value gives the same bits)
+        self._keep: List[Tensor] = []
+        self._state: Dict[tuple, Tensor] = {}
+        self._scratch: Dict[tuple, Tensor] = {}
+        self._load_encoder(state_dict)
+
+    def _load_encoder(self, sd: Dict[str, Tensor]) -> None:
+        s = self.shape
+        for k, shp in encoder_param_shapes(s).items():
+            if tuple(sd[k].shape) != tuple(shp):
+                raise ValueError(f"{k}: expected shape {shp}, got {tuple(sd[k].shape)}")
+        dims = encoder_dims(s)
+        if any(d % 32 for d in dims) or dims[-1] % 64:
+            raise ValueError(f"encoder widths {dims} must be multiples of 32 (last: 64)")
+        if len(s.dim_mult) > _lib.VAE_MAX_STAGES:
+            raise ValueError("at most 4 encoder stages")
+        stages, middle = encoder_layout(s)
+        m = _lib.VaeEncoder()
+        m.z_dim, m.n_stages, m.res_per_stage = s.z_dim, len(s.dim_mult), s.num_res_blocks
+        m.latent_mean = self._dev(torch.tensor(LATENT_MEAN[:s.z_dim]), torch.float32).data_ptr()
+        m.latent_std = self._dev(torch.tensor(LATENT_STD[:s.z_dim]), torch.float32).data_ptr()
+        z2 = 2 * s.z_dim
+        m.conv1_w = self._dev(sd["conv1.weight"].reshape(z2, z2)[:s.z_dim]).data_ptr()      # mu rows only (vae.py:538)
+        m.conv1_b = self._dev(sd["conv1.bias"][:s.z_dim]).data_ptr()
+        self._conv(m.in_conv, sd, "encoder.conv1")
+        blocks = [spec for st in stages for spec in st if isinstance(spec, ResBlockSpec)]
+        res = (_lib.VaeResBlock * len(blocks))()
+        for i, spec in enumerate(blocks):
+            self._res(res[i], sd, spec)
+        self._res_array = res
+        m.res_host = C.cast(res, C.POINTER(_lib.VaeResBlock))
+        for i, st in enumerate(stages):
+            for spec in st:
+                if isinstance(spec, ResampleSpec):
+                    self._conv(m.down_conv[i], sd, spec.prefix + "resample.1")
+                    if spec.mode == "downsample3d":
+                        m.temporal_down[i] = 1
+                        self._conv(m.time_conv[i], sd, spec.prefix + "time_conv")
+        self._res(m.mid0, sd, middle[0])
+        self._res(m.mid2, sd, middle[2])
+        a, c = middle[1], dims[-1]
+        qkv_w, qkv_b = sd[a + "to_qkv.weight"].reshape(3 * c, c), sd[a + "to_qkv.bias"]
+        m.attn_gamma = self._dev(sd[a + "norm.gamma"].flatten()).data_ptr()
+        m.attn_qk_w, m.attn_qk_b = self._dev(qkv_w[:2 * c]).data_ptr(), self._dev(qkv_b[:2 * c]).data_ptr()
+        m.attn_v_w, m.attn_v_b = self._dev(qkv_w[2 * c:]).data_ptr(), self._dev(qkv_b[2 * c:]).data_ptr()
+        m.attn_proj_w = self._dev(sd[a + "proj.weight"].reshape(c, c)).data_ptr()
+        m.attn_proj_b = self._dev(sd[a + "proj.bias"]).data_ptr()
+        m.head_gamma = self._dev(sd["encoder.head.0.gamma"].flatten()).data_ptr()
+        self._conv(m.head_conv, sd, "encoder.head.2")
+        self.cmodel = m
+        self._handle = torch_ops.register_model(self)
+
+    def _enc_buffers(self, H: int, W: int, K: int):
+        if (2 + K * 4) * H * W * encoder_dims(self.shape)[0] * 2 >= 0xFFFFFF00:
+            raise ValueError(f"frames_per_call={self.frames_per_call} at {H}x{W}: a convolution's input volume would pass 4 GiB "
+                             "(the kernels address a volume through one 32-bit-ranged buffer descriptor); use fewer frames per call")
+        key = (H, W, K)
+        if key not in self._state:
+            n = _lib.lib().sf_vae_encode_state_bytes(C.byref(self.cmodel), H, W, K)
+            if n == 0:
+                _lib.check(-1, "sf_vae_encode_state_bytes")
+            self._state[key] = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        skey = (H, W, K, torch.cuda.current_stream(self.device).cuda_stream)
+        if skey not in self._scratch:
+            n = _lib.lib().sf_vae_encode_scratch_bytes(C.byref(self.cmodel), H, W, K)
+            self._scratch[skey] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        return self._state[key], self._scratch[skey]
+
+    def encode(self, x: Tensor) -> Tensor:
+        """`WanVAE_.encode` (vae.py:517-543) for one sample: x [3, T, H, W] (bf16 or float32, in [-1, 1]) -> float32
+        normalised mu [1 + (T-1)//4, z_dim, H/8, W/8].  Starts from cleared histories; frames past the last whole chunk
+        of 4 are dropped, as the reference does."""
+        if x.dim() != 4 or x.shape[0] != 3:
+            raise ValueError(f"expected pixels [3, T, H, W], got {tuple(x.shape)}")
+        _, T, H, W = x.shape
+        sf = self.shape.spatial_factor
+        if H % sf or W % sf:
+            raise ValueError(f"encode: height and width must be multiples of {sf}, got {H}x{W}")
+        n = encode_chunks(T)
+        if x.dtype not in (torch.bfloat16, torch.float32):
+            x = x.float()
+        x = x.to(self.device)[:, :1 + 4 * (n - 1)].contiguous()
+        # histories for the first frame + up to frames_per_call chunks per call; fewer slots when the input is short
+        K = min(self.frames_per_call, max(n - 1, 1)) + 1
+        state, scratch = self._enc_buffers(H, W, K)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(_lib.lib().sf_vae_encode_reset(C.byref(self.cmodel), state.data_ptr(), state.numel(), H, W, K, stream), "sf_vae_encode_reset")
+        out = torch.empty(n, self.shape.z_dim, H // sf, W // sf, dtype=torch.float32, device=self.device)
+        i, slot, f0 = 0, 0, 0
+        while i < n:
+            g = 1 if i == 0 else min(self.frames_per_call, n - i)
+            if slot + g > K:
+                window, history_at = 0, slot
+            else:
+                window = history_at = slot
+            nf = 1 if i == 0 else 4 * g
+            torch.ops.sf_hip.vae_encode_frames(self._handle, state, scratch, x[:, f0:f0 + nf], out[i:i + g], H, W, K, i, window,
+                                               history_at)
+            slot = window + g
+            f0 += nf
+            i += g
+        return out
+
+
 VAE_CHECKPOINT = "wan_models/Wan2.1-T2V-1.3B/Wan2.1_VAE.pth"   # utils/wan_wrapper.py:74
 
 
@@ -228,7 +343,7 @@ class WanVAEWrapper(torch.nn.Module):
     """Drop-in for the reference's `WanVAEWrapper` (utils/wan_wrapper.py:56-117), decode side.
 
     `state_dict`: the tensors of `Wan2.1_VAE.pth` (or the seeded stand-in of `vae_weights.synth_vae_state_dict`);
-    encoder tensors, if present, are ignored.  Without one the reference's default checkpoint path is loaded
+    when it holds the encoder tensors as well, `encode_to_latent` works too.  Without one the reference's default checkpoint path is loaded
     (weights-only); FileNotFoundError when it is absent."""
 
     def __init__(self, state_dict: Optional[Dict[str, Tensor]] = None, device="cuda", shape: VaeShape = WAN_VAE,
@@ -243,9 +358,26 @@ class WanVAEWrapper(torch.nn.Module):
         self.mean = torch.tensor(LATENT_MEAN, dtype=torch.float32)
         self.std = torch.tensor(LATENT_STD, dtype=torch.float32)
         self.model = WanVAEDecoder(shape, state_dict, device, frames_per_call=frames_per_call)
+        self.shape = shape
+        missing = [k for k in encoder_param_shapes(shape) if k not in state_dict]
+        self.encoder: Optional[WanVAEEncoder] = None
+        self._encoder_missing = missing
+        if not missing:
+            self.encoder = WanVAEEncoder(shape, state_dict, device, frames_per_call=frames_per_call)
 
     def encode_to_latent(self, pixel: Tensor) -> Tensor:
-        raise NotImplementedError("the VAE encoder (image-to-video conditioning, inference.py:145) is outside this path")
+        """pixel [B, 3, T, H, W] in [-1, 1] -> float32 latents [B, 1 + (T-1)//4, 16, H/8, W/8] (wan_wrapper.py:78-92):
+        one `WanVAE_.encode` per sample, histories cleared before and after each."""
+        if self.encoder is None:
+            m = self._encoder_missing
+            raise NotImplementedError(f"this VAE state dict has no encoder: {len(m)} encoder.* / conv1.* tensors are missing, "
+                                      f"e.g. {m[:3]} (load Wan2.1_VAE.pth, or synth_vae_state_dict(..., encoder=True))")
+        if pixel.dim() != 5 or pixel.shape[1] != 3:
+            raise ValueError(f"encode_to_latent expects pixels [B, 3, T, H, W], got {tuple(pixel.shape)}")
+        sf = self.shape.spatial_factor
+        if pixel.shape[3] % sf or pixel.shape[4] % sf:
+            raise ValueError(f"encode_to_latent: height and width must be multiples of {sf}, got {pixel.shape[3]}x{pixel.shape[4]}")
+        return torch.stack([self.encoder.encode(u) for u in pixel], dim=0)
 
     def decode_to_pixel(self, latent: Tensor, use_cache: bool = False) -> Tensor:
         """latent [B, F, C, h, w] -> float32 [B, T, 3, 8h, 8w] clamped to [-1, 1] (wan_wrapper.py:95-117)."""

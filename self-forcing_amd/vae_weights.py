@@ -1,8 +1,9 @@
-"""Shape description and weight handling of the Wan VAE *decoder* (latents -> pixels).
+"""Shape description and weight handling of the Wan VAE: the decoder (latents -> pixels) and the encoder
+(pixels -> latents, for image-to-video).
 
-Key names are those of the reference's `WanVAE_.state_dict()` restricted to what `decode` reads
-(wan/modules/vae.py:369-429 Decoder3d, :503 conv2), so `Wan2.1_VAE.pth` loads unchanged (its encoder /
-conv1 tensors are ignored).
+Key names are those of the reference's `WanVAE_.state_dict()`: `vae_param_shapes` lists what `decode` reads
+(wan/modules/vae.py:369-429 Decoder3d, :503 conv2), `encoder_param_shapes` what `encode` reads (:265-367 Encoder3d,
+:502 conv1), so `Wan2.1_VAE.pth` loads unchanged.
 """
 from __future__ import annotations
 
@@ -63,7 +64,7 @@ class ResBlockSpec:
 class ResampleSpec:
     prefix: str
     dim: int
-    mode: str   # 'upsample2d' | 'upsample3d'
+    mode: str   # 'upsample2d' | 'upsample3d' | 'downsample2d' | 'downsample3d'
 
 
 def decoder_layout(s: VaeShape):
@@ -86,6 +87,96 @@ def decoder_layout(s: VaeShape):
                                     "upsample3d" if s.temperal_upsample[i] else "upsample2d"))
             idx += 1
     return middle, ups
+
+
+def encoder_dims(s: VaeShape) -> List[int]:
+    """Widths of Encoder3d (vae.py:286): dim * [1, *dim_mult] -- [96, 96, 192, 384, 384] for Wan2.1."""
+    return [s.dim * u for u in (1,) + tuple(s.dim_mult)]
+
+
+def temporal_downsample(s: VaeShape) -> Tuple[bool, ...]:
+    return tuple(s.temperal_upsample[::-1])        # WanVAE_: temperal_upsample = temperal_downsample[::-1] (vae.py:500)
+
+
+def encoder_layout(s: VaeShape):
+    """The module sequence of Encoder3d (vae.py:286-319): returns (stages, middle) where stages[i] is the list of
+    ResBlockSpec of stage i followed by its ResampleSpec ('downsample2d' / 'downsample3d'; none for the last stage) and
+    middle is [ResBlockSpec, attention prefix, ResBlockSpec]."""
+    dims = encoder_dims(s)
+    tdown = temporal_downsample(s)
+    stages = []
+    idx = 0
+    for i, (in_dim, out_dim) in enumerate(zip(dims[:-1], dims[1:])):
+        st = []
+        for _ in range(s.num_res_blocks):
+            st.append(ResBlockSpec(f"encoder.downsamples.{idx}.", in_dim, out_dim))
+            idx += 1
+            in_dim = out_dim
+        if i != len(s.dim_mult) - 1:
+            st.append(ResampleSpec(f"encoder.downsamples.{idx}.", out_dim, "downsample3d" if tdown[i] else "downsample2d"))
+            idx += 1
+        stages.append(st)
+    c = dims[-1]
+    middle = [ResBlockSpec("encoder.middle.0.", c, c), "encoder.middle.1.", ResBlockSpec("encoder.middle.2.", c, c)]
+    return stages, middle
+
+
+def _res_shapes(out: Dict[str, Tuple[int, ...]], spec: ResBlockSpec) -> None:
+    p = spec.prefix
+    out[p + "residual.0.gamma"] = (spec.in_dim, 1, 1, 1)
+    out[p + "residual.2.weight"] = (spec.out_dim, spec.in_dim, 3, 3, 3)
+    out[p + "residual.2.bias"] = (spec.out_dim,)
+    out[p + "residual.3.gamma"] = (spec.out_dim, 1, 1, 1)
+    out[p + "residual.6.weight"] = (spec.out_dim, spec.out_dim, 3, 3, 3)
+    out[p + "residual.6.bias"] = (spec.out_dim,)
+    if spec.in_dim != spec.out_dim:
+        out[p + "shortcut.weight"] = (spec.out_dim, spec.in_dim, 1, 1, 1)
+        out[p + "shortcut.bias"] = (spec.out_dim,)
+
+
+def _attn_shapes(out: Dict[str, Tuple[int, ...]], a: str, c: int) -> None:
+    out[a + "norm.gamma"] = (c, 1, 1)
+    out[a + "to_qkv.weight"] = (3 * c, c, 1, 1)
+    out[a + "to_qkv.bias"] = (3 * c,)
+    out[a + "proj.weight"] = (c, c, 1, 1)
+    out[a + "proj.bias"] = (c,)
+
+
+def encoder_param_shapes(s: VaeShape) -> Dict[str, Tuple[int, ...]]:
+    """Every tensor `WanVAE_.encode` reads, in `state_dict()` order: `encoder.*`, then the 1x1x1 `conv1` (2z -> 2z)."""
+    out: Dict[str, Tuple[int, ...]] = {}
+    dims = encoder_dims(s)
+    out["encoder.conv1.weight"] = (dims[0], 3, 3, 3, 3)
+    out["encoder.conv1.bias"] = (dims[0],)
+    stages, middle = encoder_layout(s)
+    for st in stages:
+        for spec in st:
+            if isinstance(spec, ResBlockSpec):
+                _res_shapes(out, spec)
+            else:
+                out[spec.prefix + "resample.1.weight"] = (spec.dim, spec.dim, 3, 3)
+                out[spec.prefix + "resample.1.bias"] = (spec.dim,)
+                if spec.mode == "downsample3d":
+                    out[spec.prefix + "time_conv.weight"] = (spec.dim, spec.dim, 3, 1, 1)
+                    out[spec.prefix + "time_conv.bias"] = (spec.dim,)
+    _res_shapes(out, middle[0])
+    _attn_shapes(out, middle[1], dims[-1])
+    _res_shapes(out, middle[2])
+    z2 = 2 * s.z_dim
+    out["encoder.head.0.gamma"] = (dims[-1], 1, 1, 1)
+    out["encoder.head.2.weight"] = (z2, dims[-1], 3, 3, 3)
+    out["encoder.head.2.bias"] = (z2,)
+    out["conv1.weight"] = (z2, z2, 1, 1, 1)
+    out["conv1.bias"] = (z2,)
+    return out
+
+
+def encode_chunks(frames: int) -> int:
+    """Chunks (= latent frames) `WanVAE_.encode` makes of `frames` pixel frames (vae.py:521-522): the first frame
+    alone, then whole groups of 4; trailing frames past the last full group are dropped."""
+    if frames < 1:
+        raise ValueError("encode needs at least one pixel frame")
+    return 1 + (frames - 1) // 4
 
 
 def vae_param_shapes(s: VaeShape) -> Dict[str, Tuple[int, ...]]:
@@ -133,15 +224,9 @@ def vae_param_shapes(s: VaeShape) -> Dict[str, Tuple[int, ...]]:
     return out
 
 
-def synth_vae_state_dict(s: VaeShape, seed: int = 0, dtype=torch.bfloat16) -> Dict[str, Tensor]:
-    """Seeded random-init decoder weights on the CPU (there is no network for Wan2.1_VAE.pth).
-    Convolutions ~ U(-a, a) with a = sqrt(3 / fan_in) (unit gain: activations keep their scale through
-    the 30-odd layers), biases ~ N(0, .02), RMS-norm gammas ~ 1 + N(0, .1).  The attention projection
-    `proj` is NOT zero (the reference zero-initialises it, vae.py:239, which would make the block the
-    identity and the test vacuous).  Drawn tensor by tensor in `vae_param_shapes` order."""
-    g = torch.Generator(device="cpu").manual_seed(seed)
+def _synth(shapes: Dict[str, Tuple[int, ...]], g: torch.Generator, dtype) -> Dict[str, Tensor]:
     sd: Dict[str, Tensor] = {}
-    for name, shape in vae_param_shapes(s).items():
+    for name, shape in shapes.items():
         if name.endswith("gamma"):
             t = 1.0 + 0.1 * torch.randn(shape, generator=g)
         elif name.endswith(".bias"):
@@ -153,6 +238,25 @@ def synth_vae_state_dict(s: VaeShape, seed: int = 0, dtype=torch.bfloat16) -> Di
             a = math.sqrt(3.0 / fan_in)
             t = torch.empty(shape).uniform_(-a, a, generator=g)
         sd[name] = t.to(dtype)
+    return sd
+
+
+# the encoder's tensors come from a generator of their own, so that the decoder's stay what they were without them
+ENCODER_SEED_OFFSET = 0x5EED
+
+
+def synth_vae_state_dict(s: VaeShape, seed: int = 0, dtype=torch.bfloat16, encoder: bool = False) -> Dict[str, Tensor]:
+    """Seeded random-init decoder weights on the CPU (there is no network for Wan2.1_VAE.pth).
+    Convolutions ~ U(-a, a) with a = sqrt(3 / fan_in) (unit gain: activations keep their scale through
+    the 30-odd layers), biases ~ N(0, .02), RMS-norm gammas ~ 1 + N(0, .1).  The attention projection
+    `proj` is NOT zero (the reference zero-initialises it, vae.py:239, which would make the block the
+    identity and the test vacuous).  Drawn tensor by tensor in `vae_param_shapes` order.
+
+    `encoder=True` adds the encoder (`encoder_param_shapes`, same recipe, its own proj non-zero too), drawn from a
+    separate generator seeded `seed + ENCODER_SEED_OFFSET`: the decoder tensors are bit-identical either way."""
+    sd = _synth(vae_param_shapes(s), torch.Generator(device="cpu").manual_seed(seed), dtype)
+    if encoder:
+        sd.update(_synth(encoder_param_shapes(s), torch.Generator(device="cpu").manual_seed(seed + ENCODER_SEED_OFFSET), dtype))
     return sd
 
 
@@ -186,3 +290,39 @@ def vae_decode_flops(s: VaeShape, lat_h: int, lat_w: int, latent_frames: int) ->
         return fl
 
     return one(True) + (latent_frames - 1) * one(False)
+
+
+def vae_encode_flops(s: VaeShape, height: int, width: int, frames: int) -> float:
+    """Algorithmic FLOPs (multiply-add = 2) of `encode` on `frames` pixel frames of height x width: every convolution at
+    its true channel counts (encoder.conv1 reads 3 channels), the stride-2 convolutions at their output positions, the
+    middle attention block, and conv1's mu rows.  The first chunk is one frame at every stage (no time convolution);
+    every later chunk is 4 frames, halved by each downsample3d."""
+    stages, middle = encoder_layout(s)
+    dims = encoder_dims(s)
+
+    def res(spec: ResBlockSpec, pos: float) -> float:
+        fl = 2.0 * 27 * spec.in_dim * spec.out_dim * pos + 2.0 * 27 * spec.out_dim * spec.out_dim * pos
+        if spec.in_dim != spec.out_dim:
+            fl += 2.0 * spec.in_dim * spec.out_dim * pos
+        return fl
+
+    def one(first: bool) -> float:
+        h, w, t = height, width, 1 if first else 4
+        fl = 2.0 * 27 * 3 * dims[0] * t * h * w                                                # encoder.conv1
+        for st in stages:
+            for spec in st:
+                if isinstance(spec, ResBlockSpec):
+                    fl += res(spec, t * h * w)
+                else:
+                    h, w = h // 2, w // 2
+                    fl += 2.0 * 9 * spec.dim * spec.dim * t * h * w
+                    if spec.mode == "downsample3d" and not first:
+                        t //= 2
+                        fl += 2.0 * 3 * spec.dim * spec.dim * t * h * w
+        pos, c = t * h * w, dims[-1]
+        fl += res(middle[0], pos) + res(middle[2], pos)
+        fl += t * (2.0 * c * 3 * c * h * w + 2.0 * c * c * h * w + 4.0 * (h * w) ** 2 * c)    # attention block per frame
+        fl += 2.0 * 27 * c * 2 * s.z_dim * pos + 2.0 * 2 * s.z_dim * s.z_dim * pos              # head, conv1 (mu rows)
+        return fl
+
+    return one(True) + (encode_chunks(frames) - 1) * one(False)
