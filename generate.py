@@ -102,6 +102,8 @@ def main():
     ap.add_argument("--sampling_steps", type=int, default=0, help="multi-step sampler only: override its 50 steps")
     ap.add_argument("--vae_random_init_seed", type=int, default=None,
                     help="seeded random VAE weights instead (decoder; with --i2v the encoder too)")
+    ap.add_argument("--fp8", action="store_true",
+                    help="FP8 linear layers in the generator (the reference's enable_fp8 / torchao PerTensor quantisation)")
     a = ap.parse_args()
 
     # inference.py:39-45: one process per GPU under torch.distributed.run, RCCL for the start / end barriers only
@@ -127,9 +129,9 @@ def main():
         else:
             ck = torch.load(a.checkpoint_path, map_location="cpu", weights_only=True)
             sd = ck["generator_ema" if a.use_ema else "generator"] if "generator" in ck or "generator_ema" in ck else ck
-        gen = sfa.WanDiffusionWrapper(**kwargs, is_causal=True, state_dict=sd, device=device)
+        gen = sfa.WanDiffusionWrapper(**kwargs, is_causal=True, state_dict=sd, device=device, fp8=a.fp8)
     else:
-        gen = sfa.WanDiffusionWrapper(**kwargs, is_causal=True, random_init_seed=a.random_init_seed, device=device)
+        gen = sfa.WanDiffusionWrapper(**kwargs, is_causal=True, random_init_seed=a.random_init_seed, device=device, fp8=a.fp8)
     shape = gen.model.shape
     if a.i2v:
         pairs = read_image_pairs(a.data_path, a.eval_first_n)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_HIP_ABI_VERSION 9
+#define SF_HIP_ABI_VERSION 10
 
 int sf_abi_version(void);
 const char* sf_last_error(void);
@@ -73,6 +73,34 @@ enum sf_gemm_structure { SF_GEMM_AUTO = 0, SF_GEMM_T128 = 1 /* 128 x 128 tile, 4
                                                                  workgroups mostly empty */ };
 
 int sf_gemm_bf16(const sf_gemm_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * FP8 linear layers (opt-in).  Replaces the reference's optional torchao quantisation of the
+ * generator, `quantize_(transformer, Float8DynamicActivationFloat8WeightConfig(granularity=PerTensor()))`
+ * (demo.py:277-283), whose F.linear calls then run as scaled fp8 matmuls.  Format: OCP e4m3fn (torch.float8_e4m3fn).
+ * The recipe (ours, pinned by the tests; torchao is not reproduced bit for bit), for weights once at load and for
+ * activations on every call, over one SEGMENT of rows (activations: the rows of one generator pass, all its samples):
+ *   s = max(amax(|x|) as fp32, 1e-12) / 448,   q = e4m3fn_rne(clamp(x.float() / s, -448, 448))   (true fp32 division)
+ *
+ * sf_quantize_fp8: x [M, K] bf16 (row stride ldx) -> q_out [M, K] e4m3 (contiguous), scale_out[seg] = s of rows
+ * [seg * rows_per_segment, (seg + 1) * rows_per_segment).  scale_out is float32 [segments * (1 + SF_FP8_AMAX_PARTS)]:
+ * the scales, then scratch for the partial maxima (written and read by the call; the result does not depend on
+ * the order of the reduction).  Two launches. */
+#define SF_FP8_AMAX_PARTS 1024
+int sf_quantize_fp8(const void* x, int ldx, int M, int K, int rows_per_segment, void* q_out, float* scale_out, void* stream);
+
+/* out = epi(acc * (a_scale[m / rows_per_segment] * w_scale[n]) + bias[n]), acc the fp32 sum of the e4m3 products of
+ * args->a [M, K] and args->w [N, K] (both e4m3; lda / ldw in bytes); one rounding to bf16.  Every epilogue but
+ * SF_EPI_F32, every structure of sf_gemm_bf16 (bit-identical to each other; SF_GEMM_AUTO picks by the same rule),
+ * no batch.  K % 128 == 0.  w_scale: fp32 [N], 16-byte aligned (a stacked q|k|v weight carries 3 values). */
+int sf_gemm_fp8(const sf_gemm_args* args, const float* a_scale, int rows_per_segment, const float* w_scale, void* stream);
+
+/* sf_small_linear on e4m3 weights w_q [N, K] with column scales w_scale [N]: the activation act_in(x) (rounded to
+ * bf16) is quantised inside the kernel with one scale per segment of rows_per_segment rows, then
+ * out = act_out(acc * (sa[seg(m)] * w_scale[n]) + bias[n]).  Replaces the time-embedding MLPs' F.linear under the
+ * reference's fp8 quantisation (causal_model.py:464-467, :829-832; demo.py:277-283).  One launch. */
+int sf_small_linear_fp8(const void* x, const void* w_q, const float* w_scale, const void* bias, void* out, int M, int N, int K,
+                        int rows_per_segment, int act_in, int act_out, void* stream);
 
 /* Small-M linear layer (M <= 32), weight-bandwidth bound: out = act_out(act_in(x) @ w^T + b).
  * Replaces the time-embedding MLPs, causal_model.py:464-467, :829-832.
@@ -202,7 +230,19 @@ typedef struct sf_model {
   const float *rope_cos, *rope_sin;       /* float32 [1024, 64] */
   const float *sched_sigmas, *sched_timesteps; /* float32 [n_table] */
   int32_t n_table;
+  /* ---- ABI 10: FP8 linear layers (sf_gemm_fp8).  All zero = bf16 (the fields above).  With fp8 = 1 every nn.Linear of
+   * the reference's CausalWanModel reads the e4m3 weight *_q [N, K] and its fp32 column scales *_s [N] instead of the
+   * bf16 *_w (which may then be NULL); the patch embedding (a Conv3d) stays bf16.  Activations are quantised per pass. */
+  int32_t fp8;
+  const void *text0_q, *text2_q, *time0_q, *time2_q, *tproj_q, *head_q, *pose_q;
+  const float *text0_s, *text2_s, *time0_s, *time2_s, *tproj_s, *head_s, *pose_s;
+  const struct sf_layer_fp8* layers_fp8_host;   /* HOST array [num_layers] */
 } sf_model;
+
+typedef struct sf_layer_fp8 {             /* e4m3 weights [N, K] + fp32 column scales [N] of one block */
+  const void *qkv_q, *o_q, *cq_q, *ckv_q, *co_q, *ffn0_q, *ffn2_q;
+  const float *qkv_s, *o_s, *cq_s, *ckv_s, *co_s, *ffn0_s, *ffn2_s;
+} sf_layer_fp8;
 
 typedef struct sf_forward_args {
   int32_t batch, frames, lat_h, lat_w;    /* noisy: [B, F, in_dim, H, W] */

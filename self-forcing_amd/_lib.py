@@ -21,7 +21,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("SF_HIP_LIB") or os.path.join(CSRC, "libsf_hip.so")   # SF_HIP_LIB: alternate builds (kernel ablation timing)
 
-ABI_VERSION = 9
+ABI_VERSION = 10
+FP8_AMAX_PARTS = 1024   # SF_FP8_AMAX_PARTS: scratch floats per segment behind the scales of sf_quantize_fp8
 
 # epilogue codes (enum sf_epilogue)
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_GATE_RESID, EPI_F32 = 0, 1, 2, 3, 4
@@ -55,6 +56,21 @@ class LayerWeights(C.Structure):
         "ffn0_w", "ffn0_b", "ffn2_w", "ffn2_b")]
 
 
+class LayerFp8(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "qkv_q", "o_q", "cq_q", "ckv_q", "co_q", "ffn0_q", "ffn2_q",
+        "qkv_s", "o_s", "cq_s", "ckv_s", "co_s", "ffn0_s", "ffn2_s")]
+
+
+# (field of sf_model / sf_layer_fp8 without its _q / _s suffix, the reference Linear(s) it stands for); a stacked weight
+# carries one scale per reference Linear
+FP8_MODEL_LINEARS = (("text0", ("text_embedding.0",)), ("text2", ("text_embedding.2",)), ("time0", ("time_embedding.0",)),
+                     ("time2", ("time_embedding.2",)), ("tproj", ("time_projection.1",)), ("head", ("head.head",)),
+                     ("pose", ("pose_proj",)))
+FP8_LAYER_LINEARS = (("qkv", ("self_attn.q", "self_attn.k", "self_attn.v")), ("o", ("self_attn.o",)), ("cq", ("cross_attn.q",)),
+                     ("ckv", ("cross_attn.k", "cross_attn.v")), ("co", ("cross_attn.o",)), ("ffn0", ("ffn.0",)), ("ffn2", ("ffn.2",)))
+
+
 class Model(C.Structure):
     _fields_ = (
         [(n, C.c_int32) for n in ("dim", "ffn_dim", "num_heads", "num_layers", "in_dim", "out_dim",
@@ -68,6 +84,11 @@ class Model(C.Structure):
            ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p),
            ("sched_sigmas", C.c_void_p), ("sched_timesteps", C.c_void_p),
            ("n_table", C.c_int32)]
+        # ABI 10: FP8 linear layers (all zero = bf16)
+        + [("fp8", C.c_int32)]
+        + [(n + "_q", C.c_void_p) for n, _ in FP8_MODEL_LINEARS]
+        + [(n + "_s", C.c_void_p) for n, _ in FP8_MODEL_LINEARS]
+        + [("layers_fp8_host", C.POINTER(LayerFp8))]
     )
 
 
@@ -154,6 +175,9 @@ SIGNATURES = {
     "sf_last_error": (C.c_char_p, []),
     "sf_gemm_bf16": (C.c_int, [C.POINTER(GemmArgs), _vp]),
     "sf_small_linear": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sf_quantize_fp8": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sf_gemm_fp8": (C.c_int, [C.POINTER(GemmArgs), _vp, _i, _vp, _vp]),
+    "sf_small_linear_fp8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "sf_sinusoid_embedding": (C.c_int, [_vp, _i, _vp, _i, _i, _vp]),
     "sf_layernorm_modulate": (C.c_int, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
     "sf_layernorm_affine": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),

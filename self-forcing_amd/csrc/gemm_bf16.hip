@@ -13,6 +13,15 @@
 // bank-conflict free.  The MFMA is issued as D = W_frag x X_frag (operands swapped) so that each
 // lane ends up with 4 CONSECUTIVE output columns of one row: 8-byte bf16x4 stores/loads in the
 // epilogue instead of 2-byte scattered ones.
+//
+// FP8 (sf_gemm_fp8): every structure below is also instantiated with F8 = true for e4m3 operands on the block-scaled
+// MFMA v_mfma_scale_f32_16x16x128_f8f6f4 (E8M0 scales fixed at 127 = 2^0; the per-tensor scales are applied in the
+// epilogue: out = epi(acc * (a_scale[segment(m)] * w_scale[n]) + bias[n])).  A 128-deep fp8 k-tile is 128 bytes per row
+// -- exactly the bf16 kernels' 64-deep k-tile -- so the launcher hands the kernels K, lda and ldw in 2-byte units and
+// the LDS layout, the swizzle, the LDS-DMA pieces and the stages carry over byte for byte.  The lane fragments of the
+// two bf16 sub-steps (16-byte chunks kq and 4 + kq of a row) together are the 32 bytes of one scaled-MFMA operand;
+// A and W use the same lane -> k map, so every k is paired with itself.  One scaled MFMA (2x the bf16 rate, 4x the
+// depth) replaces the two bf16 MFMAs of a 16 x 16 tile: the cycles per k-tile and the phase schedule stay as they are.
 #include <type_traits>
 #include "sf_common.h"
 #include "../../include/sf_hip.h"
@@ -38,6 +47,9 @@ struct GemmP {
   int M, N, K, lda, ldw, ldo, ldr;
   int tiles_m, tiles_n;
   long a_bs, w_bs, o_bs, r_bs;   // batch strides (elements; o_bs in floats for SF_EPI_F32); batch index = blockIdx.y
+  const float* a_scale;          // F8 only: fp32 per row segment (segment(m) = m / rows_per_seg)
+  const float* w_scale;          // F8 only: fp32 [N]
+  int rows_per_seg;
 };
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -45,6 +57,35 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 
 __device__ __forceinline__ void glds16(const bf16_t* src, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_wave_base, 16, 0, 0);
+}
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+
+// One 16 x 16 x 128 e4m3 product: (w0 | w1) and (x0 | x1) are the fragments of a row's chunks kq and 4 + kq (see the
+// header).  Operands swapped as in the bf16 MFMAs (D = W_frag x X_frag).  Format codes 0 / 0 = e4m3 for both.
+__device__ __forceinline__ f32x4 mfma_f8(const bf16x8& w0, const bf16x8& w1, const bf16x8& x0, const bf16x8& x1, const f32x4& acc) {
+  const i32x8 wv = __builtin_shufflevector(__builtin_bit_cast(i32x4, w0), __builtin_bit_cast(i32x4, w1), 0, 1, 2, 3, 4, 5, 6, 7);
+  const i32x8 xv = __builtin_shufflevector(__builtin_bit_cast(i32x4, x0), __builtin_bit_cast(i32x4, x1), 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wv, xv, acc, 0, 0, 0, 127, 0, 127);
+}
+
+// F8: the per-tensor scales, acc *= a_scale[segment(m)] * w_scale[n], on the lane's (mt, nt) pieces (rows
+// m_base + 16 mt + (lane & 15), columns n_base + 16 nt + 4 (lane >> 4) .. + 3) before any epilogue.  Indices are
+// clamped: pieces outside the output are computed and never stored.
+template <int MT>
+__device__ __forceinline__ void fp8_scale_acc(const GemmP& p, f32x4 (&acc)[MT][4], int m_base, int n_base, int lane) {
+  f32x4 ws[4];
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) ws[nt] = *reinterpret_cast<const f32x4*>(p.w_scale + min(n_base + nt * 16 + (lane >> 4) * 4, p.N - 4));
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const float sa = p.a_scale[min(m_base + mt * 16 + (lane & 15), p.M - 1) / p.rows_per_seg];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[mt][nt][j] = acc[mt][nt][j] * (sa * ws[nt][j]);
+  }
 }
 
 // Epilogue arithmetic on the 4 consecutive output columns a lane owns of row m: bias, GELU, gate, residual.
@@ -196,7 +237,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmP& p, f32x4 (&acc)[M
   }
 }
 
-template <int EPI>
+template <int EPI, bool F8>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(GemmP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -280,6 +321,29 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(GemmP p) {
     const int kn = min(kt + 1, nk - 1) * BK;
     char* sbase = smem + (cur ^ 1) * STAGE_BYTES + wave * 4096;
     bf16x8 xf0[4], wf0[4], xf1[4], wf1[4];
+    if constexpr (F8) {
+      // fp8: a scaled MFMA needs both halves of its k-tile, so all 16 fragments are read first; then eight slices of
+      // {2 MFMAs, ONE LDS-DMA request} as above
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        xf0[t] = *reinterpret_cast<const bf16x8*>(buf + x_row_off + t * 2048 + coff0);
+        wf0[t] = *reinterpret_cast<const bf16x8*>(buf + w_row_off + t * 2048 + coff0);
+        xf1[t] = *reinterpret_cast<const bf16x8*>(buf + x_row_off + t * 2048 + coff1);
+        wf1[t] = *reinterpret_cast<const bf16x8*>(buf + w_row_off + t * 2048 + coff1);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int mt = i >> 1, nt0 = (i & 1) * 2;
+        acc[mt][nt0] = mfma_f8(wf0[nt0], wf1[nt0], xf0[mt], xf1[mt], acc[mt][nt0]);
+        acc[mt][nt0 + 1] = mfma_f8(wf0[nt0 + 1], wf1[nt0 + 1], xf0[mt], xf1[mt], acc[mt][nt0 + 1]);
+        if (i < 4) glds16(a_src[i] + kn, sbase + i * 1024);
+        else glds16(w_src[i - 4] + kn, sbase + TILE_BYTES + (i - 4) * 1024);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      __syncthreads();
+      continue;
+    }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       xf0[t] = *reinterpret_cast<const bf16x8*>(buf + x_row_off + t * 2048 + coff0);
@@ -310,6 +374,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(GemmP p) {
   }
 
   // ---- epilogue: lane holds out[m][n .. n+3] for (mt, nt)
+  if constexpr (F8) fp8_scale_acc<4>(p, acc, m0 + wr * 64, n0 + wc * 64, lane);
   const int mrow = m0 + wr * 64 + (lane & 15);
   const int ncol = n0 + wc * 64 + (lane >> 4) * 4;
   if (EPI != SF_EPI_F32 && (p.N & 7) == 0 && (p.ldo & 7) == 0)   // (the k-loop's last __syncthreads has released the stages)
@@ -379,7 +444,7 @@ struct PPCfg {
   static constexpr int PA = (2 * MT + 7) / 8;       // LDS-DMA pieces (8 rows x 128 B) per wave per A half-tile (2 MT pieces over 8 waves)
 };
 
-template <int EPI, int MT>
+template <int EPI, int MT, bool F8>
 __global__ __launch_bounds__(PP_THREADS) void gemm_pp_kernel(GemmP p) {
   using Cfg = PPCfg<MT>;
   constexpr int BMp = Cfg::BM, PA = Cfg::PA;
@@ -470,13 +535,21 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp_kernel(GemmP p) {
   auto cluster = [&](auto qc, int c0) {             // one quarter: HQA / HQB row tiles x 2 column tiles x 2 sub-steps of 32
     constexpr int q = decltype(qc)::value, NQ = q == 0 ? HQA : HQB;
     __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+    if constexpr (F8) {
 #pragma unroll
       for (int mt = 0; mt < NQ; ++mt)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
-          acc[q * HQA + mt][c0 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[c0 + nt][ks], af[mt][ks], acc[q * HQA + mt][c0 + nt], 0, 0, 0);
+          acc[q * HQA + mt][c0 + nt] = mfma_f8(bfr[c0 + nt][0], bfr[c0 + nt][1], af[mt][0], af[mt][1], acc[q * HQA + mt][c0 + nt]);
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int mt = 0; mt < NQ; ++mt)
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt)
+            acc[q * HQA + mt][c0 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[c0 + nt][ks], af[mt][ks], acc[q * HQA + mt][c0 + nt], 0, 0, 0);
+    }
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -536,6 +609,7 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp_kernel(GemmP p) {
 
   // ---- epilogue (no LDS-DMA is in flight, every fragment read is retired: the stages are free)
   const int m_base = m0 + grp * (BMp / 2), n_base = n0 + wc * 64;
+  if constexpr (F8) fp8_scale_acc<MT>(p, acc, m_base, n_base, lane);
   if ((p.N & 7) == 0 && (p.ldo & 7) == 0)
     gemm_epilogue_lds<EPI, MT>(p, acc, m_base, n_base, smem + wave * (MT * 2048), lane);
   else
@@ -559,7 +633,7 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp_kernel(GemmP p) {
 constexpr int PP2_A = 128 * 128, PP2_B = 256 * 128;      // bytes per k-tile
 constexpr int PP2_LDS = 3 * (PP2_A + PP2_B);             // 144 KiB
 
-template <int EPI>
+template <int EPI, bool F8>
 __global__ __launch_bounds__(PP_THREADS) void gemm_pp2_kernel(GemmP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -629,13 +703,21 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp2_kernel(GemmP p) {
   };
   auto cluster = [&](int c0) {
     __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+    if constexpr (F8) {
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
-          acc[mt][c0 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[c0 + nt][ks], af[mt][ks], acc[mt][c0 + nt], 0, 0, 0);
+          acc[mt][c0 + nt] = mfma_f8(bfr[c0 + nt][0], bfr[c0 + nt][1], af[mt][0], af[mt][1], acc[mt][c0 + nt]);
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt)
+            acc[mt][c0 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[c0 + nt][ks], af[mt][ks], acc[mt][c0 + nt], 0, 0, 0);
+    }
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -678,136 +760,168 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp2_kernel(GemmP p) {
   if (grp == 0) __builtin_amdgcn_s_barrier();
 
   const int m_base = m0 + grp * 64, n_base = n0 + wc * 64;
+  if constexpr (F8) fp8_scale_acc<4>(p, acc, m_base, n_base, lane);
   if ((p.N & 7) == 0 && (p.ldo & 7) == 0)
     gemm_epilogue_lds<EPI, 4>(p, acc, m_base, n_base, smem + wave * 8192, lane);
   else
     gemm_epilogue<EPI, 4>(p, acc, m_base + (lane & 15), n_base + (lane >> 4) * 4);
 }
 
-template <int EPI>
+template <int EPI, bool F8>
 int launch_pp2(GemmP& p, hipStream_t s) {
   static bool attr = false;   // one-time registration of the kernel's LDS size (idempotent)
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp2_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, PP2_LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp2_kernel<EPI, F8>), hipFuncAttributeMaxDynamicSharedMemorySize, PP2_LDS);
     attr = true;
   }
   p.tiles_m = (p.M + 127) / 128;
   p.tiles_n = (p.N + 255) / 256;
-  hipLaunchKernelGGL((gemm_pp2_kernel<EPI>), dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), PP2_LDS, s, p);
+  hipLaunchKernelGGL((gemm_pp2_kernel<EPI, F8>), dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), PP2_LDS, s, p);
   return 0;
 }
 
+template <bool F8>
 int launch_pp2_epi(GemmP& p, int epilogue, hipStream_t s) {
   switch (epilogue) {
-    case SF_EPI_BIAS: return launch_pp2<SF_EPI_BIAS>(p, s);
-    case SF_EPI_BIAS_GELU: return launch_pp2<SF_EPI_BIAS_GELU>(p, s);
-    case SF_EPI_BIAS_RESID: return launch_pp2<SF_EPI_BIAS_RESID>(p, s);
-    case SF_EPI_BIAS_GATE_RESID: return launch_pp2<SF_EPI_BIAS_GATE_RESID>(p, s);
+    case SF_EPI_BIAS: return launch_pp2<SF_EPI_BIAS, F8>(p, s);
+    case SF_EPI_BIAS_GELU: return launch_pp2<SF_EPI_BIAS_GELU, F8>(p, s);
+    case SF_EPI_BIAS_RESID: return launch_pp2<SF_EPI_BIAS_RESID, F8>(p, s);
+    case SF_EPI_BIAS_GATE_RESID: return launch_pp2<SF_EPI_BIAS_GATE_RESID, F8>(p, s);
     default: return -1;
   }
 }
 
-template <int EPI, int MT>
+template <int EPI, int MT, bool F8>
 int launch_pp(GemmP& p, hipStream_t s) {
   using Cfg = PPCfg<MT>;
   static bool attr = false;   // one-time registration of the kernel's LDS size (idempotent)
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<EPI, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<EPI, MT, F8>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
     attr = true;
   }
   p.tiles_m = (p.M + Cfg::BM - 1) / Cfg::BM;
   p.tiles_n = (p.N + 255) / 256;
-  hipLaunchKernelGGL((gemm_pp_kernel<EPI, MT>), dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), Cfg::LDS, s, p);
+  hipLaunchKernelGGL((gemm_pp_kernel<EPI, MT, F8>), dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), Cfg::LDS, s, p);
   return 0;
 }
 
-template <int MT>
+template <int MT, bool F8>
 int launch_pp_epi(GemmP& p, int epilogue, hipStream_t s) {
   switch (epilogue) {
-    case SF_EPI_BIAS: return launch_pp<SF_EPI_BIAS, MT>(p, s);
-    case SF_EPI_BIAS_GELU: return launch_pp<SF_EPI_BIAS_GELU, MT>(p, s);
-    case SF_EPI_BIAS_RESID: return launch_pp<SF_EPI_BIAS_RESID, MT>(p, s);
-    case SF_EPI_BIAS_GATE_RESID: return launch_pp<SF_EPI_BIAS_GATE_RESID, MT>(p, s);
+    case SF_EPI_BIAS: return launch_pp<SF_EPI_BIAS, MT, F8>(p, s);
+    case SF_EPI_BIAS_GELU: return launch_pp<SF_EPI_BIAS_GELU, MT, F8>(p, s);
+    case SF_EPI_BIAS_RESID: return launch_pp<SF_EPI_BIAS_RESID, MT, F8>(p, s);
+    case SF_EPI_BIAS_GATE_RESID: return launch_pp<SF_EPI_BIAS_GATE_RESID, MT, F8>(p, s);
     default: return -1;
   }
+}
+
+// Argument checks shared by both entry points (`name` prefixes the messages); K is in elements of the operand type.
+int check_args(const sf_gemm_args* a, const char* name, int bk) {
+  SF_CHECK(a != nullptr, "%s: null args", name);
+  SF_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "%s: empty problem M=%d N=%d K=%d", name, a->M, a->N, a->K);
+  SF_CHECK(a->K % bk == 0, "%s: K=%d must be a multiple of %d", name, a->K, bk);
+  SF_CHECK(a->N % 4 == 0, "%s: N=%d must be a multiple of 4", name, a->N);
+  SF_CHECK(a->lda % (bk / 8) == 0 && a->ldw % (bk / 8) == 0 && a->ldo % 4 == 0, "%s: lda/ldw must be multiples of %d, ldo of 4", name, bk / 8);
+  SF_CHECK(a->lda >= a->K && a->ldw >= a->K && a->ldo >= a->N, "%s: leading dimension too small", name);
+  SF_CHECK(a->a && a->w && a->out, "%s: null tensor", name);
+  SF_CHECK(((uintptr_t)a->a % 16 == 0) && ((uintptr_t)a->w % 16 == 0) && ((uintptr_t)a->out % 8 == 0), "%s: misaligned tensor", name);
+  if (a->epilogue == SF_EPI_BIAS_RESID || a->epilogue == SF_EPI_BIAS_GATE_RESID) {
+    SF_CHECK(a->resid != nullptr && a->ldr >= a->N && a->ldr % 4 == 0, "%s: residual epilogue needs resid/ldr", name);
+  }
+  if (a->epilogue == SF_EPI_BIAS_GATE_RESID) {
+    SF_CHECK(a->gate_mod && a->gate_e0 && a->rows_per_group > 0, "%s: gate epilogue needs gate_mod/gate_e0/rows_per_group", name);
+  }
+  SF_CHECK(a->structure >= SF_GEMM_AUTO && a->structure <= SF_GEMM_PP192, "%s: unknown structure %d", name, a->structure);
+  return 0;
+}
+
+// The structure choice (identical for both operand types: the same tiles, rounds and k-tile counts) and the launch.
+// p.K / p.lda / p.ldw are in 2-byte units (= fp8 pairs for F8), so nk = p.K / BK is the k-tile count either way.
+template <bool F8>
+int run_gemm(const sf_gemm_args* a, GemmP& p, const char* name, hipStream_t s) {
+  int st = a->structure;
+  const int nk = p.K / BK;
+  const bool pp_ok = a->batch <= 1 && a->epilogue != SF_EPI_F32 && nk >= 2;
+  if (st == SF_GEMM_AUTO) {
+    // Large problems take the ping-pong structure with the row tile (256 / 224 / 192 / 128 rows x 256 columns, one
+    // workgroup per CU) that needs the least time for its ROUNDS of 256 workgroups: rounds x (a tile's k-loop, which
+    // scales with its rows, slightly worse for the smaller register tiles, + a fixed prologue share).  Everything
+    // else: 128 x 128 tiles, two per CU.
+    st = SF_GEMM_T128;
+    if (pp_ok && a->M >= 1024 && a->N >= 1024 && a->K >= 512) {
+      static const struct { int st, rows; double rel; } cand[] = {
+          {SF_GEMM_PP256, 256, 1.00}, {SF_GEMM_PP224, 224, 1.02}, {SF_GEMM_PP192, 192, 1.05}, {SF_GEMM_PP128, 128, 1.14}};
+      const long tn = (a->N + 255) / 256;
+      double best = 1e30;
+      for (const auto& c : cand) {
+        const long tiles = (long)((a->M + c.rows - 1) / c.rows) * tn;
+        const double cost = (double)((tiles + 255) / 256) * (c.rows / 256.0 * c.rel + 0.04);
+        if (cost < best - 1e-9) { best = cost; st = c.st; }
+      }
+    }
+  }
+  const bool is_pp = st == SF_GEMM_PP256 || st == SF_GEMM_PP224 || st == SF_GEMM_PP192 || st == SF_GEMM_PP128;
+  if (is_pp && !pp_ok) st = SF_GEMM_T128;
+  else if (is_pp) {
+    const int rc = st == SF_GEMM_PP256 ? launch_pp_epi<8, F8>(p, a->epilogue, s)
+                 : st == SF_GEMM_PP224 ? launch_pp_epi<7, F8>(p, a->epilogue, s)
+                 : st == SF_GEMM_PP192 ? launch_pp_epi<6, F8>(p, a->epilogue, s) : launch_pp2_epi<F8>(p, a->epilogue, s);
+    SF_CHECK(rc == 0, "%s: unknown epilogue %d", name, a->epilogue);
+    SF_HIP_LAUNCH_CHECK(name);
+    return 0;
+  }
+  const int batch = a->batch > 1 ? a->batch : 1;
+  p.a_bs = a->a_bstride; p.w_bs = a->w_bstride; p.o_bs = a->o_bstride; p.r_bs = a->r_bstride;
+  SF_CHECK(batch == 1 || (a->a_bstride % 8 == 0 && a->w_bstride % 8 == 0 && a->o_bstride % 4 == 0 && a->r_bstride % 4 == 0),
+           "%s: batch strides must keep 16-byte (operands) / 8-byte (output) alignment", name);
+  const dim3 grid(p.tiles_m * p.tiles_n, batch), block(GEMM_THREADS);
+  switch (a->epilogue) {
+    case SF_EPI_BIAS: hipLaunchKernelGGL((gemm_bf16_kernel<SF_EPI_BIAS, F8>), grid, block, GEMM_LDS, s, p); break;
+    case SF_EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_bf16_kernel<SF_EPI_BIAS_GELU, F8>), grid, block, GEMM_LDS, s, p); break;
+    case SF_EPI_BIAS_RESID: hipLaunchKernelGGL((gemm_bf16_kernel<SF_EPI_BIAS_RESID, F8>), grid, block, GEMM_LDS, s, p); break;
+    case SF_EPI_BIAS_GATE_RESID: hipLaunchKernelGGL((gemm_bf16_kernel<SF_EPI_BIAS_GATE_RESID, F8>), grid, block, GEMM_LDS, s, p); break;
+    case SF_EPI_F32:
+      if constexpr (F8) {
+        SF_CHECK(false, "%s: the raw fp32 epilogue is bf16-only", name);
+      } else {
+        SF_CHECK((uintptr_t)a->out % 16 == 0, "%s: fp32 output must be 16-byte aligned", name);
+        hipLaunchKernelGGL((gemm_bf16_kernel<SF_EPI_F32, false>), grid, block, GEMM_LDS, s, p);
+      }
+      break;
+    default: SF_CHECK(false, "%s: unknown epilogue %d", name, a->epilogue);
+  }
+  SF_HIP_LAUNCH_CHECK(name);
+  return 0;
+}
+
+void fill_params(const sf_gemm_args* a, GemmP& p, int unit) {   // unit: operand elements per 2-byte unit (1 bf16, 2 fp8)
+  p.a = (const bf16_t*)a->a; p.w = (const bf16_t*)a->w; p.bias = (const bf16_t*)a->bias;
+  p.out = (bf16_t*)a->out; p.resid = (const bf16_t*)a->resid;
+  p.gate_mod = (const bf16_t*)a->gate_mod; p.gate_e0 = (const bf16_t*)a->gate_e0;
+  p.gate_group_stride = a->gate_group_stride; p.rows_per_group = a->rows_per_group;
+  p.M = a->M; p.N = a->N; p.K = a->K / unit; p.lda = a->lda / unit; p.ldw = a->ldw / unit; p.ldo = a->ldo; p.ldr = a->ldr;
+  p.tiles_n = (a->N + BN - 1) / BN;
+  p.tiles_m = (a->M + BM - 1) / BM;
+  p.a_scale = nullptr; p.w_scale = nullptr; p.rows_per_seg = 1;
 }
 
 }  // namespace
 
 extern "C" int sf_gemm_bf16(const sf_gemm_args* a, void* stream) {
-  SF_CHECK(a != nullptr, "sf_gemm_bf16: null args");
-  SF_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "sf_gemm_bf16: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
-  SF_CHECK(a->K % BK == 0, "sf_gemm_bf16: K=%d must be a multiple of %d", a->K, BK);
-  SF_CHECK(a->N % 4 == 0, "sf_gemm_bf16: N=%d must be a multiple of 4", a->N);
-  SF_CHECK(a->lda % 8 == 0 && a->ldw % 8 == 0 && a->ldo % 4 == 0, "sf_gemm_bf16: lda/ldw must be multiples of 8, ldo of 4");
-  SF_CHECK(a->lda >= a->K && a->ldw >= a->K && a->ldo >= a->N, "sf_gemm_bf16: leading dimension too small");
-  SF_CHECK(a->a && a->w && a->out, "sf_gemm_bf16: null tensor");
-  SF_CHECK(((uintptr_t)a->a % 16 == 0) && ((uintptr_t)a->w % 16 == 0) && ((uintptr_t)a->out % 8 == 0),
-           "sf_gemm_bf16: misaligned tensor");
-  if (a->epilogue == SF_EPI_BIAS_RESID || a->epilogue == SF_EPI_BIAS_GATE_RESID) {
-    SF_CHECK(a->resid != nullptr && a->ldr >= a->N && a->ldr % 4 == 0, "sf_gemm_bf16: residual epilogue needs resid/ldr");
-  }
-  if (a->epilogue == SF_EPI_BIAS_GATE_RESID) {
-    SF_CHECK(a->gate_mod && a->gate_e0 && a->rows_per_group > 0, "sf_gemm_bf16: gate epilogue needs gate_mod/gate_e0/rows_per_group");
-  }
+  if (const int rc = check_args(a, "sf_gemm_bf16", BK)) return rc;
   GemmP p;
-  p.a = (const bf16_t*)a->a; p.w = (const bf16_t*)a->w; p.bias = (const bf16_t*)a->bias;
-  p.out = (bf16_t*)a->out; p.resid = (const bf16_t*)a->resid;
-  p.gate_mod = (const bf16_t*)a->gate_mod; p.gate_e0 = (const bf16_t*)a->gate_e0;
-  p.gate_group_stride = a->gate_group_stride; p.rows_per_group = a->rows_per_group;
-  p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldw = a->ldw; p.ldo = a->ldo; p.ldr = a->ldr;
-  p.tiles_n = (a->N + BN - 1) / BN;
-  hipStream_t s = (hipStream_t)stream;
-  p.tiles_m = (a->M + BM - 1) / BM;
-  SF_CHECK(a->structure >= SF_GEMM_AUTO && a->structure <= SF_GEMM_PP192, "sf_gemm_bf16: unknown structure %d", a->structure);
-  {
-    int st = a->structure;
-    const bool pp_ok = a->batch <= 1 && a->epilogue != SF_EPI_F32 && a->K >= 2 * BK;
-    if (st == SF_GEMM_AUTO) {
-      // Large problems take the ping-pong structure with the row tile (256 / 224 / 192 / 128 rows x 256 columns, one
-      // workgroup per CU) that needs the least time for its ROUNDS of 256 workgroups: rounds x (a tile's k-loop, which
-      // scales with its rows, slightly worse for the smaller register tiles, + a fixed prologue share).  Everything
-      // else: 128 x 128 tiles, two per CU.
-      st = SF_GEMM_T128;
-      if (pp_ok && a->M >= 1024 && a->N >= 1024 && a->K >= 512) {
-        static const struct { int st, rows; double rel; } cand[] = {
-            {SF_GEMM_PP256, 256, 1.00}, {SF_GEMM_PP224, 224, 1.02}, {SF_GEMM_PP192, 192, 1.05}, {SF_GEMM_PP128, 128, 1.14}};
-        const long tn = (a->N + 255) / 256;
-        double best = 1e30;
-        for (const auto& c : cand) {
-          const long tiles = (long)((a->M + c.rows - 1) / c.rows) * tn;
-          const double cost = (double)((tiles + 255) / 256) * (c.rows / 256.0 * c.rel + 0.04);
-          if (cost < best - 1e-9) { best = cost; st = c.st; }
-        }
-      }
-    }
-    const bool is_pp = st == SF_GEMM_PP256 || st == SF_GEMM_PP224 || st == SF_GEMM_PP192 || st == SF_GEMM_PP128;
-    if (is_pp && !pp_ok) st = SF_GEMM_T128;
-    else if (is_pp) {
-      const int rc = st == SF_GEMM_PP256 ? launch_pp_epi<8>(p, a->epilogue, s)
-                   : st == SF_GEMM_PP224 ? launch_pp_epi<7>(p, a->epilogue, s)
-                   : st == SF_GEMM_PP192 ? launch_pp_epi<6>(p, a->epilogue, s) : launch_pp2_epi(p, a->epilogue, s);
-      SF_CHECK(rc == 0, "sf_gemm_bf16: unknown epilogue %d", a->epilogue);
-      SF_HIP_LAUNCH_CHECK("sf_gemm_bf16");
-      return 0;
-    }
-  }
-  const int batch = a->batch > 1 ? a->batch : 1;
-  p.a_bs = a->a_bstride; p.w_bs = a->w_bstride; p.o_bs = a->o_bstride; p.r_bs = a->r_bstride;
-  SF_CHECK(batch == 1 || (a->a_bstride % 8 == 0 && a->w_bstride % 8 == 0 && a->o_bstride % 4 == 0 && a->r_bstride % 4 == 0),
-           "sf_gemm_bf16: batch strides must keep 16-byte (operands) / 8-byte (output) alignment");
-  const dim3 grid(p.tiles_m * p.tiles_n, batch), block(GEMM_THREADS);
-  switch (a->epilogue) {
-    case SF_EPI_BIAS: hipLaunchKernelGGL(gemm_bf16_kernel<SF_EPI_BIAS>, grid, block, GEMM_LDS, s, p); break;
-    case SF_EPI_BIAS_GELU: hipLaunchKernelGGL(gemm_bf16_kernel<SF_EPI_BIAS_GELU>, grid, block, GEMM_LDS, s, p); break;
-    case SF_EPI_BIAS_RESID: hipLaunchKernelGGL(gemm_bf16_kernel<SF_EPI_BIAS_RESID>, grid, block, GEMM_LDS, s, p); break;
-    case SF_EPI_BIAS_GATE_RESID: hipLaunchKernelGGL(gemm_bf16_kernel<SF_EPI_BIAS_GATE_RESID>, grid, block, GEMM_LDS, s, p); break;
-    case SF_EPI_F32:
-      SF_CHECK((uintptr_t)a->out % 16 == 0, "sf_gemm_bf16: fp32 output must be 16-byte aligned");
-      hipLaunchKernelGGL(gemm_bf16_kernel<SF_EPI_F32>, grid, block, GEMM_LDS, s, p);
-      break;
-    default: SF_CHECK(false, "sf_gemm_bf16: unknown epilogue %d", a->epilogue);
-  }
-  SF_HIP_LAUNCH_CHECK("sf_gemm_bf16");
-  return 0;
+  fill_params(a, p, 1);
+  return run_gemm<false>(a, p, "sf_gemm_bf16", (hipStream_t)stream);
+}
+
+extern "C" int sf_gemm_fp8(const sf_gemm_args* a, const float* a_scale, int rows_per_segment, const float* w_scale, void* stream) {
+  if (const int rc = check_args(a, "sf_gemm_fp8", 2 * BK)) return rc;
+  SF_CHECK(a->batch <= 1, "sf_gemm_fp8: batched products are bf16-only");
+  SF_CHECK(a_scale && w_scale && rows_per_segment > 0, "sf_gemm_fp8: needs a_scale, w_scale and rows_per_segment > 0");
+  SF_CHECK((uintptr_t)w_scale % 16 == 0, "sf_gemm_fp8: w_scale must be 16-byte aligned");
+  GemmP p;
+  fill_params(a, p, 2);
+  p.a_scale = a_scale; p.w_scale = w_scale; p.rows_per_seg = rows_per_segment;
+  return run_gemm<true>(a, p, "sf_gemm_fp8", (hipStream_t)stream);
 }

@@ -1,7 +1,8 @@
 """Device-resident causal Wan DiT: weights in HBM + the C-ABI descriptor of one forward.
 
 Counterpart of `CausalWanModel` (wan/modules/causal_model.py:370-513) for the KV-cached
-inference branch only (`_forward_inference`, :725-893).  It owns the bf16 weights, laid out for
+inference branch only (`_forward_inference`, :725-893).  It owns the bf16 weights (with `fp8=True`: e4m3 copies of
+every Linear's weight plus fp32 column scales instead, fp8.py), laid out for
 the kernels (q|k|v and cross k|v projection matrices stacked so that one GEMM serves three / two
 Linears), the fp32 RoPE tables and a per-shape workspace; `forward` is ONE C call
 (`sf_dit_forward`) that enqueues every kernel of the pass on the current stream.
@@ -13,7 +14,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import _lib, torch_ops
+from . import _lib, fp8 as fp8_recipe, torch_ops
 from .kvcache import CachePlan
 from .weights import WanShape, param_shapes
 
@@ -39,7 +40,7 @@ class CausalWanModel:
     from `generator.model`: `local_attn_size`, `sink_size`, `num_frame_per_block`, plus the shape."""
 
     def __init__(self, shape: WanShape, state_dict: Dict[str, Tensor], device, sched_sigmas: Tensor,
-                 sched_timesteps: Tensor):
+                 sched_timesteps: Tensor, fp8: bool = False):
         if shape.head_dim != 128:
             raise ValueError(f"head_dim must be 128 (dim={shape.dim}, heads={shape.num_heads})")
         if tuple(shape.patch_size) != (1, 2, 2):
@@ -51,6 +52,8 @@ class CausalWanModel:
         self.sink_size = shape.sink_size
         self.num_frame_per_block = 1
         self.independent_first_frame = False
+        self.fp8 = bool(fp8)
+        self.fp8_weights: Dict[str, tuple] = {}
         self._keep: List[Tensor] = []      # every device tensor the C struct points into
         self._workspaces: Dict[tuple, Tensor] = {}
         self._load(state_dict, sched_sigmas, sched_timesteps)
@@ -62,6 +65,15 @@ class CausalWanModel:
         self._keep.append(t)
         return t
 
+    def _dev8(self, name: str, parts: List[Tensor]):
+        """FP8: the reference Linears `parts` (stacked along N) -> device e4m3 weight + fp32 column scales, quantised on
+        the device from the bf16 weights the reference model holds (fp8.py); only these copies are kept
+        (`fp8_weights[name]` = (q, s))."""
+        q, s = fp8_recipe.quantize_weight([p.detach().to(device=self.device, dtype=torch.bfloat16) for p in parts])
+        self._keep += [q, s]
+        self.fp8_weights[name] = (q, s)
+        return C.c_void_p(q.data_ptr()), C.c_void_p(s.data_ptr())
+
     def _load(self, sd: Dict[str, Tensor], sigmas: Tensor, timesteps: Tensor) -> None:
         need = param_shapes(self.shape)
         missing = [k for k in need if k not in sd]
@@ -71,7 +83,13 @@ class CausalWanModel:
             if tuple(sd[k].shape) != tuple(shp):
                 raise ValueError(f"{k}: expected shape {shp}, got {tuple(sd[k].shape)}")
         s = self.shape
+        if self.fp8:   # every K an fp8 GEMM sees must be a multiple of its 128-deep k-tile: fail here, not at the first call
+            for name, k in (("text_embedding.0", s.text_dim), ("the dim-wide Linears", s.dim), ("ffn.2", s.ffn_dim)):
+                fp8_recipe.check_k(name, k)
+            if "pose_proj.weight" in sd:
+                fp8_recipe.check_k("pose_proj", sd["pose_proj.weight"].shape[1])
         m = _lib.Model()
+        m.fp8 = int(self.fp8)
         m.dim, m.ffn_dim, m.num_heads, m.num_layers = s.dim, s.ffn_dim, s.num_heads, s.num_layers
         m.in_dim, m.out_dim, m.freq_dim, m.text_dim, m.text_len = s.in_dim, s.out_dim, s.freq_dim, s.text_dim, s.text_len
         m.eps = s.eps
@@ -80,37 +98,56 @@ class CausalWanModel:
         m.patch_b = P(self._dev(sd["patch_embedding.bias"]))
         for dst, src in (("text0", "text_embedding.0"), ("text2", "text_embedding.2"), ("time0", "time_embedding.0"),
                          ("time2", "time_embedding.2"), ("tproj", "time_projection.1"), ("head", "head.head")):
-            setattr(m, dst + "_w", P(self._dev(sd[src + ".weight"])))
+            if self.fp8:
+                q8, s8 = self._dev8(src, [sd[src + ".weight"]])
+                setattr(m, dst + "_q", q8)
+                setattr(m, dst + "_s", s8)
+            else:
+                setattr(m, dst + "_w", P(self._dev(sd[src + ".weight"])))
             setattr(m, dst + "_b", P(self._dev(sd[src + ".bias"])))
         m.head_mod = P(self._dev(sd["head.modulation"].reshape(2, s.dim)))
         from .weights import POSE_DIM
         self.has_pose_proj = "pose_proj.weight" in sd
         if self.has_pose_proj:   # optional: the fork's pose conditioning (Linear(5120, dim), causal_model.py:493-503)
-            m.pose_w, m.pose_b = P(self._dev(sd["pose_proj.weight"])), P(self._dev(sd["pose_proj.bias"]))
+            if self.fp8:
+                m.pose_q, m.pose_s = self._dev8("pose_proj", [sd["pose_proj.weight"]])
+            else:
+                m.pose_w = P(self._dev(sd["pose_proj.weight"]))
+            m.pose_b = P(self._dev(sd["pose_proj.bias"]))
             m.pose_dim = sd["pose_proj.weight"].shape[1]
         elif s.dim == POSE_DIM:  # `pose_proj = nn.Identity()` for dim-5120 models (:500-501): no weights, x += add_condition
             m.pose_dim = s.dim
         self.accepts_pose = self.has_pose_proj or s.dim == POSE_DIM
         layers = (_lib.LayerWeights * s.num_layers)()
+        layers8 = (_lib.LayerFp8 * s.num_layers)()
         for i in range(s.num_layers):
             p = f"blocks.{i}."
             lw = layers[i]
+            if self.fp8:   # the Linears' weights in e4m3 only; biases, norms and modulation stay bf16 (below)
+                for dst, srcs in _lib.FP8_LAYER_LINEARS:
+                    q8, s8 = self._dev8(p + dst, [sd[p + src + ".weight"] for src in srcs])
+                    setattr(layers8[i], dst + "_q", q8)
+                    setattr(layers8[i], dst + "_s", s8)
             lw.modulation = P(self._dev(sd[p + "modulation"].reshape(6, s.dim)))
             lw.norm3_w, lw.norm3_b = P(self._dev(sd[p + "norm3.weight"])), P(self._dev(sd[p + "norm3.bias"]))
             sa, ca = p + "self_attn.", p + "cross_attn."
-            lw.qkv_w = P(self._dev(torch.cat([sd[sa + "q.weight"], sd[sa + "k.weight"], sd[sa + "v.weight"]], 0)))
+            W = (lambda t: None) if self.fp8 else (lambda t: P(self._dev(t)))  # noqa: E731  (bf16 Linear weights: bf16 mode only)
+            lw.qkv_w = W(torch.cat([sd[sa + "q.weight"], sd[sa + "k.weight"], sd[sa + "v.weight"]], 0))
             lw.qkv_b = P(self._dev(torch.cat([sd[sa + "q.bias"], sd[sa + "k.bias"], sd[sa + "v.bias"]], 0)))
             lw.norm_q_w, lw.norm_k_w = P(self._dev(sd[sa + "norm_q.weight"])), P(self._dev(sd[sa + "norm_k.weight"]))
-            lw.o_w, lw.o_b = P(self._dev(sd[sa + "o.weight"])), P(self._dev(sd[sa + "o.bias"]))
-            lw.cq_w, lw.cq_b = P(self._dev(sd[ca + "q.weight"])), P(self._dev(sd[ca + "q.bias"]))
-            lw.ckv_w = P(self._dev(torch.cat([sd[ca + "k.weight"], sd[ca + "v.weight"]], 0)))
+            lw.o_w, lw.o_b = W(sd[sa + "o.weight"]), P(self._dev(sd[sa + "o.bias"]))
+            lw.cq_w, lw.cq_b = W(sd[ca + "q.weight"]), P(self._dev(sd[ca + "q.bias"]))
+            lw.ckv_w = W(torch.cat([sd[ca + "k.weight"], sd[ca + "v.weight"]], 0))
             lw.ckv_b = P(self._dev(torch.cat([sd[ca + "k.bias"], sd[ca + "v.bias"]], 0)))
             lw.cnorm_q_w, lw.cnorm_k_w = P(self._dev(sd[ca + "norm_q.weight"])), P(self._dev(sd[ca + "norm_k.weight"]))
-            lw.co_w, lw.co_b = P(self._dev(sd[ca + "o.weight"])), P(self._dev(sd[ca + "o.bias"]))
-            lw.ffn0_w, lw.ffn0_b = P(self._dev(sd[p + "ffn.0.weight"])), P(self._dev(sd[p + "ffn.0.bias"]))
-            lw.ffn2_w, lw.ffn2_b = P(self._dev(sd[p + "ffn.2.weight"])), P(self._dev(sd[p + "ffn.2.bias"]))
+            lw.co_w, lw.co_b = W(sd[ca + "o.weight"]), P(self._dev(sd[ca + "o.bias"]))
+            lw.ffn0_w, lw.ffn0_b = W(sd[p + "ffn.0.weight"]), P(self._dev(sd[p + "ffn.0.bias"]))
+            lw.ffn2_w, lw.ffn2_b = W(sd[p + "ffn.2.weight"]), P(self._dev(sd[p + "ffn.2.bias"]))
         self._layers = layers
         m.layers_host = C.cast(layers, C.POINTER(_lib.LayerWeights))
+        if self.fp8:
+            self._layers8 = layers8
+            m.layers_fp8_host = C.cast(layers8, C.POINTER(_lib.LayerFp8))
         cos, sin = rope_tables(s.head_dim)
         self.rope_cos = cos.to(self.device)
         self.rope_sin = sin.to(self.device)

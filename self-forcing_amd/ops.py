@@ -36,9 +36,12 @@ def _bf16(t: Tensor, name: str) -> Tensor:
     return t
 
 
-def _rows(t: Tensor, name: str) -> Tensor:
+def _rows(t: Tensor, name: str, dtype=torch.bfloat16) -> Tensor:
     """2-D view with unit inner stride."""
-    _bf16(t, name)
+    if not t.is_cuda:
+        raise ValueError(f"{name}: expected a CUDA/ROCm tensor (the HIP path has no CPU fallback)")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: expected {dtype}, got {t.dtype}")
     if t.dim() != 2 or t.stride(1) != 1:
         raise ValueError(f"{name}: expected a 2-D tensor with contiguous rows, got shape {tuple(t.shape)} strides {t.stride()}")
     return t
@@ -75,6 +78,39 @@ def small_linear(x: Tensor, w: Tensor, bias: Optional[Tensor], act_in=None, act_
     out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
     check(lib().sf_small_linear(x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K,
                                 _ACT[act_in], _ACT[act_out], stream_handle()), "sf_small_linear")
+    return out
+
+
+def quantize_fp8(x: Tensor, rows_per_segment: Optional[int] = None):
+    """x [M, K] bf16 -> (e4m3fn [M, K], fp32 scales [segments]): one dynamic scale per `rows_per_segment` rows (default:
+    all of them), fp8.py's recipe on the device."""
+    x = _rows(x, "x")
+    return torch.ops.sf_hip.quantize_fp8(x, rows_per_segment or x.shape[0])
+
+
+def gemm_fp8(a: Tensor, a_scale: Tensor, w: Tensor, w_scale: Tensor, bias: Optional[Tensor] = None, epilogue: str = "bias",
+             resid: Optional[Tensor] = None, gate_mod: Optional[Tensor] = None, gate_e0: Optional[Tensor] = None,
+             rows_per_group: int = 1, rows_per_segment: Optional[int] = None, structure: str = "auto") -> Tensor:
+    """out[M,N] = epi((a @ w^T) * (a_scale[m // rows_per_segment] * w_scale[n]) + bias) on e4m3fn operands; w_scale is
+    fp32 [N] (a scalar tensor is expanded)."""
+    a, w = _rows(a, "a", torch.float8_e4m3fn), _rows(w, "w", torch.float8_e4m3fn)
+    if w_scale.numel() == 1:
+        w_scale = w_scale.reshape(1).expand(w.shape[0])
+    return torch.ops.sf_hip.gemm_fp8(a, a_scale.float().contiguous(), rows_per_segment or a.shape[0], w, w_scale.float().contiguous(), bias,
+                                     _EPI[epilogue], resid, gate_mod, gate_e0, rows_per_group, _lib.GEMM_STRUCTURES[structure])
+
+
+def small_linear_fp8(x: Tensor, w_q: Tensor, w_scale: Tensor, bias: Optional[Tensor], act_in=None, act_out=None,
+                     rows_per_segment: Optional[int] = None) -> Tensor:
+    """small_linear on e4m3fn weights [N, K] with fp32 column scales [N]; the activation is quantised in the kernel,
+    one scale per `rows_per_segment` rows (default: all)."""
+    x, w_q = _rows(x, "x").contiguous(), _rows(w_q, "w_q", torch.float8_e4m3fn).contiguous()
+    M, K = x.shape
+    N = w_q.shape[0]
+    w_scale = (w_scale.reshape(1).expand(N) if w_scale.numel() == 1 else w_scale).float().contiguous()
+    out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+    check(lib().sf_small_linear_fp8(x.data_ptr(), w_q.data_ptr(), w_scale.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K,
+                                    rows_per_segment or M, _ACT[act_in], _ACT[act_out], stream_handle()), "sf_small_linear_fp8")
     return out
 
 

@@ -11,6 +11,8 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::attention(q, k, v, structure) -> out
     sf_hip::gemm(a, w, bias?, epilogue, resid?, gate_mod?, gate_e0?, rows_per_group, structure) -> out
     sf_hip::gemm_out(out!, a, w, ...) -> ()                         (caller-provided / aliased output)
+    sf_hip::quantize_fp8(x, rows_per_segment) -> (q e4m3fn, scales)  (FP8 linear layers, fp8.py)
+    sf_hip::gemm_fp8(a, a_scale, rows_per_segment, w, w_scale, bias?, epilogue, resid?, gate_mod?, gate_e0?, rows_per_group, structure) -> out
     sf_hip::lincomb(tensors[], coefs[]) -> out ;  sf_hip::lincomb_out(out!, tensors[], coefs[]) -> ()
     sf_hip::add_noise(x0, eps, timestep, sigmas, timesteps) -> out
     sf_hip::dit_forward(model, noisy, timestep, prompt_embeds?, add_condition?, k_cache![], v_cache![], ck_cache![],
@@ -143,6 +145,75 @@ def _(a, w, bias, epilogue, resid, gate_mod, gate_e0, rows_per_group, structure)
 def gemm_out(out: Tensor, a: Tensor, w: Tensor, bias: Optional[Tensor], epilogue: int, resid: Optional[Tensor],
              gate_mod: Optional[Tensor], gate_e0: Optional[Tensor], rows_per_group: int, structure: int) -> None:
     _gemm_launch(out, a, w, bias, epilogue, resid, gate_mod, gate_e0, rows_per_group, structure)
+
+
+# ------------------------------------------------------------------------------------------ FP8 (fp8.py)
+def _segments(M: int, rows_per_segment: int) -> int:
+    if rows_per_segment <= 0:
+        raise ValueError("rows_per_segment must be positive")
+    return (M + rows_per_segment - 1) // rows_per_segment
+
+
+@custom_op(f"{NAMESPACE}::quantize_fp8", mutates_args=())
+def quantize_fp8(x: Tensor, rows_per_segment: int) -> Tuple[Tensor, Tensor]:
+    """x [M, K] bf16 -> (e4m3fn [M, K], fp32 scales [segments]) by sf_quantize_fp8."""
+    _need_gpu(x, "x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"quantize_fp8: x must be 2-D with contiguous rows, got {tuple(x.shape)} {x.stride()}")
+    M, K = x.shape
+    segs = _segments(M, rows_per_segment)
+    q = torch.empty(M, K, dtype=torch.float8_e4m3fn, device=x.device)
+    buf = torch.empty(segs * (1 + _lib.FP8_AMAX_PARTS), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().sf_quantize_fp8(x.data_ptr(), x.stride(0), M, K, rows_per_segment, q.data_ptr(), buf.data_ptr(), _stream(x)),
+               "sf_quantize_fp8")
+    return q, buf[:segs].clone()
+
+
+@quantize_fp8.register_fake
+def _(x, rows_per_segment):
+    return x.new_empty(x.shape, dtype=torch.float8_e4m3fn), x.new_empty((_segments(x.shape[0], rows_per_segment),), dtype=torch.float32)
+
+
+@custom_op(f"{NAMESPACE}::gemm_fp8", mutates_args=())
+def gemm_fp8(a: Tensor, a_scale: Tensor, rows_per_segment: int, w: Tensor, w_scale: Tensor, bias: Optional[Tensor], epilogue: int,
+             resid: Optional[Tensor], gate_mod: Optional[Tensor], gate_e0: Optional[Tensor], rows_per_group: int, structure: int) -> Tensor:
+    """out = epi(acc * (a_scale[m // rows_per_segment] * w_scale[n]) + bias[n]) with e4m3fn a [M, K], w [N, K] (sf_gemm_fp8)."""
+    for n, t in (("a", a), ("w", w)):
+        _need_gpu(t, n, torch.float8_e4m3fn)
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"gemm_fp8: {n} must be 2-D with contiguous rows, got {tuple(t.shape)} {t.stride()}")
+    M, K = a.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError(f"gemm_fp8: a is [{M},{K}] but w is {tuple(w.shape)}")
+    for n, t, size in (("a_scale", a_scale, _segments(M, rows_per_segment)), ("w_scale", w_scale, N)):
+        _need_gpu(t, n, torch.float32)
+        if t.dim() != 1 or t.numel() != size or not t.is_contiguous():
+            raise ValueError(f"gemm_fp8: {n} must be a contiguous fp32 vector of {size}, got {tuple(t.shape)}")
+    out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
+    g = _lib.GemmArgs()
+    g.a, g.w, g.bias, g.out = a.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr()
+    g.M, g.N, g.K = M, N, K
+    g.lda, g.ldw, g.ldo = a.stride(0), w.stride(0), out.stride(0)
+    g.epilogue, g.rows_per_group, g.structure = epilogue, rows_per_group, structure
+    if bias is not None:
+        _need_gpu(bias, "bias")
+    if resid is not None:
+        _need_gpu(resid, "resid")
+        g.resid, g.ldr = resid.data_ptr(), resid.stride(0)
+    if gate_mod is not None:
+        _need_gpu(gate_mod, "gate_mod")
+        g.gate_mod = gate_mod.data_ptr()
+    if gate_e0 is not None:
+        _need_gpu(gate_e0, "gate_e0")
+        g.gate_e0, g.gate_group_stride = gate_e0.data_ptr(), gate_e0.stride(0)
+    _lib.check(_lib.lib().sf_gemm_fp8(g, a_scale.data_ptr(), rows_per_segment, w_scale.data_ptr(), _stream(a)), "sf_gemm_fp8")
+    return out
+
+
+@gemm_fp8.register_fake
+def _(a, a_scale, rows_per_segment, w, w_scale, bias, epilogue, resid, gate_mod, gate_e0, rows_per_group, structure):
+    return a.new_empty((a.shape[0], w.shape[0]), dtype=torch.bfloat16)
 
 
 # ------------------------------------------------------------------------------------------ lincomb / add_noise

@@ -17,6 +17,10 @@ Differences from the reference, all deliberate:
   * the attention window for `local_attn_size == -1` is the cache capacity and for rolling mode
     `local_attn_size * frame_seqlen` of the CURRENT latent size (the reference hard-codes
     32760 / `local_attn_size * 1560`, causal_model.py:77, which is only right for 60x104 latents);
+  * FP8 linear layers (`fp8=True`, keyword-only): the counterpart of the reference's optional
+    `quantize_(transformer, Float8DynamicActivationFloat8WeightConfig(granularity=PerTensor()))` (demo.py:277-283) --
+    every nn.Linear runs as an e4m3 GEMM with a per-tensor weight scale and a dynamic per-pass activation scale
+    (fp8.py, DESIGN.md section 11); off by default, and with it off nothing changes;
   * the non-cached branches (`kv_cache is None`, classify_mode, clean_x teacher forcing) and the i2v inputs
     (`clip_feature`, `y`) raise NotImplementedError; the fork's pose tokens (`add_condition`) are supported.
 """
@@ -57,7 +61,7 @@ class WanDiffusionWrapper(torch.nn.Module):
                  lora_alpha: float = 1.0, lora_dropout: float = 0.0, lora_targets: Optional[List[str]] = None,
                  lora_path: Optional[str] = None, *, shape: Optional[WanShape] = None,
                  state_dict: Optional[Dict[str, Tensor]] = None, random_init_seed: Optional[int] = None,
-                 device="cuda"):
+                 device="cuda", fp8: bool = False):
         super().__init__()
         if not is_causal:
             raise NotImplementedError("only the causal (KV-cached) generator is implemented on this path")
@@ -88,7 +92,7 @@ class WanDiffusionWrapper(torch.nn.Module):
         self.uniform_timestep = not is_causal
         self.scheduler = FlowMatchScheduler(shift=timestep_shift, sigma_min=0.0, extra_one_step=True)
         self.scheduler.set_timesteps(1000, training=True)
-        self.model = CausalWanModel(shape, state_dict, device, self.scheduler.sigmas, self.scheduler.timesteps)
+        self.model = CausalWanModel(shape, state_dict, device, self.scheduler.sigmas, self.scheduler.timesteps, fp8=fp8)
         self.seq_len = 32760
         self._evict_scratch: Optional[Tensor] = None
         self._init_throttle()
@@ -132,6 +136,11 @@ class WanDiffusionWrapper(torch.nn.Module):
         other._evict_scratch = None
         other._init_throttle()
         return other
+
+    @property
+    def fp8(self) -> bool:
+        """True when the generator's Linears run in FP8 (constructed with fp8=True)."""
+        return self.model.fp8
 
     # --- reference API ------------------------------------------------------------------------
     def get_scheduler(self):
