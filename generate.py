@@ -10,7 +10,8 @@ Keeps the reference's semantics: OmegaConf-style merge of a default config under
 `DistributedSampler(shuffle=False, drop_last=True)` prompt sharding (rank r takes r, r+W, ...),
 seed = `--seed + rank`, noise `[num_samples, num_output_frames, 16, 60, 104]` bf16 drawn per prompt,
 one barrier after set-up.  It writes LATENTS (`<idx>-<sample>.pt`) and, when a VAE is given
-(`--vae_path Wan2.1_VAE.pth`, loaded with weights_only=True, or `--vae_random_init_seed N`), the decoded
+(`--vae_path Wan2.1_VAE.pth`, loaded with weights_only=True, or `--vae_random_init_seed N`; or the TAEHV tiny
+decoder for a fast preview, `--taehv_path taew2_1.pth` / `--taehv_random_init_seed N`), the decoded
 video as a uint8 tensor [T, H, W, 3] (`<idx>-<sample>.video.pt`: what the reference hands to
 `write_video`, inference.py:186-196; no video-file writer is used here).  The umT5 encoder is
 outside this path, so embeddings are synthetic unless `--prompt_embeds` (a .pt dict prompt -> [L, 4096]
@@ -102,9 +103,16 @@ def main():
     ap.add_argument("--sampling_steps", type=int, default=0, help="multi-step sampler only: override its 50 steps")
     ap.add_argument("--vae_random_init_seed", type=int, default=None,
                     help="seeded random VAE weights instead (decoder; with --i2v the encoder too)")
+    ap.add_argument("--taehv_path", default=None,
+                    help="taew2_1.pth: decode with the TAEHV tiny decoder instead (fast preview; not with --vae_path / --vae_random_init_seed)")
+    ap.add_argument("--taehv_random_init_seed", type=int, default=None, help="seeded random TAEHV decoder weights instead")
     ap.add_argument("--fp8", action="store_true",
                     help="FP8 linear layers in the generator (the reference's enable_fp8 / torchao PerTensor quantisation)")
     a = ap.parse_args()
+    if a.taehv_path and a.taehv_random_init_seed is not None:
+        ap.error("--taehv_path and --taehv_random_init_seed are mutually exclusive")
+    if (a.taehv_path or a.taehv_random_init_seed is not None) and (a.vae_path or a.vae_random_init_seed is not None):
+        ap.error("--taehv_path / --taehv_random_init_seed choose the decoder: not together with --vae_path / --vae_random_init_seed")
 
     # inference.py:39-45: one process per GPU under torch.distributed.run, RCCL for the start / end barriers only
     from self_forcing_amd.distributed import RankGroup, env_rank_world
@@ -147,6 +155,10 @@ def main():
         vae = sfa.WanVAEWrapper(torch.load(a.vae_path, map_location="cpu", weights_only=True), device=device)
     elif a.vae_random_init_seed is not None:
         vae = sfa.WanVAEWrapper(sfa.synth_vae_state_dict(sfa.WAN_VAE, seed=a.vae_random_init_seed, encoder=a.i2v), device=device)
+    if a.taehv_path:
+        vae = sfa.TAEHVWrapper(checkpoint_path=a.taehv_path, device=device)
+    elif a.taehv_random_init_seed is not None:
+        vae = sfa.TAEHVWrapper(sfa.synth_taehv_state_dict(seed=a.taehv_random_init_seed), device=device)
     decode = not isinstance(vae, sfa.IdentityVAE)
     few_step = is_few_step(cfg)        # inference.py:62-67: few-step rollout iff the config has denoising_step_list
     if few_step:

@@ -492,6 +492,88 @@ int sf_vae_encode_frames(const sf_vae_encoder* enc, void* state, size_t state_by
                          int chunk_index, int n_chunks, int window, int history_at, float* latents_out, void* stream);
 
 /* ==========================================================================================
+ * TAEHV tiny decoder (latents -> pixels, the fast preview path): the demo's TAEHVDiffusersWrapper.decode ->
+ * TAEHV.decode_video -> apply_model_with_memblocks over TAEHV.decoder (demo.py:60-100, demo_utils/taehv.py:60-156,
+ * :181-190, :222-234).  Activations are channels-last bf16 volumes [T][H][W][C].  A MemBlock's `past` (the input of the
+ * same block for the previous frame, taehv.py:33-34, :113-120) is ONE history frame kept physically in front of the new
+ * frames of the block's input volume, so conv(cat[x, past]) is a causal convolution with two temporal taps.
+ * ========================================================================================== */
+
+/* The decoder's 3x3 convolution, fp32 accumulation on the matrix cores:
+ *   y[(t,h,w)][n] = sum_{dt<kt,dh,dw,ci} x[t+dt][(h+dh-1)>>up][(w+dw-1)>>up][ci] * w[n][((dt*3+dh)*3+dw)*Cin + ci]
+ * with zero padding in h/w.  Replaces nn.Conv2d 3x3 (taehv.py:16-17) with: the torch.cat([x, past], 1) in front of it
+ * (kt = 2: tap 0 = the previous frame with weight[:, C:], tap 1 = the frame itself with weight[:, :C]; taehv.py:34), the
+ * nn.ReLU behind it (taehv.py:28-31, :182, :189), a MemBlock's skip add + ReLU (taehv.py:34), nn.Upsample(scale_factor=2)
+ * in front of it (taehv.py:183-188; upsample = 1), TGrow's channel -> frame re-read (taehv.py:54-57; the 1x1 convolution
+ * itself is folded into w by the caller) and the demo wrapper's `* 2 - 1` with decode_to_pixel's clamp
+ * (demo.py:84-89, utils/wan_wrapper.py:113). */
+enum sf_taehv_epilogue {
+  SF_TAEHV_BIAS_RELU = 0,        /* bf16 out = relu(y + bias)                                                    */
+  SF_TAEHV_BIAS_RESID_RELU = 1,  /* bf16 out = relu(y + bias + resid[row][n])                                    */
+  SF_TAEHV_PLAIN = 2,            /* bf16 out = y            (no bias read)                                       */
+  SF_TAEHV_RELU = 3,             /* bf16 out = relu(y)      (no bias read)                                       */
+  SF_TAEHV_HEAD_F32 = 4          /* float out_f32[t][n][h][w] = 2 (y + bias) - 1, clamped to [-1, 1] when `clamp` */
+};
+
+typedef struct sf_taehv_conv_args {
+  const void* x;          /* [Tout - 1 + kt][Hin][Win][Cin], Cin % 32 == 0; kt = 2: frame 0 is the history frame  */
+  const void* w;          /* [Cout][ldw]: k = tap*Cin + ci, zero padded to ldw >= roundup(kt*9*Cin, 64)           */
+  const void* bias;       /* [Cout]; may be NULL for the bias-free epilogues                                      */
+  void* out;              /* rows of ldo channels; row = t'*H*W + h*W + w                                         */
+  const void* resid;      /* [Tout*H*W] rows of ldr channels                                                      */
+  float* out_f32;         /* SF_TAEHV_HEAD_F32 only: [Tout][Cout][H][W], Cout <= 32                               */
+  int32_t Tout, H, W;     /* output frames and frame size; the input frame is (H, W), or (H/2, W/2) with upsample */
+  int32_t Cin, Cout;
+  int32_t kt;             /* temporal taps, 1 or 2                                                                */
+  int32_t upsample;       /* 1: read the input through a nearest-neighbour 2x upsampling                          */
+  int32_t ldw, ldo, ldr;
+  int32_t tgrow;          /* 0 / 1: none; 2: channel n of frame t goes to frame t' = 2t + n / (Cout/2), channel
+                             n % (Cout/2) (bias-free epilogues only)                                              */
+  int32_t epilogue;       /* enum sf_taehv_epilogue */
+  int32_t clamp;          /* SF_TAEHV_HEAD_F32: clamp to [-1, 1]                                                  */
+} sf_taehv_conv_args;
+
+int sf_taehv_conv(const sf_taehv_conv_args* args, void* stream);
+int sf_taehv_pick_nt(int cout);   /* column tiles (of 16) per wave the launcher will use for Cout: 4, 2 or 1       */
+
+/* Latent frames -> input of decoder.1: Clamp (3 tanh(z / 3) in fp32, taehv.py:20-22) and the layout change
+ * [n][z][h][w] bf16 -> [n][h][w][c_pad] bf16 (channels z..c_pad-1 zero). */
+int sf_taehv_prepare_latent(const void* latent, void* out, int n, int z, int h, int w, int c_pad, void* stream);
+
+typedef struct sf_taehv_layer {
+  const void* w;          /* repacked [cout][ldw] as sf_taehv_conv_args.w                                         */
+  const void* bias;       /* [cout], NULL where the reference layer has none                                      */
+  int32_t cin, cout, kt, ldw;   /* cin already padded to a multiple of 32                                         */
+} sf_taehv_layer;
+
+#define SF_TAEHV_STAGES 3
+#define SF_TAEHV_BLOCKS 3
+
+typedef struct sf_taehv_model {           /* TAEHV.decoder, taehv.py:181-190 (default time / space upscale)       */
+  int32_t z_dim;                          /* 16 */
+  sf_taehv_layer in_conv;                 /* decoder.1 (z_dim -> 256), cin padded to 32                           */
+  sf_taehv_layer block[SF_TAEHV_STAGES][SF_TAEHV_BLOCKS][3];   /* MemBlock.conv.0 (kt = 2) / .2 / .4              */
+  sf_taehv_layer exit_conv[SF_TAEHV_STAGES];   /* TGrow folded into the bias-free 3x3 behind it: cout = tgrow * C' */
+  int32_t tgrow[SF_TAEHV_STAGES];         /* frames per input frame at each stage exit: 1, 2, 2                   */
+  sf_taehv_layer head;                    /* decoder.22 (64 -> 3)                                                 */
+} sf_taehv_model;
+
+/* Per-stream persistent state = the one-frame history of each of the nine MemBlock input volumes (channels-last bf16);
+ * scratch = everything else (the volumes themselves included: a call copies the nine histories in, and its last frames
+ * out), reusable by any stream that does not overlap in time.  0 = malformed arguments (sf_last_error says which). */
+size_t sf_taehv_state_bytes(const sf_taehv_model* model, int lat_h, int lat_w);
+size_t sf_taehv_scratch_bytes(const sf_taehv_model* model, int lat_h, int lat_w, int max_frames);
+/* Zero every history: the first frame's `past` is zero (taehv.py:115-116). */
+int sf_taehv_reset(const sf_taehv_model* model, void* state, size_t state_bytes, int lat_h, int lat_w, void* stream);
+/* n_frames latent frames [n_frames][z][lat_h][lat_w] bf16, as the generator emits them, -> 4 n_frames pixel frames
+ * [4 n_frames][3][8 lat_h][8 lat_w] float32 = decode_video(...) * 2 - 1 (demo.py:84-89), clamped to [-1, 1] when `clamp`.
+ * Nothing is trimmed: the caller drops the first 3 frames after a reset (demo.py:432-433).  Bit-identical to n_frames
+ * single-frame calls.  The library keeps no state of its own. */
+int sf_taehv_decode_frames(const sf_taehv_model* model, void* state, size_t state_bytes, void* scratch,
+                           size_t scratch_bytes, const void* latent_frames, int lat_h, int lat_w, int n_frames,
+                           int clamp, float* pixels_out, void* stream);
+
+/* ==========================================================================================
  * umT5 text encoder (prompt token ids -> prompt embeddings): WanTextEncoder.forward after its tokenizer
  * (utils/wan_wrapper.py:40-55) -> T5Encoder.forward (wan/modules/t5.py:299-312).  Runs once per prompt.
  * ========================================================================================== */

@@ -18,6 +18,9 @@ from .concurrent import RolloutPool  # noqa: F401
 from .vae_weights import (VaeShape, WAN_VAE, VAE_REDUCED, synth_vae_state_dict, vae_param_shapes,  # noqa: F401
                           encoder_param_shapes, vae_encode_flops)
 from .vae import WanVAEWrapper, WanVAEDecoder, WanVAEEncoder, repack_conv  # noqa: F401
+from .taehv_weights import taehv_param_shapes, synth_taehv_state_dict, taehv_decode_flops  # noqa: F401
+from .taehv import TAEHVWrapper, TAEHVDecoder  # noqa: F401
+from . import taehv_weights  # noqa: F401
 from .t5_weights import T5Shape, UMT5_XXL, T5_REDUCED, synth_t5_state_dict, t5_param_shapes  # noqa: F401
 from .text_encoder import WanTextEncoder, UMT5Encoder, relative_position_buckets  # noqa: F401
 from . import unipc  # noqa: F401
@@ -31,5 +34,6 @@ __all__ = ["WanShape", "WAN_1_3B", "WAN_14B", "WAN_REDUCED", "NAMED_SHAPES", "sy
            "FlowMatchScheduler", "WanDiffusionWrapper", "CausalInferencePipeline",
            "SyntheticTextEncoder", "FixedTextEncoder", "IdentityVAE", "RolloutPool", "ops", "torch_ops",
            "VaeShape", "WAN_VAE", "VAE_REDUCED", "synth_vae_state_dict", "vae_param_shapes", "WanVAEWrapper",
+           "TAEHVWrapper", "TAEHVDecoder", "taehv_param_shapes", "synth_taehv_state_dict", "taehv_decode_flops",
            "WanVAEDecoder", "repack_conv", "T5Shape", "UMT5_XXL", "T5_REDUCED", "synth_t5_state_dict", "t5_param_shapes",
            "WanTextEncoder", "UMT5Encoder", "relative_position_buckets", "FlowUniPCMultistepScheduler", "CausalDiffusionInferencePipeline"]

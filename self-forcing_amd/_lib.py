@@ -29,6 +29,9 @@ EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_GATE_RESID, EPI_F32 = 0, 1, 2,
 # enum sf_conv_epilogue
 CONV_BIAS, CONV_BIAS_RESID, CONV_BIAS_CLAMP_F32 = 0, 1, 2
 VAE_MAX_STAGES = 4
+# enum sf_taehv_epilogue
+TAEHV_EPILOGUES = {"bias_relu": 0, "bias_resid_relu": 1, "plain": 2, "relu": 3, "head_f32": 4}
+TAEHV_STAGES, TAEHV_BLOCKS = 3, 3
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 # enum sf_attn_structure / sf_gemm_structure
 ATTN_STRUCTURES = {"auto": 0, "r64": 1, "w8": 2, "w4": 3}
@@ -158,6 +161,20 @@ class VaeEncoder(C.Structure):
     ]
 
 
+class TaehvConvArgs(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("x", "w", "bias", "out", "resid", "out_f32")]
+                + [(n, C.c_int32) for n in ("Tout", "H", "W", "Cin", "Cout", "kt", "upsample", "ldw", "ldo", "ldr", "tgrow", "epilogue", "clamp")])
+
+
+class TaehvLayer(C.Structure):
+    _fields_ = [("w", C.c_void_p), ("bias", C.c_void_p)] + [(n, C.c_int32) for n in ("cin", "cout", "kt", "ldw")]
+
+
+class TaehvModel(C.Structure):
+    _fields_ = [("z_dim", C.c_int32), ("in_conv", TaehvLayer), ("block", ((TaehvLayer * 3) * TAEHV_BLOCKS) * TAEHV_STAGES),
+                ("exit_conv", TaehvLayer * TAEHV_STAGES), ("tgrow", C.c_int32 * TAEHV_STAGES), ("head", TaehvLayer)]
+
+
 class T5Layer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("norm1_w", "qk_w", "v_w", "o_w", "norm2_w", "gate_w", "fc1_w", "fc2_w", "pos_emb")]
 
@@ -210,6 +227,13 @@ SIGNATURES = {
     "sf_vae_encode_reset": (C.c_int, [C.POINTER(VaeEncoder), _vp, _sz, _i, _i, _i, _vp]),
     "sf_vae_encode_frames": (C.c_int, [C.POINTER(VaeEncoder), _vp, _sz, _vp, _sz, _vp, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _vp,
                                        _vp]),
+    "sf_taehv_conv": (C.c_int, [C.POINTER(TaehvConvArgs), _vp]),
+    "sf_taehv_pick_nt": (C.c_int, [_i]),
+    "sf_taehv_prepare_latent": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sf_taehv_state_bytes": (C.c_size_t, [C.POINTER(TaehvModel), _i, _i]),
+    "sf_taehv_scratch_bytes": (C.c_size_t, [C.POINTER(TaehvModel), _i, _i, _i]),
+    "sf_taehv_reset": (C.c_int, [C.POINTER(TaehvModel), _vp, _sz, _i, _i, _vp]),
+    "sf_taehv_decode_frames": (C.c_int, [C.POINTER(TaehvModel), _vp, _sz, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sf_embedding_gather": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_t5_softmax_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_mul_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),

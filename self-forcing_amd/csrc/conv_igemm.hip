@@ -28,6 +28,7 @@
 // NT in {1,2,3,4,6} covers Cout = 3 (head) ... 96, 192, 384, 768 without padding waste.
 #include <cstdlib>
 #include "sf_common.h"
+#include "lds_dma.h"
 #include "../../include/sf_hip.h"
 
 namespace {
@@ -52,13 +53,6 @@ struct ConvP {
   int tiles_m, tiles_n;
   unsigned x_bytes;   // size of the input volume the gather may touch (range check of the LDS-DMA)
 };
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_wave_base, 16, 0, 0);
-}
 
 template <int NT, int EPI>
 __global__ __launch_bounds__(CONV_THREADS, 2) void conv_igemm_kernel(ConvP p) {
@@ -116,20 +110,9 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_igemm_kernel(ConvP p) {
     w_src[j] = p.w + (long)n * p.ldw + c * 8;
   }
   // range-checked view of the input volume (offsets past x_bytes read as zero)
-  u32x4 x_srd;
-  {
-    const unsigned long long a64 = (unsigned long long)p.x;
-    x_srd[0] = __builtin_amdgcn_readfirstlane((unsigned)a64);
-    x_srd[1] = __builtin_amdgcn_readfirstlane((unsigned)(a64 >> 32) & 0xFFFFu);
-    x_srd[2] = __builtin_amdgcn_readfirstlane(p.x_bytes);
-    x_srd[3] = 0x00020000u;
-  }
+  const u32x4 x_srd = lds_dma_srd(p.x, p.x_bytes);
   const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
-  auto dma_a = [&](unsigned voff, unsigned lds_addr) __attribute__((always_inline)) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 4\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_addr), "v"(voff), "s"(x_srd) : "memory");
-  };
+  auto dma_a = [&](unsigned voff, unsigned lds_addr) __attribute__((always_inline)) { lds_dma16_checked(x_srd, voff, lds_addr); };
 
   // slice cursor of the NEXT stage to issue: slice 2 kt = (tap, cc), cc counting 32-channel groups
   int tap = 0, cc = 0;

@@ -276,6 +276,45 @@ def conv_igemm(x: Tensor, w_packed: Tensor, bias: Tensor, kernel, t_out: int, up
     return out
 
 
+def taehv_conv(x: Tensor, w_packed: Tensor, bias: Optional[Tensor], kt: int, t_out: int, epilogue: str = "bias_relu", upsample: bool = False,
+               resid: Optional[Tensor] = None, tgrow: int = 1, clamp: bool = False, cin: Optional[int] = None) -> Tensor:
+    """The TAEHV decoder's 3x3 convolution (sf_taehv_conv).  x [t_out - 1 + kt, Hin, Win, Cin] channels-last (kt = 2: the
+    history frame in front); w_packed from `taehv_weights.repack_taehv_conv`; epilogue one of `_lib.TAEHV_EPILOGUES`.
+    Returns bf16 [tgrow * t_out, H, W, Cout / tgrow], or float32 [t_out, Cout, H, W] = 2 y - 1 for "head_f32"."""
+    _bf16(x, "x"), _bf16(w_packed, "w_packed")
+    if bias is not None:
+        _bf16(bias, "bias")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("taehv_conv: x must be a contiguous [T, H, W, C] volume")
+    if epilogue not in _lib.TAEHV_EPILOGUES:
+        raise ValueError(f"taehv_conv: unknown epilogue {epilogue!r}")
+    tin, hin, win, c = x.shape
+    if t_out - 1 + kt > tin:
+        raise ValueError(f"taehv_conv: {tin} input frames do not cover {t_out} output frames (kt={kt})")
+    cout = w_packed.shape[0]
+    H, W = (2 * hin, 2 * win) if upsample else (hin, win)
+    a = _lib.TaehvConvArgs()
+    a.x, a.w, a.bias = x.data_ptr(), w_packed.data_ptr(), None if bias is None else bias.data_ptr()
+    a.Tout, a.H, a.W, a.Cin, a.Cout, a.kt = t_out, H, W, cin or c, cout, kt
+    a.upsample, a.ldw, a.tgrow, a.epilogue, a.clamp = int(upsample), w_packed.stride(0), tgrow, _lib.TAEHV_EPILOGUES[epilogue], int(clamp)
+    if epilogue == "head_f32":
+        out = torch.empty(t_out, cout, H, W, dtype=torch.float32, device=x.device)
+        a.out_f32 = out.data_ptr()
+    else:
+        if tgrow < 1 or cout % tgrow:
+            raise ValueError(f"taehv_conv: tgrow={tgrow} does not divide Cout={cout}")
+        co = cout // tgrow
+        out = torch.empty(tgrow * t_out, H, W, co, dtype=torch.bfloat16, device=x.device)
+        a.out, a.ldo = out.data_ptr(), co
+        if resid is not None:
+            _bf16(resid, "resid")
+            if tuple(resid.shape) != tuple(out.shape) or not resid.is_contiguous():
+                raise ValueError("taehv_conv: resid must match the output volume")
+            a.resid, a.ldr = resid.data_ptr(), cout
+    check(lib().sf_taehv_conv(a, stream_handle()), "sf_taehv_conv")
+    return out
+
+
 def rmsnorm_silu_cl(x: Tensor, gamma: Tensor, silu: bool = True) -> Tensor:
     """VAE RMS_norm over the last (channel) dim of a contiguous channels-last tensor, optional SiLU."""
     _bf16(x, "x"), _bf16(gamma, "gamma")

@@ -21,6 +21,7 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
                              plan[7], kv_index!?, global_end) -> (flow, x0)        (context pass of chunk k + first pass of chunk k + 1)
     sf_hip::vae_decode_frames(model, state!, scratch!, z, out!, h, w, window_frames, frame_index, window, history_at) -> ()
     sf_hip::vae_encode_frames(model, state!, scratch!, pixels, out!, H, W, window_frames, chunk_index, window, history_at) -> ()
+    sf_hip::taehv_decode_frames(model, state!, scratch!, z, out!, h, w, clamp) -> ()
     sf_hip::t5_encode(model, ids, mask, buckets, workspace!) -> out
 
 Models (weights + C descriptors) are Python objects that own device memory; operators take an integer HANDLE from
@@ -488,6 +489,30 @@ def vae_decode_frames(model: int, state: Tensor, scratch: Tensor, z: Tensor, out
                "sf_vae_decode_frames")
 
 
+@custom_op(f"{NAMESPACE}::taehv_decode_frames", mutates_args=("state", "scratch", "out"))
+def taehv_decode_frames(model: int, state: Tensor, scratch: Tensor, z: Tensor, out: Tensor, h: int, w: int, clamp: bool) -> None:
+    """Consecutive latent frames z [F, 16, h, w] -> 4 F pixel frames written to the front of `out` (float32
+    [T, 3, 8h, 8w] = decode_video * 2 - 1, clamped to [-1, 1] when `clamp`); `state` carries the one-frame memory of the
+    nine MemBlocks between calls (sf_taehv_decode_frames in include/sf_hip.h; `TAEHVDecoder.cached_decode` drives it)."""
+    m = _model(model)
+    _need_gpu(z, "z")
+    _need_gpu(out, "out", torch.float32)
+    if z.dim() != 4 or not z.is_contiguous() or not out.is_contiguous():
+        raise ValueError("taehv_decode_frames: contiguous z [F, z_dim, h, w] and out expected")
+    zc = m.cmodel.z_dim
+    if tuple(z.shape[1:]) != (zc, h, w):
+        raise ValueError(f"taehv_decode_frames: z must be [F, {zc}, {h}, {w}], got {tuple(z.shape)}")
+    for name, t in (("state", state), ("scratch", scratch)):       # their element counts are passed on as BYTE counts
+        if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError(f"taehv_decode_frames: {name} must be a contiguous CUDA uint8 tensor")
+    need = 4 * z.shape[0] * 3 * (8 * h) * (8 * w)
+    if out.numel() < need:
+        raise ValueError(f"taehv_decode_frames: out holds {out.numel()} floats, {4 * z.shape[0]} frames of 3 x {8 * h} x {8 * w} need {need}")
+    _lib.check(_lib.lib().sf_taehv_decode_frames(C.byref(m.cmodel), state.data_ptr(), state.numel(), scratch.data_ptr(), scratch.numel(),
+                                                 z.data_ptr(), h, w, z.shape[0], int(clamp), out.data_ptr(), _stream(z)),
+               "sf_taehv_decode_frames")
+
+
 @custom_op(f"{NAMESPACE}::vae_encode_frames", mutates_args=("state", "scratch", "out"))
 def vae_encode_frames(model: int, state: Tensor, scratch: Tensor, pixels: Tensor, out: Tensor, H: int, W: int, window_frames: int,
                       chunk_index: int, window: int, history_at: int) -> None:
@@ -547,4 +572,5 @@ def _(model, ids, mask, buckets, workspace):
     return ids.new_empty((ids.shape[0], ids.shape[1], _model(model).shape.dim), dtype=torch.bfloat16)
 
 
-OPS = ("attention", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "vae_encode_frames", "t5_encode")
+OPS = ("attention", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "vae_encode_frames", "taehv_decode_frames",
+       "t5_encode")
