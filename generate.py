@@ -19,6 +19,11 @@ tensor) is given.  A config WITHOUT `denoising_step_list` selects the multi-step
 (`CausalDiffusionInferencePipeline`), as inference.py:62-67 does; it needs `num_train_timestep`, `timestep_shift`,
 `guidance_scale` and `negative_prompt`.
 
+`--pose_path` (multi-step configs only) drives the generation with a pose clip: a `.pt` (dict) or `.npy` (pickled dict)
+holding `dwpose_data` [3, F, H, W] and `random_ref_dwpose` [H, W, 3] in 0..255, embedded on the GPU by `PoseEmbedder`
+with the weights of `--pose_weights_path` (a file with `dwpose_embedding.*` / `randomref_embedding_pose.*` tensors) or
+`--pose_random_init_seed N`.  Rendering skeletons and reading video files are outside this driver.
+
 `--i2v` (inference.py:83-90, 136-149) reads `--data_path` as a TextImagePairDataset directory -- one
 `target_crop_info_<ratio>.json` listing `file_name` / `caption` entries, images under `<ratio>/` --, encodes each
 image with the VAE encoder (so it needs a VAE with encoder weights: `--vae_path`, or `--vae_random_init_seed`) as the
@@ -82,6 +87,19 @@ def load_image(path: str, height: int, width: int) -> torch.Tensor:
     return (x - 0.5) / 0.5
 
 
+def load_pose(path: str):
+    """(dwpose_data [3, F, H, W], random_ref_dwpose [H, W, 3]) from a .pt dict or a .npy holding a pickled dict."""
+    if path.endswith(".npy"):
+        import numpy as np
+        d = np.load(path, allow_pickle=True).item()
+    else:
+        d = torch.load(path, map_location="cpu", weights_only=True)
+    missing = [k for k in ("dwpose_data", "random_ref_dwpose") if k not in d]
+    if missing:
+        raise SystemExit(f"{path}: no {' / '.join(missing)} in the pose file")
+    return tuple(torch.as_tensor(d[k]) for k in ("dwpose_data", "random_ref_dwpose"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_path", required=True)
@@ -108,7 +126,15 @@ def main():
     ap.add_argument("--taehv_random_init_seed", type=int, default=None, help="seeded random TAEHV decoder weights instead")
     ap.add_argument("--fp8", action="store_true",
                     help="FP8 linear layers in the generator (the reference's enable_fp8 / torchao PerTensor quantisation)")
+    ap.add_argument("--pose_path", default=None, help=".pt / .npy dict with dwpose_data [3, F, H, W] and random_ref_dwpose [H, W, 3] (multi-step sampler)")
+    ap.add_argument("--pose_weights_path", default=None, help="pose embedding weights (dwpose_embedding.* / randomref_embedding_pose.*)")
+    ap.add_argument("--pose_random_init_seed", type=int, default=None, help="seeded random pose embedding weights instead")
     a = ap.parse_args()
+    if a.pose_path or a.pose_weights_path or a.pose_random_init_seed is not None:
+        if not a.pose_path or (a.pose_weights_path is None) == (a.pose_random_init_seed is None):
+            ap.error("pose conditioning needs --pose_path and exactly one of --pose_weights_path / --pose_random_init_seed")
+        if is_few_step(load_config(a.config_path, a.default_config_path)):
+            ap.error("--pose_path needs a multi-step config (one without denoising_step_list): the few-step pipeline takes no pose input")
     if a.taehv_path and a.taehv_random_init_seed is not None:
         ap.error("--taehv_path and --taehv_random_init_seed are mutually exclusive")
     if (a.taehv_path or a.taehv_random_init_seed is not None) and (a.vae_path or a.vae_random_init_seed is not None):
@@ -167,7 +193,12 @@ def main():
         for key in ("num_train_timestep", "timestep_shift", "guidance_scale", "negative_prompt"):
             if key not in cfg:
                 raise SystemExit(f"config has neither denoising_step_list nor {key}: cannot build a sampler from it")
-        pipe = sfa.CausalDiffusionInferencePipeline(cfg, device, generator=gen, text_encoder=enc, vae=vae)
+        pose_embedder = None
+        if a.pose_path:
+            weights = a.pose_weights_path if a.pose_weights_path else sfa.synth_pose_state_dict(seed=a.pose_random_init_seed)
+            pose_embedder = sfa.PoseEmbedder(weights, device=device, strict=cfg.get("pose_weights_strict", True))
+            pose_data = load_pose(a.pose_path)
+        pipe = sfa.CausalDiffusionInferencePipeline(cfg, device, generator=gen, text_encoder=enc, vae=vae, pose_embedder=pose_embedder)
         if a.sampling_steps:
             pipe.sampling_steps = a.sampling_steps
 
@@ -189,7 +220,8 @@ def main():
             video, latents = pipe.inference(noise=noise, text_prompts=[prompts[idx]] * a.num_samples, initial_latent=initial,
                                             return_latents=True)
         else:
-            video, latents = pipe.inference(noise, [prompts[idx]] * a.num_samples, None, None, None, initial_latent=initial,
+            dwpose, ref_pose = pose_data if a.pose_path else (None, None)
+            video, latents = pipe.inference(noise, [prompts[idx]] * a.num_samples, None, dwpose, ref_pose, initial_latent=initial,
                                             return_latents=True)
         for s in range(a.num_samples):
             torch.save(latents[s].cpu(), os.path.join(a.output_folder, f"{idx}-{s}.pt"))

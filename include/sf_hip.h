@@ -574,6 +574,83 @@ int sf_taehv_decode_frames(const sf_taehv_model* model, void* state, size_t stat
                            int clamp, float* pixels_out, void* stream);
 
 /* ==========================================================================================
+ * Pose front end (DWPose frames -> pose tokens): `dwpose_embedding` and `randomref_embedding_pose` of the many-step
+ * sampler (pipeline/causal_diffusion_inference.py:87-122) with their input transform (:337-343).  Runs once per clip.
+ * Activations are channels-last bf16 volumes [T][H][W][C] with C = 8 (the three input channels, stored padded with
+ * zeros) or 16.  Every volume must stay under 4 GiB (32-bit byte offsets); larger ones are refused.
+ * ========================================================================================== */
+
+enum sf_pose_dtype { SF_POSE_U8 = 0, SF_POSE_F32 = 1, SF_POSE_BF16 = 2 };
+
+/* Output size of the stacks' layers along one axis: kernel 3 with padding 1, or kernel 2 without padding
+ * (nn.Conv3d / nn.Conv2d arithmetic, causal_diffusion_inference.py:90-102, :110-120). */
+int sf_pose_out_size(int n, int kernel, int stride);
+
+/* One convolution of the stacks, fp32 accumulation on the matrix cores, fp32 bias, optional SiLU, one rounding:
+ *   out[(t,h,w)][n] = act(bias[n] + sum_{dt<kt,dh,dw,ci} x[t*st-pt+dt][h*ss-1+dh][w*ss-1+dw][ci] * w[n][((dt*3+dh)*3+dw)*Cin+ci])
+ * with symmetric zero padding (pt = 1 for kt = 3, else 0).  Replaces nn.Conv3d 3x3x3 / nn.Conv2d 3x3 (kt = 1, T = 1) and
+ * the nn.SiLU behind it (causal_diffusion_inference.py:90-101, :110-120).  Supported: (Cin, kt, stride_t, stride_s) in
+ * (8|16, 3, 1, 1), (16, 3, 1, 2), (16, 3, 2, 2), (8|16, 1, 1, 1), (16, 1, 1, 2); Cout <= 16, or <= 32 for (16, 1, 1, 2). */
+typedef struct sf_pose_conv_args {
+  const void* x;          /* [T][H][W][Cin] bf16                                                                  */
+  const void* w;          /* [16 or 32 rows][ldw] bf16: k = tap*Cin + ci, zero padded to ldw >= roundup(kt*9*Cin, 32);
+                             rows past Cout zero                                                                  */
+  const float* bias;      /* fp32 [16 or 32], zero past Cout                                                      */
+  void* out;              /* [Tout][Hout][Wout] rows of ldo bf16 channels; channels >= Cout are not written       */
+  int32_t T, H, W;        /* input volume; Tout = (T-1)/stride_t + 1 (kt = 3) or T, Hout = (H-1)/stride_s + 1     */
+  int32_t Cin, Cout;
+  int32_t kt, stride_t, stride_s;
+  int32_t ldw, ldo;
+  int32_t silu;           /* 1: SiLU behind the bias                                                              */
+} sf_pose_conv_args;
+
+int sf_pose_conv(const sf_pose_conv_args* args, void* stream);
+
+/* The input transform (causal_diffusion_inference.py:337-343): pose frames holding 0..255 as uint8 / float32 / bf16
+ * (enum sf_pose_dtype), planar [3][F][H][W] (hwc = 0) or one image [H][W][3] (hwc = 1, F = 1), -> bf16
+ * [lead + F][H][W][8]: `lead` copies of the first frame in front (3 for the clip, :339), value / 255 (the fp32 quotient
+ * rounded once), channels 3..7 zero. */
+int sf_pose_prepare(const void* src, int dtype, int hwc, int F, int H, int W, int lead, void* out, void* stream);
+
+typedef struct sf_pose_layer {
+  const void* w;          /* as sf_pose_conv_args.w                                                               */
+  const float* bias;      /* as sf_pose_conv_args.bias                                                            */
+  int32_t cin, cout, kt, stride_t, stride_s, ldw, silu;   /* cin as stored (8 or 16)                              */
+} sf_pose_layer;
+
+#define SF_POSE_CONVS 6
+
+typedef struct sf_pose_model {
+  sf_pose_layer conv[SF_POSE_CONVS];      /* dwpose_embedding.0, .2, .4, .6, .8, .10 (:90-101)                    */
+  const void* embed_w;                    /* dwpose_embedding.12 (:102) as [pose_dim][64] bf16, k = (dh*2+dw)*16+ci */
+  const void* embed_b;                    /* [pose_dim] bf16                                                      */
+  int32_t pose_dim;                       /* 5120                                                                 */
+  sf_pose_layer ref_conv[SF_POSE_CONVS];  /* randomref_embedding_pose.0 .. .10 (:110-120), kt = 1                 */
+} sf_pose_model;
+
+/* The last layer of the dwpose stack (nn.Conv3d(16, 5120, (1,2,2), stride=(1,2,2)), causal_diffusion_inference.py:102) as
+ * the patch-embed pattern: x [T][H][W][16] -> rows [T*(H/2)*(W/2)][64] (scratch; row k = (dh*2+dw)*16 + ci) ->
+ * sf_gemm_bf16 with w [pose_dim][64], bias bf16 [pose_dim] -> tokens_out [T*(H/2)*(W/2)][pose_dim]. */
+int sf_pose_patch_embed(const void* x, int T, int H, int W, const void* w, const void* bias, int pose_dim, void* rows,
+                        void* tokens_out, void* stream);
+
+/* Scratch of one sf_pose_embed call on F pose frames of H x W (F >= 1), or of sf_pose_embed_ref (F = 0).
+ * 0 = malformed arguments or a volume of 4 GiB or more (sf_last_error says which). */
+size_t sf_pose_scratch_bytes(const sf_pose_model* model, int F, int H, int W);
+
+/* The whole dwpose stack in one host call (causal_diffusion_inference.py:337-340 with :388-391): frames [3][F][H][W]
+ * -> tokens_out bf16 [F'*h*w][pose_dim], token-major -- rows [f*h*w, (f+1)*h*w) are latent frame f's `add_condition`
+ * ('b c f h w -> b (f h w) c' of the reference's output).  (F', h, w) follow from sf_pose_out_size over F + 3 frames;
+ * n_tokens must equal F'*h*w. */
+int sf_pose_embed(const sf_pose_model* model, const void* frames, int dtype, int F, int H, int W, void* scratch,
+                  size_t scratch_bytes, void* tokens_out, int64_t n_tokens, void* stream);
+
+/* The reference-pose stack (causal_diffusion_inference.py:341-343): image [H][W][3] -> out bf16 [h][w][20],
+ * channels-last (the reference's [1, 20, 1, h, w] is a permuted view). */
+int sf_pose_embed_ref(const sf_pose_model* model, const void* image, int dtype, int H, int W, void* scratch,
+                      size_t scratch_bytes, void* out, void* stream);
+
+/* ==========================================================================================
  * umT5 text encoder (prompt token ids -> prompt embeddings): WanTextEncoder.forward after its tokenizer
  * (utils/wan_wrapper.py:40-55) -> T5Encoder.forward (wan/modules/t5.py:299-312).  Runs once per prompt.
  * ========================================================================================== */

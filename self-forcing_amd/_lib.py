@@ -32,6 +32,9 @@ VAE_MAX_STAGES = 4
 # enum sf_taehv_epilogue
 TAEHV_EPILOGUES = {"bias_relu": 0, "bias_resid_relu": 1, "plain": 2, "relu": 3, "head_f32": 4}
 TAEHV_STAGES, TAEHV_BLOCKS = 3, 3
+# enum sf_pose_dtype
+POSE_DTYPES = {"uint8": 0, "float32": 1, "bfloat16": 2}
+POSE_CONVS = 6
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 # enum sf_attn_structure / sf_gemm_structure
 ATTN_STRUCTURES = {"auto": 0, "r64": 1, "w8": 2, "w4": 3}
@@ -175,6 +178,20 @@ class TaehvModel(C.Structure):
                 ("exit_conv", TaehvLayer * TAEHV_STAGES), ("tgrow", C.c_int32 * TAEHV_STAGES), ("head", TaehvLayer)]
 
 
+class PoseConvArgs(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("x", "w", "bias", "out")]
+                + [(n, C.c_int32) for n in ("T", "H", "W", "Cin", "Cout", "kt", "stride_t", "stride_s", "ldw", "ldo", "silu")])
+
+
+class PoseLayer(C.Structure):
+    _fields_ = [("w", C.c_void_p), ("bias", C.c_void_p)] + [(n, C.c_int32) for n in ("cin", "cout", "kt", "stride_t", "stride_s", "ldw", "silu")]
+
+
+class PoseModel(C.Structure):
+    _fields_ = [("conv", PoseLayer * POSE_CONVS), ("embed_w", C.c_void_p), ("embed_b", C.c_void_p), ("pose_dim", C.c_int32),
+                ("ref_conv", PoseLayer * POSE_CONVS)]
+
+
 class T5Layer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("norm1_w", "qk_w", "v_w", "o_w", "norm2_w", "gate_w", "fc1_w", "fc2_w", "pos_emb")]
 
@@ -234,6 +251,13 @@ SIGNATURES = {
     "sf_taehv_scratch_bytes": (C.c_size_t, [C.POINTER(TaehvModel), _i, _i, _i]),
     "sf_taehv_reset": (C.c_int, [C.POINTER(TaehvModel), _vp, _sz, _i, _i, _vp]),
     "sf_taehv_decode_frames": (C.c_int, [C.POINTER(TaehvModel), _vp, _sz, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sf_pose_out_size": (C.c_int, [_i, _i, _i]),
+    "sf_pose_conv": (C.c_int, [C.POINTER(PoseConvArgs), _vp]),
+    "sf_pose_prepare": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sf_pose_patch_embed": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "sf_pose_scratch_bytes": (C.c_size_t, [C.POINTER(PoseModel), _i, _i, _i]),
+    "sf_pose_embed": (C.c_int, [C.POINTER(PoseModel), _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i64, _vp]),
+    "sf_pose_embed_ref": (C.c_int, [C.POINTER(PoseModel), _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "sf_embedding_gather": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_t5_softmax_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_mul_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),

@@ -1,0 +1,201 @@
+// Host sequencer of the pose front end (pipeline/causal_diffusion_inference.py:87-122, :337-343) and the gather in
+// front of its last layer.  One call embeds a whole clip:
+//
+//   prepare (first frame x3 in front, / 255, layout)          [F+3][H][W][8]
+//   dwpose_embedding.0 .. .10: six sf_pose_conv with SiLU     -> [F'][2h][2w][16]   (two ping-pong volumes)
+//   dwpose_embedding.12 (16 -> 5120, kernel = stride = (1,2,2)): the patch-embed pattern -- gather each token's 2x2x16
+//     patch into a row of [F'*h*w][64], then sf_gemm_bf16 with the bias epilogue -> tokens [F'*h*w][5120], token-major
+//
+// and the reference-pose stack is six sf_pose_conv with kt = 1 on one image.  Everything lives in scratch; the library
+// keeps no state.
+#include <cstring>
+#include "sf_common.h"
+#include "../../include/sf_hip.h"
+
+namespace {
+
+#define SF_TRY(expr)            \
+  do {                          \
+    int rc__ = (expr);          \
+    if (rc__ != 0) return rc__; \
+  } while (0)
+
+constexpr long VOL_LIMIT = 0xFFFFFF00L;   // sf_pose_conv's 32-bit byte offsets
+
+struct Vol { int T, H, W, C; };
+inline size_t vbytes(const Vol& v) { return (size_t)v.T * v.H * v.W * v.C * 2; }
+inline size_t r256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int check_layers(const sf_pose_layer* l, int kt, const char* who, const char* stack) {
+  int c = 8;
+  for (int i = 0; i < SF_POSE_CONVS; ++i) {
+    SF_CHECK(l[i].w && l[i].bias, "%s: %s layer %d has no weights", who, stack, i);
+    SF_CHECK(l[i].cin == c && l[i].kt == kt && l[i].cout > 0 && l[i].cout <= 32, "%s: malformed %s layer %d (cin=%d cout=%d kt=%d)", who, stack, i,
+             l[i].cin, l[i].cout, l[i].kt);
+    SF_CHECK(i + 1 == SF_POSE_CONVS || l[i].cout == 16, "%s: %s layer %d must have 16 output channels", who, stack, i);
+    SF_CHECK((l[i].stride_t == 1 || l[i].stride_t == 2) && (l[i].stride_s == 1 || l[i].stride_s == 2), "%s: %s layer %d has strides (%d, %d)", who, stack,
+             i, l[i].stride_t, l[i].stride_s);
+    c = 16;
+  }
+  return 0;
+}
+
+int check_model(const sf_pose_model* m, int F, int H, int W, const char* who) {
+  SF_CHECK(m != nullptr, "%s: null model", who);
+  SF_CHECK(F >= 0 && F <= (1 << 20) && H > 0 && W > 0 && H <= (1 << 16) && W <= (1 << 16), "%s: F=%d H=%d W=%d", who, F, H, W);
+  if (F > 0) {
+    SF_TRY(check_layers(m->conv, 3, who, "dwpose"));
+    SF_CHECK(m->conv[SF_POSE_CONVS - 1].cout == 16, "%s: the last dwpose convolution must have 16 output channels", who);
+    SF_CHECK(m->embed_w && m->embed_b && m->pose_dim > 0 && m->pose_dim % 4 == 0, "%s: malformed token embedding (pose_dim=%d)", who, m->pose_dim);
+  } else {
+    SF_TRY(check_layers(m->ref_conv, 1, who, "reference-pose"));
+  }
+  return 0;
+}
+
+// The volumes of a stack: v[0] the prepared input, v[i + 1] the output of layer i.  -1 when one reaches 4 GiB.
+int plan(const sf_pose_layer* l, int T, int H, int W, Vol (&v)[SF_POSE_CONVS + 1], int last_ld, const char* who) {
+  v[0] = {T, H, W, 8};
+  for (int i = 0; i < SF_POSE_CONVS; ++i) {
+    const Vol& a = v[i];
+    v[i + 1] = {l[i].kt == 3 ? sf_pose_out_size(a.T, 3, l[i].stride_t) : a.T, sf_pose_out_size(a.H, 3, l[i].stride_s),
+                sf_pose_out_size(a.W, 3, l[i].stride_s), i + 1 == SF_POSE_CONVS ? last_ld : 16};
+  }
+  for (int i = 0; i <= SF_POSE_CONVS; ++i) {
+    const long b = (long)v[i].T * v[i].H * v[i].W * v[i].C * 2;
+    SF_CHECK(b < VOL_LIMIT, "%s: a %dx%dx%d volume of %d channels is %ld bytes, beyond the 4 GiB the convolution's 32-bit offsets cover; embed the clip "
+             "in shorter pieces or at a lower resolution", who, v[i].T, v[i].H, v[i].W, v[i].C, b);
+  }
+  return 0;
+}
+
+struct Bufs { char *in, *a, *b, *rows; size_t bytes; };
+
+// in: the prepared volume; a / b: ping-pong for the layer outputs (a takes layers 0, 2, 4; b layers 1, 3, 5);
+// rows: the gathered [tokens][64] rows of the token embedding (dwpose stack only)
+Bufs carve(void* scratch, const Vol (&v)[SF_POSE_CONVS + 1], long tokens) {
+  size_t sa = 0, sb = 0;
+  for (int i = 0; i < SF_POSE_CONVS; ++i) {
+    size_t& s = (i & 1) ? sb : sa;
+    if (vbytes(v[i + 1]) > s) s = vbytes(v[i + 1]);
+  }
+  Bufs r;
+  char* base = (char*)scratch;
+  size_t off = 0;
+  auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += r256(n); return p; };
+  r.in = take(vbytes(v[0]));
+  r.a = take(sa);
+  r.b = take(sb);
+  r.rows = take((size_t)tokens * 64 * 2);
+  r.bytes = off;
+  return r;
+}
+
+int run_stack(const sf_pose_layer* l, const Vol (&v)[SF_POSE_CONVS + 1], const Bufs& b, void* last_out, void* stream) {
+  const char* x = b.in;
+  for (int i = 0; i < SF_POSE_CONVS; ++i) {
+    char* out = i + 1 == SF_POSE_CONVS && last_out ? (char*)last_out : (i & 1) ? b.b : b.a;
+    sf_pose_conv_args a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.w = l[i].w; a.bias = l[i].bias; a.out = out;
+    a.T = v[i].T; a.H = v[i].H; a.W = v[i].W; a.Cin = l[i].cin; a.Cout = l[i].cout;
+    a.kt = l[i].kt; a.stride_t = l[i].stride_t; a.stride_s = l[i].stride_s; a.ldw = l[i].ldw; a.ldo = v[i + 1].C; a.silu = l[i].silu;
+    SF_TRY(sf_pose_conv(&a, stream));
+    x = out;
+  }
+  return 0;
+}
+
+// rows[(f, i, j)][(dh*2 + dw)*16 + c] = x[f][2i + dh][2j + dw][c]: one 16-byte piece per thread
+__global__ __launch_bounds__(256) void pose_patch_gather_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ rows, long n_pieces, int H, int W, int h,
+                                                                int w) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_pieces) return;
+  const long m = i >> 3;
+  const int q = (int)(i & 7), tap = q >> 1, half = q & 1;
+  const long f = m / (h * w);
+  const int r = (int)(m - f * (h * w)), ii = r / w, jj = r - ii * w;
+  const long src = ((f * H + 2 * ii + (tap >> 1)) * W + 2 * jj + (tap & 1)) * 16 + half * 8;
+  *reinterpret_cast<bf16x8*>(rows + i * 8) = *reinterpret_cast<const bf16x8*>(x + src);
+}
+
+}  // namespace
+
+extern "C" int sf_pose_patch_embed(const void* x, int T, int H, int W, const void* w, const void* bias, int pose_dim, void* rows, void* tokens_out,
+                                   void* stream) {
+  const char* who = "sf_pose_patch_embed";
+  SF_CHECK(x && w && bias && rows && tokens_out, "%s: null tensor", who);
+  SF_CHECK(T > 0 && H >= 2 && W >= 2 && H <= (1 << 16) && W <= (1 << 16) && pose_dim > 0 && pose_dim % 4 == 0, "%s: T=%d H=%d W=%d pose_dim=%d", who, T, H, W,
+           pose_dim);
+  SF_CHECK((uintptr_t)x % 16 == 0 && (uintptr_t)w % 16 == 0 && (uintptr_t)rows % 16 == 0 && (uintptr_t)tokens_out % 16 == 0, "%s: misaligned tensor", who);
+  const int h = H / 2, wd = W / 2;
+  const long tokens = (long)T * h * wd;
+  SF_CHECK(tokens < (1L << 31) / 8, "%s: %ld tokens", who, tokens);
+  const long n_pieces = tokens * 8;
+  hipLaunchKernelGGL(pose_patch_gather_kernel, dim3((unsigned)((n_pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)rows,
+                     n_pieces, H, W, h, wd);
+  SF_HIP_LAUNCH_CHECK(who);
+  sf_gemm_args g;
+  memset(&g, 0, sizeof(g));
+  g.a = rows; g.w = w; g.bias = bias; g.out = tokens_out;
+  g.M = (int)tokens; g.N = pose_dim; g.K = 64; g.lda = 64; g.ldw = 64; g.ldo = pose_dim;
+  g.epilogue = SF_EPI_BIAS;
+  return sf_gemm_bf16(&g, stream);
+}
+
+extern "C" size_t sf_pose_scratch_bytes(const sf_pose_model* model, int F, int H, int W) {
+  const char* who = "sf_pose_scratch_bytes";
+  if (check_model(model, F, H, W, who) != 0) return 0;
+  Vol v[SF_POSE_CONVS + 1];
+  if (F > 0) {
+    if (plan(model->conv, F + 3, H, W, v, 16, who) != 0) return 0;
+    const Vol& l = v[SF_POSE_CONVS];
+    const long tokens = (long)l.T * sf_pose_out_size(l.H, 2, 2) * sf_pose_out_size(l.W, 2, 2);
+    if (tokens <= 0) {
+      sf_set_error("%s: %d frames of %dx%d give no tokens", who, F, H, W);
+      return 0;
+    }
+    return carve(nullptr, v, tokens).bytes;
+  }
+  if (plan(model->ref_conv, 1, H, W, v, model->ref_conv[SF_POSE_CONVS - 1].cout, who) != 0) return 0;
+  return carve(nullptr, v, 0).bytes;
+}
+
+extern "C" int sf_pose_embed(const sf_pose_model* model, const void* frames, int dtype, int F, int H, int W, void* scratch, size_t scratch_bytes,
+                             void* tokens_out, int64_t n_tokens, void* stream) {
+  const char* who = "sf_pose_embed";
+  SF_TRY(check_model(model, F, H, W, who));
+  SF_CHECK(F >= 1, "%s: no frames", who);
+  SF_CHECK(frames && scratch && tokens_out, "%s: null buffer", who);
+  SF_CHECK(dtype >= SF_POSE_U8 && dtype <= SF_POSE_BF16, "%s: unknown dtype %d", who, dtype);
+  SF_CHECK((uintptr_t)scratch % 256 == 0 && (uintptr_t)tokens_out % 16 == 0, "%s: scratch must be 256-byte, tokens_out 16-byte aligned", who);
+  Vol v[SF_POSE_CONVS + 1];
+  SF_TRY(plan(model->conv, F + 3, H, W, v, 16, who));
+  const Vol& l = v[SF_POSE_CONVS];
+  const int h = sf_pose_out_size(l.H, 2, 2), w = sf_pose_out_size(l.W, 2, 2);
+  const long tokens = (long)l.T * h * w;
+  SF_CHECK(tokens > 0 && tokens < (1L << 31) / 8, "%s: %d frames of %dx%d give %ld tokens", who, F, H, W, tokens);
+  SF_CHECK(n_tokens == tokens, "%s: tokens_out holds %ld rows, %d frames of %dx%d give %d x %d x %d = %ld", who, (long)n_tokens, F, H, W, l.T, h, w, tokens);
+  const Bufs b = carve(scratch, v, tokens);
+  SF_CHECK(scratch_bytes >= b.bytes, "%s: scratch of %zu bytes, %zu needed", who, scratch_bytes, b.bytes);
+
+  SF_TRY(sf_pose_prepare(frames, dtype, 0, F, H, W, 3, b.in, stream));
+  SF_TRY(run_stack(model->conv, v, b, nullptr, stream));
+  const char* x = ((SF_POSE_CONVS - 1) & 1) ? b.b : b.a;
+  return sf_pose_patch_embed(x, l.T, l.H, l.W, model->embed_w, model->embed_b, model->pose_dim, b.rows, tokens_out, stream);
+}
+
+extern "C" int sf_pose_embed_ref(const sf_pose_model* model, const void* image, int dtype, int H, int W, void* scratch, size_t scratch_bytes, void* out,
+                                 void* stream) {
+  const char* who = "sf_pose_embed_ref";
+  SF_TRY(check_model(model, 0, H, W, who));
+  SF_CHECK(image && scratch && out, "%s: null buffer", who);
+  SF_CHECK(dtype >= SF_POSE_U8 && dtype <= SF_POSE_BF16, "%s: unknown dtype %d", who, dtype);
+  SF_CHECK((uintptr_t)scratch % 256 == 0 && (uintptr_t)out % 8 == 0, "%s: scratch must be 256-byte, out 8-byte aligned", who);
+  Vol v[SF_POSE_CONVS + 1];
+  SF_TRY(plan(model->ref_conv, 1, H, W, v, model->ref_conv[SF_POSE_CONVS - 1].cout, who));
+  const Bufs b = carve(scratch, v, 0);
+  SF_CHECK(scratch_bytes >= b.bytes, "%s: scratch of %zu bytes, %zu needed", who, scratch_bytes, b.bytes);
+  SF_TRY(sf_pose_prepare(image, dtype, 1, 1, H, W, 0, b.in, stream));
+  return run_stack(model->ref_conv, v, b, out, stream);
+}

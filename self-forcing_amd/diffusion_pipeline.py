@@ -17,14 +17,21 @@ What differs:
     (`unipc.py`); timesteps come from the scheduler's host table, so the loop never waits on the device;
   * the constants the reference hard-codes (30 blocks, 1560 tokens per frame, 12x128 heads, 32760-token caches,
     :69-72, :464-487) are derived from the generator's shape and the latent size;
-  * the fork's image / pose front end (CLIP image encoder, VAE-encoded `y`, the dwpose convolution stacks,
-    :86-123, :154-173, :305-347) is outside the hot path: `input_image`, `dwpose_data`, `random_ref_dwpose` must be
-    None; already-embedded pose tokens can be passed as `dwpose_data_emb` [B, C_pose, F_total, h, w] and reach the
-    generator as `add_condition`, sliced per chunk exactly as :386-394 does;
+  * the fork's image front end (CLIP image encoder, VAE-encoded `y`, :154-173, :305-326) is not built (the reference
+    leaves it unwired too): `input_image` must be None;
+  * the pose front end runs on the GPU path (`pose.PoseEmbedder`, csrc/pose_conv.hip): `dwpose_data` [3, F, H, W] with
+    `random_ref_dwpose` [H, W, 3] are embedded once per clip with weights loaded lazily from `args.pose_weights_path`
+    (`args.pose_weights_strict`, :329-331) or by an injected `pose_embedder=`; the tokens come out token-major, so a
+    chunk's `add_condition` is a row range of them (a view; one clip is shared by every sample of the batch).  With
+    only one of the two inputs the pose branch is not taken, as in the reference (:336).  The reference-pose map is
+    only ever added to `y` (:346-347), which does not exist without image conditioning, so it is not computed here.
+    Already-embedded tokens can still be passed as `dwpose_data_emb` [B, C_pose, F_total, h, w], sliced per chunk
+    exactly as :386-394 does;
   * the 'dpm++' solver branch (:526-536) is not implemented; the per-step `print`s are dropped.
 """
 from __future__ import annotations
 
+import logging
 from typing import List, Optional
 
 import torch
@@ -32,6 +39,8 @@ import torch
 from . import ops
 from .unipc import FlowUniPCMultistepScheduler
 from .wan_wrapper import WanDiffusionWrapper
+
+log = logging.getLogger(__name__)
 
 
 def _new_kv_cache(shape, n_layers: int, batch_size: int, cache_tokens: int, dtype, device) -> List[dict]:
@@ -73,7 +82,7 @@ def _new_crossattn_cache(shape, n_layers: int, batch_size: int, dtype, device) -
 
 class CausalDiffusionInferencePipeline(torch.nn.Module):
     def __init__(self, args, device, generator=None, text_encoder=None, vae=None, image_encoder=None,
-                 overlap_cfg: Optional[bool] = None):
+                 overlap_cfg: Optional[bool] = None, pose_embedder=None):
         super().__init__()
         self.device = torch.device(device)
         self.generator = WanDiffusionWrapper(**getattr(args, "model_kwargs", {}), is_causal=True, device=device) \
@@ -89,6 +98,11 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
         self.text_encoder = text_encoder
         self.vae = vae
         self.image_encoder = image_encoder      # accepted for signature parity; the CLIP front end is out of scope
+        # pose weights load lazily on the first inference that takes the pose branch (:59-61, :329-331)
+        self.pose_embedder = pose_embedder
+        self.pose_weights_path = getattr(args, "pose_weights_path", None)
+        self.pose_weights_strict = getattr(args, "pose_weights_strict", True)
+        self.pose_weights_loaded = pose_embedder is not None
 
         self.num_train_timesteps = args.num_train_timestep
         self.sampling_steps = 50
@@ -182,13 +196,22 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
         main.wait_stream(side)
         return fc, fu
 
+    def _pose_tokens(self, dwpose_data: torch.Tensor):
+        """`dwpose_embedding` over the clip (:337-340) as (tokens [1, F'*h*w, 5120], (F', h, w)); the weights load once."""
+        if self.pose_embedder is None:
+            if self.pose_weights_path is None:
+                raise ValueError("dwpose_data needs pose weights: set args.pose_weights_path or construct the pipeline with pose_embedder=")
+            from .pose import PoseEmbedder
+            self.pose_embedder = PoseEmbedder(self.pose_weights_path, device=self.device, strict=self.pose_weights_strict)
+            self.pose_weights_loaded = True
+        return self.pose_embedder.embed(dwpose_data)
+
     def inference(self, noise: torch.Tensor, text_prompts: List[str], input_image=None, dwpose_data=None,
                   random_ref_dwpose=None, initial_latent: Optional[torch.Tensor] = None, return_latents: bool = False,
                   start_frame_index: Optional[int] = 0, dwpose_data_emb: Optional[torch.Tensor] = None):
         """noise [B, F, C, H, W] -> video in [0, 1] (and the latents)."""
-        if input_image is not None or dwpose_data is not None or random_ref_dwpose is not None:
-            raise NotImplementedError("the image / pose front end (CLIP, VAE encode, dwpose convolutions) is outside "
-                                      "this path: pass embedded pose tokens as dwpose_data_emb=, or None")
+        if input_image is not None:
+            raise NotImplementedError("the image front end (CLIP, VAE-encoded y) is not built: input_image must be None")
         batch_size, num_frames, num_channels, height, width = noise.shape
         if not self.independent_first_frame or (self.independent_first_frame and initial_latent is not None):
             assert num_frames % self.num_frame_per_block == 0
@@ -199,6 +222,24 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
         num_input_frames = initial_latent.shape[1] if initial_latent is not None else 0
         num_output_frames = num_frames + num_input_frames
         self.frame_seq_length = (height // 2) * (width // 2)
+        use_pose = dwpose_data is not None and random_ref_dwpose is not None      # both, as the reference (:336)
+        if use_pose:
+            if dwpose_data_emb is not None:
+                raise ValueError("pass either dwpose_data (with random_ref_dwpose) or dwpose_data_emb, not both")
+            if dwpose_data.dim() != 4 or dwpose_data.shape[0] != 3:
+                raise ValueError(f"dwpose_data must be one clip [3, F, H, W] (shared by the batch), got {tuple(dwpose_data.shape)}")
+            # the pose tokens must cover the whole output timeline (:362-369); known from the shapes, before any work
+            from .pose_weights import pose_plan
+            pose_fhw = pose_plan(*dwpose_data.shape[1:])
+            expected_pose_frames = (start_frame_index or 0) + num_output_frames
+            assert pose_fhw[0] == expected_pose_frames, (
+                f"dwpose_data_emb has {pose_fhw[0]} frames, "
+                f"but expected {expected_pose_frames} to match the output timeline.")
+            if pose_fhw[1] * pose_fhw[2] != self.frame_seq_length:
+                raise ValueError(f"dwpose_data gives {pose_fhw[1]}x{pose_fhw[2]} pose tokens per frame, the latents {height // 2}x{width // 2}. "
+                                 "Check pose data processing.")
+        elif dwpose_data is not None or random_ref_dwpose is not None:
+            log.warning("only one of dwpose_data / random_ref_dwpose was given: the pose branch needs both and is not taken")
         conditional_dict = dict(self.text_encoder(text_prompts=text_prompts))
         unconditional_dict = dict(self.text_encoder(text_prompts=[self.args.negative_prompt] * len(text_prompts)))
 
@@ -250,6 +291,7 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
             assert dwpose_data_emb.shape[2] == expected_pose_frames, (
                 f"dwpose_data_emb has {dwpose_data_emb.shape[2]} frames, "
                 f"but expected {expected_pose_frames} to match the output timeline.")
+        pose_tokens = self._pose_tokens(dwpose_data)[0] if use_pose else None      # [1, F'*h*w, 5120], once per clip
         guidance = float(self.args.guidance_scale)
         for current_num_frames in all_num_frames:
             latents = noise[:, cache_start_frame - num_input_frames:
@@ -259,6 +301,13 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
                 if end > dwpose_data_emb.shape[2]:
                     raise ValueError("dwpose_data has fewer frames than required for the current block.")
                 condition = dwpose_data_emb[:, :, start:end].permute(0, 2, 3, 4, 1).flatten(1, 3).contiguous()
+                conditional_dict["add_condition"] = condition
+                unconditional_dict["add_condition"] = condition
+            elif pose_tokens is not None:
+                # token-major: the chunk's tokens are a row range, no copy (batch > 1: the one clip, expanded)
+                condition = pose_tokens[:, current_start_frame * fs:(current_start_frame + current_num_frames) * fs]
+                if batch_size > 1:
+                    condition = condition.expand(batch_size, -1, -1).contiguous()
                 conditional_dict["add_condition"] = condition
                 unconditional_dict["add_condition"] = condition
             else:

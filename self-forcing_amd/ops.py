@@ -315,6 +315,64 @@ def taehv_conv(x: Tensor, w_packed: Tensor, bias: Optional[Tensor], kt: int, t_o
     return out
 
 
+def pose_prepare(src: Tensor, lead: int = 3, hwc: bool = False) -> Tensor:
+    """The pose input transform (sf_pose_prepare).  src: pose frames [3, F, H, W] holding 0..255 as uint8 / float32 /
+    bfloat16, or with `hwc` one image [H, W, 3].  Returns bf16 [lead + F, H, W, 8]: the first frame `lead` more times in
+    front, value / 255, channels 3..7 zero."""
+    if not src.is_cuda:
+        raise ValueError("pose_prepare: expected a CUDA/ROCm tensor (the HIP path has no CPU fallback)")
+    name = str(src.dtype).replace("torch.", "")
+    if name not in _lib.POSE_DTYPES:
+        raise ValueError(f"pose_prepare: pose data must be uint8, float32 or bfloat16, got {src.dtype}")
+    if hwc:
+        if src.dim() != 3 or src.shape[2] != 3:
+            raise ValueError(f"pose_prepare: expected an image [H, W, 3], got {tuple(src.shape)}")
+        F, (H, W) = 1, src.shape[:2]
+    else:
+        if src.dim() != 4 or src.shape[0] != 3:
+            raise ValueError(f"pose_prepare: expected pose frames [3, F, H, W], got {tuple(src.shape)}")
+        F, H, W = src.shape[1:]
+    src = src.contiguous()
+    out = torch.empty(lead + F, H, W, 8, dtype=torch.bfloat16, device=src.device)
+    check(lib().sf_pose_prepare(src.data_ptr(), _lib.POSE_DTYPES[name], int(hwc), F, H, W, lead, out.data_ptr(), stream_handle()), "sf_pose_prepare")
+    return out
+
+
+def pose_conv(x: Tensor, w_packed: Tensor, bias: Tensor, cout: int, kt: int = 3, stride_t: int = 1, stride_s: int = 1, silu: bool = True) -> Tensor:
+    """One convolution of the pose stacks (sf_pose_conv).  x [T, H, W, Cin] channels-last bf16 with Cin 8 or 16; w_packed /
+    bias from `pose_weights.repack_pose_conv` / `pad_pose_bias` (bf16 / float32).  Returns bf16 [Tout, Hout, Wout, cout]."""
+    _bf16(x, "x"), _bf16(w_packed, "w_packed")
+    if not bias.is_cuda or bias.dtype != torch.float32 or bias.numel() != w_packed.shape[0]:
+        raise ValueError("pose_conv: bias must be a CUDA float32 tensor padded like the weight rows")
+    if x.dim() != 4 or not x.is_contiguous() or not w_packed.is_contiguous():
+        raise ValueError("pose_conv: x must be a contiguous [T, H, W, C] volume")
+    T, H, W, c = x.shape
+    size = lib().sf_pose_out_size
+    To = size(T, 3, stride_t) if kt == 3 else T
+    out = torch.empty(To, size(H, 3, stride_s), size(W, 3, stride_s), cout, dtype=torch.bfloat16, device=x.device)
+    a = _lib.PoseConvArgs()
+    a.x, a.w, a.bias, a.out = x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr()
+    a.T, a.H, a.W, a.Cin, a.Cout, a.kt, a.stride_t, a.stride_s = T, H, W, c, cout, kt, stride_t, stride_s
+    a.ldw, a.ldo, a.silu = w_packed.stride(0), cout, int(silu)
+    check(lib().sf_pose_conv(a, stream_handle()), "sf_pose_conv")
+    return out
+
+
+def pose_patch_embed(x: Tensor, w_packed: Tensor, bias: Tensor) -> Tensor:
+    """The dwpose stack's last layer (sf_pose_patch_embed).  x [T, H, W, 16] channels-last; w_packed [N, 64] from
+    `pose_weights.repack_pose_embed`, bias [N], both bf16.  Returns the tokens bf16 [T * (H//2) * (W//2), N]."""
+    _bf16(x, "x"), _bf16(w_packed, "w_packed"), _bf16(bias, "bias")
+    if x.dim() != 4 or x.shape[3] != 16 or not x.is_contiguous() or not w_packed.is_contiguous() or w_packed.shape[1] != 64:
+        raise ValueError("pose_patch_embed: contiguous x [T, H, W, 16] and w_packed [N, 64] expected")
+    T, H, W, _ = x.shape
+    n = T * (H // 2) * (W // 2)
+    rows = torch.empty(n, 64, dtype=torch.bfloat16, device=x.device)
+    out = torch.empty(n, w_packed.shape[0], dtype=torch.bfloat16, device=x.device)
+    check(lib().sf_pose_patch_embed(x.data_ptr(), T, H, W, w_packed.data_ptr(), bias.data_ptr(), w_packed.shape[0], rows.data_ptr(), out.data_ptr(),
+                                    stream_handle()), "sf_pose_patch_embed")
+    return out
+
+
 def rmsnorm_silu_cl(x: Tensor, gamma: Tensor, silu: bool = True) -> Tensor:
     """VAE RMS_norm over the last (channel) dim of a contiguous channels-last tensor, optional SiLU."""
     _bf16(x, "x"), _bf16(gamma, "gamma")
