@@ -13,7 +13,10 @@ one barrier after set-up.  It writes LATENTS (`<idx>-<sample>.pt`) and, when a V
 (`--vae_path Wan2.1_VAE.pth`, loaded with weights_only=True, or `--vae_random_init_seed N`; or the TAEHV tiny
 decoder for a fast preview, `--taehv_path taew2_1.pth` / `--taehv_random_init_seed N`), the decoded
 video as a uint8 tensor [T, H, W, 3] (`<idx>-<sample>.video.pt`: what the reference hands to
-`write_video`, inference.py:186-196; no video-file writer is used here).  The umT5 encoder is
+`write_video`, inference.py:186-196).  `--video_format mjpeg` writes a file that plays instead: `<idx>-<sample>.avi`,
+Motion-JPEG at 16 frames/s (the reference's `write_video` rate), every frame encoded on the GPU by `JpegEncoder`
+(`--jpeg_quality`, `--jpeg_subsampling`) with the demo's truncation (demo.py:166-167) of the decoder's [-1, 1] output,
+recovered from the returned [0, 1] video as 2 v - 1.  The umT5 encoder is
 outside this path, so embeddings are synthetic unless `--prompt_embeds` (a .pt dict prompt -> [L, 4096]
 tensor) is given.  A config WITHOUT `denoising_step_list` selects the multi-step classifier-free-guidance sampler
 (`CausalDiffusionInferencePipeline`), as inference.py:62-67 does; it needs `num_train_timestep`, `timestep_shift`,
@@ -129,7 +132,13 @@ def main():
     ap.add_argument("--pose_path", default=None, help=".pt / .npy dict with dwpose_data [3, F, H, W] and random_ref_dwpose [H, W, 3] (multi-step sampler)")
     ap.add_argument("--pose_weights_path", default=None, help="pose embedding weights (dwpose_embedding.* / randomref_embedding_pose.*)")
     ap.add_argument("--pose_random_init_seed", type=int, default=None, help="seeded random pose embedding weights instead")
+    ap.add_argument("--video_format", choices=("pt", "mjpeg"), default="pt",
+                    help="pt: <idx>-<sample>.video.pt (uint8 tensor); mjpeg: <idx>-<sample>.avi, JPEG frames encoded on the GPU, 16 frames/s")
+    ap.add_argument("--jpeg_quality", type=int, default=90, help="--video_format mjpeg: 1..100")
+    ap.add_argument("--jpeg_subsampling", choices=("420", "444"), default="420", help="--video_format mjpeg: chroma subsampling")
     a = ap.parse_args()
+    if not 1 <= a.jpeg_quality <= 100:
+        ap.error("--jpeg_quality must be 1..100")
     if a.pose_path or a.pose_weights_path or a.pose_random_init_seed is not None:
         if not a.pose_path or (a.pose_weights_path is None) == (a.pose_random_init_seed is None):
             ap.error("pose conditioning needs --pose_path and exactly one of --pose_weights_path / --pose_random_init_seed")
@@ -186,6 +195,7 @@ def main():
     elif a.taehv_random_init_seed is not None:
         vae = sfa.TAEHVWrapper(sfa.synth_taehv_state_dict(seed=a.taehv_random_init_seed), device=device)
     decode = not isinstance(vae, sfa.IdentityVAE)
+    jpeg = sfa.JpegEncoder(a.jpeg_quality, a.jpeg_subsampling, device=device) if decode and a.video_format == "mjpeg" else None
     few_step = is_few_step(cfg)        # inference.py:62-67: few-step rollout iff the config has denoising_step_list
     if few_step:
         pipe = sfa.CausalInferencePipeline(cfg, device, generator=gen, text_encoder=enc, vae=vae)
@@ -225,7 +235,10 @@ def main():
                                             return_latents=True)
         for s in range(a.num_samples):
             torch.save(latents[s].cpu(), os.path.join(a.output_folder, f"{idx}-{s}.pt"))
-            if decode:   # [T, 3, H, W] in [0, 1] -> [T, H, W, 3] uint8 (inference.py:186-187)
+            if jpeg is not None:
+                frames = jpeg.encode(video[s].float() * 2 - 1)
+                sfa.mjpeg.write_avi(os.path.join(a.output_folder, f"{idx}-{s}.avi"), frames, 16, video.shape[-1], video.shape[-2])
+            elif decode:   # [T, 3, H, W] in [0, 1] -> [T, H, W, 3] uint8 (inference.py:186-187)
                 torch.save((255.0 * video[s].permute(0, 2, 3, 1)).to(torch.uint8).cpu(), os.path.join(a.output_folder, f"{idx}-{s}.video.pt"))
         if rank == 0:
             print(f"[generate] prompt {idx}: latents {tuple(latents.shape)}" + (f", video {tuple(video.shape)}" if decode else ""), flush=True)

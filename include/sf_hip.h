@@ -574,6 +574,51 @@ int sf_taehv_decode_frames(const sf_taehv_model* model, void* state, size_t stat
                            int clamp, float* pixels_out, void* stream);
 
 /* ==========================================================================================
+ * JPEG encoder (decoded frames -> JFIF files): what the demo's sender does on the host (demo.py:162-187: clamp, * 127.5
+ * + 127.5, truncate to uint8, PIL save) as three kernels, so that a frame leaves the GPU as 0.1-0.4 MB of JPEG instead
+ * of 4.8 MB of fp32.  Baseline sequential JFIF, 8 bit, Y Cb Cr (JFIF's full-range BT.601), 4:2:0 (chroma = the 2x2 mean)
+ * or 4:4:4, libjpeg's quality scaling of the Annex K tables, the Annex K Huffman tables, a DRI segment and RST0..7
+ * every `restart_interval` MCUs (one wave codes one interval).  h and w must be multiples of the MCU (16 for 4:2:0, 8
+ * for 4:4:4).  The numbers are defined by self_forcing_amd/jpeg_reference.py; the library keeps no state and uploads
+ * nothing (tables and the header travel as kernel arguments).
+ * ========================================================================================== */
+
+enum sf_jpeg_subsampling { SF_JPEG_420 = 0, SF_JPEG_444 = 1 };
+enum sf_jpeg_dtype { SF_JPEG_U8 = 0, SF_JPEG_F32 = 1, SF_JPEG_BF16 = 2 };   /* u8: [n][h][w][3]; f32 / bf16: planar [n][3][h][w] */
+enum sf_jpeg_range {
+  SF_JPEG_RANGE_PM1 = 0,   /* u8 = trunc(clamp(p, -1, 1) * 127.5 + 127.5), each operation rounded to fp32 (demo.py:166-167) */
+  SF_JPEG_RANGE_01 = 1     /* u8 = trunc(255 * clamp(x, 0, 1))                                                            */
+};
+/* bits the kernels OR into *status (0 = every file is complete) */
+enum sf_jpeg_status {
+  SF_JPEG_SLOT_OVERFLOW = 1,   /* an interval outgrew its worst-case slot (cannot happen for coefficients in range)       */
+  SF_JPEG_COEF_RANGE = 2,      /* a DC difference beyond category 11 or an AC coefficient beyond category 10              */
+  SF_JPEG_OUT_OVERFLOW = 4     /* the files need more than out_capacity bytes: offsets are valid, nothing was written     */
+};
+
+/* Bytes of workspace for n frames: the coefficient buffer (int16 [n][blocks][64], at the start), one slot per restart
+ * interval sized for its worst case (1660 bits per block, every byte stuffed), and the interval lengths and positions.
+ * 0 = malformed arguments (sf_last_error says which). */
+size_t sf_jpeg_workspace_bytes(int n, int h, int w, int subsampling, int restart_interval);
+/* frames -> quantised coefficients, zigzagged, int16 [n][blocks][64] in MCU scan order (Y00 Y01 Y10 Y11 Cb Cr per 16x16 MCU
+ * for 4:2:0, Y Cb Cr per 8x8 MCU for 4:4:4): truncation to 8 bit in fp32 (enum sf_jpeg_range), then colour conversion,
+ * chroma mean, 8x8 DCT and q = rint(c / Q) in fp64.  bf16 frames are widened to fp32 first.  value_range is ignored
+ * for SF_JPEG_U8. */
+int sf_jpeg_transform(const void* frames, int dtype, int value_range, int n, int h, int w, int subsampling, int quality,
+                      void* coef, void* stream);
+/* coefficients -> n whole files back to back in `out`; file f is out[offsets[f] .. offsets[f + 1]).  `workspace` as sized
+ * by sf_jpeg_workspace_bytes (its coefficient part is not touched unless `coef` points at it); offsets int64 [n + 1],
+ * status int32 [1] (enum sf_jpeg_status bits), both device memory written on `stream`.  out_capacity =
+ * sf_jpeg_workspace_bytes(...) always suffices. */
+int sf_jpeg_entropy(const void* coef, int n, int h, int w, int subsampling, int quality, int restart_interval,
+                    void* workspace, size_t workspace_bytes, void* out, size_t out_capacity, int64_t* offsets,
+                    int32_t* status, void* stream);
+/* Both steps for a group of frames in one host call. */
+int sf_jpeg_encode_frames(const void* frames, int dtype, int value_range, int n, int h, int w, int subsampling,
+                          int quality, int restart_interval, void* workspace, size_t workspace_bytes, void* out,
+                          size_t out_capacity, int64_t* offsets, int32_t* status, void* stream);
+
+/* ==========================================================================================
  * Pose front end (DWPose frames -> pose tokens): `dwpose_embedding` and `randomref_embedding_pose` of the many-step
  * sampler (pipeline/causal_diffusion_inference.py:87-122) with their input transform (:337-343).  Runs once per clip.
  * Activations are channels-last bf16 volumes [T][H][W][C] with C = 8 (the three input channels, stored padded with

@@ -35,6 +35,12 @@ TAEHV_STAGES, TAEHV_BLOCKS = 3, 3
 # enum sf_pose_dtype
 POSE_DTYPES = {"uint8": 0, "float32": 1, "bfloat16": 2}
 POSE_CONVS = 6
+# enum sf_jpeg_subsampling / sf_jpeg_dtype / sf_jpeg_range / sf_jpeg_status
+JPEG_SUBSAMPLINGS = {"420": 0, "444": 1}
+JPEG_DTYPES = {"uint8": 0, "float32": 1, "bfloat16": 2}
+JPEG_RANGES = {(-1, 1): 0, (0, 1): 1}
+JPEG_STATUS = {1: "an interval outgrew its worst-case slot", 2: "a coefficient is outside the baseline range",
+               4: "the files do not fit the output buffer"}
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 # enum sf_attn_structure / sf_gemm_structure
 ATTN_STRUCTURES = {"auto": 0, "r64": 1, "w8": 2, "w4": 3}
@@ -258,6 +264,10 @@ SIGNATURES = {
     "sf_pose_scratch_bytes": (C.c_size_t, [C.POINTER(PoseModel), _i, _i, _i]),
     "sf_pose_embed": (C.c_int, [C.POINTER(PoseModel), _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i64, _vp]),
     "sf_pose_embed_ref": (C.c_int, [C.POINTER(PoseModel), _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "sf_jpeg_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "sf_jpeg_transform": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sf_jpeg_entropy": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "sf_jpeg_encode_frames": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "sf_embedding_gather": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_t5_softmax_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_mul_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),

@@ -420,3 +420,38 @@ def probe_copy(src: Tensor, dst: Tensor) -> int:
         raise ValueError("probe_copy: src and dst must hold the same number of bytes, a multiple of 16")
     check(lib().sf_probe_copy(src.data_ptr(), dst.data_ptr(), nbytes, stream_handle()), "sf_probe_copy")
     return nbytes
+
+
+# -------------------------------------------------------------------------------------- JPEG encoder (csrc/jpeg.hip)
+def jpeg_workspace_bytes(n: int, h: int, w: int, subsampling: str, restart_interval: int) -> int:
+    """Bytes of workspace (and of a worst-case output buffer) for n frames of h x w (sf_jpeg_workspace_bytes)."""
+    need = lib().sf_jpeg_workspace_bytes(n, h, w, _lib.JPEG_SUBSAMPLINGS[subsampling], restart_interval)
+    if need == 0:
+        check(-1, "sf_jpeg_workspace_bytes")
+    return need
+
+
+def jpeg_transform(frames: Tensor, coef: Tensor, n: int, h: int, w: int, subsampling: str, quality: int, value_range=(-1, 1)) -> Tensor:
+    """frames (contiguous float32 / bfloat16 [n, 3, h, w] or uint8 [n, h, w, 3]) -> coef int16 [n, blocks, 64] (sf_jpeg_transform)."""
+    dtype = _lib.JPEG_DTYPES[str(frames.dtype).replace("torch.", "")]
+    check(lib().sf_jpeg_transform(frames.data_ptr(), dtype, _lib.JPEG_RANGES[tuple(value_range)], n, h, w, _lib.JPEG_SUBSAMPLINGS[subsampling],
+                                  quality, coef.data_ptr(), torch.cuda.current_stream(frames.device).cuda_stream), "sf_jpeg_transform")
+    return coef
+
+
+def jpeg_entropy(coef: Tensor, n: int, h: int, w: int, subsampling: str, quality: int, restart_interval: int, workspace: Tensor, out: Tensor,
+                 meta: Tensor) -> None:
+    """coef -> n files back to back in `out` (uint8); meta int64 [n + 2] receives offsets[n + 1], then the status word
+    (sf_jpeg_entropy)."""
+    check(lib().sf_jpeg_entropy(coef.data_ptr(), n, h, w, _lib.JPEG_SUBSAMPLINGS[subsampling], quality, restart_interval, workspace.data_ptr(),
+                                workspace.numel(), out.data_ptr(), out.numel(), meta.data_ptr(), meta[n + 1:].data_ptr(),
+                                torch.cuda.current_stream(coef.device).cuda_stream), "sf_jpeg_entropy")
+
+
+def jpeg_encode_frames(frames: Tensor, n: int, h: int, w: int, subsampling: str, quality: int, restart_interval: int, value_range, workspace: Tensor,
+                       out: Tensor, meta: Tensor) -> None:
+    """Both steps in one host call (sf_jpeg_encode_frames); arguments as `jpeg_transform` / `jpeg_entropy`."""
+    dtype = _lib.JPEG_DTYPES[str(frames.dtype).replace("torch.", "")]
+    check(lib().sf_jpeg_encode_frames(frames.data_ptr(), dtype, _lib.JPEG_RANGES[tuple(value_range)], n, h, w, _lib.JPEG_SUBSAMPLINGS[subsampling],
+                                      quality, restart_interval, workspace.data_ptr(), workspace.numel(), out.data_ptr(), out.numel(), meta.data_ptr(),
+                                      meta[n + 1:].data_ptr(), torch.cuda.current_stream(frames.device).cuda_stream), "sf_jpeg_encode_frames")

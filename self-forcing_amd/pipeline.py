@@ -253,7 +253,7 @@ class CausalInferencePipeline(torch.nn.Module):
             current_start_frame += current_num_frames
 
     def stream(self, noise: torch.Tensor, text_prompts: List[str], skip_last_context: bool = True,
-               overlap_decode: bool = False):
+               overlap_decode: bool = False, frame_encoder=None):
         """Chunk-at-a-time generation (the streaming boundary; mirrors the inline loop of the
         reference's demo.py:303-468): yields `(chunk_index, latents [B, f, C, H, W], pixels)` per chunk.
         `pixels` comes from `vae.decode_chunk(latents, chunk_index)` when the injected VAE has a streaming
@@ -262,7 +262,12 @@ class CausalInferencePipeline(torch.nn.Module):
         overlap_decode=False: chunk k is decoded right after it is denoised and yielded at once (lowest
         latency to the first frame).  overlap_decode=True: the decode of chunk k runs on a second HIP stream
         while chunk k+1 is being denoised (it fills the CUs the denoiser's single-round kernels leave idle);
-        chunk k is then yielded one chunk later, as soon as its decode has finished."""
+        chunk k is then yielded one chunk later, as soon as its decode has finished.
+
+        frame_encoder (a `JpegEncoder`): every chunk's frames are also encoded on the GPU, on the stream that decoded
+        them, and the generator yields `(chunk_index, latents, pixels, frames)` with `frames` the chunk's JPEG files
+        (B * T of them).  An encoder with value_range (-1, 1) gets the decoder's output (the demo's truncation), one with
+        (0, 1) gets `pixels`.  Without one the 3-tuples are exactly what they were."""
         batch_size, num_frames, num_channels, height, width = noise.shape
         if self.independent_first_frame:
             assert (num_frames - 1) % self.num_frame_per_block == 0
@@ -285,12 +290,21 @@ class CausalInferencePipeline(torch.nn.Module):
 
         def decode(x0, chunk_idx):
             pixels = decode_chunk(x0, chunk_idx) if decode_chunk is not None else self.vae.decode_to_pixel(x0, use_cache=False)
-            return (pixels * 0.5 + 0.5).clamp(0, 1)
+            raw, pixels = pixels, (pixels * 0.5 + 0.5).clamp(0, 1)
+            if frame_encoder is None:
+                return (pixels,)
+            src = raw if tuple(frame_encoder.value_range) == (-1, 1) else pixels
+            return pixels, frame_encoder._encode(src)              # device buffers; read back when the chunk is yielded
+
+        def finish(chunk_idx, x0, decoded):
+            if frame_encoder is None:
+                return chunk_idx, x0, decoded[0]
+            return chunk_idx, x0, decoded[0], frame_encoder._to_host(*decoded[1])
 
         chunks = self._denoise_chunks(noise, conditional_dict, all_num_frames, 0, 0, skip_last_context)
         if not overlap_decode:
             for chunk_idx, start_frame, x0 in chunks:
-                yield chunk_idx, x0, decode(x0, chunk_idx)
+                yield finish(chunk_idx, x0, decode(x0, chunk_idx))
             return
         if getattr(self, "_decode_stream", None) is None:
             self._decode_stream = torch.cuda.Stream(device=noise.device)
@@ -302,17 +316,17 @@ class CausalInferencePipeline(torch.nn.Module):
             with torch.cuda.stream(side):
                 side.wait_event(ready)
                 x0.record_stream(side)
-                pixels = decode(x0, chunk_idx)
+                decoded = decode(x0, chunk_idx)
                 done = torch.cuda.Event()
                 done.record(side)
             if pending is not None:
                 pending[3].synchronize()
-                yield pending[:3]
-            pending = (chunk_idx, x0, pixels, done)
+                yield finish(*pending[:3])
+            pending = (chunk_idx, x0, decoded, done)
         if pending is not None:
             pending[3].synchronize()
             main.wait_event(pending[3])
-            yield pending[:3]
+            yield finish(*pending[:3])
 
     # ------------------------------------------------------------------------------------------
     def _cache_tokens(self, total_frames: Optional[int] = None) -> int:
