@@ -69,8 +69,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
 
   // XCD-aware bijective remap so that workgroups on one XCD share (batch, head) -> K/V hit in L2.
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = sf_xcd_remap(bid, nwg);
   const int bh = wg / p.q_tiles, qt = wg - bh * p.q_tiles;
   const int b = bh / p.H, head = bh - b * p.H;
 
@@ -339,8 +338,7 @@ __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
   const int half = wave >> 2;  // 0 = A, 1 = B
 
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = sf_xcd_remap(bid, nwg);
   const int bh = wg / p.q_tiles, qt = wg - bh * p.q_tiles;
   const int b = bh / p.H, head = bh - b * p.H;
 

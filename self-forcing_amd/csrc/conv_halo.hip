@@ -68,8 +68,7 @@ __global__ __launch_bounds__(HALO_THREADS) void conv_halo_kernel(HaloP p) {
 
   // tile: XCD-aware bijective remap, then patch-major order (neighbouring patches share halo rows in an XCD's L2)
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = sf_xcd_remap(bid, nwg);
   const int tile_m = wg / p.tiles_n, tn = wg - tile_m * p.tiles_n;
   const int per_frame = p.patches_h * p.patches_w;
   const int t = tile_m / per_frame, pr = tile_m - t * per_frame;

@@ -67,8 +67,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_igemm_kernel(ConvP p) {
   // XCD-aware bijective remap, then row-tile-major order: consecutive workgroups of one XCD work on
   // neighbouring output positions, whose gathered inputs overlap (taps) and share that XCD's L2
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = sf_xcd_remap(bid, nwg);
   const int tm = wg / p.tiles_n, tn = wg - tm * p.tiles_n;
   const int m0 = tm * CBM, n0 = tn * BN;
 

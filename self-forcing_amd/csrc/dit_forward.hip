@@ -7,24 +7,11 @@
 // host integers (the pipeline always knows them), so the reference's >= 60 `.item()` syncs per
 // forward (causal_model.py:207-226) disappear.
 #include <algorithm>
-#include <cstring>
-#include "sf_common.h"
-#include "../../include/sf_hip.h"
+#include "sf_host.h"
 
 int sf_internal_write_kv_indices(void* buf, int layers, int64_t global_end, int64_t local_end, void* stream);   // elementwise.hip
 
 namespace {
-
-struct Carve {
-  char* base;
-  size_t off;
-  explicit Carve(void* p) : base((char*)p), off(0) {}
-  void* take(size_t bytes) {
-    void* r = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return r;
-  }
-};
 
 struct Work {
   void *x, *xn, *qkv, *q, *att, *hbuf, *cols, *headout, *sin, *etmp, *e, *e0, *ctx1, *ctx;
@@ -66,36 +53,9 @@ Work carve(const sf_model* m, void* ws, int B, int F, int lat_h, int lat_w, int 
   return w;
 }
 
-int gemm(const void* a, int lda, const void* w, const void* bias, void* out, int ldo, int M, int N, int K, int epi,
-         const void* resid, int ldr, const void* gate_mod, const void* gate_e0, long gstride, int rpg, void* stream) {
-  sf_gemm_args g;
-  memset(&g, 0, sizeof(g));
-  g.a = a; g.w = w; g.bias = bias; g.out = out; g.resid = resid; g.gate_mod = gate_mod; g.gate_e0 = gate_e0;
-  g.gate_group_stride = gstride; g.rows_per_group = rpg;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = K; g.ldo = ldo; g.ldr = ldr; g.epilogue = epi;
-  return sf_gemm_bf16(&g, stream);
-}
-
 inline const char* bptr(const void* p, size_t elems) { return (const char*)p + elems * 2; }
 
-// fp8 mode: quantise `a` (rows of `rps` per segment) into the workspace's e4m3 buffer, then the e4m3 GEMM on it
-int gemm_fp8(const Work& ws, const void* wq, const float* wsc, const void* bias, void* out, int ldo, int M, int N, int K, int epi,
-             const void* resid, int ldr, const void* gate_mod, const void* gate_e0, long gstride, int rpg, int rps, void* stream) {
-  sf_gemm_args g;
-  memset(&g, 0, sizeof(g));
-  g.a = ws.xq; g.w = wq; g.bias = bias; g.out = out; g.resid = resid; g.gate_mod = gate_mod; g.gate_e0 = gate_e0;
-  g.gate_group_stride = gstride; g.rows_per_group = rpg;
-  g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldo = ldo; g.ldr = ldr; g.epilogue = epi;
-  return sf_gemm_fp8(&g, ws.xs, rps, wsc, stream);
-}
-
 }  // namespace
-
-#define SF_TRY(expr)            \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 
 extern "C" size_t sf_dit_workspace_bytes(const sf_model* model, int batch, int frames, int lat_h, int lat_w, int groups) {
   if (!model || batch <= 0 || frames <= 0 || lat_h <= 0 || lat_w <= 0 || groups <= 0) return 0;
@@ -150,14 +110,15 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
   SF_CHECK(!a->init_cross || a->prompt_embeds, "sf_dit_forward: init_cross needs prompt_embeds");
 
   const bool f8 = m->fp8 != 0;
+  static const sf_layer_fp8 no_fp8 = {};
   SF_CHECK(!f8 || m->layers_fp8_host, "sf_dit_forward: fp8 model without per-layer fp8 weights");
-  // One Linear: the bf16 GEMM on w16 exactly as without fp8, or (fp8) the input quantised with one scale per `rps` rows
-  // (= one pass) into the workspace, then the e4m3 GEMM on w8 with column scales s8.
-  auto lin = [&](const void* x, int ldx, const void* w16, const void* w8, const float* s8, const void* bias, void* out, int ldo, int rows,
-                 int N, int K, int epi, const void* resid, int ldr, const void* gmod, const void* ge0, long gstride, int rpg_, int rps) -> int {
-    if (!f8) return gemm(x, ldx, w16, bias, out, ldo, rows, N, K, epi, resid, ldr, gmod, ge0, gstride, rpg_, stream);
-    SF_TRY(sf_quantize_fp8(x, ldx, rows, K, rps, ws.xq, ws.xs, stream));
-    return gemm_fp8(ws, w8, s8, bias, out, ldo, rows, N, K, epi, resid, ldr, gmod, ge0, gstride, rpg_, rps, stream);
+  // One Linear: the bf16 GEMM on w exactly as without fp8, or (fp8) the e4m3 GEMM on the weight named by fp8w() with its
+  // column scales.  `run` reads the input already quantised in the workspace; `lin` quantises it first, with one scale
+  // per rows_per_segment rows (= one pass).
+  auto run = [&](const Gemm& g) -> int { return f8 ? g.fp8(ws.xq, ws.xs, stream) : g.bf16(stream); };
+  auto lin = [&](const Gemm& g) -> int {
+    if (f8) SF_TRY(sf_quantize_fp8(g.g.a, g.g.lda, g.g.M, g.g.K, g.rows_per_segment, ws.xq, ws.xs, stream));
+    return run(g);
   };
   // the time MLPs: rows of one pass = one segment
   auto small = [&](const void* x, const void* w16, const void* w8, const float* s8, const void* bias, void* out, int N, int K, int act_in,
@@ -178,7 +139,7 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
   // ---- patch embedding (rows of pass p at [p M, (p + 1) M))
   for (int p = 0; p < np; ++p)
     SF_TRY(sf_patchify(ps[p]->noisy, (void*)bptr(ws.cols, (size_t)p * M * Kp), B, F, m->in_dim, a->lat_h, a->lat_w, stream));
-  SF_TRY(gemm(ws.cols, Kp, m->patch_w, m->patch_b, ws.x, C, Mt, C, Kp, SF_EPI_BIAS, nullptr, 0, nullptr, nullptr, 0, 1, stream));
+  SF_TRY(Gemm(ws.cols, Kp, m->patch_w, Kp, ws.x, C, Mt, C, Kp).bias(m->patch_b).bf16(stream));
 
   // ---- pose conditioning of the fork: x += pose_proj(add_condition)  (causal_model.py:786-819), per pass
   for (int p = 0; p < np; ++p) {
@@ -186,8 +147,8 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
     void* xp = (void*)bptr(ws.x, (size_t)p * M * C);
     if (m->pose_w || (f8 && m->pose_q)) {
       SF_CHECK(m->pose_dim > 0, "sf_dit_forward: pose_proj weights without pose_dim");
-      SF_TRY(lin(ps[p]->add_condition, m->pose_dim, m->pose_w, m->pose_q, m->pose_s, m->pose_b, xp, C, M, C, m->pose_dim, SF_EPI_BIAS_RESID, xp, C,
-                 nullptr, nullptr, 0, 1, M));
+      SF_TRY(lin(Gemm(ps[p]->add_condition, m->pose_dim, m->pose_w, m->pose_dim, xp, C, M, C, m->pose_dim).bias(m->pose_b)
+                     .epi(SF_EPI_BIAS_RESID).resid(xp, C).fp8w(m->pose_q, m->pose_s, M)));
     } else {
       // dim == 5120: `pose_proj = nn.Identity()` (causal_model.py:500-503): x += add_condition, [M, C] bf16, fp32 add, one rounding
       SF_CHECK(m->pose_dim == C, "sf_dit_forward: add_condition without pose_proj weights needs pose_dim == dim (%d != %d)", m->pose_dim, C);
@@ -208,41 +169,30 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
   // MLP on every forward although only the first call consumes it, causal_model.py:837-842)
   if (a->init_cross) {
     const int T = B * m->text_len;
-    SF_TRY(lin(a->prompt_embeds, m->text_dim, m->text0_w, m->text0_q, m->text0_s, m->text0_b, ws.ctx1, C, T, C, m->text_dim, SF_EPI_BIAS_GELU,
-               nullptr, 0, nullptr, nullptr, 0, 1, T));
-    SF_TRY(lin(ws.ctx1, C, m->text2_w, m->text2_q, m->text2_s, m->text2_b, ws.ctx, C, T, C, C, SF_EPI_BIAS, nullptr, 0, nullptr, nullptr, 0, 1, T));
+    SF_TRY(lin(Gemm(a->prompt_embeds, m->text_dim, m->text0_w, m->text_dim, ws.ctx1, C, T, C, m->text_dim).bias(m->text0_b).epi(SF_EPI_BIAS_GELU)
+                   .fp8w(m->text0_q, m->text0_s, T)));
+    SF_TRY(lin(Gemm(ws.ctx1, C, m->text2_w, C, ws.ctx, C, T, C, C).bias(m->text2_b).fp8w(m->text2_q, m->text2_s, T)));
     // fp8: the text context is quantised once (one segment: the call's B samples) and read by every layer's k and v
     if (f8) SF_TRY(sf_quantize_fp8(ws.ctx, C, T, C, T, ws.xq, ws.xs, stream));
     for (int l = 0; l < m->num_layers; ++l) {
       const sf_layer_weights& lw = m->layers_host[l];
-      if (f8) {
-        const sf_layer_fp8& lq = m->layers_fp8_host[l];
-        SF_TRY(gemm_fp8(ws, lq.ckv_q, lq.ckv_s, lw.ckv_b, a->ck_cache_host[l], C, T, C, C, SF_EPI_BIAS, nullptr, 0, nullptr, nullptr, 0, 1, T, stream));
-      } else {
-        SF_TRY(gemm(ws.ctx, C, lw.ckv_w, lw.ckv_b, a->ck_cache_host[l], C, T, C, C, SF_EPI_BIAS, nullptr, 0, nullptr, nullptr, 0, 1, stream));
-      }
+      const sf_layer_fp8& lq = f8 ? m->layers_fp8_host[l] : no_fp8;
+      SF_TRY(run(Gemm(ws.ctx, C, lw.ckv_w, C, a->ck_cache_host[l], C, T, C, C).bias(lw.ckv_b).fp8w(lq.ckv_q, lq.ckv_s, T)));
       SF_TRY(sf_rmsnorm(a->ck_cache_host[l], C, lw.cnorm_k_w, a->ck_cache_host[l], C, T, C, m->eps, stream));
-      if (f8) {
-        const sf_layer_fp8& lq = m->layers_fp8_host[l];
-        SF_TRY(gemm_fp8(ws, (const char*)lq.ckv_q + (size_t)C * C, lq.ckv_s + C, bptr(lw.ckv_b, C), a->cv_cache_host[l], C, T, C, C, SF_EPI_BIAS,
-                        nullptr, 0, nullptr, nullptr, 0, 1, T, stream));
-      } else {
-        SF_TRY(gemm(ws.ctx, C, bptr(lw.ckv_w, (size_t)C * C), bptr(lw.ckv_b, C), a->cv_cache_host[l], C, T, C, C, SF_EPI_BIAS, nullptr, 0,
-                    nullptr, nullptr, 0, 1, stream));
-      }
+      SF_TRY(run(Gemm(ws.ctx, C, bptr(lw.ckv_w, (size_t)C * C), C, a->cv_cache_host[l], C, T, C, C).bias(bptr(lw.ckv_b, C))
+                     .fp8w(f8 ? (const char*)lq.ckv_q + (size_t)C * C : nullptr, f8 ? lq.ckv_s + C : nullptr, T)));
     }
   }
 
   // ---- transformer blocks
   for (int l = 0; l < m->num_layers; ++l) {
     const sf_layer_weights& lw = m->layers_host[l];
-    static const sf_layer_fp8 no_fp8 = {};
     const sf_layer_fp8& lq = f8 ? m->layers_fp8_host[l] : no_fp8;
     const void* mod = lw.modulation;
     const bool last_layer = l == m->num_layers - 1;
     // self attention: LN + q|k|v projection for every pass at once ...
     SF_TRY(sf_layernorm_modulate(ws.x, ws.xn, Mt, C, m->eps, bptr(mod, 0), bptr(mod, C), bptr(ws.e0, 0), bptr(ws.e0, C), 6L * C, rpg, stream));
-    SF_TRY(lin(ws.xn, C, lw.qkv_w, lq.qkv_q, lq.qkv_s, lw.qkv_b, ws.qkv, 3 * C, Mt, 3 * C, C, SF_EPI_BIAS, nullptr, 0, nullptr, nullptr, 0, 1, M));
+    SF_TRY(lin(Gemm(ws.xn, C, lw.qkv_w, C, ws.qkv, 3 * C, Mt, 3 * C, C).bias(lw.qkv_b).fp8w(lq.qkv_q, lq.qkv_s, M)));
     // ... then pass by pass through the cache: eviction, K / V write, attention over the pass's own window
     for (int p = 0; p < np; ++p) {
       const sf_forward_args* q = ps[p];
@@ -268,23 +218,22 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
     void* att = (void*)bptr(ws.att, r0 * C);
     void* hb = (void*)bptr(ws.hbuf, r0 * m->ffn_dim);
     const void* e0r = bptr(ws.e0, (size_t)p0 * BG * 6 * C);
-    SF_TRY(lin(att, C, lw.o_w, lq.o_q, lq.o_s, lw.o_b, x, C, Mr, C, C, SF_EPI_BIAS_GATE_RESID, x, C, bptr(mod, 2 * (size_t)C), bptr(e0r, 2 * (size_t)C),
-               6L * C, rpg, M));
+    SF_TRY(lin(Gemm(att, C, lw.o_w, C, x, C, Mr, C, C).bias(lw.o_b).epi(SF_EPI_BIAS_GATE_RESID).resid(x, C)
+                   .gate(bptr(mod, 2 * (size_t)C), bptr(e0r, 2 * (size_t)C), 6L * C, rpg).fp8w(lq.o_q, lq.o_s, M)));
     // cross attention
     SF_TRY(sf_layernorm_affine(x, lw.norm3_w, lw.norm3_b, xn, Mr, C, m->eps, stream));
-    SF_TRY(lin(xn, C, lw.cq_w, lq.cq_q, lq.cq_s, lw.cq_b, qb, C, Mr, C, C, SF_EPI_BIAS, nullptr, 0, nullptr, nullptr, 0, 1, M));
+    SF_TRY(lin(Gemm(xn, C, lw.cq_w, C, qb, C, Mr, C, C).bias(lw.cq_b).fp8w(lq.cq_q, lq.cq_s, M)));
     SF_TRY(sf_rmsnorm(qb, C, lw.cnorm_q_w, qb, C, Mr, C, m->eps, stream));
     for (int p = p0; p < np; ++p)                            // every pass reads the same text K / V: one launch per pass
       SF_TRY(sf_attention(bptr(ws.q, (size_t)p * M * C), a->ck_cache_host[l], a->cv_cache_host[l], (void*)bptr(ws.att, (size_t)p * M * C), B, m->num_heads, L,
                           m->text_len, C, (long)L * C, C, ctx_b, C, (long)L * C, stream));
-    SF_TRY(lin(att, C, lw.co_w, lq.co_q, lq.co_s, lw.co_b, x, C, Mr, C, C, SF_EPI_BIAS_RESID, x, C, nullptr, nullptr, 0, 1, M));
+    SF_TRY(lin(Gemm(att, C, lw.co_w, C, x, C, Mr, C, C).bias(lw.co_b).epi(SF_EPI_BIAS_RESID).resid(x, C).fp8w(lq.co_q, lq.co_s, M)));
     // feed forward
     SF_TRY(sf_layernorm_modulate(x, xn, Mr, C, m->eps, bptr(mod, 3 * (size_t)C), bptr(mod, 4 * (size_t)C), bptr(e0r, 3 * (size_t)C),
                                  bptr(e0r, 4 * (size_t)C), 6L * C, rpg, stream));
-    SF_TRY(lin(xn, C, lw.ffn0_w, lq.ffn0_q, lq.ffn0_s, lw.ffn0_b, hb, m->ffn_dim, Mr, m->ffn_dim, C, SF_EPI_BIAS_GELU, nullptr, 0, nullptr, nullptr,
-               0, 1, M));
-    SF_TRY(lin(hb, m->ffn_dim, lw.ffn2_w, lq.ffn2_q, lq.ffn2_s, lw.ffn2_b, x, C, Mr, C, m->ffn_dim, SF_EPI_BIAS_GATE_RESID, x, C,
-               bptr(mod, 5 * (size_t)C), bptr(e0r, 5 * (size_t)C), 6L * C, rpg, M));
+    SF_TRY(lin(Gemm(xn, C, lw.ffn0_w, C, hb, m->ffn_dim, Mr, m->ffn_dim, C).bias(lw.ffn0_b).epi(SF_EPI_BIAS_GELU).fp8w(lq.ffn0_q, lq.ffn0_s, M)));
+    SF_TRY(lin(Gemm(hb, m->ffn_dim, lw.ffn2_w, m->ffn_dim, x, C, Mr, C, m->ffn_dim).bias(lw.ffn2_b).epi(SF_EPI_BIAS_GATE_RESID).resid(x, C)
+                   .gate(bptr(mod, 5 * (size_t)C), bptr(e0r, 5 * (size_t)C), 6L * C, rpg).fp8w(lq.ffn2_q, lq.ffn2_s, M)));
   }
 
   // ---- head (modulated by e, not e0: causal_model.py:890, :364-366), unpatchify, flow -> x0: the passes that run to the end
@@ -293,8 +242,8 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
     const int Mr = (np - first_full) * M;
     const void* er = bptr(ws.e, (size_t)first_full * BG * C);
     SF_TRY(sf_layernorm_modulate(bptr(ws.x, r0 * C), (void*)bptr(ws.xn, r0 * C), Mr, C, m->eps, bptr(m->head_mod, 0), bptr(m->head_mod, C), er, er, (long)C, rpg, stream));
-    SF_TRY(lin(bptr(ws.xn, r0 * C), C, m->head_w, m->head_q, m->head_s, m->head_b, (void*)bptr(ws.headout, r0 * Nh), Nh, Mr, Nh, C, SF_EPI_BIAS,
-               nullptr, 0, nullptr, nullptr, 0, 1, M));
+    SF_TRY(lin(Gemm(bptr(ws.xn, r0 * C), C, m->head_w, C, (void*)bptr(ws.headout, r0 * Nh), Nh, Mr, Nh, C).bias(m->head_b)
+                   .fp8w(m->head_q, m->head_s, M)));
     for (int p = first_full; p < np; ++p)
       SF_TRY(sf_unpatchify_x0(bptr(ws.headout, (size_t)p * M * Nh), ps[p]->noisy, ps[p]->timestep, ps[p]->t_is_int64, m->sched_sigmas, m->sched_timesteps, m->n_table,
                               ps[p]->flow_out, ps[p]->x0_out, B, F, G, m->out_dim, a->lat_h, a->lat_w, stream));

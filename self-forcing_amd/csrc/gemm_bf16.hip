@@ -254,8 +254,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(GemmP p) {
     if (p.resid) p.resid += bz * p.r_bs;
   }
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = sf_xcd_remap(bid, nwg);
   // Grouped order on top of the XCD remap: consecutive workgroups (which run concurrently on one
   // XCD and advance through K in step) cover GROUP_M row tiles x a run of column tiles, so both the
   // A panel and the W tiles they stream are shared in that XCD's L2.  Row-major tile order made
@@ -456,8 +455,7 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp_kernel(GemmP p) {
   const int grp = wave >> 2, wc = wave & 3;          // grp: M half of the tile = which of the two staggered wave groups
 
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = sf_xcd_remap(bid, nwg);
   constexpr int GROUP_M = MT >= 6 ? 4 : 8;
   const int width = GROUP_M * p.tiles_n;
   const int group = wg / width, first_m = group * GROUP_M;
@@ -642,8 +640,7 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp2_kernel(GemmP p) {
   const int grp = wave >> 2, wc = wave & 3;
 
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = sf_xcd_remap(bid, nwg);
   constexpr int GROUP_M = 8;
   const int width = GROUP_M * p.tiles_n;
   const int group = wg / width, first_m = group * GROUP_M;

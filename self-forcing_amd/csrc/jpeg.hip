@@ -10,14 +10,8 @@
 //
 // The format and the definition of every number are those of self_forcing_amd/jpeg_reference.py (the float64 host oracle).
 // Tables and the header travel as kernel arguments: the library uploads nothing and keeps no state.
-#include "sf_common.h"
-#include "../../include/sf_hip.h"
+#include "sf_host.h"
 
-#define SF_TRY(expr)            \
-  do {                          \
-    const int rc__ = (expr);    \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 
 namespace {
 
@@ -584,8 +578,7 @@ extern "C" int sf_jpeg_entropy(const void* coef, int n, int h, int w, int subsam
   uint32_t* ipos = (uint32_t*)(ws + g.ipos_off);
   uint32_t* fsize = (uint32_t*)(ws + g.fsize_off);
   hipStream_t s = (hipStream_t)stream;
-  const hipError_t e = hipMemsetAsync(status, 0, 4, s);
-  SF_CHECK(e == hipSuccess, "%s: clearing the status word failed: %s", who, hipGetErrorString(e));
+  SF_TRY(sf_hip_ok(hipMemsetAsync(status, 0, 4, s), who, "clearing the status word"));
   const dim3 per_interval((unsigned)g.intervals, (unsigned)n);
   hipLaunchKernelGGL(jpeg_entropy_kernel, per_interval, dim3(64), 0, s, (const int16_t*)coef, slots, lens, (int*)status, ht, g.bpm, g.mcus, restart_interval,
                      g.blocks, (unsigned)g.slot_bytes);

@@ -8,23 +8,14 @@
 //
 // and the reference-pose stack is six sf_pose_conv with kt = 1 on one image.  Everything lives in scratch; the library
 // keeps no state.
-#include <cstring>
-#include "sf_common.h"
-#include "../../include/sf_hip.h"
+#include "sf_host.h"
 
 namespace {
-
-#define SF_TRY(expr)            \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 
 constexpr long VOL_LIMIT = 0xFFFFFF00L;   // sf_pose_conv's 32-bit byte offsets
 
 struct Vol { int T, H, W, C; };
 inline size_t vbytes(const Vol& v) { return (size_t)v.T * v.H * v.W * v.C * 2; }
-inline size_t r256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int check_layers(const sf_pose_layer* l, int kt, const char* who, const char* stack) {
   int c = 8;
@@ -80,14 +71,12 @@ Bufs carve(void* scratch, const Vol (&v)[SF_POSE_CONVS + 1], long tokens) {
     if (vbytes(v[i + 1]) > s) s = vbytes(v[i + 1]);
   }
   Bufs r;
-  char* base = (char*)scratch;
-  size_t off = 0;
-  auto take = [&](size_t n) { char* p = base ? base + off : nullptr; off += r256(n); return p; };
-  r.in = take(vbytes(v[0]));
-  r.a = take(sa);
-  r.b = take(sb);
-  r.rows = take((size_t)tokens * 64 * 2);
-  r.bytes = off;
+  Carve c(scratch);
+  r.in = c.take(vbytes(v[0]));
+  r.a = c.take(sa);
+  r.b = c.take(sb);
+  r.rows = c.take((size_t)tokens * 64 * 2);
+  r.bytes = c.off;
   return r;
 }
 
@@ -135,12 +124,7 @@ extern "C" int sf_pose_patch_embed(const void* x, int T, int H, int W, const voi
   hipLaunchKernelGGL(pose_patch_gather_kernel, dim3((unsigned)((n_pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)rows,
                      n_pieces, H, W, h, wd);
   SF_HIP_LAUNCH_CHECK(who);
-  sf_gemm_args g;
-  memset(&g, 0, sizeof(g));
-  g.a = rows; g.w = w; g.bias = bias; g.out = tokens_out;
-  g.M = (int)tokens; g.N = pose_dim; g.K = 64; g.lda = 64; g.ldw = 64; g.ldo = pose_dim;
-  g.epilogue = SF_EPI_BIAS;
-  return sf_gemm_bf16(&g, stream);
+  return Gemm(rows, 64, w, 64, tokens_out, pose_dim, (int)tokens, pose_dim, 64).bias(bias).bf16(stream);
 }
 
 extern "C" size_t sf_pose_scratch_bytes(const sf_pose_model* model, int F, int H, int W) {

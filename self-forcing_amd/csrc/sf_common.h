@@ -65,6 +65,14 @@ __device__ __forceinline__ float wave_max(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
+// XCD-aware bijective remap of the workgroup index.  The hardware deals workgroups round-robin over the 8 XCDs (bid & 7);
+// this gives XCD x the contiguous run of about nwg / 8 logical indices it would own if the grid were cut into 8 chunks
+// (the first nwg & 7 XCDs one longer), so neighbouring logical workgroups run on one XCD and share its L2.
+__device__ __forceinline__ int sf_xcd_remap(int bid, int nwg) {
+  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
 // tanh-approximated GELU, nn.GELU(approximate='tanh'):  0.5 x (1 + tanh(u)), u = k0 (x + k1 x^3)
 //   = x * sigmoid(2u) = x / (1 + exp2(-2 u log2e)): one v_exp_f32 and one v_rcp_f32 instead of an exp and a full-
 // precision division (7 instructions per element; the epilogue of ffn.0 runs it 42 M times per GEMM).

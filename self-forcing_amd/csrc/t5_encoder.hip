@@ -4,9 +4,7 @@
 // two batched GEMM launches (one grid row per head) around a bias/softmax kernel.  The pass runs once per
 // prompt (0.5 % of a rollout's FLOPs): 14 ms for umT5-XXL on 512 tokens.
 #include <cmath>
-#include <cstring>
-#include "sf_common.h"
-#include "../../include/sf_hip.h"
+#include "sf_host.h"
 
 namespace {
 
@@ -64,17 +62,6 @@ __global__ __launch_bounds__(256) void zero_masked_rows_kernel(bf16_t* __restric
   for (int c = threadIdx.x; c < dim / 8; c += 256) row[c] = z;
 }
 
-struct Carve {
-  char* base;
-  size_t off;
-  explicit Carve(void* p) : base((char*)p), off(0) {}
-  char* take(size_t bytes) {
-    char* r = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return r;
-  }
-};
-
 struct Work {
   char *x, *xn, *qk, *vt, *sc, *p, *ao, *g, *h;
   int lpad;
@@ -99,16 +86,6 @@ Work carve(const sf_t5_model* m, void* ws, int B, int L) {
   return w;
 }
 
-int gemm(const void* a, int lda, const void* w, int ldw, void* out, int ldo, int M, int N, int K, int epi, const void* resid, int ldr, void* stream,
-         int batch = 1, long a_bs = 0, long w_bs = 0, long o_bs = 0) {
-  sf_gemm_args g;
-  memset(&g, 0, sizeof(g));
-  g.a = a; g.w = w; g.out = out; g.resid = resid; g.rows_per_group = 1;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldo = ldo; g.ldr = ldr; g.epilogue = epi;
-  g.batch = batch; g.a_bstride = a_bs; g.w_bstride = w_bs; g.o_bstride = o_bs;
-  return sf_gemm_bf16(&g, stream);
-}
-
 int check_model(const sf_t5_model* m, int B, int L) {
   SF_CHECK(m && m->layers_host && m->token_embedding && m->final_norm_w, "sf_t5: null model");
   SF_CHECK(B > 0 && L > 0 && L % 4 == 0, "sf_t5: batch=%d seq_len=%d (seq_len must be a multiple of 4)", B, L);
@@ -118,12 +95,6 @@ int check_model(const sf_t5_model* m, int B, int L) {
 }
 
 }  // namespace
-
-#define SF_TRY(expr)            \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 
 extern "C" int sf_embedding_gather(const int64_t* ids, const void* table, void* out, int n_tokens, int dim, int vocab, void* stream) {
   SF_CHECK(ids && table && out && n_tokens > 0 && dim > 0 && dim % 8 == 0 && vocab > 0, "sf_embedding_gather: bad arguments");
@@ -166,37 +137,34 @@ extern "C" int sf_t5_encode(const sf_t5_model* m, const int64_t* ids, const int6
   SF_CHECK(ids && mask && rel_bucket && out, "sf_t5_encode: null tensor");
   const Work w = carve(m, workspace, B, L);
   SF_CHECK(workspace && workspace_bytes >= w.total, "sf_t5_encode: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  hipStream_t s = (hipStream_t)stream;
   const int M = B * L, D = m->dim, Da = m->dim_attn, F = m->dim_ffn, H = m->num_heads, lp = w.lpad;
 
   SF_TRY(sf_embedding_gather(ids, m->token_embedding, w.x, M, D, m->vocab, stream));
-  if (lp > L) {   // padded key columns of V^T stay zero for the whole pass
-    hipError_t e = hipMemsetAsync(w.vt, 0, (size_t)Da * lp * 2, s);
-    SF_CHECK(e == hipSuccess, "sf_t5_encode: memset failed: %s", hipGetErrorString(e));
-  }
+  if (lp > L)   // padded key columns of V^T stay zero for the whole pass
+    SF_TRY(sf_hip_ok(hipMemsetAsync(w.vt, 0, (size_t)Da * lp * 2, (hipStream_t)stream), "sf_t5_encode", "memset"));
   for (int l = 0; l < m->num_layers; ++l) {
     const sf_t5_layer& ly = m->layers_host[l];
     // x = x + attn(norm1(x))   (t5.py:176)
     SF_TRY(sf_rmsnorm(w.x, D, ly.norm1_w, w.xn, D, M, D, m->eps, stream));
-    SF_TRY(gemm(w.xn, D, ly.qk_w, D, w.qk, 2 * Da, M, 2 * Da, D, SF_EPI_BIAS, nullptr, 0, stream));
+    SF_TRY(Gemm(w.xn, D, ly.qk_w, D, w.qk, 2 * Da, M, 2 * Da, D).bf16(stream));
     for (int b = 0; b < B; ++b) {
       const char* xn_b = w.xn + (size_t)b * L * D * 2;
       const char* q_b = w.qk + (size_t)b * L * 2 * Da * 2;
       const char* k_b = q_b + (size_t)Da * 2;
       // V^T [Da][L] = Wv . xn_b^T straight from the projection
-      SF_TRY(gemm(ly.v_w, D, xn_b, D, w.vt, lp, Da, L, D, SF_EPI_BIAS, nullptr, 0, stream));
+      SF_TRY(Gemm(ly.v_w, D, xn_b, D, w.vt, lp, Da, L, D).bf16(stream));
       // logits of all heads in one batched launch, unscaled (t5.py:115): head h reads columns [64 h, 64 h + 64) of q and k
-      SF_TRY(gemm(q_b, 2 * Da, k_b, 2 * Da, w.sc, lp, L, L, 64, SF_EPI_F32, nullptr, 0, stream, H, 64, 64, (long)L * lp));
+      SF_TRY(Gemm(q_b, 2 * Da, k_b, 2 * Da, w.sc, lp, L, L, 64).epi(SF_EPI_F32).batch(H, 64, 64, (long)L * lp).bf16(stream));
       SF_TRY(sf_t5_softmax_bias((const float*)w.sc, w.p, ly.pos_emb, rel_bucket, mask + (size_t)b * L, H, L, lp, stream));
-      SF_TRY(gemm(w.p, lp, w.vt, lp, w.ao + (size_t)b * L * Da * 2, Da, L, 64, lp, SF_EPI_BIAS, nullptr, 0, stream, H, (long)L * lp, 64L * lp, 64));
+      SF_TRY(Gemm(w.p, lp, w.vt, lp, w.ao + (size_t)b * L * Da * 2, Da, L, 64, lp).batch(H, (long)L * lp, 64L * lp, 64).bf16(stream));
     }
-    SF_TRY(gemm(w.ao, Da, ly.o_w, Da, w.x, D, M, D, Da, SF_EPI_BIAS_RESID, w.x, D, stream));
+    SF_TRY(Gemm(w.ao, Da, ly.o_w, Da, w.x, D, M, D, Da).epi(SF_EPI_BIAS_RESID).resid(w.x, D).bf16(stream));
     // x = x + fc2(fc1(norm2(x)) * gelu(gate(norm2(x))))   (t5.py:137-142, :177)
     SF_TRY(sf_rmsnorm(w.x, D, ly.norm2_w, w.xn, D, M, D, m->eps, stream));
-    SF_TRY(gemm(w.xn, D, ly.gate_w, D, w.g, F, M, F, D, SF_EPI_BIAS_GELU, nullptr, 0, stream));
-    SF_TRY(gemm(w.xn, D, ly.fc1_w, D, w.h, F, M, F, D, SF_EPI_BIAS, nullptr, 0, stream));
+    SF_TRY(Gemm(w.xn, D, ly.gate_w, D, w.g, F, M, F, D).epi(SF_EPI_BIAS_GELU).bf16(stream));
+    SF_TRY(Gemm(w.xn, D, ly.fc1_w, D, w.h, F, M, F, D).bf16(stream));
     SF_TRY(sf_mul_bf16(w.h, w.g, w.h, (int64_t)M * F, stream));
-    SF_TRY(gemm(w.h, F, ly.fc2_w, F, w.x, D, M, D, F, SF_EPI_BIAS_RESID, w.x, D, stream));
+    SF_TRY(Gemm(w.h, F, ly.fc2_w, F, w.x, D, M, D, F).epi(SF_EPI_BIAS_RESID).resid(w.x, D).bf16(stream));
   }
   SF_TRY(sf_rmsnorm(w.x, D, m->final_norm_w, out, D, M, D, m->eps, stream));
   SF_TRY(sf_zero_masked_rows(out, mask, M, D, stream));

@@ -12,28 +12,9 @@
 //
 // Per-stream state = the one-frame history of each of the nine MemBlock input volumes; every volume lives in scratch.
 // A call copies the histories to the front of the volumes, runs, and copies each volume's last frame back.
-#include <cstring>
-#include "sf_common.h"
-#include "../../include/sf_hip.h"
+#include "sf_host.h"
 
 namespace {
-
-struct Carve {
-  char* base;
-  size_t off;
-  explicit Carve(void* p) : base((char*)p), off(0) {}
-  char* take(size_t bytes) {
-    char* r = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return r;
-  }
-};
-
-#define SF_TRY(expr)            \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 
 inline size_t vol(long T, int H, int W, int C) { return (size_t)T * H * W * C * 2; }
 
@@ -167,9 +148,7 @@ extern "C" int sf_taehv_reset(const sf_taehv_model* model, void* state, size_t s
   char* hist[SF_TAEHV_STAGES][SF_TAEHV_BLOCKS];
   const size_t need = carve_state(model, state, lat_h, lat_w, hist);
   SF_CHECK(state_bytes >= need, "sf_taehv_reset: state of %zu bytes, %zu needed", state_bytes, need);
-  hipError_t e = hipMemsetAsync(state, 0, need, (hipStream_t)stream);
-  SF_CHECK(e == hipSuccess, "sf_taehv_reset: memset failed: %s", hipGetErrorString(e));
-  return 0;
+  return sf_hip_ok(hipMemsetAsync(state, 0, need, (hipStream_t)stream), "sf_taehv_reset", "memset");
 }
 
 extern "C" int sf_taehv_decode_frames(const sf_taehv_model* model, void* state, size_t state_bytes, void* scratch, size_t scratch_bytes,
@@ -190,10 +169,9 @@ extern "C" int sf_taehv_decode_frames(const sf_taehv_model* model, void* state, 
 
   // the histories go to the front of their volumes
   for (int i = 0; i < SF_TAEHV_STAGES; ++i)
-    for (int k = 0; k < SF_TAEHV_BLOCKS; ++k) {
-      hipError_t e = hipMemcpyAsync(b.v[i][k], hist[i][k], vol(1, st[i].H, st[i].W, st[i].C), hipMemcpyDeviceToDevice, s);
-      SF_CHECK(e == hipSuccess, "sf_taehv_decode_frames: history copy failed: %s", hipGetErrorString(e));
-    }
+    for (int k = 0; k < SF_TAEHV_BLOCKS; ++k)
+      SF_TRY(sf_hip_ok(hipMemcpyAsync(b.v[i][k], hist[i][k], vol(1, st[i].H, st[i].W, st[i].C), hipMemcpyDeviceToDevice, s), "sf_taehv_decode_frames",
+                       "history copy"));
   SF_TRY(sf_taehv_prepare_latent(latent_frames, b.x0, n, model->z_dim, lat_h, lat_w, model->in_conv.cin, stream));
   SF_TRY(conv(model->in_conv, b.x0, n, lat_h, lat_w, 0, b.v[0][0] + vol(1, st[0].H, st[0].W, st[0].C), st[0].C, SF_TAEHV_BIAS_RELU, nullptr, 1, nullptr, 0,
               stream));
@@ -220,8 +198,8 @@ extern "C" int sf_taehv_decode_frames(const sf_taehv_model* model, void* state, 
   for (int i = 0; i < SF_TAEHV_STAGES; ++i)
     for (int k = 0; k < SF_TAEHV_BLOCKS; ++k) {
       const size_t f = vol(1, st[i].H, st[i].W, st[i].C);
-      hipError_t e = hipMemcpyAsync(hist[i][k], b.v[i][k] + (size_t)n * st[i].T * f, f, hipMemcpyDeviceToDevice, s);
-      SF_CHECK(e == hipSuccess, "sf_taehv_decode_frames: history copy failed: %s", hipGetErrorString(e));
+      SF_TRY(sf_hip_ok(hipMemcpyAsync(hist[i][k], b.v[i][k] + (size_t)n * st[i].T * f, f, hipMemcpyDeviceToDevice, s), "sf_taehv_decode_frames",
+                       "history copy"));
     }
   return 0;
 }

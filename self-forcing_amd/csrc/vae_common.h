@@ -4,22 +4,9 @@
 // Host-side only.  Both sequencers enqueue exactly these calls, so the decoder's arithmetic is unchanged by the sharing.
 #pragma once
 #include <cmath>
-#include <cstring>
-#include "sf_common.h"
-#include "../../include/sf_hip.h"
+#include "sf_host.h"
 
 namespace sfvae {
-
-struct Carve {
-  char* base;
-  size_t off;
-  explicit Carve(void* p) : base((char*)p), off(0) {}
-  char* take(size_t bytes) {
-    char* r = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return r;
-  }
-};
 
 struct BlockBufs { char *a1, *a2; };   // the two cached input volumes of a ResidualBlock (conv1's, conv2's)
 struct ResScratch { char *y1, *sc; };   // conv1's raw output (when its norm is not fused), the shortcut's output
@@ -54,19 +41,11 @@ inline int place_history(const Call& c, char* buf, int Tmax, size_t frame_bytes,
   if (c.history_at == c.window) return 0;
   if (tc && c.n - c.history_at == 0 && c.history_at <= 1) return 0;   // only the first chunk so far: this volume is still all zero
   const int src = vol_off(c.n - c.history_at, c.history_at, Tmax, tc), dst = c.off(Tmax, tc);
-  for (int k = 0; k < 2; ++k) {
-    hipError_t e = hipMemcpyAsync(buf + (size_t)(dst + k) * frame_bytes, buf + (size_t)(src + k) * frame_bytes, frame_bytes, hipMemcpyDeviceToDevice, c.s);
-    SF_CHECK(e == hipSuccess, "sf_vae: history copy failed: %s", hipGetErrorString(e));
-  }
+  for (int k = 0; k < 2; ++k)
+    SF_TRY(sf_hip_ok(hipMemcpyAsync(buf + (size_t)(dst + k) * frame_bytes, buf + (size_t)(src + k) * frame_bytes, frame_bytes, hipMemcpyDeviceToDevice, c.s),
+                     "sf_vae", "history copy"));
   return 0;
 }
-
-
-#define SF_TRY(expr)            \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 
 // RMS_norm + SiLU of a convolution's output can ride in its epilogue (second output of the halo kernel) when the
 // convolution is 3 x 3 spatial with 96 or 192 output channels at a resolution the halo kernel takes
@@ -88,15 +67,6 @@ inline int conv(const sf_vae_conv& c, const void* x, int Tout, int H, int W, int
   a.ldw = c.ldw; a.ldo = ldo; a.ldr = ldr; a.out_frame_offset = out_frame0; a.interleave_c = interleave_c; a.epilogue = epi;
   a.stride_hw = stride_hw; a.stride_t = stride_t;
   return sf_conv_igemm(&a, stream);
-}
-
-inline int gemm(const void* a, int lda, const void* w, int ldw, const void* bias, void* out, int ldo, int M, int N, int K, int epi,
-         const void* resid, int ldr, void* stream) {
-  sf_gemm_args g;
-  memset(&g, 0, sizeof(g));
-  g.a = a; g.w = w; g.bias = bias; g.out = out; g.resid = resid; g.rows_per_group = 1;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldo = ldo; g.ldr = ldr; g.epilogue = epi;
-  return sf_gemm_bf16(&g, stream);
 }
 
 // ResidualBlock.forward (vae.py:202-221) on T frames of H x W.  `in_normed`: the producer of x_in already wrote
@@ -130,19 +100,17 @@ inline int resblock(const sf_vae_resblock& r, const BlockBufs& b, const ResScrat
 
 // AttentionBlock.forward (vae.py:241-264) on one frame of n = h*w positions, in place on x [n][C]
 inline int attention_block(const AttnWeights& m, const AttnScratch& p, char* x, int n, int C, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
   const int np = p.att_npad;
   SF_TRY(sf_rmsnorm_silu_cl(x, m.attn_gamma, p.att_xn, n, C, 0, stream));
-  SF_TRY(gemm(p.att_xn, C, m.attn_qk_w, C, m.attn_qk_b, p.att_qk, 2 * C, n, 2 * C, C, SF_EPI_BIAS, nullptr, 0, stream));
+  SF_TRY(Gemm(p.att_xn, C, m.attn_qk_w, C, p.att_qk, 2 * C, n, 2 * C, C).bias(m.attn_qk_b).bf16(stream));
   // V^T [C][np] = Wv . xn^T straight from the projection (no transpose pass); its bias is added after
   // the P.V product instead (softmax rows sum to one), the padded key columns stay zero
-  hipError_t e = hipMemsetAsync(p.att_vt, 0, (size_t)C * np * 2, s);
-  SF_CHECK(e == hipSuccess, "sf_vae: memset failed: %s", hipGetErrorString(e));
-  SF_TRY(gemm(m.attn_v_w, C, p.att_xn, C, nullptr, p.att_vt, np, C, n, C, SF_EPI_BIAS, nullptr, 0, stream));
-  SF_TRY(gemm(p.att_qk, 2 * C, p.att_qk + (size_t)C * 2, 2 * C, nullptr, p.att_s, np, n, n, C, SF_EPI_F32, nullptr, 0, stream));
+  SF_TRY(sf_hip_ok(hipMemsetAsync(p.att_vt, 0, (size_t)C * np * 2, (hipStream_t)stream), "sf_vae", "memset"));
+  SF_TRY(Gemm(m.attn_v_w, C, p.att_xn, C, p.att_vt, np, C, n, C).bf16(stream));
+  SF_TRY(Gemm(p.att_qk, 2 * C, p.att_qk + (size_t)C * 2, 2 * C, p.att_s, np, n, n, C).epi(SF_EPI_F32).bf16(stream));
   SF_TRY(sf_softmax_rows((const float*)p.att_s, np, p.att_p, np, n, n, np, 1.0f / sqrtf((float)C), stream));
-  SF_TRY(gemm(p.att_p, np, p.att_vt, np, m.attn_v_b, p.att_o, C, n, C, np, SF_EPI_BIAS, nullptr, 0, stream));
-  SF_TRY(gemm(p.att_o, C, m.attn_proj_w, C, m.attn_proj_b, x, C, n, C, C, SF_EPI_BIAS_RESID, x, C, stream));
+  SF_TRY(Gemm(p.att_p, np, p.att_vt, np, p.att_o, C, n, C, np).bias(m.attn_v_b).bf16(stream));
+  SF_TRY(Gemm(p.att_o, C, m.attn_proj_w, C, x, C, n, C, C).bias(m.attn_proj_b).epi(SF_EPI_BIAS_RESID).resid(x, C).bf16(stream));
   return 0;
 }
 

@@ -159,9 +159,7 @@ extern "C" int sf_vae_reset(const sf_vae_model* m, void* state, size_t state_byt
   // zeroing them -- 2 of 2 + K T frames -- is WanVAE_.clear_cache; the whole state would be ~20 GB of stores per clip.
   hipStream_t s = (hipStream_t)stream;
   return for_each_volume(m, p, h, w, [&](char* buf, int, size_t frame_bytes, bool) -> int {
-    hipError_t e = hipMemsetAsync(buf, 0, 2 * frame_bytes, s);
-    SF_CHECK(e == hipSuccess, "sf_vae_reset: memset failed: %s", hipGetErrorString(e));
-    return 0;
+    return sf_hip_ok(hipMemsetAsync(buf, 0, 2 * frame_bytes, s), "sf_vae_reset", "memset");
   });
 }
 

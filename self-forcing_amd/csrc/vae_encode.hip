@@ -169,9 +169,7 @@ extern "C" int sf_vae_encode_reset(const sf_vae_encoder* m, void* state, size_t 
   // as sf_vae_reset: only the two history frames at the front of every volume are read before they are written
   hipStream_t s = (hipStream_t)stream;
   return for_each_volume(m, p, [&](char* buf, int, size_t frame_bytes) -> int {
-    hipError_t e = hipMemsetAsync(buf, 0, 2 * frame_bytes, s);
-    SF_CHECK(e == hipSuccess, "sf_vae_encode_reset: memset failed: %s", hipGetErrorString(e));
-    return 0;
+    return sf_hip_ok(hipMemsetAsync(buf, 0, 2 * frame_bytes, s), "sf_vae_encode_reset", "memset");
   });
 }
 

@@ -37,47 +37,11 @@ from typing import List, Optional
 import torch
 
 from . import ops
+from .kvcache import new_crossattn_cache, new_kv_cache, reset_kv_indices
 from .unipc import FlowUniPCMultistepScheduler
 from .wan_wrapper import WanDiffusionWrapper
 
 log = logging.getLogger(__name__)
-
-
-def _new_kv_cache(shape, n_layers: int, batch_size: int, cache_tokens: int, dtype, device) -> List[dict]:
-    """Same dict schema as causal_diffusion_inference.py:459-487; the index tensors are views of one [L, 2] buffer."""
-    index_buffer = torch.zeros(n_layers, 2, dtype=torch.long, device=device)
-    kv = []
-    for i in range(n_layers):
-        kv.append({
-            "k": torch.zeros([batch_size, cache_tokens, shape.num_heads, shape.head_dim], dtype=dtype, device=device),
-            "v": torch.zeros([batch_size, cache_tokens, shape.num_heads, shape.head_dim], dtype=dtype, device=device),
-            "global_end_index": index_buffer[i, 0:1],
-            "local_end_index": index_buffer[i, 1:2],
-            "_sf_index_buffer": index_buffer,
-        })
-    kv[0]["_sf_mirror"] = (kv[0]["global_end_index"], kv[0]["local_end_index"], 0, 0)
-    kv[0]["_sf_index_views"] = [(d["global_end_index"], d["local_end_index"]) for d in kv]
-    return kv
-
-
-def _reset_kv_cache(kv: List[dict]) -> None:
-    buf = kv[0].get("_sf_index_buffer")
-    if buf is not None:
-        buf.zero_()
-        kv[0]["_sf_mirror"] = (kv[0]["global_end_index"], kv[0]["local_end_index"], 0, 0)
-    else:  # foreign cache: rebind as the reference does (:221-231)
-        dev = kv[0]["k"].device
-        for d in kv:
-            d["global_end_index"] = torch.tensor([0], dtype=torch.long, device=dev)
-            d["local_end_index"] = torch.tensor([0], dtype=torch.long, device=dev)
-
-
-def _new_crossattn_cache(shape, n_layers: int, batch_size: int, dtype, device) -> List[dict]:
-    return [{
-        "k": torch.zeros([batch_size, shape.text_len, shape.num_heads, shape.head_dim], dtype=dtype, device=device),
-        "v": torch.zeros([batch_size, shape.text_len, shape.num_heads, shape.head_dim], dtype=dtype, device=device),
-        "is_init": False,
-    } for _ in range(n_layers)]
 
 
 class CausalDiffusionInferencePipeline(torch.nn.Module):
@@ -159,13 +123,13 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
         shape = self.generator.model.shape
         if cache_tokens is None:
             cache_tokens = self._cache_tokens(0)
-        self.kv_cache_pos = _new_kv_cache(shape, self.num_transformer_blocks, batch_size, cache_tokens, dtype, device)
-        self.kv_cache_neg = _new_kv_cache(shape, self.num_transformer_blocks, batch_size, cache_tokens, dtype, device)
+        self.kv_cache_pos = new_kv_cache(shape, self.num_transformer_blocks, batch_size, cache_tokens, dtype, device)
+        self.kv_cache_neg = new_kv_cache(shape, self.num_transformer_blocks, batch_size, cache_tokens, dtype, device)
 
     def _initialize_crossattn_cache(self, batch_size, dtype, device):
         shape = self.generator.model.shape
-        self.crossattn_cache_pos = _new_crossattn_cache(shape, self.num_transformer_blocks, batch_size, dtype, device)
-        self.crossattn_cache_neg = _new_crossattn_cache(shape, self.num_transformer_blocks, batch_size, dtype, device)
+        self.crossattn_cache_pos = new_crossattn_cache(shape, self.num_transformer_blocks, batch_size, dtype, device)
+        self.crossattn_cache_neg = new_crossattn_cache(shape, self.num_transformer_blocks, batch_size, dtype, device)
 
     # ------------------------------------------------------------------------------------------
     def _both(self, x, cond_dict, uncond_dict, timestep, current_start, cache_only: bool):
@@ -255,8 +219,8 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
             for block_index in range(self.num_transformer_blocks):
                 self.crossattn_cache_pos[block_index]["is_init"] = False
                 self.crossattn_cache_neg[block_index]["is_init"] = False
-            _reset_kv_cache(self.kv_cache_pos)
-            _reset_kv_cache(self.kv_cache_neg)
+            reset_kv_indices(self.kv_cache_pos)
+            reset_kv_indices(self.kv_cache_neg)
 
         # Step 2: context frames into both caches (:233-297)
         fs = self.frame_seq_length

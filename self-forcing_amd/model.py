@@ -15,6 +15,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib, fp8 as fp8_recipe, torch_ops
+from .device_model import DeviceModel
 from .kvcache import CachePlan
 from .weights import WanShape, param_shapes
 
@@ -35,7 +36,7 @@ def rope_tables(head_dim: int, max_pos: int = 1024, theta: float = 10000.0):
     return ang.cos().float().contiguous(), ang.sin().float().contiguous()
 
 
-class CausalWanModel:
+class CausalWanModel(DeviceModel):
     """Inference-only causal DiT on one GPU.  Attributes mirror what the reference pipeline reads
     from `generator.model`: `local_attn_size`, `sink_size`, `num_frame_per_block`, plus the shape."""
 
@@ -45,8 +46,8 @@ class CausalWanModel:
             raise ValueError(f"head_dim must be 128 (dim={shape.dim}, heads={shape.num_heads})")
         if tuple(shape.patch_size) != (1, 2, 2):
             raise ValueError("only patch_size (1, 2, 2) is supported")
+        super().__init__(device)
         self.shape = shape
-        self.device = torch.device(device)
         self.dim, self.num_heads, self.num_layers = shape.dim, shape.num_heads, shape.num_layers
         self.local_attn_size = shape.local_attn_size
         self.sink_size = shape.sink_size
@@ -54,17 +55,10 @@ class CausalWanModel:
         self.independent_first_frame = False
         self.fp8 = bool(fp8)
         self.fp8_weights: Dict[str, tuple] = {}
-        self._keep: List[Tensor] = []      # every device tensor the C struct points into
-        self._workspaces: Dict[tuple, Tensor] = {}
         self._load(state_dict, sched_sigmas, sched_timesteps)
         self._handle = torch_ops.register_model(self)
 
     # ---------------------------------------------------------------------------------
-    def _dev(self, t: Tensor) -> Tensor:
-        t = t.detach().to(device=self.device, dtype=torch.bfloat16).contiguous()
-        self._keep.append(t)
-        return t
-
     def _dev8(self, name: str, parts: List[Tensor]):
         """FP8: the reference Linears `parts` (stacked along N) -> device e4m3 weight + fp32 column scales, quantised on
         the device from the bf16 weights the reference model holds (fp8.py); only these copies are kept
@@ -75,13 +69,7 @@ class CausalWanModel:
         return C.c_void_p(q.data_ptr()), C.c_void_p(s.data_ptr())
 
     def _load(self, sd: Dict[str, Tensor], sigmas: Tensor, timesteps: Tensor) -> None:
-        need = param_shapes(self.shape)
-        missing = [k for k in need if k not in sd]
-        if missing:
-            raise KeyError(f"state dict lacks {len(missing)} tensors, e.g. {missing[:4]}")
-        for k, shp in need.items():
-            if tuple(sd[k].shape) != tuple(shp):
-                raise ValueError(f"{k}: expected shape {shp}, got {tuple(sd[k].shape)}")
+        self._check_state_dict(sd, param_shapes(self.shape), "state dict")
         s = self.shape
         if self.fp8:   # every K an fp8 GEMM sees must be a multiple of its 128-deep k-tile: fail here, not at the first call
             for name, k in (("text_embedding.0", s.text_dim), ("the dim-wide Linears", s.dim), ("ffn.2", s.ffn_dim)):
@@ -158,20 +146,11 @@ class CausalWanModel:
         m.n_table = self.sched_sigmas.numel()
         self.cmodel = m
 
-    def param_bytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
-
     # ---------------------------------------------------------------------------------
     def workspace(self, B: int, F: int, H: int, W: int, G: int) -> Tensor:
         # one workspace per shape AND stream: concurrent rollouts on different HIP streams share the
         # weights but must not share activations
-        key = (B, F, H, W, G, torch.cuda.current_stream(self.device).cuda_stream)
-        ws = self._workspaces.get(key)
-        if ws is None:
-            n = _lib.lib().sf_dit_workspace_bytes(C.byref(self.cmodel), B, F, H, W, G)
-            ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-            self._workspaces[key] = ws
-        return ws
+        return self._stream_bytes((B, F, H, W, G), lambda: _lib.lib().sf_dit_workspace_bytes(C.byref(self.cmodel), B, F, H, W, G))
 
     def forward(self, noisy: Tensor, timestep: Tensor, prompt_embeds: Optional[Tensor], init_cross: bool,
                 k_cache: List[Tensor], v_cache: List[Tensor], ck_cache: List[Tensor], cv_cache: List[Tensor], plan: CachePlan,

@@ -20,6 +20,7 @@ from typing import Callable, List, Optional
 
 import torch
 
+from .kvcache import new_crossattn_cache, new_kv_cache, reset_kv_indices
 from .wan_wrapper import WanDiffusionWrapper
 
 
@@ -344,39 +345,12 @@ class CausalInferencePipeline(torch.nn.Module):
         shape = self.generator.model.shape
         if cache_tokens is None:
             cache_tokens = self._cache_tokens()
-        n = self.num_transformer_blocks
-        index_buffer = torch.zeros(n, 2, dtype=torch.long, device=device)
-        kv_cache1 = []
-        for i in range(n):
-            kv_cache1.append({
-                "k": torch.zeros([batch_size, cache_tokens, shape.num_heads, shape.head_dim], dtype=dtype, device=device),
-                "v": torch.zeros([batch_size, cache_tokens, shape.num_heads, shape.head_dim], dtype=dtype, device=device),
-                "global_end_index": index_buffer[i, 0:1],
-                "local_end_index": index_buffer[i, 1:2],
-                "_sf_index_buffer": index_buffer,
-            })
-        kv_cache1[0]["_sf_mirror"] = (kv_cache1[0]["global_end_index"], kv_cache1[0]["local_end_index"], 0, 0)
-        # the forward call's last kernel writes all 2 x L indices at once while the dicts still hold THESE views
-        kv_cache1[0]["_sf_index_views"] = [(kv["global_end_index"], kv["local_end_index"]) for kv in kv_cache1]
-        self.kv_cache1 = kv_cache1
+        self.kv_cache1 = new_kv_cache(shape, self.num_transformer_blocks, batch_size, cache_tokens, dtype, device)
 
     def _reset_kv_indices(self):
-        buf = self.kv_cache1[0].get("_sf_index_buffer")
-        if buf is not None:
-            buf.zero_()
-            d0 = self.kv_cache1[0]
-            d0["_sf_mirror"] = (d0["global_end_index"], d0["local_end_index"], 0, 0)
-        else:  # foreign cache: rebind as the reference does (causal_inference.py:128-132)
-            dev = self.kv_cache1[0]["k"].device
-            for kv in self.kv_cache1:
-                kv["global_end_index"] = torch.tensor([0], dtype=torch.long, device=dev)
-                kv["local_end_index"] = torch.tensor([0], dtype=torch.long, device=dev)
+        reset_kv_indices(self.kv_cache1)
 
     def _initialize_crossattn_cache(self, batch_size, dtype, device):
         """causal_inference.py:300-312."""
         shape = self.generator.model.shape
-        self.crossattn_cache = [{
-            "k": torch.zeros([batch_size, shape.text_len, shape.num_heads, shape.head_dim], dtype=dtype, device=device),
-            "v": torch.zeros([batch_size, shape.text_len, shape.num_heads, shape.head_dim], dtype=dtype, device=device),
-            "is_init": False,
-        } for _ in range(self.num_transformer_blocks)]
+        self.crossattn_cache = new_crossattn_cache(shape, self.num_transformer_blocks, batch_size, dtype, device)

@@ -14,11 +14,12 @@ There is no eager/CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Tuple, Union
+from typing import Dict, Optional, Tuple, Union
 
 import torch
 
 from . import _lib
+from .device_model import DeviceModel
 from .pose_weights import (CIN_STORE, DWPOSE_LAYERS, POSE_DIM, RANDOMREF_DIM, RANDOMREF_LAYERS, pad_pose_bias, pose_plan, ref_plan, repack_pose_conv,
                            repack_pose_embed, split_pose_state_dict)
 
@@ -32,15 +33,13 @@ def load_pose_state_dict(state_dict_or_path: Union[str, Dict[str, Tensor]]) -> D
     return state_dict_or_path
 
 
-class PoseEmbedder:
+class PoseEmbedder(DeviceModel):
     """Device-resident `dwpose_embedding` + `randomref_embedding_pose`: repacked weights and the C model descriptor.
     `state_dict` names carry the `dwpose_embedding.` / `randomref_embedding_pose.` prefixes; `strict` as
     `load_pose_embedding_weights` (:124-145).  A stack the file does not hold cannot be run."""
 
     def __init__(self, state_dict_or_path: Union[str, Dict[str, Tensor]], device="cuda", strict: bool = True):
-        self.device = torch.device(device)
-        self._keep: List[Tensor] = []
-        self._scratch: Dict[tuple, Tensor] = {}
+        super().__init__(device)
         dw, ref = split_pose_state_dict(load_pose_state_dict(state_dict_or_path), strict=strict)
         m = _lib.PoseModel()
         self.has_dwpose, self.has_randomref = dw is not None, ref is not None
@@ -55,11 +54,6 @@ class PoseEmbedder:
             for i, (idx, _, cout, _, stride, _, act) in enumerate(RANDOMREF_LAYERS):
                 self._layer(m.ref_conv[i], ref[f"{idx}.weight"], ref[f"{idx}.bias"], CIN_STORE if i == 0 else 0, 1, 1, stride[0], act)
         self.cmodel = m
-
-    def _dev(self, t: Tensor, dtype) -> Tensor:
-        t = t.detach().to(device=self.device, dtype=dtype).contiguous()
-        self._keep.append(t)
-        return t
 
     def _layer(self, dst: _lib.PoseLayer, w: Tensor, b: Tensor, cin_store: int, kt: int, stride_t: int, stride_s: int, act: bool) -> None:
         rp = self._dev(repack_pose_conv(w.float(), cin_store), torch.bfloat16)
@@ -76,11 +70,8 @@ class PoseEmbedder:
         return n
 
     def _scratch_for(self, num_frames: int, H: int, W: int) -> Tensor:
-        key = (num_frames, H, W, torch.cuda.current_stream(self.device).cuda_stream)
-        if key not in self._scratch:
-            self._scratch.clear()      # one clip at a time: a full-size clip's scratch is a few GB
-            self._scratch[key] = torch.empty(self.scratch_bytes(num_frames, H, W), dtype=torch.uint8, device=self.device)
-        return self._scratch[key]
+        # one clip at a time: a full-size clip's scratch is a few GB
+        return self._stream_bytes((num_frames, H, W), lambda: self.scratch_bytes(num_frames, H, W), keep_one=True)
 
     def _pose_input(self, x: Tensor, what: str) -> Tuple[Tensor, int]:
         name = str(x.dtype).replace("torch.", "")

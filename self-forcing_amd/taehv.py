@@ -14,18 +14,19 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import torch
 
 from . import _lib, torch_ops
+from .device_model import DeviceModel
 from .taehv_weights import (FRAMES_TO_TRIM, LATENT_CHANNELS, N_F, SPATIAL_FACTOR, STAGE_FIRST, TAEHV_CHECKPOINT, TEMPORAL_FACTOR, TGROW,
                             fold_tgrow, patch_tgrow_rows, repack_memblock_conv0, repack_taehv_conv, taehv_param_shapes)
 
 Tensor = torch.Tensor
 
 
-class TAEHVDecoder:
+class TAEHVDecoder(DeviceModel):
     """Device-resident decoder: repacked bf16 weights, the C model descriptor, and per latent size one decode state (the
     nine MemBlock memories of one stream).  Counterpart of `TAEHV.decode_video` (taehv.py:222-234)."""
 
@@ -34,19 +35,12 @@ class TAEHVDecoder:
         self.param_shapes = taehv_param_shapes(decoder_time_upscale, decoder_space_upscale)   # ValueError on other switches
         if not 1 <= frames_per_call <= 64:
             raise ValueError("frames_per_call must be in 1..64")
-        self.device = torch.device(device)
+        super().__init__(device)
         self.frames_per_call = frames_per_call          # latent frames handed to one C call (any value gives the same bits)
-        self._keep: List[Tensor] = []
         self._state: Dict[tuple, Tensor] = {}
-        self._scratch: Dict[tuple, Tensor] = {}
         self._load(state_dict)
 
     # ---------------------------------------------------------------------------------
-    def _dev(self, t: Tensor) -> Tensor:
-        t = t.detach().to(device=self.device, dtype=torch.bfloat16).contiguous()
-        self._keep.append(t)
-        return t
-
     def _layer(self, dst: _lib.TaehvLayer, w: Tensor, bias: Optional[Tensor], cin_pad: int = 0) -> None:
         if w.dim() == 4:
             w = w.unsqueeze(2)
@@ -58,13 +52,7 @@ class TAEHVDecoder:
 
     def _load(self, sd: Dict[str, Tensor]) -> None:
         sd = patch_tgrow_rows(sd)
-        need = self.param_shapes
-        missing = [k for k in need if k not in sd]
-        if missing:
-            raise KeyError(f"TAEHV state dict lacks {len(missing)} decoder tensors, e.g. {missing[:4]}")
-        for k, shp in need.items():
-            if tuple(sd[k].shape) != tuple(shp):
-                raise ValueError(f"{k}: expected shape {shp}, got {tuple(sd[k].shape)}")
+        self._check_state_dict(sd, self.param_shapes, "TAEHV state dict", "decoder tensors")
         m = _lib.TaehvModel()
         m.z_dim = LATENT_CHANNELS
         self._layer(m.in_conv, sd["decoder.1.weight"], sd["decoder.1.bias"], cin_pad=32)
@@ -79,9 +67,6 @@ class TAEHVDecoder:
         self._layer(m.head, sd["decoder.22.weight"], sd["decoder.22.bias"])
         self.cmodel = m
         self._handle = torch_ops.register_model(self)
-
-    def param_bytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
 
     def state_bytes(self, h: int, w: int) -> int:
         return int(_lib.lib().sf_taehv_state_bytes(C.byref(self.cmodel), h, w))
@@ -100,10 +85,7 @@ class TAEHVDecoder:
             if n == 0:
                 _lib.check(-1, "sf_taehv_state_bytes")
             self._state[key] = torch.zeros(n, dtype=torch.uint8, device=self.device)      # zero = a fresh memory
-        skey = (h, w, torch.cuda.current_stream(self.device).cuda_stream)
-        if skey not in self._scratch:
-            self._scratch[skey] = torch.empty(self.scratch_bytes(h, w), dtype=torch.uint8, device=self.device)
-        return self._state[key], self._scratch[skey]
+        return self._state[key], self._stream_bytes(key, lambda: self.scratch_bytes(h, w))
 
     def clear_cache(self) -> None:
         """Forget every MemBlock's memory: the next frame's `past` is zero (taehv.py:115-116)."""

@@ -21,6 +21,7 @@ from typing import Callable, Dict, List, Optional
 import torch
 
 from . import _lib, torch_ops
+from .device_model import DeviceModel
 from .t5_weights import T5Shape, UMT5_XXL, t5_param_shapes
 
 Tensor = torch.Tensor
@@ -40,22 +41,14 @@ def relative_position_buckets(seq_len: int, num_buckets: int = 32, max_dist: int
     return (buckets + torch.where(rp < max_exact, rp, large)).to(torch.int32)
 
 
-class UMT5Encoder:
+class UMT5Encoder(DeviceModel):
     """Device-resident encoder weights + the C model descriptor (counterpart of `T5Encoder`, t5.py:266-312)."""
 
     def __init__(self, shape: T5Shape, state_dict: Dict[str, Tensor], device):
+        super().__init__(device)
         self.shape = shape
-        self.device = torch.device(device)
-        self._keep: List[Tensor] = []
-        self._ws: Dict[tuple, Tensor] = {}
         self._buckets: Dict[int, Tensor] = {}
-        need = t5_param_shapes(shape)
-        missing = [k for k in need if k not in state_dict]
-        if missing:
-            raise KeyError(f"T5 state dict lacks {len(missing)} encoder tensors, e.g. {missing[:4]}")
-        for k, shp in need.items():
-            if tuple(state_dict[k].shape) != tuple(shp):
-                raise ValueError(f"{k}: expected shape {shp}, got {tuple(state_dict[k].shape)}")
+        self._check_state_dict(state_dict, t5_param_shapes(shape), "T5 state dict", "encoder tensors")
         if shape.head_dim != 64 or shape.dim % 512 or shape.dim_ffn % 64:
             raise ValueError("supported encoder shapes: head_dim 64, dim a multiple of 512, dim_ffn a multiple of 64")
         sd = state_dict
@@ -81,14 +74,6 @@ class UMT5Encoder:
         self.cmodel = m
         self._handle = torch_ops.register_model(self)
 
-    def _dev(self, t: Tensor) -> Tensor:
-        t = t.detach().to(device=self.device, dtype=torch.bfloat16).contiguous()
-        self._keep.append(t)
-        return t
-
-    def param_bytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
-
     def __call__(self, ids: Tensor, mask: Tensor) -> Tensor:
         """`T5Encoder.forward(ids, mask)` + the zero padding of `WanTextEncoder.forward`: ids, mask [B, L] ->
         bf16 [B, L, dim]."""
@@ -101,13 +86,7 @@ class UMT5Encoder:
         B, L = ids.shape
         if L not in self._buckets:
             self._buckets[L] = relative_position_buckets(L, self.shape.num_buckets, self.shape.max_dist).to(self.device)
-        key = (B, L, torch.cuda.current_stream(self.device).cuda_stream)
-        if key not in self._ws:
-            n = _lib.lib().sf_t5_workspace_bytes(C.byref(self.cmodel), B, L)
-            if n == 0:
-                _lib.check(-1, "sf_t5_workspace_bytes")
-            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self.device)
-        ws = self._ws[key]
+        ws = self._stream_bytes((B, L), lambda: _lib.lib().sf_t5_workspace_bytes(C.byref(self.cmodel), B, L), "sf_t5_workspace_bytes")
         return torch.ops.sf_hip.t5_encode(self._handle, ids, mask, self._buckets[L], ws)
 
 

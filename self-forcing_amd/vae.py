@@ -14,11 +14,12 @@ fallback.  The encoder (image-to-video, inference.py:145) needs the checkpoint's
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import torch
 
 from . import _lib, torch_ops
+from .device_model import DeviceModel
 from .vae_weights import (LATENT_MEAN, LATENT_STD, ResBlockSpec, ResampleSpec, VaeShape, WAN_VAE, decoder_layout,
                           encode_chunks, encoder_dims, encoder_layout, encoder_param_shapes, vae_param_shapes)
 
@@ -52,29 +53,27 @@ class _StreamPos:
         self.slot = 0          # ... of them in the current lap of the sliding history windows (sf_vae_decode_frames)
 
 
-class WanVAEDecoder:
-    """Device-resident decoder: repacked bf16 weights, the C model descriptor, and one decode state
-    (the convolution histories of one stream).  Counterpart of `WanVAE_` (wan/modules/vae.py:478-617)
-    for `decode` / `cached_decode` / `clear_cache`."""
+def window_step(slot: int, g: int, K: int):
+    """One step of the sliding history windows (sf_vae_decode_frames / sf_vae_encode_frames): the next group of `g`
+    frames, with `slot` of the K slots of the current lap taken, goes to slot `window`; the histories it reads are where
+    the previous call left them, at `history_at`.  A group that does not fit restarts the lap at slot 0.  The caller
+    advances: slot = window + g."""
+    if slot + g > K:
+        return 0, slot
+    return slot, slot
 
-    def __init__(self, shape: VaeShape, state_dict: Dict[str, Tensor], device, frames_per_call: int = 4):
+
+class _VAEWeights(DeviceModel):
+    """What the decoder and the encoder share: the repacking of `CausalConv3d` / `ResidualBlock` / `AttentionBlock`
+    weights into their C descriptors, and the per-size state + per-stream scratch blocks."""
+
+    def __init__(self, shape: VaeShape, device, frames_per_call: int):
         if not 1 <= frames_per_call <= 63:
             raise ValueError("frames_per_call must be in 1..63")
+        super().__init__(device)
         self.shape = shape
-        self.device = torch.device(device)
-        self.frames_per_call = frames_per_call          # latent frames handed to one C call (any value gives the same bits)
-        self.window_frames = frames_per_call + 1        # slots of the sliding history windows (the first chunk + one group)
-        self._keep: List[Tensor] = []
+        self.frames_per_call = frames_per_call          # latent frames / 4-frame chunks handed to one C call (any value gives the same bits)
         self._state: Dict[tuple, Tensor] = {}
-        self._scratch: Dict[tuple, Tensor] = {}
-        self._pos: Dict[tuple, _StreamPos] = {}     # per latent size, beside its state: where that stream stands
-        self._load(state_dict)
-
-    # ---------------------------------------------------------------------------------
-    def _dev(self, t: Tensor, dtype=torch.bfloat16) -> Tensor:
-        t = t.detach().to(device=self.device, dtype=dtype).contiguous()
-        self._keep.append(t)
-        return t
 
     def _conv(self, dst: _lib.VaeConv, sd, name: str, cin_pad: Optional[int] = None) -> None:
         w = sd[name + ".weight"]
@@ -95,15 +94,40 @@ class WanVAEDecoder:
         if spec.in_dim != spec.out_dim:
             self._conv(dst.shortcut, sd, p + "shortcut")
 
+    def _attn(self, m, sd, a: str, c: int) -> None:
+        """AttentionBlock `a` of width c into m.attn_*: to_qkv split into the q|k rows and the v rows, proj."""
+        qkv_w, qkv_b = sd[a + "to_qkv.weight"].reshape(3 * c, c), sd[a + "to_qkv.bias"]
+        m.attn_gamma = self._dev(sd[a + "norm.gamma"].flatten()).data_ptr()
+        m.attn_qk_w, m.attn_qk_b = self._dev(qkv_w[:2 * c]).data_ptr(), self._dev(qkv_b[:2 * c]).data_ptr()
+        m.attn_v_w, m.attn_v_b = self._dev(qkv_w[2 * c:]).data_ptr(), self._dev(qkv_b[2 * c:]).data_ptr()
+        m.attn_proj_w = self._dev(sd[a + "proj.weight"].reshape(c, c)).data_ptr()
+        m.attn_proj_b = self._dev(sd[a + "proj.bias"]).data_ptr()
+
+    def _state_scratch(self, key: tuple, state_bytes: str, scratch_bytes: str, *size):
+        """(state, scratch) of `key`, sized by the two C functions named on `size`: the state -- the convolution
+        histories -- zeroed on first use, the scratch per stream."""
+        if key not in self._state:
+            n = getattr(_lib.lib(), state_bytes)(C.byref(self.cmodel), *size)
+            if n == 0:
+                _lib.check(-1, state_bytes)
+            self._state[key] = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        return self._state[key], self._stream_bytes(key, lambda: getattr(_lib.lib(), scratch_bytes)(C.byref(self.cmodel), *size))
+
+
+class WanVAEDecoder(_VAEWeights):
+    """Device-resident decoder: repacked bf16 weights, the C model descriptor, and one decode state
+    (the convolution histories of one stream).  Counterpart of `WanVAE_` (wan/modules/vae.py:478-617)
+    for `decode` / `cached_decode` / `clear_cache`."""
+
+    def __init__(self, shape: VaeShape, state_dict: Dict[str, Tensor], device, frames_per_call: int = 4):
+        super().__init__(shape, device, frames_per_call)
+        self.window_frames = frames_per_call + 1        # slots of the sliding history windows (the first chunk + one group)
+        self._pos: Dict[tuple, _StreamPos] = {}     # per latent size, beside its state: where that stream stands
+        self._load(state_dict)
+
     def _load(self, sd: Dict[str, Tensor]) -> None:
         s = self.shape
-        need = vae_param_shapes(s)
-        missing = [k for k in need if k not in sd]
-        if missing:
-            raise KeyError(f"VAE state dict lacks {len(missing)} decoder tensors, e.g. {missing[:4]}")
-        for k, shp in need.items():
-            if tuple(sd[k].shape) != tuple(shp):
-                raise ValueError(f"{k}: expected shape {shp}, got {tuple(sd[k].shape)}")
+        self._check_state_dict(sd, vae_param_shapes(s), "VAE state dict", "decoder tensors")
         if any(d % 32 for d in s.dims) or s.dims[0] % 64:
             raise ValueError(f"decoder widths {s.dims} must be multiples of 32 (first: 64)")
         if len(s.dim_mult) > _lib.VAE_MAX_STAGES:
@@ -120,13 +144,7 @@ class WanVAEDecoder:
         middle, ups = decoder_layout(s)
         self._res(m.mid0, sd, middle[0])
         self._res(m.mid2, sd, middle[2])
-        a, c = middle[1], s.dims[0]
-        qkv_w, qkv_b = sd[a + "to_qkv.weight"].reshape(3 * c, c), sd[a + "to_qkv.bias"]
-        m.attn_gamma = self._dev(sd[a + "norm.gamma"].flatten()).data_ptr()
-        m.attn_qk_w, m.attn_qk_b = self._dev(qkv_w[:2 * c]).data_ptr(), self._dev(qkv_b[:2 * c]).data_ptr()
-        m.attn_v_w, m.attn_v_b = self._dev(qkv_w[2 * c:]).data_ptr(), self._dev(qkv_b[2 * c:]).data_ptr()
-        m.attn_proj_w = self._dev(sd[a + "proj.weight"].reshape(c, c)).data_ptr()
-        m.attn_proj_b = self._dev(sd[a + "proj.bias"]).data_ptr()
+        self._attn(m, sd, middle[1], s.dims[0])
         blocks = [u for u in ups if isinstance(u, ResBlockSpec)]
         res = (_lib.VaeResBlock * len(blocks))()
         for i, spec in enumerate(blocks):
@@ -142,9 +160,6 @@ class WanVAEDecoder:
         self.cmodel = m
         self._handle = torch_ops.register_model(self)
 
-    def param_bytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
-
     # ---------------------------------------------------------------------------------
     def _buffers(self, h: int, w: int):
         key = (h, w)
@@ -152,17 +167,10 @@ class WanVAEDecoder:
         if (2 + self.window_frames * tf) * (sf * h) * (sf * w) * self.cmodel.head_conv.cin * 2 >= 0xFFFFFF00:
             raise ValueError(f"frames_per_call={self.frames_per_call} at {sf * h}x{sf * w}: a convolution's input volume would pass 4 GiB "
                              "(the kernels address a volume through one 32-bit-ranged buffer descriptor); use fewer frames per call")
-        if key not in self._state:
-            n = _lib.lib().sf_vae_state_bytes(C.byref(self.cmodel), h, w, self.window_frames)
-            if n == 0:
-                _lib.check(-1, "sf_vae_state_bytes")
-            self._state[key] = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        bufs = self._state_scratch(key, "sf_vae_state_bytes", "sf_vae_scratch_bytes", h, w, self.window_frames)
+        if key not in self._pos:
             self._pos[key] = _StreamPos()          # every latent size streams on its own: counters live beside its state
-        skey = (h, w, torch.cuda.current_stream(self.device).cuda_stream)
-        if skey not in self._scratch:
-            n = _lib.lib().sf_vae_scratch_bytes(C.byref(self.cmodel), h, w, self.window_frames)
-            self._scratch[skey] = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return self._state[key], self._scratch[skey]
+        return bufs
 
     def clear_cache(self) -> None:
         """`WanVAE_.clear_cache` (vae.py:610-617): forget every convolution's history."""
@@ -201,10 +209,7 @@ class WanVAEDecoder:
             # frames_per_call latent frames per C call -- bit-identical to one call per frame, but the low-resolution
             # stages fill the chip and every launch has a shorter tail
             g = 1 if pos.fresh else min(self.frames_per_call, F - i)
-            if pos.slot + g > self.window_frames:
-                window, history_at = 0, pos.slot
-            else:
-                window = history_at = pos.slot
+            window, history_at = window_step(pos.slot, g, self.window_frames)
             torch.ops.sf_hip.vae_decode_frames(self._handle, state, scratch, z[i:i + g], out[t0:], h, w, self.window_frames,
                                                pos.nframes, window, history_at)
             pos.slot = window + g
@@ -222,27 +227,18 @@ class WanVAEDecoder:
         return out
 
 
-class WanVAEEncoder(WanVAEDecoder):
+class WanVAEEncoder(_VAEWeights):
     """Device-resident encoder: repacked bf16 weights of `Encoder3d` + `conv1` and the C descriptor; per-(H, W) state
     (the convolution histories) and scratch allocated on first use.  Counterpart of `WanVAE_.encode`
-    (wan/modules/vae.py:517-543).  Shares the decoder's weight repacking (`_conv`, `_res`)."""
+    (wan/modules/vae.py:517-543)."""
 
     def __init__(self, shape: VaeShape, state_dict: Dict[str, Tensor], device, frames_per_call: int = 4):
-        if not 1 <= frames_per_call <= 63:
-            raise ValueError("frames_per_call must be in 1..63")
-        self.shape = shape
-        self.device = torch.device(device)
-        self.frames_per_call = frames_per_call          # 4-frame chunks handed to one C call (any value gives the same bits)
-        self._keep: List[Tensor] = []
-        self._state: Dict[tuple, Tensor] = {}
-        self._scratch: Dict[tuple, Tensor] = {}
+        super().__init__(shape, device, frames_per_call)
         self._load_encoder(state_dict)
 
     def _load_encoder(self, sd: Dict[str, Tensor]) -> None:
         s = self.shape
-        for k, shp in encoder_param_shapes(s).items():
-            if tuple(sd[k].shape) != tuple(shp):
-                raise ValueError(f"{k}: expected shape {shp}, got {tuple(sd[k].shape)}")
+        self._check_state_dict(sd, encoder_param_shapes(s))
         dims = encoder_dims(s)
         if any(d % 32 for d in dims) or dims[-1] % 64:
             raise ValueError(f"encoder widths {dims} must be multiples of 32 (last: 64)")
@@ -272,13 +268,7 @@ class WanVAEEncoder(WanVAEDecoder):
                         self._conv(m.time_conv[i], sd, spec.prefix + "time_conv")
         self._res(m.mid0, sd, middle[0])
         self._res(m.mid2, sd, middle[2])
-        a, c = middle[1], dims[-1]
-        qkv_w, qkv_b = sd[a + "to_qkv.weight"].reshape(3 * c, c), sd[a + "to_qkv.bias"]
-        m.attn_gamma = self._dev(sd[a + "norm.gamma"].flatten()).data_ptr()
-        m.attn_qk_w, m.attn_qk_b = self._dev(qkv_w[:2 * c]).data_ptr(), self._dev(qkv_b[:2 * c]).data_ptr()
-        m.attn_v_w, m.attn_v_b = self._dev(qkv_w[2 * c:]).data_ptr(), self._dev(qkv_b[2 * c:]).data_ptr()
-        m.attn_proj_w = self._dev(sd[a + "proj.weight"].reshape(c, c)).data_ptr()
-        m.attn_proj_b = self._dev(sd[a + "proj.bias"]).data_ptr()
+        self._attn(m, sd, middle[1], dims[-1])
         m.head_gamma = self._dev(sd["encoder.head.0.gamma"].flatten()).data_ptr()
         self._conv(m.head_conv, sd, "encoder.head.2")
         self.cmodel = m
@@ -288,17 +278,7 @@ class WanVAEEncoder(WanVAEDecoder):
         if (2 + K * 4) * H * W * encoder_dims(self.shape)[0] * 2 >= 0xFFFFFF00:
             raise ValueError(f"frames_per_call={self.frames_per_call} at {H}x{W}: a convolution's input volume would pass 4 GiB "
                              "(the kernels address a volume through one 32-bit-ranged buffer descriptor); use fewer frames per call")
-        key = (H, W, K)
-        if key not in self._state:
-            n = _lib.lib().sf_vae_encode_state_bytes(C.byref(self.cmodel), H, W, K)
-            if n == 0:
-                _lib.check(-1, "sf_vae_encode_state_bytes")
-            self._state[key] = torch.zeros(n, dtype=torch.uint8, device=self.device)
-        skey = (H, W, K, torch.cuda.current_stream(self.device).cuda_stream)
-        if skey not in self._scratch:
-            n = _lib.lib().sf_vae_encode_scratch_bytes(C.byref(self.cmodel), H, W, K)
-            self._scratch[skey] = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return self._state[key], self._scratch[skey]
+        return self._state_scratch((H, W, K), "sf_vae_encode_state_bytes", "sf_vae_encode_scratch_bytes", H, W, K)
 
     def encode(self, x: Tensor) -> Tensor:
         """`WanVAE_.encode` (vae.py:517-543) for one sample: x [3, T, H, W] (bf16 or float32, in [-1, 1]) -> float32
@@ -323,10 +303,7 @@ class WanVAEEncoder(WanVAEDecoder):
         i, slot, f0 = 0, 0, 0
         while i < n:
             g = 1 if i == 0 else min(self.frames_per_call, n - i)
-            if slot + g > K:
-                window, history_at = 0, slot
-            else:
-                window = history_at = slot
+            window, history_at = window_step(slot, g, K)
             nf = 1 if i == 0 else 4 * g
             torch.ops.sf_hip.vae_encode_frames(self._handle, state, scratch, x[:, f0:f0 + nf], out[i:i + g], H, W, K, i, window,
                                                history_at)

@@ -33,7 +33,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from .kvcache import plan_cache_update
+from .kvcache import plan_cache_update, read_indices, shared_index_buffer, write_indices
 from .model import CausalWanModel
 from .scheduler import FlowMatchScheduler
 from .weights import (LORA_DEFAULT_TARGETS, NAMED_SHAPES, WanShape, apply_lora_file, load_lora_file, merge_lora, strip_prefix,
@@ -153,40 +153,24 @@ class WanDiffusionWrapper(torch.nn.Module):
         raise NotImplementedError("inference-only path")
 
     # --- cache plumbing -----------------------------------------------------------------------
-    @staticmethod
-    def _read_indices(kv_cache: List[dict]):
-        """Host values of (global_end, local_end).  The pipeline's integers are mirrored in the
-        first layer's dict; a mirror is valid only while the dict still holds the very index
-        tensors we last updated (the reference's reset REBINDS them, causal_inference.py:128-132)."""
-        d = kv_cache[0]
-        mir = d.get("_sf_mirror")
-        if mir is not None and mir[0] is d["global_end_index"] and mir[1] is d["local_end_index"]:
-            return mir[2], mir[3]
-        return int(d["global_end_index"].item()), int(d["local_end_index"].item())
+    _write_indices = staticmethod(write_indices)   # (kv_cache, global_end, local_end): set a cache's position by hand
 
-    @staticmethod
-    def _shared_index_buffer(kv_cache: List[dict]) -> Optional[Tensor]:
-        """The int64 [L, 2] buffer all layers' index tensors are views of (caches built by our pipeline,
-        `_initialize_kv_cache`), while the dicts still hold those very views; None for foreign or rebound caches."""
-        d0 = kv_cache[0]
-        buf, views = d0.get("_sf_index_buffer"), d0.get("_sf_index_views")
-        if buf is None or views is None or len(views) != len(kv_cache):
-            return None
-        for kv, (g, l) in zip(kv_cache, views):
-            if kv["global_end_index"] is not g or kv["local_end_index"] is not l:
-                return None
-        return buf
+    def _latents(self, x: Tensor) -> Tensor:
+        return x.to(device=self.model.device, dtype=torch.bfloat16).contiguous()
 
-    @staticmethod
-    def _write_indices(kv_cache: List[dict], global_end: int, local_end: int, done_by_kernel: bool = False) -> None:
-        """causal_model.py:235-236.  With the shared buffer the forward call's last kernel has written every row
-        (`kv_index_out`); foreign caches get the reference's per-layer fills.  The host mirror is refreshed either way."""
-        d0 = kv_cache[0]
-        if not done_by_kernel:
-            for kv in kv_cache:
-                kv["global_end_index"].fill_(global_end)
-                kv["local_end_index"].fill_(local_end)
-        d0["_sf_mirror"] = (d0["global_end_index"], d0["local_end_index"], global_end, local_end)
+    def _timestep(self, t: Tensor) -> Tensor:
+        """[B] or [B, G] -> [B, G] on the device, int64 kept, anything else float32."""
+        t = t.to(self.model.device)
+        if t.dim() == 1:
+            t = t.unsqueeze(1)
+        return (t if t.dtype == torch.int64 else t.to(torch.float32)).contiguous()
+
+    def _eviction_scratch(self, batch: int, keep: int, cap: int) -> Tensor:
+        """Where sf_kv_evict parks the `keep` tokens it moves; sized once for the whole cache."""
+        dim = self.model.shape.dim
+        if self._evict_scratch is None or self._evict_scratch.numel() < batch * keep * dim * 2:
+            self._evict_scratch = torch.empty(batch * cap * dim * 2, dtype=torch.uint8, device=self.model.device)
+        return self._evict_scratch
 
     # --- two passes in one call ------------------------------------------------------------------
     def can_pair(self, conditional_dict: dict) -> bool:
@@ -207,15 +191,10 @@ class WanDiffusionWrapper(torch.nn.Module):
         xs = []
         for x in (context_input, noisy_image_or_video):
             assert x.dim() == 5 and x.shape[2] == shape.in_dim, "inputs must be [B, F, C, H, W] latents"
-            xs.append(x.to(device=mdl.device, dtype=torch.bfloat16).contiguous())
+            xs.append(self._latents(x))
         assert xs[0].shape == xs[1].shape, "forward_pair: both passes must have the same number of frames"
         B, F, _, H, W = xs[1].shape
-        ts = []
-        for t in (context_timestep, timestep):
-            t = t.to(mdl.device)
-            if t.dim() == 1:
-                t = t.unsqueeze(1)
-            ts.append((t if t.dtype == torch.int64 else t.to(torch.float32)).contiguous())
+        ts = [self._timestep(context_timestep), self._timestep(timestep)]
         assert ts[0].shape == ts[1].shape and ts[0].dtype == ts[1].dtype and ts[0].shape[0] == B, "forward_pair: timesteps must match in shape and dtype"
         assert len(kv_cache) == mdl.num_layers and len(crossattn_cache) == mdl.num_layers
         assert crossattn_cache[0]["is_init"], "forward_pair: the cross-attention cache is filled by the chunk's earlier passes"
@@ -223,20 +202,15 @@ class WanDiffusionWrapper(torch.nn.Module):
         n_new = F * fs
         cap = kv_cache[0]["k"].shape[1]
         window = cap if mdl.local_attn_size == -1 else mdl.local_attn_size * fs
-        global_end, local_end = self._read_indices(kv_cache)
+        global_end, local_end = read_indices(kv_cache)
         plan0 = plan_cache_update(local_end, global_end, context_start, n_new, cap, mdl.local_attn_size, mdl.sink_size * fs, window)
         plan1 = plan_cache_update(plan0.local_end, plan0.global_end, current_start, n_new, cap, mdl.local_attn_size, mdl.sink_size * fs, window)
-        scratch = None
-        if plan0.evict > 0 or plan1.evict > 0:
-            need = B * max(plan0.keep, plan1.keep) * shape.dim * 2
-            if self._evict_scratch is None or self._evict_scratch.numel() < need:
-                self._evict_scratch = torch.empty(B * cap * shape.dim * 2, dtype=torch.uint8, device=mdl.device)
-            scratch = self._evict_scratch
-        index_buf = self._shared_index_buffer(kv_cache)
+        scratch = self._eviction_scratch(B, max(plan0.keep, plan1.keep), cap) if plan0.evict > 0 or plan1.evict > 0 else None
+        index_buf = shared_index_buffer(kv_cache)
         flow, x0 = mdl.forward_pair(xs[0], ts[0], xs[1], ts[1], [kv["k"] for kv in kv_cache], [kv["v"] for kv in kv_cache],
                                     [c["k"] for c in crossattn_cache], [c["v"] for c in crossattn_cache], plan0, plan1,
                                     context_start // fs, current_start // fs, scratch, kv_index=index_buf)
-        self._write_indices(kv_cache, plan1.global_end, plan1.local_end, done_by_kernel=index_buf is not None)
+        write_indices(kv_cache, plan1.global_end, plan1.local_end, done_by_kernel=index_buf is not None)
         self._pace(mdl.device)
         return flow, x0
 
@@ -270,11 +244,8 @@ class WanDiffusionWrapper(torch.nn.Module):
             "cache lists must have one entry per transformer block"
         if current_start is None:
             current_start = 0
-        x = x.to(device=mdl.device, dtype=torch.bfloat16).contiguous()
-        t = timestep.to(mdl.device)
-        if t.dim() == 1:
-            t = t.unsqueeze(1)
-        t = (t if t.dtype == torch.int64 else t.to(torch.float32)).contiguous()
+        x = self._latents(x)
+        t = self._timestep(timestep)
         assert t.shape[0] == B, "timestep must be [B, groups]"
 
         fs = (H // 2) * (W // 2)
@@ -287,16 +258,11 @@ class WanDiffusionWrapper(torch.nn.Module):
         assert tuple(c0.shape) == (B, shape.text_len, shape.num_heads, shape.head_dim) and c0.is_contiguous(), \
             f"cross-attention cache must be [B, {shape.text_len}, {shape.num_heads}, {shape.head_dim}]"
 
-        global_end, local_end = self._read_indices(kv_cache)
+        global_end, local_end = read_indices(kv_cache)
         window = cap if mdl.local_attn_size == -1 else mdl.local_attn_size * fs
         plan = plan_cache_update(local_end, global_end, current_start, n_new, cap, mdl.local_attn_size,
                                  mdl.sink_size * fs, window)
-        scratch = None
-        if plan.evict > 0:
-            need = B * plan.keep * shape.dim * 2
-            if self._evict_scratch is None or self._evict_scratch.numel() < need:
-                self._evict_scratch = torch.empty(B * cap * shape.dim * 2, dtype=torch.uint8, device=mdl.device)
-            scratch = self._evict_scratch
+        scratch = self._eviction_scratch(B, plan.keep, cap) if plan.evict > 0 else None
 
         init_cross = not crossattn_cache[0]["is_init"]
         pe = None
@@ -317,7 +283,7 @@ class WanDiffusionWrapper(torch.nn.Module):
                 raise ValueError(f"add_condition spatial dim {add_condition.shape[1]} doesn't match "
                                  f"x spatial dim {n_new}. Check pose data processing.")
             assert add_condition.shape[2] == mdl.cmodel.pose_dim, "add_condition channel width must match pose_proj"
-        index_buf = self._shared_index_buffer(kv_cache)
+        index_buf = shared_index_buffer(kv_cache)
         flow, x0 = mdl.forward(x, t, pe, init_cross, [kv["k"] for kv in kv_cache], [kv["v"] for kv in kv_cache],
                                [c["k"] for c in crossattn_cache], [c["v"] for c in crossattn_cache], plan,
                                current_start // fs, scratch, cache_only=cache_only, add_condition=add_condition,
@@ -325,6 +291,6 @@ class WanDiffusionWrapper(torch.nn.Module):
         if init_cross:
             for c in crossattn_cache:
                 c["is_init"] = True
-        self._write_indices(kv_cache, plan.global_end, plan.local_end, done_by_kernel=index_buf is not None)
+        write_indices(kv_cache, plan.global_end, plan.local_end, done_by_kernel=index_buf is not None)
         self._pace(mdl.device)
         return flow, x0

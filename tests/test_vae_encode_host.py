@@ -31,6 +31,11 @@ def test_encoder_weights_leave_the_decoder_weights_unchanged():
         for k, shp in vw.encoder_param_shapes(shape).items():
             assert tuple(both[k].shape) == shp
         assert both["encoder.middle.1.proj.weight"].float().abs().sum() > 0      # the attention block is not the identity
+    # the encoder object shares the decoder's weight repacking, not its decode methods
+    from self_forcing_amd.vae import WanVAEDecoder, WanVAEEncoder
+    encoder = WanVAEEncoder(vw.VAE_REDUCED, vw.synth_vae_state_dict(vw.VAE_REDUCED, seed=0, encoder=True), "cpu")
+    assert not issubclass(WanVAEEncoder, WanVAEDecoder)
+    assert not hasattr(encoder, "cached_decode")
 
 
 def test_chunk_plan_matches_the_reference_loop():
