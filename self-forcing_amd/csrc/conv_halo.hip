@@ -21,6 +21,7 @@
 // conflicts for every alignment of the first position (checked exhaustively against the lane groups of
 // MI355X_MICROARCH.md): the taps' shifts cost nothing.  The swizzle is applied on the LDS-DMA's source address.
 #include "sf_common.h"
+#include "lds_dma.h"
 #include "../../include/sf_hip.h"
 
 namespace {
@@ -44,9 +45,6 @@ struct HaloP {
   int patches_h, patches_w, tiles_n;
   unsigned x_bytes;
 };
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 __device__ __forceinline__ int swz16(int r, int c) { return (c ^ (((r >> 2) & 1) << 1)) << 4; }
 
@@ -89,20 +87,8 @@ __global__ __launch_bounds__(HALO_THREADS) void conv_halo_kernel(HaloP p) {
     const int kq = (lane & 3) ^ (((pos >> 2) & 1) << 1);
     pl_off[i] = valid ? (unsigned)((((long)hin * p.Win + win) * p.Cin) * 2 + kq * 16) : OOR;
   }
-  u32x4 x_srd;
-  {
-    const unsigned long long a64 = (unsigned long long)p.x;
-    x_srd[0] = __builtin_amdgcn_readfirstlane((unsigned)a64);
-    x_srd[1] = __builtin_amdgcn_readfirstlane((unsigned)(a64 >> 32) & 0xFFFFu);
-    x_srd[2] = __builtin_amdgcn_readfirstlane(p.x_bytes);
-    x_srd[3] = 0x00020000u;
-  }
+  const u32x4 x_srd = lds_dma_srd(p.x, p.x_bytes);   // range-checked view of the input volume
   const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
-  auto dma_x = [&](unsigned voff, unsigned lds_addr) __attribute__((always_inline)) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 4\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_addr), "v"(voff), "s"(x_srd) : "memory");
-  };
   const unsigned frameB = (unsigned)(p.Hin * p.Win * p.Cin * 2);
   auto request_plane = [&](int P) __attribute__((always_inline)) {     // plane P = (channel slice cs, temporal tap dt)
     const int cs = P / p.kt, dt = P - cs * p.kt;
@@ -112,7 +98,7 @@ __global__ __launch_bounds__(HALO_THREADS) void conv_halo_kernel(HaloP p) {
     for (int i = 0; i < 3; ++i) {
       const int j = wave + 8 * i;
       const unsigned dst = __builtin_amdgcn_readfirstlane(j < NP ? slot + (unsigned)j * 1024u : lds_base + (unsigned)(DUMMY + wave * 1024));
-      dma_x(pl_off[i] == OOR ? OOR : pl_off[i] + add, dst);
+      lds_dma16_checked(x_srd, pl_off[i] == OOR ? OOR : pl_off[i] + add, dst);
     }
   };
   // A weight piece = 16 rows (output channels) x 64 B of one tap; wave w requests pieces w + 8 i of the cluster

@@ -24,6 +24,7 @@
 // depth) replaces the two bf16 MFMAs of a 16 x 16 tile: the cycles per k-tile and the phase schedule stay as they are.
 #include <type_traits>
 #include "sf_common.h"
+#include "lds_dma.h"
 #include "../../include/sf_hip.h"
 
 namespace {
@@ -51,13 +52,6 @@ struct GemmP {
   const float* w_scale;          // F8 only: fp32 [N]
   int rows_per_seg;
 };
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ void glds16(const bf16_t* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)lds_wave_base, 16, 0, 0);
-}
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));

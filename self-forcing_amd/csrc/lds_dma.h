@@ -1,5 +1,6 @@
-// Global -> LDS copies without a register round trip (LDS-DMA) for the implicit-GEMM convolutions (conv_igemm.hip,
-// taehv_conv.hip): the flat form, and the range-checked buffer form whose out-of-range lanes write zeros to LDS.
+// Global -> LDS copies without a register round trip (LDS-DMA): the flat form (gemm_bf16.hip, conv_halo.hip's weights, the
+// W tiles of conv_igemm_core.h), and the range-checked buffer form whose out-of-range lanes write zeros to LDS (the
+// gathered A tiles of conv_igemm_core.h, i.e. conv_igemm.hip and taehv_conv.hip, and conv_halo.hip's planes).
 #pragma once
 #include "sf_common.h"
 
@@ -29,7 +30,4 @@ __device__ __forceinline__ void lds_dma16_checked(u32x4 srd, unsigned voff, unsi
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 4\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "s"(lds_addr), "v"(voff), "s"(srd) : "memory");
 }
-
-// chunk swizzle of a 128-byte LDS row: 16-byte chunk c of row r lives at chunk c ^ ((r >> 1) & 7)
-__device__ __forceinline__ int lds_swizzle(int r, int c) { return c ^ ((r >> 1) & 7); }
 #endif

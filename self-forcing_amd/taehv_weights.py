@@ -17,7 +17,7 @@ from typing import Dict, List, Tuple
 
 import torch
 
-from .vae_weights import _synth
+from .vae_weights import _synth, repack_conv
 
 Tensor = torch.Tensor
 
@@ -95,20 +95,7 @@ def fold_tgrow(tgrow_w: Tensor, conv_w: Tensor) -> Tensor:
     return out.reshape(s * conv_w.shape[0], c, 3, 3)
 
 
-def repack_taehv_conv(w: Tensor, cin_pad: int = 0) -> Tensor:
-    """Conv weight [Cout, Cin, 3, 3] or [Cout, Cin, kt, 3, 3] -> `sf_taehv_conv_args.w`: [Cout][Kpad] with
-    k = ((dt*3 + dh)*3 + dw)*Cin_pad + ci, Cin padded to a multiple of 32 and K to a multiple of 64 (zeros)."""
-    if w.dim() == 4:
-        w = w.unsqueeze(2)
-    cout, cin, kt, kh, kw = w.shape
-    cp = cin_pad or ((cin + 31) // 32) * 32
-    t = torch.zeros(cout, kt, kh, kw, cp, dtype=w.dtype, device=w.device)
-    t[..., :cin] = w.permute(0, 2, 3, 4, 1)
-    k = kt * kh * kw * cp
-    kpad = ((k + 63) // 64) * 64
-    out = torch.zeros(cout, kpad, dtype=w.dtype, device=w.device)
-    out[:, :k] = t.reshape(cout, k)
-    return out
+repack_taehv_conv = repack_conv   # one packer for both convolution kernels: they read the same layout
 
 
 def frames_out(latent_frames: int, fresh: bool) -> int:

@@ -21,26 +21,9 @@ import torch
 from . import _lib, torch_ops
 from .device_model import DeviceModel
 from .vae_weights import (LATENT_MEAN, LATENT_STD, ResBlockSpec, ResampleSpec, VaeShape, WAN_VAE, decoder_layout,
-                          encode_chunks, encoder_dims, encoder_layout, encoder_param_shapes, vae_param_shapes)
+                          encode_chunks, encoder_dims, encoder_layout, encoder_param_shapes, repack_conv, vae_param_shapes)
 
 Tensor = torch.Tensor
-
-
-def repack_conv(w: Tensor, cin_pad: Optional[int] = None) -> Tensor:
-    """Conv3d / Conv2d weight [Cout, Cin, (kt,) kh, kw] -> the implicit-GEMM layout of `sf_conv_args.w`:
-    [Cout][Kpad] with k = ((dt*kh + dh)*kw + dw)*Cin_pad + ci, Cin padded to a multiple of 32 and K to a
-    multiple of 64 (zeros)."""
-    if w.dim() == 4:
-        w = w.unsqueeze(2)
-    cout, cin, kt, kh, kw = w.shape
-    cp = cin_pad or ((cin + 31) // 32) * 32
-    t = torch.zeros(cout, kt, kh, kw, cp, dtype=w.dtype, device=w.device)
-    t[..., :cin] = w.permute(0, 2, 3, 4, 1)
-    k = kt * kh * kw * cp
-    kpad = ((k + 63) // 64) * 64
-    out = torch.zeros(cout, kpad, dtype=w.dtype, device=w.device)
-    out[:, :k] = t.reshape(cout, k)
-    return out
 
 
 class _StreamPos:

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, asdict
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -239,6 +239,23 @@ def _synth(shapes: Dict[str, Tuple[int, ...]], g: torch.Generator, dtype) -> Dic
             t = torch.empty(shape).uniform_(-a, a, generator=g)
         sd[name] = t.to(dtype)
     return sd
+
+
+def repack_conv(w: Tensor, cin_pad: Optional[int] = None) -> Tensor:
+    """Conv3d / Conv2d weight [Cout, Cin, (kt,) kh, kw] -> the implicit-GEMM layout of `sf_conv_args.w` and
+    `sf_taehv_conv_args.w`: [Cout][Kpad] with k = ((dt*kh + dh)*kw + dw)*Cin_pad + ci, Cin padded to a multiple of 32
+    and K to a multiple of 64 (zeros).  Public as `vae.repack_conv`; `taehv_weights.repack_taehv_conv` is this function."""
+    if w.dim() == 4:
+        w = w.unsqueeze(2)
+    cout, cin, kt, kh, kw = w.shape
+    cp = cin_pad or ((cin + 31) // 32) * 32
+    t = torch.zeros(cout, kt, kh, kw, cp, dtype=w.dtype, device=w.device)
+    t[..., :cin] = w.permute(0, 2, 3, 4, 1)
+    k = kt * kh * kw * cp
+    kpad = ((k + 63) // 64) * 64
+    out = torch.zeros(cout, kpad, dtype=w.dtype, device=w.device)
+    out[:, :k] = t.reshape(cout, k)
+    return out
 
 
 # the encoder's tensors come from a generator of their own, so that the decoder's stay what they were without them

@@ -7,6 +7,7 @@
 - the wrapper contract and a reduced pipeline run with `TAEHVWrapper` injected;
 - every convolution the sequencer issues at 60 x 104, per kernel against fp32 torch, overall and per 16 x 16 patch;
 - the MemBlock's first convolution against the Wan VAE's implicit-GEMM kernel (kt = 3, zero oldest tap).
+- kt = 1 against the Wan VAE's implicit-GEMM kernel, bit for bit: the property that lets both kernels share one core.
 
 All comparisons of the whole decode are on y = (out + 1) / 2, the decoder's own output (the `- 1` offset would
 flatter a relative error).  Run with `-m gpu` (`-s` shows the measured figures).
@@ -367,3 +368,23 @@ def test_memblock_conv0_against_the_wan_vae_kernel(c, H, W):
     d = rel(new, old)
     print(f"\nMemBlock conv.0 {c} ch {H}x{W}: new kernel vs conv_igemm(kt=3, zero tap) + relu: rel {d:.2e}", end="")
     assert d <= CROSS_TOL
+
+
+@pytest.mark.parametrize("cin,cout,T,hin,win,up", [(64, 64, 2, 9, 14, False), (32, 128, 1, 5, 7, True)], ids=["plain-252rows", "upsample-9slices"])
+def test_kt1_is_bit_identical_to_the_wan_vae_kernel(cin, cout, T, hin, win, up):
+    """What lets the two kernels share one implicit-GEMM core: with kt = 1 both walk k in the same order into fp32
+    accumulators, add the bias in fp32 and round once, and ReLU commutes with the rounding to bf16.  The plain case has two
+    row tiles, the second partial (M = 252); the upsampled one both parities on both axes and an odd slice count (9: the
+    padding slice).  The equality follows from the code; no GPU run of it is on record yet, neither with the kernels'
+    own copies of the core nor with the shared one."""
+    g = torch.Generator().manual_seed(cin + cout + hin)
+    x = bf((T, hin, win, cin), g)
+    w = bf((cout, cin, 1, 3, 3), g, (9 * cin) ** -0.5)
+    b = bf((cout,), g, 0.1)
+    new = ops.taehv_conv(x.to(DEV), tw.repack_taehv_conv(w).to(DEV), b.to(DEV), 1, T, epilogue="bias_relu", upsample=up)
+    pre = ops.conv_igemm(x.to(DEV), repack_conv(w).to(DEV), b.to(DEV), (1, 3, 3), T, upsample=up, structure="igemm")
+    zeros = float((pre <= 0).float().mean())
+    print(f"\nkt = 1 {cin}->{cout} {tuple(pre.shape)}: {int((new != F.relu(pre)).sum())} differing elements, {zeros:.2f} non-positive", end="")
+    assert 0.2 <= zeros <= 0.8, zeros                                      # the ReLU is exercised
+    assert new.shape == pre.shape == (T, hin * (2 if up else 1), win * (2 if up else 1), cout)
+    assert torch.equal(new, F.relu(pre))
