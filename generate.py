@@ -29,7 +29,8 @@ with the weights of `--pose_weights_path` (a file with `dwpose_embedding.*` / `r
 
 `--i2v` (inference.py:83-90, 136-149) reads `--data_path` as a TextImagePairDataset directory -- one
 `target_crop_info_<ratio>.json` listing `file_name` / `caption` entries, images under `<ratio>/` --, encodes each
-image with the VAE encoder (so it needs a VAE with encoder weights: `--vae_path`, or `--vae_random_init_seed`) as the
+image with the VAE encoder (so it needs a VAE with encoder weights: `--vae_path`, `--vae_random_init_seed`, a
+`--taehv_path` checkpoint that holds the `encoder.*` tensors, as taew2_1.pth does, or `--taehv_random_init_seed`) as the
 first latent frame and draws noise for the `num_output_frames - 1` frames after it.  Single process only, as in the
 reference.
 """
@@ -126,7 +127,7 @@ def main():
                     help="seeded random VAE weights instead (decoder; with --i2v the encoder too)")
     ap.add_argument("--taehv_path", default=None,
                     help="taew2_1.pth: decode with the TAEHV tiny decoder instead (fast preview; not with --vae_path / --vae_random_init_seed)")
-    ap.add_argument("--taehv_random_init_seed", type=int, default=None, help="seeded random TAEHV decoder weights instead")
+    ap.add_argument("--taehv_random_init_seed", type=int, default=None, help="seeded random TAEHV decoder weights instead (with --i2v the encoder too)")
     ap.add_argument("--fp8", action="store_true",
                     help="FP8 linear layers in the generator (the reference's enable_fp8 / torchao PerTensor quantisation)")
     ap.add_argument("--pose_path", default=None, help=".pt / .npy dict with dwpose_data [3, F, H, W] and random_ref_dwpose [H, W, 3] (multi-step sampler)")
@@ -155,8 +156,8 @@ def main():
     if a.i2v:
         if world > 1:
             raise SystemExit("I2V does not support distributed inference yet (inference.py:83)")
-        if not a.vae_path and a.vae_random_init_seed is None:
-            raise SystemExit("--i2v needs a VAE with encoder weights: --vae_path or --vae_random_init_seed")
+        if not a.vae_path and a.vae_random_init_seed is None and not a.taehv_path and a.taehv_random_init_seed is None:
+            raise SystemExit("--i2v needs a VAE with encoder weights: --vae_path, --vae_random_init_seed, --taehv_path or --taehv_random_init_seed")
     torch.cuda.set_device(local_rank)
     grp = RankGroup(backend="nccl", device=torch.device(f"cuda:{local_rank}"))
     device = torch.device(f"cuda:{local_rank}")
@@ -193,7 +194,12 @@ def main():
     if a.taehv_path:
         vae = sfa.TAEHVWrapper(checkpoint_path=a.taehv_path, device=device)
     elif a.taehv_random_init_seed is not None:
-        vae = sfa.TAEHVWrapper(sfa.synth_taehv_state_dict(seed=a.taehv_random_init_seed), device=device)
+        tsd = sfa.synth_taehv_state_dict(seed=a.taehv_random_init_seed)
+        if a.i2v:
+            tsd.update(sfa.synth_taehv_encoder_state_dict(seed=a.taehv_random_init_seed))
+        vae = sfa.TAEHVWrapper(tsd, device=device)
+    if a.i2v and isinstance(vae, sfa.TAEHVWrapper) and vae.encoder is None:
+        raise SystemExit(f"--i2v needs the TAEHV encoder, but {a.taehv_path} holds no encoder.* tensors (taew2_1.pth does)")
     decode = not isinstance(vae, sfa.IdentityVAE)
     jpeg = sfa.JpegEncoder(a.jpeg_quality, a.jpeg_subsampling, device=device) if decode and a.video_format == "mjpeg" else None
     few_step = is_few_step(cfg)        # inference.py:62-67: few-step rollout iff the config has denoising_step_list

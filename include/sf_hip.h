@@ -512,7 +512,8 @@ enum sf_taehv_epilogue {
   SF_TAEHV_BIAS_RESID_RELU = 1,  /* bf16 out = relu(y + bias + resid[row][n])                                    */
   SF_TAEHV_PLAIN = 2,            /* bf16 out = y            (no bias read)                                       */
   SF_TAEHV_RELU = 3,             /* bf16 out = relu(y)      (no bias read)                                       */
-  SF_TAEHV_HEAD_F32 = 4          /* float out_f32[t][n][h][w] = 2 (y + bias) - 1, clamped to [-1, 1] when `clamp` */
+  SF_TAEHV_HEAD_F32 = 4,         /* float out_f32[t][n][h][w] = 2 (y + bias) - 1, clamped to [-1, 1] when `clamp` */
+  SF_TAEHV_LATENT_F32 = 5        /* float out_f32[t][n][h][w] = y + bias (the encoder's head, no scaling)        */
 };
 
 typedef struct sf_taehv_conv_args {
@@ -521,7 +522,7 @@ typedef struct sf_taehv_conv_args {
   const void* bias;       /* [Cout]; may be NULL for the bias-free epilogues                                      */
   void* out;              /* rows of ldo channels; row = t'*H*W + h*W + w                                         */
   const void* resid;      /* [Tout*H*W] rows of ldr channels                                                      */
-  float* out_f32;         /* SF_TAEHV_HEAD_F32 only: [Tout][Cout][H][W], Cout <= 32                               */
+  float* out_f32;         /* SF_TAEHV_HEAD_F32 / SF_TAEHV_LATENT_F32 only: [Tout][Cout][H][W], Cout <= 32         */
   int32_t Tout, H, W;     /* output frames and frame size; the input frame is (H, W), or (H/2, W/2) with upsample */
   int32_t Cin, Cout;
   int32_t kt;             /* temporal taps, 1 or 2                                                                */
@@ -572,6 +573,63 @@ int sf_taehv_reset(const sf_taehv_model* model, void* state, size_t state_bytes,
 int sf_taehv_decode_frames(const sf_taehv_model* model, void* state, size_t state_bytes, void* scratch,
                            size_t scratch_bytes, const void* latent_frames, int lat_h, int lat_w, int n_frames,
                            int clamp, float* pixels_out, void* stream);
+
+/* ==========================================================================================
+ * TAEHV tiny encoder (pixels -> latents): TAEHV.encode_video -> apply_model_with_memblocks over TAEHV.encoder
+ * (demo_utils/taehv.py:172-178, :210-220).  Four pixel frames make one latent frame at 1/8 of the size.  The volumes
+ * and the MemBlock histories are the decoder's; TPool (taehv.py:37-45) never runs as a layer: it is folded by the caller
+ * into the bias-free stride-2 convolution behind it, which then has kt = TPool's stride temporal taps and that temporal
+ * stride (taehv_weights.fold_tpool).
+ * ========================================================================================== */
+
+enum sf_taehv_pixel_dtype { SF_TAEHV_PIXEL_BF16 = 0, SF_TAEHV_PIXEL_F32 = 1 };
+
+/* encoder.0 + ReLU at full resolution, straight from the caller's pixels:
+ *   out[t][h][w][n] = relu(bias[n] + sum_{dh,dw,c} u[src(t)][h+dh-1][w+dw-1][c] * w[n][(dh*3+dw)*3 + c]),
+ *   u = bf16(0.5 * pixel + 0.5) inside the image and 0 outside, src(t) = max(t - lead, 0).
+ * pixels: [3][n_frames - lead][H][W] with channel stride c_stride (elements), values in [-1, 1], bf16 or float32.
+ * w: bf16 [64][32], k = (dh*3+dw)*3 + c, columns 27..31 zero; bias bf16 [64]; out: channels-last bf16
+ * [n_frames][H][W][64].  lead in 0..3 and below n_frames. */
+int sf_taehv_encode_stem(const void* pixels, int dtype, int64_t c_stride, int H, int W, int n_frames, int lead,
+                         const void* w, const void* bias, void* out, void* stream);
+
+/* The encoder's strided convolution (TPool folded in), bf16 out, no bias:
+ *   y[(t,h,w)][n] = sum_{dt<kt,dh,dw,ci} x[kt*t + dt][2h+dh-1][2w+dw-1][ci] * w[n][((dt*3+dh)*3+dw)*Cin + ci]
+ * with zero padding in h/w: kt temporal taps at temporal stride kt, spatial stride 2.  The shared implicit-GEMM core of
+ * sf_taehv_conv with compile-time strides. */
+typedef struct sf_taehv_down_conv_args {
+  const void* x;          /* [kt*Tout][2H][2W][Cin], Cin % 32 == 0                                                */
+  const void* w;          /* [Cout][ldw] as sf_taehv_conv_args.w                                                  */
+  void* out;              /* rows of ldo channels; row = t*H*W + h*W + w                                          */
+  int32_t Tout, H, W;     /* output frames and frame size; the input frame is (2H, 2W)                            */
+  int32_t Cin, Cout;      /* Cout % 64 == 0                                                                       */
+  int32_t kt;             /* temporal taps = temporal stride, 1 or 2                                              */
+  int32_t ldw, ldo;
+} sf_taehv_down_conv_args;
+
+int sf_taehv_down_conv(const sf_taehv_down_conv_args* args, void* stream);
+
+typedef struct sf_taehv_encoder {         /* TAEHV.encoder, taehv.py:172-178                                      */
+  sf_taehv_layer stem;                    /* encoder.0 (3 -> 64) as sf_taehv_encode_stem reads it: cin = ldw = 32 */
+  sf_taehv_layer down[SF_TAEHV_STAGES];   /* TPool folded into the stride-2 3x3 behind it: kt = 2, 2, 1           */
+  sf_taehv_layer block[SF_TAEHV_STAGES][SF_TAEHV_BLOCKS][3];   /* MemBlock.conv.0 (kt = 2) / .2 / .4              */
+  sf_taehv_layer head;                    /* encoder.17 (64 -> z_dim = head.cout)                                 */
+} sf_taehv_encoder;
+
+/* Per-stream persistent state = the one-frame history of each of the nine MemBlock input volumes (at 1/2, 1/4 and 1/8
+ * of H x W); a call carries whole groups of four pixel frames, so TPool holds nothing between calls.  scratch =
+ * everything else, for calls of up to max_frames pixel frames.  0 = malformed arguments (sf_last_error says which). */
+size_t sf_taehv_encode_state_bytes(const sf_taehv_encoder* enc, int H, int W);
+size_t sf_taehv_encode_scratch_bytes(const sf_taehv_encoder* enc, int H, int W, int max_frames);
+/* Zero every history: the first frame's `past` is zero (taehv.py:115-116). */
+int sf_taehv_encode_reset(const sf_taehv_encoder* enc, void* state, size_t state_bytes, int H, int W, void* stream);
+/* n_frames frames (a multiple of 4; H, W multiples of 8), frame t being pixel frame max(t - lead, 0) of `pixels`
+ * ([3][n_frames - lead][H][W] with channel stride c_stride, enum sf_taehv_pixel_dtype, values in [-1, 1]) ->
+ * n_frames / 4 latent frames float32 [n_frames / 4][z_dim][H/8][W/8] = encode_video((pixels + 1) / 2), in the
+ * generator's space (no mean / std).  Bit-identical however a clip is cut into calls.  The library keeps no state. */
+int sf_taehv_encode_frames(const sf_taehv_encoder* enc, void* state, size_t state_bytes, void* scratch,
+                           size_t scratch_bytes, const void* pixels, int dtype, int64_t c_stride, int H, int W,
+                           int n_frames, int lead, float* latents_out, void* stream);
 
 /* ==========================================================================================
  * JPEG encoder (decoded frames -> JFIF files): what the demo's sender does on the host (demo.py:162-187: clamp, * 127.5

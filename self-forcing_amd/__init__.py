@@ -19,7 +19,8 @@ from .vae_weights import (VaeShape, WAN_VAE, VAE_REDUCED, synth_vae_state_dict, 
                           encoder_param_shapes, vae_encode_flops)
 from .vae import WanVAEWrapper, WanVAEDecoder, WanVAEEncoder, repack_conv  # noqa: F401
 from .taehv_weights import taehv_param_shapes, synth_taehv_state_dict, taehv_decode_flops  # noqa: F401
-from .taehv import TAEHVWrapper, TAEHVDecoder  # noqa: F401
+from .taehv_weights import taehv_encoder_param_shapes, synth_taehv_encoder_state_dict, taehv_encode_flops  # noqa: F401
+from .taehv import TAEHVWrapper, TAEHVDecoder, TAEHVEncoder  # noqa: F401
 from . import taehv_weights  # noqa: F401
 from .pose_weights import pose_param_shapes, synth_pose_state_dict, pose_plan, pose_embed_flops, pose_embed_bytes  # noqa: F401
 from .pose import PoseEmbedder  # noqa: F401
@@ -40,6 +41,7 @@ __all__ = ["WanShape", "WAN_1_3B", "WAN_14B", "WAN_REDUCED", "NAMED_SHAPES", "sy
            "SyntheticTextEncoder", "FixedTextEncoder", "IdentityVAE", "RolloutPool", "ops", "torch_ops",
            "VaeShape", "WAN_VAE", "VAE_REDUCED", "synth_vae_state_dict", "vae_param_shapes", "WanVAEWrapper",
            "TAEHVWrapper", "TAEHVDecoder", "taehv_param_shapes", "synth_taehv_state_dict", "taehv_decode_flops",
+           "TAEHVEncoder", "taehv_encoder_param_shapes", "synth_taehv_encoder_state_dict", "taehv_encode_flops",
            "JpegEncoder", "jpeg_reference", "mjpeg", "PoseEmbedder", "pose_param_shapes", "synth_pose_state_dict", "pose_plan", "pose_embed_flops", "pose_embed_bytes",
            "WanVAEDecoder", "repack_conv", "T5Shape", "UMT5_XXL", "T5_REDUCED", "synth_t5_state_dict", "t5_param_shapes",
            "WanTextEncoder", "UMT5Encoder", "relative_position_buckets", "FlowUniPCMultistepScheduler", "CausalDiffusionInferencePipeline"]

@@ -30,8 +30,10 @@ EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_BIAS_GATE_RESID, EPI_F32 = 0, 1, 2,
 CONV_BIAS, CONV_BIAS_RESID, CONV_BIAS_CLAMP_F32 = 0, 1, 2
 VAE_MAX_STAGES = 4
 # enum sf_taehv_epilogue
-TAEHV_EPILOGUES = {"bias_relu": 0, "bias_resid_relu": 1, "plain": 2, "relu": 3, "head_f32": 4}
+TAEHV_EPILOGUES = {"bias_relu": 0, "bias_resid_relu": 1, "plain": 2, "relu": 3, "head_f32": 4, "latent_f32": 5}
 TAEHV_STAGES, TAEHV_BLOCKS = 3, 3
+# enum sf_taehv_pixel_dtype
+TAEHV_PIXEL_DTYPES = {"bfloat16": 0, "float32": 1}
 # enum sf_pose_dtype
 POSE_DTYPES = {"uint8": 0, "float32": 1, "bfloat16": 2}
 POSE_CONVS = 6
@@ -184,6 +186,16 @@ class TaehvModel(C.Structure):
                 ("exit_conv", TaehvLayer * TAEHV_STAGES), ("tgrow", C.c_int32 * TAEHV_STAGES), ("head", TaehvLayer)]
 
 
+class TaehvDownConvArgs(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("x", "w", "out")]
+                + [(n, C.c_int32) for n in ("Tout", "H", "W", "Cin", "Cout", "kt", "ldw", "ldo")])
+
+
+class TaehvEncoder(C.Structure):
+    _fields_ = [("stem", TaehvLayer), ("down", TaehvLayer * TAEHV_STAGES), ("block", ((TaehvLayer * 3) * TAEHV_BLOCKS) * TAEHV_STAGES),
+                ("head", TaehvLayer)]
+
+
 class PoseConvArgs(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("x", "w", "bias", "out")]
                 + [(n, C.c_int32) for n in ("T", "H", "W", "Cin", "Cout", "kt", "stride_t", "stride_s", "ldw", "ldo", "silu")])
@@ -257,6 +269,12 @@ SIGNATURES = {
     "sf_taehv_scratch_bytes": (C.c_size_t, [C.POINTER(TaehvModel), _i, _i, _i]),
     "sf_taehv_reset": (C.c_int, [C.POINTER(TaehvModel), _vp, _sz, _i, _i, _vp]),
     "sf_taehv_decode_frames": (C.c_int, [C.POINTER(TaehvModel), _vp, _sz, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sf_taehv_encode_stem": (C.c_int, [_vp, _i, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "sf_taehv_down_conv": (C.c_int, [C.POINTER(TaehvDownConvArgs), _vp]),
+    "sf_taehv_encode_state_bytes": (C.c_size_t, [C.POINTER(TaehvEncoder), _i, _i]),
+    "sf_taehv_encode_scratch_bytes": (C.c_size_t, [C.POINTER(TaehvEncoder), _i, _i, _i]),
+    "sf_taehv_encode_reset": (C.c_int, [C.POINTER(TaehvEncoder), _vp, _sz, _i, _i, _vp]),
+    "sf_taehv_encode_frames": (C.c_int, [C.POINTER(TaehvEncoder), _vp, _sz, _vp, _sz, _vp, _i, _i64, _i, _i, _i, _i, _vp, _vp]),
     "sf_pose_out_size": (C.c_int, [_i, _i, _i]),
     "sf_pose_conv": (C.c_int, [C.POINTER(PoseConvArgs), _vp]),
     "sf_pose_prepare": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),

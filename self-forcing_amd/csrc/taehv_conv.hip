@@ -22,7 +22,7 @@
 // adds to the core: kt in {1, 2}, always 3x3 and unstrided as compile-time geometry (the tap arithmetic folds to a shorter
 // form), NT in {4, 2, 1} for Cout = 256 / 128, 64 and 3 without padding waste, the ReLU epilogues, the interleave through
 // the coalesced LDS write-back (the 64-channel volumes at 240x416 and 480x832 hold most of the decoder's bytes) and the
-// float head.
+// float heads (the decoder's 2 y - 1 with its clamp; the encoder's 64 -> 16 latents, y + bias as they are).
 #include <cstdlib>
 #include "conv_igemm_core.h"
 #include "../../include/sf_hip.h"
@@ -65,8 +65,9 @@ struct TConvP {
 template <int NT, int EPI>
 __global__ __launch_bounds__(igemm::THREADS, 2) void taehv_conv_kernel(TConvP p) {
   constexpr int BN = 32 * NT;
-  constexpr bool HAS_BIAS = EPI == SF_TAEHV_BIAS_RELU || EPI == SF_TAEHV_BIAS_RESID_RELU || EPI == SF_TAEHV_HEAD_F32;
-  constexpr bool RELU = EPI != SF_TAEHV_PLAIN && EPI != SF_TAEHV_HEAD_F32;
+  constexpr bool F32_OUT = EPI == SF_TAEHV_HEAD_F32 || EPI == SF_TAEHV_LATENT_F32;
+  constexpr bool HAS_BIAS = EPI == SF_TAEHV_BIAS_RELU || EPI == SF_TAEHV_BIAS_RESID_RELU || F32_OUT;
+  constexpr bool RELU = EPI != SF_TAEHV_PLAIN && !F32_OUT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -82,9 +83,9 @@ __global__ __launch_bounds__(igemm::THREADS, 2) void taehv_conv_kernel(TConvP p)
 #include "conv_igemm_mainloop.inc"
 
   // ---- epilogue: the lane holds y[m][n .. n+3] for (mt, nt); m = m0 + wr*64 + 16 mt + (lane & 15), n = n0 + wc*16NT + 16 nt + 4 (lane >> 4)
-  if (EPI == SF_TAEHV_HEAD_F32) {
-    // Cout is tiny (3): per-element guards, planar float output [Tout][Cout][H][W] = 2 (y + bias) - 1; 16 lanes write 16
-    // consecutive positions of one plane
+  if (F32_OUT) {
+    // Cout is tiny (3, or the encoder's 16): per-element guards, planar float output [Tout][Cout][H][W] = 2 (y + bias) - 1
+    // (the encoder's latents: y + bias); 16 lanes write 16 consecutive positions of one plane
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
       const int m = m0 + wr * 64 + mt * 16 + (lane & 15);
@@ -96,8 +97,11 @@ __global__ __launch_bounds__(igemm::THREADS, 2) void taehv_conv_kernel(TConvP p)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           if (n + j < p.Cout) {
-            float v = 2.0f * (acc[mt][nt][j] + (float)p.bias[n + j]) - 1.0f;
-            if (p.clamp) v = fminf(fmaxf(v, -1.f), 1.f);
+            float v = acc[mt][nt][j] + (float)p.bias[n + j];
+            if (EPI == SF_TAEHV_HEAD_F32) {
+              v = 2.0f * v - 1.0f;
+              if (p.clamp) v = fminf(fmaxf(v, -1.f), 1.f);
+            }
             p.out_f32[((long)t * p.Cout + n + j) * p.HW + hw] = v;
           }
         }
@@ -126,6 +130,7 @@ int launch_nt(const TConvP& p, int epi, hipStream_t s) {
     case SF_TAEHV_PLAIN: return launch_epi<NT, SF_TAEHV_PLAIN>(p, s);
     case SF_TAEHV_RELU: return launch_epi<NT, SF_TAEHV_RELU>(p, s);
     case SF_TAEHV_HEAD_F32: return launch_epi<NT, SF_TAEHV_HEAD_F32>(p, s);
+    case SF_TAEHV_LATENT_F32: return launch_epi<NT, SF_TAEHV_LATENT_F32>(p, s);
     default: return -1;
   }
 }
@@ -140,13 +145,14 @@ extern "C" int sf_taehv_pick_nt(int cout) {
 extern "C" int sf_taehv_conv(const sf_taehv_conv_args* a, void* stream) {
   SF_CHECK(a != nullptr, "sf_taehv_conv: null args");
   SF_CHECK(a->x && a->w, "sf_taehv_conv: null tensor");
-  SF_CHECK(a->epilogue >= SF_TAEHV_BIAS_RELU && a->epilogue <= SF_TAEHV_HEAD_F32, "sf_taehv_conv: unknown epilogue %d", a->epilogue);
+  SF_CHECK(a->epilogue >= SF_TAEHV_BIAS_RELU && a->epilogue <= SF_TAEHV_LATENT_F32, "sf_taehv_conv: unknown epilogue %d", a->epilogue);
   SF_CHECK(a->Tout > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, "sf_taehv_conv: empty problem");
   SF_CHECK(a->Cin % 32 == 0, "sf_taehv_conv: Cin=%d must be a multiple of 32 (pad the channels)", a->Cin);
   SF_CHECK(a->kt == 1 || a->kt == 2, "sf_taehv_conv: kt must be 1 or 2, got %d", a->kt);
   SF_CHECK(a->upsample == 0 || a->upsample == 1, "sf_taehv_conv: upsample must be 0 or 1");
   SF_CHECK(!a->upsample || (a->H % 2 == 0 && a->W % 2 == 0), "sf_taehv_conv: an upsampled output %dx%d must be even", a->H, a->W);
-  const bool has_bias = a->epilogue == SF_TAEHV_BIAS_RELU || a->epilogue == SF_TAEHV_BIAS_RESID_RELU || a->epilogue == SF_TAEHV_HEAD_F32;
+  const bool f32_out = a->epilogue == SF_TAEHV_HEAD_F32 || a->epilogue == SF_TAEHV_LATENT_F32;
+  const bool has_bias = a->epilogue == SF_TAEHV_BIAS_RELU || a->epilogue == SF_TAEHV_BIAS_RESID_RELU || f32_out;
   SF_CHECK(!has_bias || a->bias, "sf_taehv_conv: epilogue %d needs a bias", a->epilogue);
   const int slices = a->kt * 9 * (a->Cin / 32);
   const int nk = (slices + 1) / 2;
@@ -155,7 +161,7 @@ extern "C" int sf_taehv_conv(const sf_taehv_conv_args* a, void* stream) {
   SF_CHECK(((uintptr_t)a->x % 16 == 0) && ((uintptr_t)a->w % 16 == 0) && ((uintptr_t)a->bias % 8 == 0), "sf_taehv_conv: misaligned tensor");
   const int tgrow = a->tgrow <= 1 ? 1 : a->tgrow;
   SF_CHECK(tgrow <= 2, "sf_taehv_conv: tgrow must be 1 or 2, got %d", a->tgrow);
-  if (a->epilogue == SF_TAEHV_HEAD_F32) {
+  if (f32_out) {
     SF_CHECK(a->out_f32 != nullptr && tgrow == 1 && a->Cout <= 32, "sf_taehv_conv: the float head needs out_f32, no tgrow and Cout <= 32");
   } else {
     SF_CHECK(a->out != nullptr && a->Cout % 8 == 0, "sf_taehv_conv: bf16 output needs out and Cout %% 8 == 0");

@@ -280,7 +280,8 @@ def taehv_conv(x: Tensor, w_packed: Tensor, bias: Optional[Tensor], kt: int, t_o
                resid: Optional[Tensor] = None, tgrow: int = 1, clamp: bool = False, cin: Optional[int] = None) -> Tensor:
     """The TAEHV decoder's 3x3 convolution (sf_taehv_conv).  x [t_out - 1 + kt, Hin, Win, Cin] channels-last (kt = 2: the
     history frame in front); w_packed from `taehv_weights.repack_taehv_conv`; epilogue one of `_lib.TAEHV_EPILOGUES`.
-    Returns bf16 [tgrow * t_out, H, W, Cout / tgrow], or float32 [t_out, Cout, H, W] = 2 y - 1 for "head_f32"."""
+    Returns bf16 [tgrow * t_out, H, W, Cout / tgrow], or float32 [t_out, Cout, H, W] = 2 y - 1 for "head_f32" (y for the
+    encoder's "latent_f32")."""
     _bf16(x, "x"), _bf16(w_packed, "w_packed")
     if bias is not None:
         _bf16(bias, "bias")
@@ -297,7 +298,7 @@ def taehv_conv(x: Tensor, w_packed: Tensor, bias: Optional[Tensor], kt: int, t_o
     a.x, a.w, a.bias = x.data_ptr(), w_packed.data_ptr(), None if bias is None else bias.data_ptr()
     a.Tout, a.H, a.W, a.Cin, a.Cout, a.kt = t_out, H, W, cin or c, cout, kt
     a.upsample, a.ldw, a.tgrow, a.epilogue, a.clamp = int(upsample), w_packed.stride(0), tgrow, _lib.TAEHV_EPILOGUES[epilogue], int(clamp)
-    if epilogue == "head_f32":
+    if epilogue in ("head_f32", "latent_f32"):
         out = torch.empty(t_out, cout, H, W, dtype=torch.float32, device=x.device)
         a.out_f32 = out.data_ptr()
     else:
@@ -312,6 +313,41 @@ def taehv_conv(x: Tensor, w_packed: Tensor, bias: Optional[Tensor], kt: int, t_o
                 raise ValueError("taehv_conv: resid must match the output volume")
             a.resid, a.ldr = resid.data_ptr(), cout
     check(lib().sf_taehv_conv(a, stream_handle()), "sf_taehv_conv")
+    return out
+
+
+def taehv_encode_stem(pixels: Tensor, w_packed: Tensor, bias: Tensor, lead: int = 0) -> Tensor:
+    """The TAEHV encoder's first convolution + ReLU straight from pixels (sf_taehv_encode_stem).  pixels [3, T, H, W] in
+    [-1, 1], bf16 or float32, any channel stride with contiguous frames; w_packed from `taehv_weights.repack_stem`.
+    Returns bf16 [lead + T, H, W, 64]: the first frame `lead` more times in front."""
+    _bf16(w_packed, "w_packed"), _bf16(bias, "bias")
+    if not pixels.is_cuda or pixels.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("taehv_encode_stem: pixels must be a CUDA/ROCm bf16 or float32 tensor (the HIP path has no CPU fallback)")
+    if pixels.dim() != 4 or pixels.shape[0] != 3 or not pixels[0].is_contiguous():
+        raise ValueError(f"taehv_encode_stem: pixels must be [3, T, H, W] with contiguous frames, got {tuple(pixels.shape)}")
+    if tuple(w_packed.shape) != (64, 32) or not w_packed.is_contiguous() or bias.numel() != 64:
+        raise ValueError("taehv_encode_stem: w_packed [64, 32] and bias [64] expected")
+    _, T, H, W = pixels.shape
+    out = torch.empty(lead + T, H, W, 64, dtype=torch.bfloat16, device=pixels.device)
+    check(lib().sf_taehv_encode_stem(pixels.data_ptr(), _lib.TAEHV_PIXEL_DTYPES[str(pixels.dtype).replace("torch.", "")], pixels.stride(0), H, W,
+                                     lead + T, lead, w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), stream_handle()), "sf_taehv_encode_stem")
+    return out
+
+
+def taehv_down_conv(x: Tensor, w_packed: Tensor, kt: int) -> Tensor:
+    """The TAEHV encoder's strided convolution with TPool folded in (sf_taehv_down_conv): x [kt * t_out, 2H, 2W, Cin]
+    channels-last, kt temporal taps at temporal stride kt, spatial stride 2; w_packed from
+    `taehv_weights.repack_taehv_conv(tpool_taps(fold_tpool(...)))`.  Returns bf16 [t_out, H, W, Cout]."""
+    _bf16(x, "x"), _bf16(w_packed, "w_packed")
+    if x.dim() != 4 or not x.is_contiguous() or x.shape[1] % 2 or x.shape[2] % 2 or kt not in (1, 2) or x.shape[0] % kt:
+        raise ValueError(f"taehv_down_conv: x must be a contiguous [kt * T, 2H, 2W, C] volume, got {tuple(x.shape)} with kt={kt}")
+    tin, hin, win, c = x.shape
+    cout = w_packed.shape[0]
+    out = torch.empty(tin // kt, hin // 2, win // 2, cout, dtype=torch.bfloat16, device=x.device)
+    a = _lib.TaehvDownConvArgs()
+    a.x, a.w, a.out = x.data_ptr(), w_packed.data_ptr(), out.data_ptr()
+    a.Tout, a.H, a.W, a.Cin, a.Cout, a.kt, a.ldw, a.ldo = tin // kt, hin // 2, win // 2, c, cout, kt, w_packed.stride(0), cout
+    check(lib().sf_taehv_down_conv(a, stream_handle()), "sf_taehv_down_conv")
     return out
 
 

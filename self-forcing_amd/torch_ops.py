@@ -22,6 +22,7 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::vae_decode_frames(model, state!, scratch!, z, out!, h, w, window_frames, frame_index, window, history_at) -> ()
     sf_hip::vae_encode_frames(model, state!, scratch!, pixels, out!, H, W, window_frames, chunk_index, window, history_at) -> ()
     sf_hip::taehv_decode_frames(model, state!, scratch!, z, out!, h, w, clamp) -> ()
+    sf_hip::taehv_encode_frames(model, state!, scratch!, pixels, out!, H, W, lead) -> ()
     sf_hip::t5_encode(model, ids, mask, buckets, workspace!) -> out
 
 Models (weights + C descriptors) are Python objects that own device memory; operators take an integer HANDLE from
@@ -553,6 +554,39 @@ def _(model, state, scratch, pixels, out, H, W, window_frames, chunk_index, wind
     return None   # writes only its mutated arguments
 
 
+@custom_op(f"{NAMESPACE}::taehv_encode_frames", mutates_args=("state", "scratch", "out"))
+def taehv_encode_frames(model: int, state: Tensor, scratch: Tensor, pixels: Tensor, out: Tensor, H: int, W: int, lead: int) -> None:
+    """Pixel frames [3, T, H, W] (bf16 or float32 in [-1, 1]; any channel stride, frames contiguous) with the first frame
+    `lead` more times in front, lead + T a multiple of 4 -> float32 latents written to `out` [(lead + T) / 4, 16, H/8,
+    W/8]; `state` carries the one-frame memory of the nine MemBlocks between calls (sf_taehv_encode_frames in
+    include/sf_hip.h; `TAEHVEncoder.cached_encode` drives it)."""
+    m = _model(model)
+    _need_gpu(pixels, "pixels", None)
+    _need_gpu(out, "out", torch.float32)
+    if pixels.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"taehv_encode_frames: pixels must be bf16 or float32, got {pixels.dtype}")
+    if pixels.dim() != 4 or pixels.shape[0] != 3 or pixels.shape[1] < 1 or tuple(pixels.shape[2:]) != (H, W) or not pixels[0].is_contiguous():
+        raise ValueError(f"taehv_encode_frames: pixels must be [3, T, {H}, {W}] with contiguous frames, got {tuple(pixels.shape)}")
+    for name, t in (("state", state), ("scratch", scratch)):       # their element counts are passed on as BYTE counts
+        if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError(f"taehv_encode_frames: {name} must be a contiguous CUDA uint8 tensor")
+    n = lead + pixels.shape[1]
+    if not 0 <= lead <= 3 or n % 4:
+        raise ValueError(f"taehv_encode_frames: lead={lead} + {pixels.shape[1]} pixel frames is not a whole number of 4-frame groups")
+    zc = m.cmodel.head.cout
+    if tuple(out.shape) != (n // 4, zc, H // 8, W // 8) or not out.is_contiguous():
+        raise ValueError(f"taehv_encode_frames: out must be contiguous [{n // 4}, {zc}, {H // 8}, {W // 8}], got {tuple(out.shape)}")
+    _lib.check(_lib.lib().sf_taehv_encode_frames(C.byref(m.cmodel), state.data_ptr(), state.numel(), scratch.data_ptr(), scratch.numel(),
+                                                 pixels.data_ptr(), _lib.TAEHV_PIXEL_DTYPES[str(pixels.dtype).replace("torch.", "")],
+                                                 pixels.stride(0), H, W, n, lead, out.data_ptr(), _stream(pixels)),
+               "sf_taehv_encode_frames")
+
+
+@taehv_encode_frames.register_fake
+def _(model, state, scratch, pixels, out, H, W, lead):
+    return None   # writes only its mutated arguments
+
+
 @custom_op(f"{NAMESPACE}::t5_encode", mutates_args=("workspace",))
 def t5_encode(model: int, ids: Tensor, mask: Tensor, buckets: Tensor, workspace: Tensor) -> Tensor:
     """umT5 encoder pass: ids, mask int64 [B, L] -> bf16 [B, L, dim], rows past each prompt's length zeroed (sf_t5_encode)."""
@@ -573,4 +607,4 @@ def _(model, ids, mask, buckets, workspace):
 
 
 OPS = ("attention", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "vae_encode_frames", "taehv_decode_frames",
-       "t5_encode")
+       "taehv_encode_frames", "t5_encode")
