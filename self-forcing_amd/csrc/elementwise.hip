@@ -261,20 +261,18 @@ __device__ __forceinline__ double block_sigma_lookup(double t, const float* __re
   return (double)sigmas[bi];
 }
 
-// double -> bf16 with a single round-to-nearest-even (torch's `.to(bfloat16)` on a float64 tensor);
-// going through float would round twice.
+// double -> bf16 as torch's `.to(bfloat16)` on a float64 tensor does it: double -> float -> bf16, each step round-to-nearest-
+// even.  The two roundings can land one bf16 step from the single correctly rounded result (1 + 2^-8 + 2^-40 gives 1.0,
+// not 1 + 2^-7); the reference's `x0_pred.to(original_dtype)` and its sinusoidal embedding round this way, and the
+// contract is the reference's bits.
+// The second step is spelled out on the float's bits: the compiler folds `(bf16_t)(float)d` into ONE correctly rounded
+// double -> bf16 conversion (it did: the kernel then missed the reference's recorded x0 in 38 of 1536 elements at
+// t = 833.33).
 __device__ __forceinline__ bf16_t double_to_bf16(double d) {
   const float f = (float)d;
   const unsigned u = __float_as_uint(f);
-  if ((u & 0xFFFFu) == 0x8000u) {      // f sits on a bf16 tie point: decide by the residual
-    const double r = d - (double)f;
-    if (r != 0.0) {
-      const bool up = (f > 0.f) ? (r > 0.0) : (r < 0.0);  // magnitude up?
-      const unsigned hi = (u >> 16) + (up ? 1u : 0u);
-      return __builtin_bit_cast(bf16_t, (unsigned short)hi);
-    }
-  }
-  return (bf16_t)f;
+  if (f != f) return __builtin_bit_cast(bf16_t, (unsigned short)((u >> 16) | 0x40u));      // NaN stays NaN (quiet)
+  return __builtin_bit_cast(bf16_t, (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16));
 }
 
 __device__ __forceinline__ double read_timestep(const void* t, int is_i64, long idx) {

@@ -182,6 +182,17 @@ __global__ __launch_bounds__(SLR_MAX_THREADS) void small_linear_reg_kernel(const
   }
 }
 
+// Dynamic LDS above 64 KB has to be registered with the runtime before the launch (8 rows at K = 5120, the 14B time
+// projection at batch x groups >= 5, stage 80 KB): one-time registration of the largest size asked for (idempotent).
+template <int R>
+void allow_large_lds(size_t bytes) {
+  static int attr_lds = 0;
+  if ((int)bytes > attr_lds && bytes > 64 * 1024) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_linear_kernel<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    attr_lds = (int)bytes;
+  }
+}
+
 }  // namespace
 
 extern "C" int sf_small_linear(const void* x, const void* w, const void* bias, void* out, int M, int N, int K,
@@ -219,9 +230,12 @@ extern "C" int sf_small_linear(const void* x, const void* w, const void* bias, v
   const int blocks = min(1024, (waves_needed + 3) / 4);
   for (int m0 = 0; m0 < M; m0 += SL_MB_MAX) {
     const int mc = min(SL_MB_MAX, M - m0);
-#define SF_SL_LAUNCH(R)                                                                                                  \
-  hipLaunchKernelGGL(small_linear_kernel<R>, dim3(blocks), dim3(SL_THREADS), (size_t)R * K * 2, (hipStream_t)stream,      \
-                     (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)out, m0, mc, N, K, act_in, act_out)
+#define SF_SL_LAUNCH(R)                                                                                                     \
+  do {                                                                                                                      \
+    allow_large_lds<R>((size_t)R * K * 2);                                                                                  \
+    hipLaunchKernelGGL(small_linear_kernel<R>, dim3(blocks), dim3(SL_THREADS), (size_t)R * K * 2, (hipStream_t)stream,      \
+                       (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)out, m0, mc, N, K, act_in, act_out); \
+  } while (0)
     if (mc == 1) SF_SL_LAUNCH(1);
     else if (mc == 2) SF_SL_LAUNCH(2);
     else if (mc == 3) SF_SL_LAUNCH(3);

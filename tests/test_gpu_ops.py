@@ -449,7 +449,7 @@ def test_unpatchify_x0_golden(opsgold):
     ref_flow = T(mods["unp_out_bf16"]).permute(1, 0, 2, 3)[None]          # [16,2,8,12] -> [1,2,16,8,12]
     assert torch.equal(flow.float().cpu(), ref_flow)
     ref_x0 = wo.flow_to_x0(sched, ref_flow[0].bfloat16(), xt[0], ts[0])
-    assert torch.equal(x0[0].cpu(), ref_x0)              # fp64 math, one rounding: bit exact
+    assert torch.equal(x0[0].cpu(), ref_x0)              # fp64 math, rounded fp64 -> fp32 -> bf16 as torch does: bit exact
     # one modulation group for both frames: a single sigma is broadcast
     flow1, x01 = ops.unpatchify_x0(hx.to(DEV), xt.to(DEV), ts[:, :1].to(DEV), sched.sigmas.to(DEV), sched.timesteps.to(DEV))
     ref1 = wo.flow_to_x0(sched, ref_flow[0].bfloat16(), xt[0], ts[0, :1].repeat(2))
