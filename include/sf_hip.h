@@ -803,6 +803,77 @@ size_t sf_t5_workspace_bytes(const sf_t5_model* model, int batch, int seq_len);
 int sf_t5_encode(const sf_t5_model* model, const int64_t* ids, const int64_t* mask, const int32_t* rel_bucket,
                  int batch, int seq_len, void* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ==========================================================================================
+ * CLIP image encoder (frames -> clip_feature): CLIPModel.visual (wan/modules/clip.py:527-542) -> VisionTransformer.forward
+ * with use_31_block=True (clip.py:279-297).  ViT: patch 14, head dimension 80, exact GELU, LayerNorm eps 1e-5.  The
+ * residual stream is fp32 (clip.py:47-50: the norms run on x.float(), bf16 sub-layer outputs are added into an fp32 x);
+ * every matrix product is sf_gemm_bf16 with SF_EPI_BIAS.  Runs once per conditioning image.
+ * ========================================================================================== */
+
+enum sf_clip_dtype { SF_CLIP_F32 = 0, SF_CLIP_BF16 = 1 };
+
+/* CLIPModel.visual's preprocessing (clip.py:529-537): frames [n][3][H][W] (dtype: sf_clip_dtype) in [-1, 1] ->
+ * F.interpolate(size = image_size, mode = 'bicubic', align_corners = False) (A = -0.75, taps clamped to the edge, no
+ * antialiasing, overshoot kept) -> (v/2 + 1/2 - mean_c) / std_c, written as bf16 patch rows for the patch-embedding GEMM:
+ * rows [n * (image_size/patch)^2][kp], row = (frame, patch row-major), column k = (c*patch + i)*patch + j for pixel (i, j)
+ * of the patch; columns 3*patch^2 <= k < kp are zero.  kp >= 3*patch^2, image_size % patch == 0. */
+int sf_clip_preprocess(const void* frames, int dtype, int n, int H, int W, int image_size, int patch, int kp, void* rows,
+                       void* stream);
+
+/* Start of the fp32 residual stream, x32 [n*L][dim] with L = P + 1:
+ *   x32[b][0] = cls + pos[0];  x32[b][1 + p] = float(patch_out[b*P + p]) + pos[1 + p];  x32 = LN(x32; pre_w, pre_b)
+ * and its first normalised copy xn bf16 [n*L][dim] = LN(x32; ln_w, ln_b) (norm1 of block 0).  patch_out bf16 [n*P][dim];
+ * cls [dim], pos [L][dim] and the norm vectors are fp32; statistics in fp32.  With ln_w == NULL only the stream is
+ * written (ln_b, xn may be NULL).  dim % 4 == 0, dim <= 8192. */
+int sf_clip_embed_norm(const void* patch_out, const float* cls, const float* pos, const float* pre_w, const float* pre_b,
+                       const float* ln_w, const float* ln_b, float* x32, void* xn, int n, int P, int dim, float eps, void* stream);
+
+/* Fused residual add and LayerNorm on the fp32 stream: x32[r][:] += float(y[r][:]) (y bf16 [rows][dim]); with ln_w the
+ * normalised copy xn = bf16(LN(x32[r]) * ln_w + ln_b) is written too (fp32 statistics, one pass over the row in memory);
+ * with ln_w == NULL only the add happens and xn is not touched (ln_b, xn may be NULL).  dim % 4 == 0, dim <= 8192. */
+int sf_clip_add_layernorm(float* x32, const void* y, const float* ln_w, const float* ln_b, void* xn, int rows, int dim, float eps,
+                          void* stream);
+
+/* Non-causal softmax attention at head dimension 80, straight off the packed projection: qkv bf16 [n][L][3][H][80] (the
+ * memory layout of to_qkv(x).view(b, s, 3, n, d), clip.py:81) -> out bf16 [n][L][H*80]; scale 1/sqrt(80), scores and softmax
+ * in fp32, probabilities rounded to bf16 in front of P.V.  K and V of one (image, head) stay in LDS: 1 <= L <= 480. */
+int sf_clip_attention(const void* qkv, void* out, int n, int L, int H, void* stream);
+
+/* nn.GELU() (erf form), evaluated in fp32: out[i] = bf16(x[i] * Phi(x[i])), bf16 [count]; in place allowed. count % 8 == 0. */
+int sf_clip_gelu(const void* x, void* out, int64_t count, void* stream);
+
+typedef struct sf_clip_layer {     /* AttentionBlock, clip.py:112-153 */
+  const float* norm1_w;            /* [dim] fp32 */
+  const float* norm1_b;
+  const void* qkv_w;               /* attn.to_qkv.weight bf16 [3*dim][dim] */
+  const void* qkv_b;               /* bf16 [3*dim] */
+  const void* proj_w;              /* attn.proj.weight bf16 [dim][dim] */
+  const void* proj_b;
+  const float* norm2_w;
+  const float* norm2_b;
+  const void* fc1_w;               /* mlp.0.weight bf16 [mlp_dim][dim] */
+  const void* fc1_b;
+  const void* fc2_w;               /* mlp.2.weight bf16 [dim][mlp_dim] */
+  const void* fc2_b;
+} sf_clip_layer;
+
+typedef struct sf_clip_model {
+  int32_t image_size, patch, dim, heads, mlp_dim, layers_built;
+  float eps;
+  const void* patch_w;             /* patch_embedding.weight repacked bf16 [dim][kp], kp = 3*patch^2 rounded up to 64 */
+  const float* cls;                /* cls_embedding fp32 [dim] */
+  const float* pos;                /* pos_embedding fp32 [(image_size/patch)^2 + 1][dim] */
+  const float* pre_norm_w;         /* fp32 [dim] */
+  const float* pre_norm_b;
+  const sf_clip_layer* layers_host; /* HOST array [layers_built]: every block but the last (use_31_block) */
+} sf_clip_model;
+
+size_t sf_clip_workspace_bytes(const sf_clip_model* model, int n);
+/* frames [n][3][H][W] (dtype: sf_clip_dtype) -> out fp32 [n][(image_size/patch)^2 + 1][dim], the un-normed stream after
+ * the last built block.  `out` is the residual stream itself: it is written throughout the call. */
+int sf_clip_encode(const sf_clip_model* model, const void* frames, int dtype, int n, int H, int W, float* out,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Measured ceilings of the box ("Peaks to divide by": "re-measure on the box (a peak-MFMA micro-kernel
  * and a streaming-copy kernel) and use the measured ceilings in the fraction").  Measurement entry points for

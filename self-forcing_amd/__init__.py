@@ -29,6 +29,9 @@ from .jpeg import JpegEncoder  # noqa: F401
 from . import jpeg_reference, mjpeg  # noqa: F401
 from .t5_weights import T5Shape, UMT5_XXL, T5_REDUCED, synth_t5_state_dict, t5_param_shapes  # noqa: F401
 from .text_encoder import WanTextEncoder, UMT5Encoder, relative_position_buckets  # noqa: F401
+from .clip_weights import ClipVisionShape, CLIP_VIT_H_14, CLIP_REDUCED, clip_param_shapes, synth_clip_state_dict  # noqa: F401
+from .clip import CLIPModel, CLIPVisionEncoder  # noqa: F401
+from . import clip_weights, clip_reference  # noqa: F401
 from . import unipc  # noqa: F401
 from .diffusion_pipeline import CausalDiffusionInferencePipeline  # noqa: F401
 from .unipc import FlowUniPCMultistepScheduler  # noqa: F401
@@ -44,4 +47,6 @@ __all__ = ["WanShape", "WAN_1_3B", "WAN_14B", "WAN_REDUCED", "NAMED_SHAPES", "sy
            "TAEHVEncoder", "taehv_encoder_param_shapes", "synth_taehv_encoder_state_dict", "taehv_encode_flops",
            "JpegEncoder", "jpeg_reference", "mjpeg", "PoseEmbedder", "pose_param_shapes", "synth_pose_state_dict", "pose_plan", "pose_embed_flops", "pose_embed_bytes",
            "WanVAEDecoder", "repack_conv", "T5Shape", "UMT5_XXL", "T5_REDUCED", "synth_t5_state_dict", "t5_param_shapes",
-           "WanTextEncoder", "UMT5Encoder", "relative_position_buckets", "FlowUniPCMultistepScheduler", "CausalDiffusionInferencePipeline"]
+           "WanTextEncoder", "UMT5Encoder", "relative_position_buckets", "FlowUniPCMultistepScheduler", "CausalDiffusionInferencePipeline",
+           "ClipVisionShape", "CLIP_VIT_H_14", "CLIP_REDUCED", "clip_param_shapes", "synth_clip_state_dict", "CLIPModel", "CLIPVisionEncoder",
+           "clip_weights", "clip_reference"]

@@ -43,6 +43,8 @@ JPEG_DTYPES = {"uint8": 0, "float32": 1, "bfloat16": 2}
 JPEG_RANGES = {(-1, 1): 0, (0, 1): 1}
 JPEG_STATUS = {1: "an interval outgrew its worst-case slot", 2: "a coefficient is outside the baseline range",
                4: "the files do not fit the output buffer"}
+# enum sf_clip_dtype
+CLIP_DTYPES = {"float32": 0, "bfloat16": 1}
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 # enum sf_attn_structure / sf_gemm_structure
 ATTN_STRUCTURES = {"auto": 0, "r64": 1, "w8": 2, "w4": 3}
@@ -220,6 +222,18 @@ class T5Model(C.Structure):
                    ("final_norm_w", C.c_void_p)])
 
 
+class ClipLayer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("norm1_w", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "norm2_b",
+                                          "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+
+
+class ClipModel(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("image_size", "patch", "dim", "heads", "mlp_dim", "layers_built")]
+                + [("eps", C.c_float)]
+                + [(n, C.c_void_p) for n in ("patch_w", "cls", "pos", "pre_norm_w", "pre_norm_b")]
+                + [("layers_host", C.POINTER(ClipLayer))])
+
+
 # name -> (restype, argtypes); every symbol include/sf_hip.h declares
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 SIGNATURES = {
@@ -292,6 +306,13 @@ SIGNATURES = {
     "sf_zero_masked_rows": (C.c_int, [_vp, _vp, _i, _i, _vp]),
     "sf_t5_workspace_bytes": (C.c_size_t, [C.POINTER(T5Model), _i, _i]),
     "sf_t5_encode": (C.c_int, [C.POINTER(T5Model), _vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "sf_clip_preprocess": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sf_clip_embed_norm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "sf_clip_add_layernorm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "sf_clip_attention": (C.c_int, [_vp, _vp, _i, _i, _i, _vp]),
+    "sf_clip_gelu": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "sf_clip_workspace_bytes": (C.c_size_t, [C.POINTER(ClipModel), _i]),
+    "sf_clip_encode": (C.c_int, [C.POINTER(ClipModel), _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "sf_probe_mfma": (C.c_int, [_i, _i, _i, _vp, _vp, C.POINTER(C.c_double), _vp]),
     "sf_probe_copy": (C.c_int, [_vp, _vp, _sz, _vp]),
 }

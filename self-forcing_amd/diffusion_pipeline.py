@@ -17,8 +17,11 @@ What differs:
     (`unipc.py`); timesteps come from the scheduler's host table, so the loop never waits on the device;
   * the constants the reference hard-codes (30 blocks, 1560 tokens per frame, 12x128 heads, 32760-token caches,
     :69-72, :464-487) are derived from the generator's shape and the latent size;
-  * the fork's image front end (CLIP image encoder, VAE-encoded `y`, :154-173, :305-326) is not built (the reference
-    leaves it unwired too): `input_image` must be None;
+  * the producing half of the fork's image front end is built: `encode_image` (:151-172) runs the CLIP image encoder
+    (`clip.CLIPModel`, csrc/clip_encoder.hip; injected as `image_encoder=` or loaded lazily from
+    `args.clip_checkpoint_path`) and the VAE encoder and returns `clip_feature` and `y`.  The consuming half -- the i2v
+    branch of the generator (`img_emb`, `k_img` / `v_img`, the 36-channel patch embedding, :305-326) -- is not, so
+    `inference(input_image=...)` still raises;
   * the pose front end runs on the GPU path (`pose.PoseEmbedder`, csrc/pose_conv.hip): `dwpose_data` [3, F, H, W] with
     `random_ref_dwpose` [H, W, 3] are embedded once per clip with weights loaded lazily from `args.pose_weights_path`
     (`args.pose_weights_strict`, :329-331) or by an injected `pose_embedder=`; the tokens come out token-major, so a
@@ -61,7 +64,9 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
             vae = WanVAEWrapper(device=device)
         self.text_encoder = text_encoder
         self.vae = vae
-        self.image_encoder = image_encoder      # accepted for signature parity; the CLIP front end is out of scope
+        # used by encode_image; when none is injected it loads lazily from args.clip_checkpoint_path on first need
+        self.image_encoder = image_encoder
+        self.clip_checkpoint_path = getattr(args, "clip_checkpoint_path", None)
         # pose weights load lazily on the first inference that takes the pose branch (:59-61, :329-331)
         self.pose_embedder = pose_embedder
         self.pose_weights_path = getattr(args, "pose_weights_path", None)
@@ -170,12 +175,57 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
             self.pose_weights_loaded = True
         return self.pose_embedder.embed(dwpose_data)
 
+    def _image_encoder(self):
+        if self.image_encoder is None:
+            if self.clip_checkpoint_path is None:
+                raise ValueError("encode_image needs the CLIP image encoder: set args.clip_checkpoint_path or construct the pipeline "
+                                 "with image_encoder=")
+            from .clip import CLIPModel
+            self.image_encoder = CLIPModel(dtype=self.torch_dtype, device=self.device, checkpoint_path=self.clip_checkpoint_path)
+        return self.image_encoder
+
+    def encode_image(self, image, num_frames: int, height: int, width: int) -> dict:
+        """The conditioning of the i2v model type (:151-172): {"clip_feature": bf16 [1, L, dim], "y": bf16
+        [1, 20, (num_frames - 1)//4 + 1, height/8, width/8]}.
+
+        `image`: a tensor [1, 3, height, width] or [3, height, width] in [-1, 1], or a PIL image (resized to width x
+        height and scaled by 2/255 - 1, as :147-148 and :158 do).  `clip_feature` is `image_encoder.visual` of the image as
+        a one-frame video -- `visual` takes a list of [3, T, H, W] tensors (clip.py:527-536); the reference passes its
+        [1, 3, H, W] tensor, which that contract reads as a 3-frame single-channel video and which fails in the patch
+        embedding.  `y` = 4 mask channels (first pixel frame known, repeated 4 times so that the mask folds to the latent
+        timeline, :160-164 with the stray fourth view dimension of :163 dropped) on top of the 16 latent channels of
+        `vae.encode_to_latent` of the clip "image, then zeros" (:166-167)."""
+        if num_frames < 1 or (num_frames - 1) % 4:
+            raise ValueError(f"num_frames must be 4 k + 1 (the VAE's timeline), got {num_frames}")
+        if height % 8 or width % 8:
+            raise ValueError(f"height and width must be multiples of 8, got {height}x{width}")
+        encoder = self._image_encoder()
+        if not torch.is_tensor(image):
+            import numpy as np
+            image = torch.from_numpy(np.array(image.resize((width, height)), dtype=np.float32) * (2 / 255) - 1).permute(2, 0, 1)
+        if image.dim() == 4 and image.shape[0] == 1:
+            image = image[0]
+        if tuple(image.shape) != (3, height, width):
+            raise ValueError(f"image must be [1, 3, {height}, {width}] or [3, {height}, {width}], got {tuple(image.shape)}")
+        image = image.to(self.device, torch.float32)
+        clip_feature = encoder.visual([image.unsqueeze(1)]).to(self.torch_dtype)
+        lat_t, h, w = (num_frames - 1) // 4 + 1, height // 8, width // 8
+        msk = torch.zeros(4, lat_t, h, w, device=self.device)
+        msk[:, 0] = 1
+        clip = torch.zeros(1, 3, num_frames, height, width, device=self.device, dtype=self.torch_dtype)
+        clip[0, :, 0] = image.to(self.torch_dtype)
+        latent = self.vae.encode_to_latent(clip)[0].transpose(0, 1)                 # [16, lat_t, h, w]
+        y = torch.cat([msk, latent.float()]).unsqueeze(0).to(self.torch_dtype)
+        return {"clip_feature": clip_feature, "y": y}
+
     def inference(self, noise: torch.Tensor, text_prompts: List[str], input_image=None, dwpose_data=None,
                   random_ref_dwpose=None, initial_latent: Optional[torch.Tensor] = None, return_latents: bool = False,
                   start_frame_index: Optional[int] = 0, dwpose_data_emb: Optional[torch.Tensor] = None):
         """noise [B, F, C, H, W] -> video in [0, 1] (and the latents)."""
         if input_image is not None:
-            raise NotImplementedError("the image front end (CLIP, VAE-encoded y) is not built: input_image must be None")
+            raise NotImplementedError("input_image: the generator's i2v branch (img_emb, k_img / v_img, the 36-channel patch "
+                                      "embedding) is not built, so the rollout cannot consume an image; encode_image() already "
+                                      "produces its clip_feature and y")
         batch_size, num_frames, num_channels, height, width = noise.shape
         if not self.independent_first_frame or (self.independent_first_frame and initial_latent is not None):
             assert num_frames % self.num_frame_per_block == 0

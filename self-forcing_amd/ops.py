@@ -491,3 +491,66 @@ def jpeg_encode_frames(frames: Tensor, n: int, h: int, w: int, subsampling: str,
     check(lib().sf_jpeg_encode_frames(frames.data_ptr(), dtype, _lib.JPEG_RANGES[tuple(value_range)], n, h, w, _lib.JPEG_SUBSAMPLINGS[subsampling],
                                       quality, restart_interval, workspace.data_ptr(), workspace.numel(), out.data_ptr(), out.numel(), meta.data_ptr(),
                                       meta[n + 1:].data_ptr(), torch.cuda.current_stream(frames.device).cuda_stream), "sf_jpeg_encode_frames")
+
+
+# -------------------------------------------------------------------------------------- CLIP image encoder (csrc/clip_encoder.hip)
+def _cur(t: Tensor) -> int:
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def clip_preprocess(frames: Tensor, image_size: int = 224, patch: int = 14, kp: Optional[int] = None) -> Tensor:
+    """frames [n, 3, H, W] float32 / bfloat16 in [-1, 1] -> bf16 patch rows [n * (image_size/patch)^2, kp] (sf_clip_preprocess)."""
+    if not frames.is_cuda or frames.dim() != 4 or frames.shape[1] != 3 or not frames.is_contiguous():
+        raise ValueError("clip_preprocess: contiguous CUDA frames [n, 3, H, W] expected")
+    kp = (3 * patch * patch + 63) // 64 * 64 if kp is None else kp
+    n, _, H, W = frames.shape
+    rows = torch.empty(n * (image_size // patch) ** 2, kp, dtype=torch.bfloat16, device=frames.device)
+    check(lib().sf_clip_preprocess(frames.data_ptr(), _lib.CLIP_DTYPES[str(frames.dtype).replace("torch.", "")], n, H, W, image_size, patch, kp,
+                                   rows.data_ptr(), _cur(frames)), "sf_clip_preprocess")
+    return rows
+
+
+def clip_embed_norm(patch_out: Tensor, cls: Tensor, pos: Tensor, pre_w: Tensor, pre_b: Tensor, ln_w: Optional[Tensor], ln_b: Optional[Tensor],
+                    eps: float = 1e-5):
+    """patch_out bf16 [n, P, dim] -> (x32 float32 [n, P + 1, dim], xn bf16 or None) (sf_clip_embed_norm)."""
+    n, P, dim = patch_out.shape
+    _bf16(patch_out, "patch_out")
+    x32 = torch.empty(n, P + 1, dim, dtype=torch.float32, device=patch_out.device)
+    xn = torch.empty(n, P + 1, dim, dtype=torch.bfloat16, device=patch_out.device) if ln_w is not None else None
+    check(lib().sf_clip_embed_norm(patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), pre_w.data_ptr(), pre_b.data_ptr(), _ptr(ln_w), _ptr(ln_b),
+                                   x32.data_ptr(), _ptr(xn), n, P, dim, eps, _cur(patch_out)), "sf_clip_embed_norm")
+    return x32, xn
+
+
+def clip_add_layernorm(x32: Tensor, y: Tensor, ln_w: Optional[Tensor] = None, ln_b: Optional[Tensor] = None, xn: Optional[Tensor] = None,
+                       eps: float = 1e-5) -> Optional[Tensor]:
+    """x32 (float32 [rows, dim], updated in place) += y (bf16); with ln_w returns xn = bf16(LN(x32)) (written into `xn` when
+    given); without, only adds (sf_clip_add_layernorm)."""
+    _bf16(y, "y")
+    if x32.dtype != torch.float32 or not x32.is_cuda or not x32.is_contiguous() or x32.shape != y.shape or x32.dim() != 2:
+        raise ValueError("clip_add_layernorm: contiguous CUDA float32 x32 [rows, dim] and bf16 y of the same shape expected")
+    if ln_w is not None and xn is None:
+        xn = torch.empty_like(y)
+    check(lib().sf_clip_add_layernorm(x32.data_ptr(), y.data_ptr(), _ptr(ln_w), _ptr(ln_b), _ptr(xn), x32.shape[0], x32.shape[1], eps, _cur(x32)),
+          "sf_clip_add_layernorm")
+    return xn if ln_w is not None else None
+
+
+def clip_attention(qkv: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """qkv bf16 [n, L, 3, H, 80] -> bf16 [n, L, H * 80], non-causal softmax attention at scale 1/sqrt(80) (sf_clip_attention)."""
+    _bf16(qkv, "qkv")
+    if qkv.dim() != 5 or qkv.shape[2] != 3 or qkv.shape[4] != 80:
+        raise ValueError(f"clip_attention: qkv [n, L, 3, H, 80] expected, got {tuple(qkv.shape)}")
+    n, L, _, H, _ = qkv.shape
+    if out is None:
+        out = torch.empty(n, L, H * 80, dtype=torch.bfloat16, device=qkv.device)
+    check(lib().sf_clip_attention(qkv.data_ptr(), out.data_ptr(), n, L, H, _cur(qkv)), "sf_clip_attention")
+    return out
+
+
+def clip_gelu(x: Tensor) -> Tensor:
+    """nn.GELU() (erf form) of a bf16 tensor, evaluated in fp32 (sf_clip_gelu)."""
+    _bf16(x, "x")
+    out = torch.empty_like(x)
+    check(lib().sf_clip_gelu(x.data_ptr(), out.data_ptr(), x.numel(), _cur(x)), "sf_clip_gelu")
+    return out

@@ -24,6 +24,7 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::taehv_decode_frames(model, state!, scratch!, z, out!, h, w, clamp) -> ()
     sf_hip::taehv_encode_frames(model, state!, scratch!, pixels, out!, H, W, lead) -> ()
     sf_hip::t5_encode(model, ids, mask, buckets, workspace!) -> out
+    sf_hip::clip_encode(model, frames, workspace!) -> out
 
 Models (weights + C descriptors) are Python objects that own device memory; operators take an integer HANDLE from
 `register_model` (a constant to a tracer).  There is no CPU implementation: CPU tensors raise.
@@ -606,5 +607,27 @@ def _(model, ids, mask, buckets, workspace):
     return ids.new_empty((ids.shape[0], ids.shape[1], _model(model).shape.dim), dtype=torch.bfloat16)
 
 
+@custom_op(f"{NAMESPACE}::clip_encode", mutates_args=("workspace",))
+def clip_encode(model: int, frames: Tensor, workspace: Tensor) -> Tensor:
+    """CLIP vision tower: frames [n, 3, H, W] float32 or bfloat16 in [-1, 1] -> float32 [n, L, dim] (sf_clip_encode)."""
+    m = _model(model)
+    _need_gpu(frames, "frames", None)
+    if frames.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"clip_encode: frames must be float32 or bfloat16, got {frames.dtype}")
+    if frames.dim() != 4 or frames.shape[1] != 3 or not frames.is_contiguous():
+        raise ValueError(f"clip_encode: frames must be contiguous [n, 3, H, W], got {tuple(frames.shape)}")
+    n, _, H, W = frames.shape
+    out = torch.empty(n, m.shape.seq_len, m.shape.dim, dtype=torch.float32, device=frames.device)
+    _lib.check(_lib.lib().sf_clip_encode(C.byref(m.cmodel), frames.data_ptr(), _lib.CLIP_DTYPES[str(frames.dtype).split(".")[-1]], n, H, W,
+                                         out.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(frames)), "sf_clip_encode")
+    return out
+
+
+@clip_encode.register_fake
+def _(model, frames, workspace):
+    s = _model(model).shape
+    return frames.new_empty((frames.shape[0], s.seq_len, s.dim), dtype=torch.float32)
+
+
 OPS = ("attention", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "vae_encode_frames", "taehv_decode_frames",
-       "taehv_encode_frames", "t5_encode")
+       "taehv_encode_frames", "t5_encode", "clip_encode")

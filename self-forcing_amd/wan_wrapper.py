@@ -233,7 +233,8 @@ class WanDiffusionWrapper(torch.nn.Module):
             add_condition = conditional_dict.get("add_condition")
         if clip_feature is not None or y is not None \
                 or conditional_dict.get("clip_feature") is not None or conditional_dict.get("y") is not None:
-            raise NotImplementedError("image conditioning (clip_feature, y: the i2v model type) is not implemented")
+            raise NotImplementedError("image conditioning (clip_feature, y: the i2v model type) is not implemented in the generator; "
+                                      "CausalDiffusionInferencePipeline.encode_image produces the two tensors")
         mdl = self.model
         shape = mdl.shape
         x = noisy_image_or_video
