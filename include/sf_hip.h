@@ -166,6 +166,23 @@ int sf_attention_ex(const void* q, const void* k, const void* v, void* out, int 
                     int64_t q_stride, int64_t q_bstride, int64_t kv_stride, int64_t kv_bstride,
                     int64_t o_stride, int64_t o_bstride, int structure, void* stream);
 
+/* The same over a key slab whose trailing rows repeat (a prompt's padding keys): sample b attends only rows
+ * [0, keys[b]) and log2w[b] is added to the exp2-domain score of row keys[b] - 1, which so stands for 2^log2w[b]
+ * identical rows.  `keys` (int32 [B]) and `log2w` (float [B]) are DEVICE arrays as sf_cross_fold_scan writes them, read
+ * by the kernels only; both NULL: every row, exactly sf_attention_ex.  SF_ATTN_AUTO decides on Lk, not on the counts. */
+int sf_attention_fold(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq, int Lk,
+                      int64_t q_stride, int64_t q_bstride, int64_t kv_stride, int64_t kv_bstride,
+                      int64_t o_stride, int64_t o_bstride, int structure, const int32_t* keys, const float* log2w,
+                      void* stream);
+
+/* Per layer l and sample b of the cross-attention caches ck / cv (HOST arrays [layers] of device pointers, each
+ * [B, text_len, row_elems] bf16): same = the number of trailing rows that equal the last row bit for bit in BOTH caches;
+ * keys[l * B + b] = text_len - same + 1 (the rows in front plus one representative; text_len when same == 1) and
+ * log2w[l * B + b] = log2(same).  Zero-padded prompt embeddings give same = text_len - prompt length; any other cache
+ * contents just fold less.  Nothing is read back to the host. */
+int sf_cross_fold_scan(const void* const* ck_cache_host, const void* const* cv_cache_host, int layers, int B, int text_len,
+                       int row_elems, int32_t* keys, float* log2w, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Patch gather for the (1,2,2) Conv3d patch embedding, causal_model.py:458-459, :775-781:
  * x [B, F, Cin, H, W] (the wrapper's layout) -> cols [B*F*(H/2)*(W/2), Cin*4] with column index
@@ -294,6 +311,14 @@ int sf_dit_forward(const sf_model* model, const sf_forward_args* args, void* str
  * `next_pass->kv_index_out` (if any) receives the final indices. */
 int sf_dit_forward_pair(const sf_model* model, const sf_forward_args* context_pass, const sf_forward_args* next_pass,
                         void* stream);
+/* The two calls above with the cross-attention padding folded: `cross_keys` (int32) and `cross_log2w` (float) are device
+ * arrays [num_layers][batch] that belong to the cross-attention caches.  A pass with init_cross fills them
+ * (sf_cross_fold_scan) behind the caches; every pass hands layer l's slices to its cross-attention (sf_attention_fold).
+ * Caches filled by anything else need one sf_cross_fold_scan first.  Both NULL: sf_dit_forward / sf_dit_forward_pair. */
+int sf_dit_forward_fold(const sf_model* model, const sf_forward_args* args, int32_t* cross_keys, float* cross_log2w,
+                        void* stream);
+int sf_dit_forward_pair_fold(const sf_model* model, const sf_forward_args* context_pass, const sf_forward_args* next_pass,
+                             const int32_t* cross_keys, const float* cross_log2w, void* stream);
 
 /* ==========================================================================================
  * Wan VAE decode (latents -> pixels): WanVAEWrapper.decode_to_pixel -> WanVAE_.decode /

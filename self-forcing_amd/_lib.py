@@ -253,6 +253,8 @@ SIGNATURES = {
     "sf_kv_evict": (C.c_int, [_vp, _i, _i64, _i, _i, _i, _i, _vp, _sz, _vp]),
     "sf_attention": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _vp]),
     "sf_attention_ex": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp]),
+    "sf_attention_fold": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp]),
+    "sf_cross_fold_scan": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _i, _i, _i, _vp, _vp, _vp]),
     "sf_patchify": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sf_unpatchify_x0": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "sf_add_noise": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i64, _vp]),
@@ -260,6 +262,8 @@ SIGNATURES = {
     "sf_dit_workspace_bytes": (C.c_size_t, [C.POINTER(Model), _i, _i, _i, _i, _i]),
     "sf_dit_forward": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), _vp]),
     "sf_dit_forward_pair": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), C.POINTER(ForwardArgs), _vp]),
+    "sf_dit_forward_fold": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), _vp, _vp, _vp]),
+    "sf_dit_forward_pair_fold": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), C.POINTER(ForwardArgs), _vp, _vp, _vp]),
     "sf_conv_igemm": (C.c_int, [C.POINTER(ConvArgs), _vp]),
     "sf_conv_pick_nt": (C.c_int, [_i]),
     "sf_rmsnorm_silu_cl": (C.c_int, [_vp, _vp, _vp, _i64, _i, _i, _vp]),

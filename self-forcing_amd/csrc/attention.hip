@@ -46,7 +46,22 @@ struct AttP {
   long q_stride, q_bstride, kv_stride, kv_bstride, o_stride, o_bstride;
   int q_tiles;
   float scale_log2;  // (1/sqrt(D)) * log2(e)
+  // Optional (both or neither), one entry per sample: sample b attends only its first keys[b] rows, and log2w[b] is added
+  // to the exp2-domain score of row keys[b] - 1 -- that row then stands for 2^log2w identical rows (a prompt's padding
+  // keys folded into one, see sf_cross_fold_scan).  NULL: all Lk rows, nothing added.
+  const int* keys;
+  const float* log2w;
 };
+
+// This workgroup's key count and the weight of its last key: wave-uniform, read with scalar loads.
+__device__ __forceinline__ void fold_of_sample(const AttP& p, int b, int& lk, float& wl) {
+  lk = p.Lk;
+  wl = 0.f;
+  if (p.keys) {
+    lk = min(max(p.keys[b], 1), p.Lk);
+    wl = p.log2w[b];
+  }
+}
 
 __device__ __forceinline__ int lds_off(int row, int ch) {
   return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
@@ -77,6 +92,9 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
   const bf16_t* kbase = p.k + (long)b * p.kv_bstride + head * HD;
   const bf16_t* vbase = p.v + (long)b * p.kv_bstride + head * HD;
   bf16_t* obase = p.o + (long)b * p.o_bstride + head * HD;
+  int lk;
+  float wl;
+  fold_of_sample(p, b, lk, wl);
 
   const int r32 = lane & 31, hh = lane >> 5;
   const int qrow = qt * QT + wave * 32 + r32;
@@ -101,7 +119,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
   // advances through the scalar offset, and rows past Lk fall outside the descriptor's range and
   // read as zero (no clamping, no per-tile address arithmetic).  The range of one (batch, head)
   // slab is (Lk-1) * stride + 128 elements < 2^31 bytes (checked on the host).
-  const unsigned kv_bytes = (unsigned)(((long)(p.Lk - 1) * p.kv_stride + HD) * 2);
+  const unsigned kv_bytes = (unsigned)(((long)(lk - 1) * p.kv_stride + HD) * 2);
   const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(kbase), 0, kv_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(vbase), 0, kv_bytes, 0x00020000);
   unsigned st_goff[4];
@@ -160,7 +178,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
   float m_run = -1e30f, l_run = 0.f;
   const float c = p.scale_log2;
 
-  const int ntiles = (p.Lk + KT - 1) / KT;
+  const int ntiles = (lk + KT - 1) / KT;
+  const float wadd = wl / c;   // the scores here are still s: (s + w / c) c = s c + w
   load_tile(0);
   write_tile(0);
   __syncthreads();
@@ -207,7 +226,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = key0 + kb * 32 + (r & 3) + 8 * (r >> 2);
-          if (key >= p.Lk) st[kb][r] = -1e30f;
+          if (key >= lk) st[kb][r] = -1e30f;
+          else if (key == lk - 1) st[kb][r] += wadd;
         }
     }
 
@@ -275,7 +295,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
     write_tile(cur ^ 1);
     __syncthreads();
   };
-  const bool tail = (p.Lk & (KT - 1)) != 0;
+  const bool tail = (lk & (KT - 1)) != 0 || wl != 0.f;   // the masked path also carries the last key's weight
   const int nfull = tail ? ntiles - 1 : ntiles;
   for (int t = 0; t < nfull; ++t) process_tile(t, std::false_type{});
   if (tail) process_tile(ntiles - 1, std::true_type{});
@@ -346,6 +366,9 @@ __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
   const bf16_t* kbase = p.k + (long)b * p.kv_bstride + head * HD;
   const bf16_t* vbase = p.v + (long)b * p.kv_bstride + head * HD;
   bf16_t* obase = p.o + (long)b * p.o_bstride + head * HD;
+  int lk;
+  float wl;
+  fold_of_sample(p, b, lk, wl);
 
   const int r32 = lane & 31, hh = lane >> 5;
   const int qrow = qt * QT8 + wave * 32 + r32;
@@ -364,7 +387,7 @@ __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
   // slot ^ swz(row): the swizzle sits on the source side.  Issued from inline asm: with the builtin
   // hipcc puts `s_waitcnt vmcnt(0)` in front of every later ds_read (it cannot tell the buffers apart).
   // No staging registers, no ds_write; completion = one vmcnt(0) before the barrier of the next step.
-  const unsigned kv_bytes = (unsigned)(((long)(p.Lk - 1) * p.kv_stride + HD) * 2);
+  const unsigned kv_bytes = (unsigned)(((long)(lk - 1) * p.kv_stride + HD) * 2);
   auto make_srd = [&](const bf16_t* base) {
     const unsigned long long a64 = (unsigned long long)base;
     u32x4 d;
@@ -438,8 +461,9 @@ __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) st[kb][r] = 0.f;
 
-  const int ntiles = (p.Lk + KT - 1) / KT;
-  const bool tail = (p.Lk & (KT - 1)) != 0;
+  const int ntiles = (lk + KT - 1) / KT;
+  const float wadd = wl / c;   // the scores here are still s: (s + w / c) c = s c + w
+  const bool tail = (lk & (KT - 1)) != 0 || wl != 0.f;   // the masked path also carries the last key's weight
 
   // ---- matrix segment
   auto seg_pv = [&](int t) {   // O^T += V^T(t) . P^T
@@ -517,7 +541,8 @@ __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = key0 + kb * 32 + (r & 3) + 8 * (r >> 2);
-          if (key >= p.Lk) st[kb][r] = -1e30f;
+          if (key >= lk) st[kb][r] = -1e30f;
+          else if (key == lk - 1) st[kb][r] += wadd;
         }
     }
     float mx = fmaxf(st[0][0], st[1][0]);
@@ -706,6 +731,9 @@ __global__ __launch_bounds__(256) void attention_r64_kernel(AttP p) {
   const bf16_t* kbase = p.k + (long)b * p.kv_bstride + head * HD;
   const bf16_t* vbase = p.v + (long)b * p.kv_bstride + head * HD;
   bf16_t* obase = p.o + (long)b * p.o_bstride + head * HD;
+  int lk_b;
+  float wl;
+  fold_of_sample(p, b, lk_b, wl);
 
   const int r32 = lane & 31, hh = lane >> 5;
   const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
@@ -746,7 +774,7 @@ __global__ __launch_bounds__(256) void attention_r64_kernel(AttP p) {
 #pragma unroll
   for (int j = 0; j < SF_R64_N_PARAM; ++j) pl[j * 256 + tid] = prm[j];
 
-  const unsigned kv_bytes = (unsigned)(((long)(p.Lk - 1) * p.kv_stride + HD) * 2);
+  const unsigned kv_bytes = (unsigned)(((long)(lk_b - 1) * p.kv_stride + HD) * 2);
   auto make_srd = [&](const bf16_t* base) {
     const unsigned long long a64 = (unsigned long long)base;
     u32x4 d;
@@ -758,15 +786,16 @@ __global__ __launch_bounds__(256) void attention_r64_kernel(AttP p) {
   };
   const u32x4 k_srd = make_srd(kbase), v_srd = make_srd(vbase);
   const unsigned tile_bytes = __builtin_amdgcn_readfirstlane((unsigned)((long)KT * p.kv_stride * 2));
-  const int ntiles = __builtin_amdgcn_readfirstlane((p.Lk + KT - 1) / KT);
-  const int lk = __builtin_amdgcn_readfirstlane(p.Lk);
+  const int ntiles = __builtin_amdgcn_readfirstlane((lk_b + KT - 1) / KT);
+  const int lk = __builtin_amdgcn_readfirstlane(lk_b);
+  const unsigned wbits = __builtin_amdgcn_readfirstlane(__float_as_uint(wl));   // 0: no weight on the last key
   const unsigned cbits = __builtin_amdgcn_readfirstlane(__float_as_uint(p.scale_log2));
   const unsigned lds_wave = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)wave * 4096u);
   const unsigned lds_b = __builtin_amdgcn_readfirstlane(lds_base);
   const unsigned tid4 = lds_base + 4u * (unsigned)tid;
   asm volatile(SF_R64_ASM_BODY
                :
-               : "s"(k_srd), "s"(v_srd), "s"(tile_bytes), "s"(ntiles), "s"(lk), "s"(cbits), "s"(lds_wave), "v"(tid4), "s"(lds_b)
+               : "s"(k_srd), "s"(v_srd), "s"(tile_bytes), "s"(ntiles), "s"(lk), "s"(cbits), "s"(lds_wave), "v"(tid4), "s"(lds_b), "s"(wbits)
                : SF_R64_CLOBBERS);
 }
 
@@ -774,10 +803,12 @@ __global__ __launch_bounds__(256) void attention_r64_kernel(AttP p) {
 
 }  // namespace
 
-extern "C" int sf_attention_ex(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
-                               int Lk, int64_t q_stride, int64_t q_bstride, int64_t kv_stride,
-                               int64_t kv_bstride, int64_t o_stride, int64_t o_bstride, int structure, void* stream) {
+extern "C" int sf_attention_fold(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
+                                 int Lk, int64_t q_stride, int64_t q_bstride, int64_t kv_stride,
+                                 int64_t kv_bstride, int64_t o_stride, int64_t o_bstride, int structure,
+                                 const int32_t* keys, const float* log2w, void* stream) {
   SF_CHECK(q && k && v && out, "sf_attention: null tensor");
+  SF_CHECK((keys == nullptr) == (log2w == nullptr), "sf_attention: keys and log2w come together");
   SF_CHECK(B > 0 && H > 0 && Lq > 0 && Lk > 0, "sf_attention: empty problem B=%d H=%d Lq=%d Lk=%d", B, H, Lq, Lk);
   SF_CHECK(q_stride % 8 == 0 && kv_stride % 8 == 0 && o_stride % 4 == 0, "sf_attention: strides must keep 16-byte row alignment");
   SF_CHECK(q_bstride % 8 == 0 && kv_bstride % 8 == 0 && o_bstride % 4 == 0, "sf_attention: batch strides must keep alignment");
@@ -792,7 +823,8 @@ extern "C" int sf_attention_ex(const void* q, const void* k, const void* v, void
   p.o_stride = o_stride; p.o_bstride = o_bstride;
   p.q_tiles = (Lq + QT - 1) / QT;
   p.scale_log2 = 1.4426950408889634f / sqrtf((float)HD);
-  // Structure (SF_ATTN_AUTO): long key sequences that fill the chip run the hand-scheduled 64-rows-per-wave
+  p.keys = keys; p.log2w = log2w;
+  // Structure (SF_ATTN_AUTO; decided on the slab's Lk, whatever the samples' key counts): long key sequences that fill the chip run the hand-scheduled 64-rows-per-wave
   // kernel; short ones that fill it (cross-attention: 8 key tiles) the 8-wave anti-phase kernel (256 query rows
   // per workgroup); small problems the 4-wave one (128 rows, two workgroups per CU).  Every structure is correct
   // for every shape; the explicit values exist for tests and A/B timing.
@@ -837,6 +869,13 @@ extern "C" int sf_attention_ex(const void* q, const void* k, const void* v, void
     hipLaunchKernelGGL(attention_kernel<1>, dim3((unsigned)nwg), dim3(ATT_THREADS), ATT_LDS, (hipStream_t)stream, p);
   SF_HIP_LAUNCH_CHECK("sf_attention");
   return 0;
+}
+
+extern "C" int sf_attention_ex(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
+                               int Lk, int64_t q_stride, int64_t q_bstride, int64_t kv_stride,
+                               int64_t kv_bstride, int64_t o_stride, int64_t o_bstride, int structure, void* stream) {
+  return sf_attention_fold(q, k, v, out, B, H, Lq, Lk, q_stride, q_bstride, kv_stride, kv_bstride, o_stride, o_bstride,
+                           structure, nullptr, nullptr, stream);
 }
 
 extern "C" int sf_attention(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,

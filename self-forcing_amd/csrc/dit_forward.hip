@@ -71,7 +71,8 @@ extern "C" size_t sf_dit_workspace_bytes(const sf_model* model, int batch, int f
 // output element, so the results are bit-identical to separate calls; what changes is M (two passes of 4680 tokens give
 // the GEMMs 9360 rows: 1040-1440 instead of 810-1160 TFLOP/s) and the launch count.
 // cache_only passes must come first; past the LAST layer's K / V write only the remaining passes' rows continue.
-static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, int np, void* stream) {
+static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, int np, int32_t* cross_keys, float* cross_log2w, void* stream) {
+  SF_CHECK((cross_keys == nullptr) == (cross_log2w == nullptr), "sf_dit_forward: cross_keys and cross_log2w come together");
   const sf_forward_args* a = ps[0];
   SF_CHECK(m && a, "sf_dit_forward: null argument");
   SF_CHECK(m->layers_host && m->num_layers > 0, "sf_dit_forward: model has no layers");
@@ -182,6 +183,8 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
       SF_TRY(run(Gemm(ws.ctx, C, bptr(lw.ckv_w, (size_t)C * C), C, a->cv_cache_host[l], C, T, C, C).bias(bptr(lw.ckv_b, C))
                      .fp8w(f8 ? (const char*)lq.ckv_q + (size_t)C * C : nullptr, f8 ? lq.ckv_s + C : nullptr, T)));
     }
+    // how many trailing rows of each layer's and sample's K / V repeat the last one (the prompt's padding): folded into one key
+    if (cross_keys) SF_TRY(sf_cross_fold_scan(a->ck_cache_host, a->cv_cache_host, m->num_layers, B, m->text_len, C, cross_keys, cross_log2w, stream));
   }
 
   // ---- transformer blocks
@@ -225,8 +228,9 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
     SF_TRY(lin(Gemm(xn, C, lw.cq_w, C, qb, C, Mr, C, C).bias(lw.cq_b).fp8w(lq.cq_q, lq.cq_s, M)));
     SF_TRY(sf_rmsnorm(qb, C, lw.cnorm_q_w, qb, C, Mr, C, m->eps, stream));
     for (int p = p0; p < np; ++p)                            // every pass reads the same text K / V: one launch per pass
-      SF_TRY(sf_attention(bptr(ws.q, (size_t)p * M * C), a->ck_cache_host[l], a->cv_cache_host[l], (void*)bptr(ws.att, (size_t)p * M * C), B, m->num_heads, L,
-                          m->text_len, C, (long)L * C, C, ctx_b, C, (long)L * C, stream));
+      SF_TRY(sf_attention_fold(bptr(ws.q, (size_t)p * M * C), a->ck_cache_host[l], a->cv_cache_host[l], (void*)bptr(ws.att, (size_t)p * M * C), B, m->num_heads, L,
+                               m->text_len, C, (long)L * C, C, ctx_b, C, (long)L * C, SF_ATTN_AUTO, cross_keys ? cross_keys + (size_t)l * B : nullptr,
+                               cross_keys ? cross_log2w + (size_t)l * B : nullptr, stream));
     SF_TRY(lin(Gemm(att, C, lw.co_w, C, x, C, Mr, C, C).bias(lw.co_b).epi(SF_EPI_BIAS_RESID).resid(x, C).fp8w(lq.co_q, lq.co_s, M)));
     // feed forward
     SF_TRY(sf_layernorm_modulate(x, xn, Mr, C, m->eps, bptr(mod, 3 * (size_t)C), bptr(mod, 4 * (size_t)C), bptr(e0r, 3 * (size_t)C),
@@ -254,13 +258,24 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
 extern "C" int sf_dit_forward(const sf_model* m, const sf_forward_args* a, void* stream) {
   SF_CHECK(m && a, "sf_dit_forward: null argument");
   const sf_forward_args* one[1] = {a};
-  return forward_passes(m, one, 1, stream);
+  return forward_passes(m, one, 1, nullptr, nullptr, stream);
 }
 
-extern "C" int sf_dit_forward_pair(const sf_model* m, const sf_forward_args* context_pass, const sf_forward_args* next_pass, void* stream) {
+extern "C" int sf_dit_forward_fold(const sf_model* m, const sf_forward_args* a, int32_t* cross_keys, float* cross_log2w, void* stream) {
+  SF_CHECK(m && a, "sf_dit_forward: null argument");
+  const sf_forward_args* one[1] = {a};
+  return forward_passes(m, one, 1, cross_keys, cross_log2w, stream);
+}
+
+extern "C" int sf_dit_forward_pair_fold(const sf_model* m, const sf_forward_args* context_pass, const sf_forward_args* next_pass,
+                                        const int32_t* cross_keys, const float* cross_log2w, void* stream) {
   SF_CHECK(m && context_pass && next_pass, "sf_dit_forward_pair: null argument");
   SF_CHECK(context_pass->workspace == next_pass->workspace && context_pass->workspace_bytes == next_pass->workspace_bytes,
            "sf_dit_forward_pair: both passes name the same workspace (sized for 2 x batch)");
   const sf_forward_args* two[2] = {context_pass, next_pass};
-  return forward_passes(m, two, 2, stream);
+  return forward_passes(m, two, 2, const_cast<int32_t*>(cross_keys), const_cast<float*>(cross_log2w), stream);   // (written only with init_cross)
+}
+
+extern "C" int sf_dit_forward_pair(const sf_model* m, const sf_forward_args* context_pass, const sf_forward_args* next_pass, void* stream) {
+  return sf_dit_forward_pair_fold(m, context_pass, next_pass, nullptr, nullptr, stream);
 }

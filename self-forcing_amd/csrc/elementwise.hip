@@ -564,3 +564,61 @@ extern "C" int sf_sinusoid_embedding(const void* t, int t_is_int64, void* out, i
   SF_HIP_LAUNCH_CHECK("sf_sinusoid_embedding");
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------
+// Folding a prompt's padding keys (sf_cross_fold_scan).  The text encoder zero-fills the rows behind a prompt's tokens and
+// everything between those rows and the cross-attention K / V caches is row-wise, so the padded rows of a cache are
+// bit-identical to one another; n identical keys weigh in the softmax like one key whose score carries + log n.  The scan
+// looks at the CACHES (not at the embeddings), so whatever filled them, the count is right: per layer and sample, the
+// highest row that differs from the LAST row in K or in V (bitwise) is found with one wave per row, then
+//   same = text_len - 1 - that row  (>= 1: the last row itself),  keys = text_len - same + 1,  log2w = log2(same).
+__global__ void fold_reset_kernel(int* __restrict__ keys, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) keys[i] = -1;
+}
+
+__global__ __launch_bounds__(256) void fold_scan_kernel(const uint4* __restrict__ k, const uint4* __restrict__ v, int text_len, int row_chunks,
+                                                        int* __restrict__ last_diff) {
+  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= text_len - 1) return;                    // wave-uniform
+  const size_t slab = (size_t)b * text_len * row_chunks;
+  const uint4* kr = k + slab + (size_t)row * row_chunks;
+  const uint4* vr = v + slab + (size_t)row * row_chunks;
+  const uint4* kl = k + slab + (size_t)(text_len - 1) * row_chunks;
+  const uint4* vl = v + slab + (size_t)(text_len - 1) * row_chunks;
+  unsigned diff = 0;
+  for (int c = lane; c < row_chunks; c += 64) {
+    const uint4 a = kr[c], al = kl[c], d = vr[c], dl = vl[c];
+    diff |= (a.x ^ al.x) | (a.y ^ al.y) | (a.z ^ al.z) | (a.w ^ al.w) | (d.x ^ dl.x) | (d.y ^ dl.y) | (d.z ^ dl.z) | (d.w ^ dl.w);
+  }
+  if (__any(diff != 0) && lane == 0) atomicMax(last_diff + b, row);
+}
+
+__global__ void fold_finish_kernel(int* __restrict__ keys, float* __restrict__ log2w, int n, int text_len) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int same = text_len - 1 - keys[i];
+  keys[i] = text_len - same + 1;
+  log2w[i] = log2f((float)same);                      // exactly 0 when nothing is folded (same == 1)
+}
+
+extern "C" int sf_cross_fold_scan(const void* const* ck_cache_host, const void* const* cv_cache_host, int layers, int B, int text_len,
+                                  int row_elems, int32_t* keys, float* log2w, void* stream) {
+  SF_CHECK(ck_cache_host && cv_cache_host && keys && log2w, "sf_cross_fold_scan: null argument");
+  SF_CHECK(layers > 0 && B > 0 && text_len > 0 && row_elems > 0 && row_elems % 8 == 0, "sf_cross_fold_scan: bad shape layers=%d B=%d text_len=%d row=%d",
+           layers, B, text_len, row_elems);
+  hipStream_t s = (hipStream_t)stream;
+  const int n = layers * B;
+  hipLaunchKernelGGL(fold_reset_kernel, dim3((n + 255) / 256), dim3(256), 0, s, keys, n);
+  if (text_len > 1)
+    for (int l = 0; l < layers; ++l) {
+      SF_CHECK(ck_cache_host[l] && cv_cache_host[l], "sf_cross_fold_scan: null cache of layer %d", l);
+      SF_CHECK(((uintptr_t)ck_cache_host[l] | (uintptr_t)cv_cache_host[l]) % 16 == 0, "sf_cross_fold_scan: misaligned cache of layer %d", l);
+      hipLaunchKernelGGL(fold_scan_kernel, dim3((text_len - 1 + 3) / 4, B), dim3(256), 0, s, (const uint4*)ck_cache_host[l],
+                         (const uint4*)cv_cache_host[l], text_len, row_elems / 8, keys + (size_t)l * B);
+    }
+  hipLaunchKernelGGL(fold_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, s, keys, log2w, n, text_len);
+  SF_HIP_LAUNCH_CHECK("sf_cross_fold_scan");
+  return 0;
+}

@@ -10,7 +10,7 @@ Linears), the fp32 RoPE tables and a per-shape workspace; `forward` is ONE C cal
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -155,23 +155,28 @@ class CausalWanModel(DeviceModel):
     def forward(self, noisy: Tensor, timestep: Tensor, prompt_embeds: Optional[Tensor], init_cross: bool,
                 k_cache: List[Tensor], v_cache: List[Tensor], ck_cache: List[Tensor], cv_cache: List[Tensor], plan: CachePlan,
                 start_frame: int, evict_scratch: Optional[Tensor] = None, cache_only: bool = False,
-                add_condition: Optional[Tensor] = None, kv_index: Optional[Tensor] = None):
+                add_condition: Optional[Tensor] = None, kv_index: Optional[Tensor] = None,
+                cross_fold: Optional[Tuple[Tensor, Tensor]] = None):
         """noisy [B,F,in_dim,H,W] bf16 (contiguous); timestep [B,G] float32|int64 on device; *_cache: per-layer cache
         tensors (mutated in place); kv_index: the shared int64 [L, 2] buffer behind the cache dicts' index tensors (the
         pass ends by setting every row to (plan.global_end, plan.local_end)), or None.  Returns (flow, x0)
         [B,F,out_dim,H,W], or (None, None) with cache_only.
-        ONE custom-op call: torch.ops.sf_hip.dit_forward -> sf_dit_forward."""
+        cross_fold: the cross-attention caches' (keys, log2w) buffers (int32 / float32 [L, B], torch_ops.cross_fold_scan):
+        filled by this call with init_cross, read by every layer's cross-attention; None: all text_len keys are attended.
+        ONE custom-op call: torch.ops.sf_hip.dit_forward[_fold] -> sf_dit_forward_fold."""
         B, F, Cin, H, W = noisy.shape
         ws = self.workspace(B, F, H, W, timestep.shape[1])
-        flow, x0 = torch.ops.sf_hip.dit_forward(
+        op = torch.ops.sf_hip.dit_forward_fold if cross_fold else torch.ops.sf_hip.dit_forward
+        flow, x0 = op(
             self._handle, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, ws, evict_scratch,
             bool(init_cross), bool(cache_only), plan.sink, plan.evict, plan.keep, plan.write_start, plan.attn_start, plan.local_end,
-            start_frame, kv_index, plan.global_end)
+            start_frame, kv_index, plan.global_end, *(cross_fold or ()))
         return (None, None) if cache_only else (flow, x0)
 
     def forward_pair(self, ctx_noisy: Tensor, ctx_timestep: Tensor, noisy: Tensor, timestep: Tensor, k_cache: List[Tensor],
                      v_cache: List[Tensor], ck_cache: List[Tensor], cv_cache: List[Tensor], ctx_plan: CachePlan, plan: CachePlan,
-                     ctx_start_frame: int, start_frame: int, evict_scratch: Optional[Tensor] = None, kv_index: Optional[Tensor] = None):
+                     ctx_start_frame: int, start_frame: int, evict_scratch: Optional[Tensor] = None, kv_index: Optional[Tensor] = None,
+                     cross_fold: Optional[Tuple[Tensor, Tensor]] = None):
         """The context pass of chunk k (cache only) + the first denoising pass of chunk k + 1 as ONE call
         (torch.ops.sf_hip.dit_forward_pair -> sf_dit_forward_pair): bit-identical to two `forward` calls, but every
         row-wise kernel and GEMM sees both passes' rows at once.  Returns (flow, x0) of the denoising pass."""
@@ -180,4 +185,4 @@ class CausalWanModel(DeviceModel):
         as_list = lambda pl, sf: [pl.sink, pl.evict, pl.keep, pl.write_start, pl.attn_start, pl.local_end, sf]  # noqa: E731
         return torch.ops.sf_hip.dit_forward_pair(self._handle, ctx_noisy, ctx_timestep, noisy, timestep, k_cache, v_cache, ck_cache, cv_cache,
                                                  ws, evict_scratch, as_list(ctx_plan, ctx_start_frame), as_list(plan, start_frame), kv_index,
-                                                 plan.global_end)
+                                                 plan.global_end, *(cross_fold or (None, None)))

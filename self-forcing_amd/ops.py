@@ -177,10 +177,24 @@ def kv_evict(cache: Tensor, sink: int, evict: int, keep: int, scratch: Tensor) -
                             scratch.numel() * scratch.element_size(), stream_handle()), "sf_kv_evict")
 
 
-def attention(q: Tensor, k: Tensor, v: Tensor, structure: str = "auto") -> Tensor:
+def attention(q: Tensor, k: Tensor, v: Tensor, structure: str = "auto", keys: Optional[Tensor] = None,
+              log2w: Optional[Tensor] = None) -> Tensor:
     """q [B,Lq,H,128], k/v [B,Lk,H,128] (token/batch strides free, [H,D] contiguous) -> [B,Lq,H,128].
-    `structure` ("auto" | "r64" | "w8" | "w4") forces a kernel structure (tests / A-B timing)."""
-    return torch.ops.sf_hip.attention(q, k, v, _lib.ATTN_STRUCTURES[structure])
+    `structure` ("auto" | "r64" | "w8" | "w4") forces a kernel structure (tests / A-B timing).
+    `keys` int32 [B] / `log2w` float32 [B] (both or neither): sample b attends its first keys[b] rows only and the last
+    of them weighs 2^log2w[b] rows -- a slab whose trailing rows are identical, folded (`cross_fold_scan`)."""
+    return torch.ops.sf_hip.attention(q, k, v, _lib.ATTN_STRUCTURES[structure], keys, log2w)
+
+
+def cross_fold_scan(ck_cache, cv_cache) -> tuple:
+    """Lists (one entry per layer) of contiguous bf16 [B, Lk, H, 128] K and V slabs -> (keys int32 [L, B], log2w float32
+    [L, B]): per layer and sample, `same` = the trailing rows that repeat the last row bit for bit in K and in V;
+    keys = Lk - same + 1, log2w = log2(same)."""
+    L, B = len(ck_cache), ck_cache[0].shape[0]
+    keys = torch.empty(L, B, dtype=torch.int32, device=ck_cache[0].device)
+    log2w = torch.empty(L, B, dtype=torch.float32, device=ck_cache[0].device)
+    torch.ops.sf_hip.cross_fold_scan(list(ck_cache), list(cv_cache), keys, log2w)
+    return keys, log2w
 
 
 def patchify(x: Tensor) -> Tensor:

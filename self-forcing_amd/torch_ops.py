@@ -79,7 +79,10 @@ def _ptr(t: Optional[Tensor]) -> Optional[int]:
 
 # ------------------------------------------------------------------------------------------ attention
 @custom_op(f"{NAMESPACE}::attention", mutates_args=())
-def attention(q: Tensor, k: Tensor, v: Tensor, structure: int = 0) -> Tensor:
+def attention(q: Tensor, k: Tensor, v: Tensor, structure: int = 0, keys: Optional[Tensor] = None,
+              log2w: Optional[Tensor] = None) -> Tensor:
+    """softmax(q k^T / sqrt(D)) v.  `keys` (int32 [B]) / `log2w` (float32 [B]), both or neither: sample b attends only its
+    first keys[b] key rows and the last of them counts 2^log2w[b] times (sf_attention_fold; see cross_fold_scan)."""
     for n, t in (("q", q), ("k", k), ("v", v)):
         _need_gpu(t, n)
         if t.dim() != 4 or t.shape[3] != 128 or t.stride(3) != 1 or t.stride(2) != 128:
@@ -87,16 +90,55 @@ def attention(q: Tensor, k: Tensor, v: Tensor, structure: int = 0) -> Tensor:
     B, Lq, H, D = q.shape
     if k.stride() != v.stride() or k.shape != v.shape:
         raise ValueError("attention: k and v must share shape and strides")
+    _fold_pair(keys, log2w, (B,), q.device, "attention")
     out = torch.empty(B, Lq, H, D, dtype=torch.bfloat16, device=q.device)
-    _lib.check(_lib.lib().sf_attention_ex(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Lq, k.shape[1],
-                                          q.stride(1), q.stride(0), k.stride(1), k.stride(0), out.stride(1), out.stride(0),
-                                          structure, _stream(q)), "sf_attention")
+    _lib.check(_lib.lib().sf_attention_fold(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Lq, k.shape[1],
+                                            q.stride(1), q.stride(0), k.stride(1), k.stride(0), out.stride(1), out.stride(0),
+                                            structure, _ptr(keys), _ptr(log2w), _stream(q)), "sf_attention")
     return out
 
 
 @attention.register_fake
-def _(q, k, v, structure=0):
+def _(q, k, v, structure=0, keys=None, log2w=None):
     return q.new_empty(q.shape)
+
+
+@custom_op(f"{NAMESPACE}::cross_fold_scan", mutates_args=("keys", "log2w"))
+def cross_fold_scan(ck_cache: List[Tensor], cv_cache: List[Tensor], keys: Tensor, log2w: Tensor) -> None:
+    """Per layer l and sample b of the cross-attention caches (lists of contiguous bf16 [B, text_len, H, D]): how many
+    trailing rows repeat the last row bit for bit in both K and V (a zero-padded prompt's padding) -> keys[l, b] =
+    text_len - same + 1 (int32) and log2w[l, b] = log2(same) (float32), what `attention` / `dit_forward` take to attend one
+    key in place of `same` identical ones (sf_cross_fold_scan)."""
+    L = len(ck_cache)
+    if L == 0 or len(cv_cache) != L:
+        raise ValueError("cross_fold_scan: one K and one V cache per layer expected")
+    want = tuple(ck_cache[0].shape)
+    for name, ts in (("ck_cache", ck_cache), ("cv_cache", cv_cache)):
+        for i, t in enumerate(ts):
+            if not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 4 or tuple(t.shape) != want or not t.is_contiguous() \
+                    or t.device != keys.device:
+                raise ValueError(f"cross_fold_scan: {name}[{i}] must be a contiguous bf16 tensor {want} on {keys.device}")
+    B, T = want[0], want[1]
+    _fold_pair(keys, log2w, (L, B), ck_cache[0].device, "cross_fold_scan")
+    arr = lambda ts: (C.c_void_p * L)(*[t.data_ptr() for t in ts])  # noqa: E731
+    _lib.check(_lib.lib().sf_cross_fold_scan(arr(ck_cache), arr(cv_cache), L, B, T, want[2] * want[3], keys.data_ptr(), log2w.data_ptr(),
+                                             _stream(keys)), "sf_cross_fold_scan")
+
+
+@cross_fold_scan.register_fake
+def _(ck_cache, cv_cache, keys, log2w):
+    return None
+
+
+def _fold_pair(keys: Optional[Tensor], log2w: Optional[Tensor], shape: tuple, device, who: str) -> None:
+    """The kernels index these two by sample (and layer) without a bound of their own: check them here."""
+    if (keys is None) != (log2w is None):
+        raise ValueError(f"{who}: keys and log2w come together")
+    if keys is None:
+        return
+    for name, t, dt in (("keys", keys, torch.int32), ("log2w", log2w, torch.float32)):
+        if not t.is_cuda or t.device != device or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor {shape} on {device}, got {tuple(t.shape)} {t.dtype} {t.device}")
 
 
 # ------------------------------------------------------------------------------------------ GEMM
@@ -413,11 +455,36 @@ def dit_forward(model: int, noisy: Tensor, timestep: Tensor, prompt_embeds: Opti
     into k_cache / v_cache (and, with init_cross, the text K/V into ck_cache / cv_cache); returns (flow, x0), or two
     empty tensors with cache_only.  kv_index (optional, int64 [num_layers, 2]): every row <- (global_end, attn_end),
     the cache dicts' index tensors when they are views of one buffer."""
+    return _dit_forward(model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
+                        init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame, kv_index, global_end,
+                        None, None)
+
+
+@custom_op(f"{NAMESPACE}::dit_forward_fold",
+           mutates_args=("k_cache", "v_cache", "ck_cache", "cv_cache", "workspace", "evict_scratch", "kv_index", "cross_keys", "cross_log2w"))
+def dit_forward_fold(model: int, noisy: Tensor, timestep: Tensor, prompt_embeds: Optional[Tensor], add_condition: Optional[Tensor],
+                     k_cache: List[Tensor], v_cache: List[Tensor], ck_cache: List[Tensor], cv_cache: List[Tensor],
+                     workspace: Tensor, evict_scratch: Optional[Tensor], init_cross: bool, cache_only: bool, sink: int, evict: int,
+                     keep: int, write_start: int, attn_start: int, attn_end: int, start_frame: int,
+                     kv_index: Optional[Tensor], global_end: int, cross_keys: Tensor, cross_log2w: Tensor) -> Tuple[Tensor, Tensor]:
+    """dit_forward with the cross-attention padding folded (sf_dit_forward_fold): cross_keys / cross_log2w (int32 / float32
+    [num_layers, B]) are the cross-attention caches' folded key counts (cross_fold_scan), written with init_cross and
+    read by every layer's cross-attention."""
+    return _dit_forward(model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
+                        init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame, kv_index, global_end,
+                        cross_keys, cross_log2w)
+
+
+def _dit_forward(model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
+                 init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame, kv_index, global_end,
+                 cross_keys, cross_log2w):
     m = _model(model)
     a, flow, x0 = _forward_args(m, model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace,
                                 evict_scratch, init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame,
                                 kv_index, global_end)
-    _lib.check(_timed_call(_lib.lib().sf_dit_forward, C.byref(m.cmodel), C.byref(a), _stream(noisy)), "sf_dit_forward")
+    _fold_pair(cross_keys, cross_log2w, (m.num_layers, noisy.shape[0]), noisy.device, "dit_forward")
+    _lib.check(_timed_call(_lib.lib().sf_dit_forward_fold, C.byref(m.cmodel), C.byref(a), _ptr(cross_keys), _ptr(cross_log2w), _stream(noisy)),
+               "sf_dit_forward")
     return flow, x0
 
 
@@ -426,11 +493,12 @@ def dit_forward(model: int, noisy: Tensor, timestep: Tensor, prompt_embeds: Opti
 def dit_forward_pair(model: int, ctx_noisy: Tensor, ctx_timestep: Tensor, noisy: Tensor, timestep: Tensor,
                      k_cache: List[Tensor], v_cache: List[Tensor], ck_cache: List[Tensor], cv_cache: List[Tensor],
                      workspace: Tensor, evict_scratch: Optional[Tensor], ctx_plan: List[int], plan: List[int],
-                     kv_index: Optional[Tensor], global_end: int) -> Tuple[Tensor, Tensor]:
+                     kv_index: Optional[Tensor], global_end: int, cross_keys: Optional[Tensor] = None,
+                     cross_log2w: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """The context pass of one chunk (cache_only) and the first denoising pass of the next in ONE call
     (sf_dit_forward_pair): bit-identical to the two calls, twice the rows per GEMM.  `ctx_plan` / `plan` =
     [sink, evict, keep, write_start, attn_start, attn_end, start_frame] of the two passes; workspace sized for 2 x batch.
-    Returns (flow, x0) of the denoising pass."""
+    cross_keys / cross_log2w as in dit_forward (read only).  Returns (flow, x0) of the denoising pass."""
     m = _model(model)
     if len(ctx_plan) != 7 or len(plan) != 7 or ctx_noisy.shape != noisy.shape or ctx_timestep.shape != timestep.shape:
         raise ValueError("dit_forward_pair: two passes of one shape with 7 plan integers each expected")
@@ -438,21 +506,34 @@ def dit_forward_pair(model: int, ctx_noisy: Tensor, ctx_timestep: Tensor, noisy:
                              False, True, *ctx_plan, None, 0)
     a1, flow, x0 = _forward_args(m, model, noisy, timestep, None, None, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
                                  False, False, *plan, kv_index, global_end)
-    _lib.check(_timed_call(_lib.lib().sf_dit_forward_pair, C.byref(m.cmodel), C.byref(a0), C.byref(a1), _stream(noisy)), "sf_dit_forward_pair")
+    _fold_pair(cross_keys, cross_log2w, (m.num_layers, noisy.shape[0]), noisy.device, "dit_forward_pair")
+    _lib.check(_timed_call(_lib.lib().sf_dit_forward_pair_fold, C.byref(m.cmodel), C.byref(a0), C.byref(a1), _ptr(cross_keys), _ptr(cross_log2w),
+                           _stream(noisy)), "sf_dit_forward_pair")
     return flow, x0
 
 
 @dit_forward_pair.register_fake
 def _(model, ctx_noisy, ctx_timestep, noisy, timestep, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch, ctx_plan, plan,
-      kv_index, global_end):
+      kv_index, global_end, cross_keys=None, cross_log2w=None):
     B, F, _, H, W = noisy.shape
     out_dim = _model(model).shape.out_dim
     return noisy.new_empty((B, F, out_dim, H, W)), noisy.new_empty((B, F, out_dim, H, W))
 
 
+@dit_forward_fold.register_fake
+def _(model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
+      init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame, kv_index, global_end,
+      cross_keys, cross_log2w):
+    return _dit_forward_fake(model, noisy, cache_only)
+
+
 @dit_forward.register_fake
 def _(model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
       init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame, kv_index, global_end):
+    return _dit_forward_fake(model, noisy, cache_only)
+
+
+def _dit_forward_fake(model, noisy, cache_only):
     if cache_only:
         return noisy.new_empty((0,)), noisy.new_empty((0,))
     B, F, _, H, W = noisy.shape

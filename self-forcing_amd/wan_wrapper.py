@@ -95,6 +95,7 @@ class WanDiffusionWrapper(torch.nn.Module):
         self.model = CausalWanModel(shape, state_dict, device, self.scheduler.sigmas, self.scheduler.timesteps, fp8=fp8)
         self.seq_len = 32760
         self._evict_scratch: Optional[Tensor] = None
+        self._cross_fold: Dict[tuple, tuple] = {}
         self._init_throttle()
 
     # --- host-side pacing ---------------------------------------------------------------------
@@ -134,6 +135,7 @@ class WanDiffusionWrapper(torch.nn.Module):
         other.model = self.model
         other.seq_len = self.seq_len
         other._evict_scratch = None
+        other._cross_fold = {}
         other._init_throttle()
         return other
 
@@ -172,6 +174,37 @@ class WanDiffusionWrapper(torch.nn.Module):
             self._evict_scratch = torch.empty(batch * cap * dim * 2, dtype=torch.uint8, device=self.model.device)
         return self._evict_scratch
 
+    # --- cross-attention: a prompt's padding keys folded into one ---------------------------------
+    # The rows of `prompt_embeds` behind the prompt's tokens are zero (utils/wan_wrapper.py:50-51) and everything from
+    # there to the cross-attention K / V caches is row-wise, so a cache's padded rows are identical: one of them, with
+    # log2(their number) added to its score, gives the same softmax as all of them, and the kernel walks 1-4 key tiles
+    # instead of 8.  The counts are taken from the caches themselves on the device (torch_ops.cross_fold_scan) and live
+    # in two small buffers that belong to the caches' tensors: a cache dict keeps the reference's schema.  False: attend
+    # every key, as the reference does.
+    fold_cross_padding = True
+
+    def _cross_fold_buffers(self, crossattn_cache: List[dict], init_cross: bool):
+        """(keys, log2w) of these cache tensors, or None with folding off.  The pass that fills the caches (init_cross) also
+        fills the buffers; caches this wrapper has not seen filled -- adopted from elsewhere with is_init set, or rebound to
+        other tensors -- are scanned here once.  (A caller that rewrites an initialised cache IN PLACE must clear is_init or
+        rebind the tensors: nothing on the host can see that.)"""
+        if not self.fold_cross_padding:
+            return None
+        ck, cv = [c["k"] for c in crossattn_cache], [c["v"] for c in crossattn_cache]
+        key = tuple(t.data_ptr() for t in ck) + tuple(t.data_ptr() for t in cv) + tuple(ck[0].shape) \
+            + (torch.cuda.current_stream(ck[0].device).cuda_stream,)
+        hit = self._cross_fold.get(key)
+        if hit is None:
+            if len(self._cross_fold) > 16:
+                self._cross_fold.clear()
+            B = ck[0].shape[0]
+            hit = (torch.empty(len(ck), B, dtype=torch.int32, device=ck[0].device),
+                   torch.empty(len(ck), B, dtype=torch.float32, device=ck[0].device))
+            self._cross_fold[key] = hit
+            if not init_cross:
+                torch.ops.sf_hip.cross_fold_scan(ck, cv, hit[0], hit[1])
+        return hit
+
     # --- two passes in one call ------------------------------------------------------------------
     def can_pair(self, conditional_dict: dict) -> bool:
         """`forward_pair` covers the plain text-conditioned rollout (no pose tokens / image conditioning)."""
@@ -209,7 +242,8 @@ class WanDiffusionWrapper(torch.nn.Module):
         index_buf = shared_index_buffer(kv_cache)
         flow, x0 = mdl.forward_pair(xs[0], ts[0], xs[1], ts[1], [kv["k"] for kv in kv_cache], [kv["v"] for kv in kv_cache],
                                     [c["k"] for c in crossattn_cache], [c["v"] for c in crossattn_cache], plan0, plan1,
-                                    context_start // fs, current_start // fs, scratch, kv_index=index_buf)
+                                    context_start // fs, current_start // fs, scratch, kv_index=index_buf,
+                                    cross_fold=self._cross_fold_buffers(crossattn_cache, False))
         write_indices(kv_cache, plan1.global_end, plan1.local_end, done_by_kernel=index_buf is not None)
         self._pace(mdl.device)
         return flow, x0
@@ -288,7 +322,7 @@ class WanDiffusionWrapper(torch.nn.Module):
         flow, x0 = mdl.forward(x, t, pe, init_cross, [kv["k"] for kv in kv_cache], [kv["v"] for kv in kv_cache],
                                [c["k"] for c in crossattn_cache], [c["v"] for c in crossattn_cache], plan,
                                current_start // fs, scratch, cache_only=cache_only, add_condition=add_condition,
-                               kv_index=index_buf)
+                               kv_index=index_buf, cross_fold=self._cross_fold_buffers(crossattn_cache, init_cross))
         if init_cross:
             for c in crossattn_cache:
                 c["is_init"] = True

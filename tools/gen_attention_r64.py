@@ -56,7 +56,7 @@ OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 
                    "attention_r64_asm.inc")
 
 # ---- inline-asm operands (inputs only)
-K_SRD, V_SRD, TILE_BYTES, NTILES, LK, CSCALE, LDS_WAVE, TID4, LDS_BASE = "%0", "%1", "%2", "%3", "%4", "%5", "%6", "%7", "%8"
+K_SRD, V_SRD, TILE_BYTES, NTILES, LK, CSCALE, LDS_WAVE, TID4, LDS_BASE, LOG2W = "%0", "%1", "%2", "%3", "%4", "%5", "%6", "%7", "%8", "%9"
 
 # ---- register map
 KADDR = [1 + i for i in range(8)]
@@ -78,6 +78,7 @@ MRC = [242, 243]      # m c per query block (log2 units)
 L2 = [244, 246]
 DLT = [248, 250]      # rescale amount
 NEG = 254
+WLAST, WSEL = 50, 51  # log2 weight of key Lk - 1 (all lanes) | that, or 0, for the score register at hand
 A_O = lambda qb, db: (qb * 4 + db) * 16          # noqa: E731
 A_Q = lambda qb, s: 128 + (qb * 8 + s) * 4       # noqa: E731
 KF, VF = 192, 224     # AGPR fragment slots
@@ -179,6 +180,24 @@ def new_label(stem):
     return f".Lr64_{stem}_{label_n[0]}%="
 
 
+def last_key_weight(sbuf, kb):
+    """Key Lk - 1 may stand for several identical keys (folded padding): its score, already in the exp2 domain, gets
+    log2 of their number (LOG2W) before the row maxima, so that the lazy rescale sees it.  Weight 0 -- always in
+    self-attention -- costs one scalar compare and an untaken branch per masked unit; the adds sit out of line."""
+    blk, back = new_label("wlast"), new_label("wlast_done")
+    c = [f"{blk}:"]
+    for r in range(16):
+        # this lane's key of score register r is Lk - 1  <=>  SLIM - 1 - (32 kb + (r&3) + 8 (r>>2)) == 4 hh
+        c.append(f"s_sub_i32 s{STMP2}, s{SLIM}, {32 * kb + (r & 3) + 8 * (r >> 2) + 1}")
+        c.append(f"v_cmp_eq_i32 vcc, s{STMP2}, {vr(HH4)}")
+        c.append(f"v_cndmask_b32 {vr(WSEL)}, 0, {vr(WLAST)}, vcc")
+        for qb in range(2):
+            c.append(f"v_add_f32 {vr(S[sbuf] + 16 * qb + r)}, {vr(S[sbuf] + 16 * qb + r)}, {vr(WSEL)}")
+    c.append(f"s_branch {back}")
+    cold.extend(c)
+    return f"s_cmp_lg_u32 {LOG2W}, 0\n\ts_cbranch_scc1 {blk}\n\t{back}:"
+
+
 def max_items(sbuf, masked, kb):
     """row maxima of one unit's scores (already s c - m c) for both query blocks -> MX"""
     it = []
@@ -186,6 +205,7 @@ def max_items(sbuf, masked, kb):
     if "nosoftmax" in ABL or "nomax" in ABL:
         return it
     if masked:
+        it.append(("valu", last_key_weight(sbuf, kb)))
         # key = 64 t + 32 kb + (r&3) + 8 (r>>2) + 4 hh ; SLIM = Lk - 64 t
         for r in range(16):
             it.append(("valu", f"s_sub_i32 s{STMP}, s{SLIM}, {32 * kb + (r & 3) + 8 * (r >> 2)}"))
@@ -461,6 +481,7 @@ def main():
     e(f"s_mov_b32 s{C2}, {CSCALE}")
     e(f"s_mov_b32 s{C2 + 1}, {CSCALE}")
     e(f"v_mov_b32 {vr(NEG)}, 0xf149f2ca")          # -1e30
+    e(f"v_mov_b32 {vr(WLAST)}, {LOG2W}")
     for qb in range(2):
         e(f"v_mov_b32 {vr(L2[qb])}, 0")
         e(f"v_mov_b32 {vr(L2[qb] + 1)}, 0")
