@@ -33,6 +33,12 @@ image with the VAE encoder (so it needs a VAE with encoder weights: `--vae_path`
 `--taehv_path` checkpoint that holds the `encoder.*` tensors, as taew2_1.pth does, or `--taehv_random_init_seed`) as the
 first latent frame and draws noise for the `num_output_frames - 1` frames after it.  Single process only, as in the
 reference.
+
+`--input_image PATH` is the other image conditioning: the i2v MODEL TYPE (a generator whose shape says so, selected by
+`model_name: Wan2.1-I2V-14B` in the config's `model_kwargs`; multi-step configs only).  The image is resized to the output
+size and handed to `CausalDiffusionInferencePipeline.inference(input_image=...)`, which encodes it with the CLIP image
+encoder (`--clip_path` checkpoint or `--clip_random_init_seed N`) and the VAE encoder (a VAE with encoder weights, as
+for `--i2v`) into the generator's `clip_feature` and `y`.  `--i2v` stays "first frame as initial latent" of a t2v model.
 """
 import argparse
 import glob
@@ -113,6 +119,9 @@ def main():
     ap.add_argument("--random_init_seed", type=int, default=None, help="seeded random weights instead of a checkpoint")
     ap.add_argument("--data_path", required=True, help="one prompt per line; with --i2v a TextImagePairDataset directory")
     ap.add_argument("--i2v", action="store_true", help="image-to-video: encode each image as the first latent frame")
+    ap.add_argument("--input_image", default=None, help="condition an i2v-type generator on this image (multi-step sampler; CLIP + VAE encoder)")
+    ap.add_argument("--clip_path", default=None, help="--input_image: the CLIP image encoder's checkpoint")
+    ap.add_argument("--clip_random_init_seed", type=int, default=None, help="--input_image: seeded random CLIP weights instead")
     ap.add_argument("--eval_first_n", type=int, default=0)
     ap.add_argument("--prompt_embeds", default=None)
     ap.add_argument("--output_folder", required=True)
@@ -145,6 +154,15 @@ def main():
             ap.error("pose conditioning needs --pose_path and exactly one of --pose_weights_path / --pose_random_init_seed")
         if is_few_step(load_config(a.config_path, a.default_config_path)):
             ap.error("--pose_path needs a multi-step config (one without denoising_step_list): the few-step pipeline takes no pose input")
+    if a.input_image:
+        if (a.clip_path is None) == (a.clip_random_init_seed is None):
+            ap.error("--input_image needs exactly one of --clip_path / --clip_random_init_seed")
+        if not a.vae_path and a.vae_random_init_seed is None:
+            ap.error("--input_image needs a VAE with encoder weights: --vae_path or --vae_random_init_seed")
+        if a.i2v:
+            ap.error("--input_image (the i2v model type) and --i2v (first frame as initial latent) are different paths: pick one")
+        if is_few_step(load_config(a.config_path, a.default_config_path)):
+            ap.error("--input_image needs a multi-step config (one without denoising_step_list): the few-step pipeline takes no image")
     if a.taehv_path and a.taehv_random_init_seed is not None:
         ap.error("--taehv_path and --taehv_random_init_seed are mutually exclusive")
     if (a.taehv_path or a.taehv_random_init_seed is not None) and (a.vae_path or a.vae_random_init_seed is not None):
@@ -190,7 +208,8 @@ def main():
     if a.vae_path:
         vae = sfa.WanVAEWrapper(torch.load(a.vae_path, map_location="cpu", weights_only=True), device=device)
     elif a.vae_random_init_seed is not None:
-        vae = sfa.WanVAEWrapper(sfa.synth_vae_state_dict(sfa.WAN_VAE, seed=a.vae_random_init_seed, encoder=a.i2v), device=device)
+        vae = sfa.WanVAEWrapper(sfa.synth_vae_state_dict(sfa.WAN_VAE, seed=a.vae_random_init_seed, encoder=a.i2v or bool(a.input_image)),
+                                device=device)
     if a.taehv_path:
         vae = sfa.TAEHVWrapper(checkpoint_path=a.taehv_path, device=device)
     elif a.taehv_random_init_seed is not None:
@@ -214,7 +233,18 @@ def main():
             weights = a.pose_weights_path if a.pose_weights_path else sfa.synth_pose_state_dict(seed=a.pose_random_init_seed)
             pose_embedder = sfa.PoseEmbedder(weights, device=device, strict=cfg.get("pose_weights_strict", True))
             pose_data = load_pose(a.pose_path)
-        pipe = sfa.CausalDiffusionInferencePipeline(cfg, device, generator=gen, text_encoder=enc, vae=vae, pose_embedder=pose_embedder)
+        image_encoder = input_image = None
+        if a.input_image:
+            if gen.model.model_type != "i2v":
+                raise SystemExit(f"--input_image needs a generator of the i2v model type, this one is {gen.model.model_type!r}")
+            clip_shape = sfa.CLIP_VIT_H_14 if shape.clip_dim == sfa.CLIP_VIT_H_14.dim else sfa.CLIP_REDUCED
+            if a.clip_path:
+                image_encoder = sfa.CLIPModel(device=device, checkpoint_path=a.clip_path, shape=clip_shape)
+            else:
+                image_encoder = sfa.CLIPModel(device=device, state_dict=sfa.synth_clip_state_dict(clip_shape, a.clip_random_init_seed), shape=clip_shape)
+            input_image = load_image(a.input_image, 8 * a.latent_height, 8 * a.latent_width)
+        pipe = sfa.CausalDiffusionInferencePipeline(cfg, device, generator=gen, text_encoder=enc, vae=vae, pose_embedder=pose_embedder,
+                                                    image_encoder=image_encoder)
         if a.sampling_steps:
             pipe.sampling_steps = a.sampling_steps
 
@@ -237,7 +267,7 @@ def main():
                                             return_latents=True)
         else:
             dwpose, ref_pose = pose_data if a.pose_path else (None, None)
-            video, latents = pipe.inference(noise, [prompts[idx]] * a.num_samples, None, dwpose, ref_pose, initial_latent=initial,
+            video, latents = pipe.inference(noise, [prompts[idx]] * a.num_samples, input_image, dwpose, ref_pose, initial_latent=initial,
                                             return_latents=True)
         for s in range(a.num_samples):
             torch.save(latents[s].cpu(), os.path.join(a.output_folder, f"{idx}-{s}.pt"))

@@ -175,6 +175,16 @@ int sf_attention_fold(const void* q, const void* k, const void* v, void* out, in
                       int64_t o_stride, int64_t o_bstride, int structure, const int32_t* keys, const float* log2w,
                       void* stream);
 
+/* sf_attention_ex that ADDS into `out` instead of overwriting it: out = bf16(float(out) + softmax(q k^T / sqrt(D)) v), the
+ * sum taken in fp32 in the kernel's epilogue and rounded once.  The i2v cross-attention (model.py:240-266) is
+ * o(attn(q, k, v) + attn(q, k_img, v_img)): the image attention accumulates into the buffer the text attention wrote,
+ * with no third buffer and no elementwise pass.  A compile-time epilogue variant of the SF_ATTN_W8 and SF_ATTN_W4
+ * structures; SF_ATTN_AUTO picks between those two, SF_ATTN_R64 is an error (the hand-scheduled stream has no such
+ * epilogue).  Every query row of `out` must hold a finite value on entry. */
+int sf_attention_accum(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq, int Lk,
+                       int64_t q_stride, int64_t q_bstride, int64_t kv_stride, int64_t kv_bstride,
+                       int64_t o_stride, int64_t o_bstride, int structure, void* stream);
+
 /* Per layer l and sample b of the cross-attention caches ck / cv (HOST arrays [layers] of device pointers, each
  * [B, text_len, row_elems] bf16): same = the number of trailing rows that equal the last row bit for bit in BOTH caches;
  * keys[l * B + b] = text_len - same + 1 (the rows in front plus one representative; text_len when same == 1) and
@@ -319,6 +329,63 @@ int sf_dit_forward_fold(const sf_model* model, const sf_forward_args* args, int3
                         void* stream);
 int sf_dit_forward_pair_fold(const sf_model* model, const sf_forward_args* context_pass, const sf_forward_args* next_pass,
                              const int32_t* cross_keys, const float* cross_log2w, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The i2v model type (CausalWanModel(model_type='i2v', in_dim=36), causal_model.py:767-775, :844-846; WanI2VCrossAttention
+ * and MLPProj, model.py:222-266, :469-481).  Everything i2v travels in the structs below, beside an sf_model /
+ * sf_forward_args pair that keeps its layout:
+ *   patch embedding  cat([x, y], channel) = 16 + 20 = 36 channels -> 144 columns, zero-padded to the GEMM's K % 64 == 0:
+ *                    the sf_model of an i2v generator says in_dim = 48 and carries patch_w [dim, 192] with columns
+ *                    144..191 zero; `noisy` stays [B, F, 16, H, W]
+ *   context          img_emb(clip_feature) -> 257 image tokens, once per prompt (init_cross)
+ *   cross-attention  out = o(attn(q, k, v) + attn(q, k_img, v_img)), k_img = norm_k_img(k_img(ctx_img)), v_img = v_img(ctx_img),
+ *                    both cached per layer beside the text K / V. */
+
+/* The 36-channel patch gather: x [B, F, x_channels, H, W] -> columns c * 4 + p * 2 + q (c < x_channels) of cols
+ * [B*F*(H/2)*(W/2), pad_channels * 4]; y [B, y_channels, F, H, W] CHANNEL-first through its element strides (batch, channel,
+ * frame; H x W planes contiguous; y_bstride 0 = one image for the whole batch) -> channels x_channels ..; the remaining
+ * channels up to pad_channels are written as zeros. */
+int sf_patchify_i2v(const void* x, const void* y, void* cols, int B, int F, int x_channels, int y_channels, int pad_channels,
+                    int H, int W, int64_t y_bstride, int64_t y_cstride, int64_t y_fstride, void* stream);
+
+/* nn.LayerNorm with affine weight / bias over rows of any width C % 8 == 0 (bf16 in / out, fp32 statistics):
+ * img_emb.proj.0 normalises clip_dim = 1280, which sf_layernorm_affine (C = 512 * {1,2,3,4,5,6,8,10}) cannot hold. */
+int sf_layernorm_rows(const void* x, const void* weight, const void* bias, void* out, int M, int C, float eps, void* stream);
+
+typedef struct sf_i2v_layer {             /* WanI2VCrossAttention beyond WanT2VCrossAttention */
+  const void *kvimg_w, *kvimg_b;          /* [2C, C], [2C]: cross_attn k_img|v_img stacked */
+  const void* norm_k_img_w;               /* [C] */
+} sf_i2v_layer;
+
+typedef struct sf_i2v_model {
+  int32_t clip_dim, clip_len;             /* clip_feature: [B, clip_len, clip_dim]; clip_dim % 64 == 0 */
+  float img_eps;                          /* eps of img_emb's two LayerNorms (nn.LayerNorm's default 1e-5) */
+  const void *img_ln0_w, *img_ln0_b;      /* img_emb.proj.0  LayerNorm(clip_dim)        */
+  const void *img_fc1_w, *img_fc1_b;      /* img_emb.proj.1  Linear(clip_dim, clip_dim), then erf-GELU */
+  const void *img_fc2_w, *img_fc2_b;      /* img_emb.proj.3  Linear(clip_dim, dim)      */
+  const void *img_ln1_w, *img_ln1_b;      /* img_emb.proj.4  LayerNorm(dim)             */
+  const sf_i2v_layer* layers_host;        /* HOST array [num_layers] */
+} sf_i2v_model;
+
+typedef struct sf_i2v_args {
+  const void* clip_feature;               /* bf16 [B, clip_len, clip_dim]; read only with init_cross */
+  const void* y;                          /* bf16 [B or 1, y_channels, F, H, W] of THIS pass's frames, through its strides */
+  int64_t y_bstride, y_cstride, y_fstride;/* elements; y_bstride 0 broadcasts one image over the batch */
+  int32_t y_channels;                     /* 16 + y_channels must be the generator's in_dim (36) */
+  void* const* kimg_cache_host;           /* HOST arrays [num_layers] of device pointers, each [B, clip_len, H, D] bf16: */
+  void* const* vimg_cache_host;           /*   written with init_cross, read by every pass                              */
+} sf_i2v_args;
+
+/* sf_dit_workspace_bytes plus the image context's buffers (the workspace an i2v pass needs). */
+size_t sf_dit_i2v_workspace_bytes(const sf_model* model, const sf_i2v_model* i2v_model, int batch, int frames, int lat_h,
+                                  int lat_w, int groups);
+/* One pass of an i2v generator: sf_dit_forward_fold (cross_keys / cross_log2w both NULL: no folding of the text keys)
+ * with the 36-channel patch embedding and, behind every layer's text cross-attention, sf_attention_accum over the
+ * clip_len image keys.  With init_cross the image context and every layer's k_img / v_img are computed beside the text
+ * K / V; cache_only and the rolling window behave as in sf_dit_forward.  Not built: the two-pass call and fp8 Linears
+ * (model->fp8 != 0 is an error). */
+int sf_dit_forward_i2v(const sf_model* model, const sf_i2v_model* i2v_model, const sf_forward_args* args, const sf_i2v_args* i2v_args,
+                       int32_t* cross_keys, float* cross_log2w, void* stream);
 
 /* ==========================================================================================
  * Wan VAE decode (latents -> pixels): WanVAEWrapper.decode_to_pixel -> WanVAE_.decode /

@@ -6,7 +6,7 @@ declared in `include/sf_hip.h` (built into `self-forcing_amd/csrc/libsf_hip.so`)
 There is no CPU or eager-PyTorch fallback: the compute entry points raise when the
 library has not been built.
 """
-from .weights import (WanShape, WAN_1_3B, WAN_14B, WAN_REDUCED, NAMED_SHAPES, synth_state_dict,  # noqa: F401
+from .weights import (WanShape, WAN_1_3B, WAN_14B, WAN_REDUCED, WAN_I2V_14B, WAN_I2V_REDUCED, NAMED_SHAPES, synth_state_dict,  # noqa: F401
                       param_shapes, merge_lora, strip_prefix, synth_lora_state_dict, apply_lora_file,
                       load_lora_file, lora_target_linears)
 from .kvcache import CachePlan, plan_cache_update  # noqa: F401
@@ -31,7 +31,7 @@ from .t5_weights import T5Shape, UMT5_XXL, T5_REDUCED, synth_t5_state_dict, t5_p
 from .text_encoder import WanTextEncoder, UMT5Encoder, relative_position_buckets  # noqa: F401
 from .clip_weights import ClipVisionShape, CLIP_VIT_H_14, CLIP_REDUCED, clip_param_shapes, synth_clip_state_dict  # noqa: F401
 from .clip import CLIPModel, CLIPVisionEncoder  # noqa: F401
-from . import clip_weights, clip_reference  # noqa: F401
+from . import clip_weights, clip_reference, i2v_reference  # noqa: F401
 from . import unipc  # noqa: F401
 from .diffusion_pipeline import CausalDiffusionInferencePipeline  # noqa: F401
 from .unipc import FlowUniPCMultistepScheduler  # noqa: F401
@@ -49,4 +49,4 @@ __all__ = ["WanShape", "WAN_1_3B", "WAN_14B", "WAN_REDUCED", "NAMED_SHAPES", "sy
            "WanVAEDecoder", "repack_conv", "T5Shape", "UMT5_XXL", "T5_REDUCED", "synth_t5_state_dict", "t5_param_shapes",
            "WanTextEncoder", "UMT5Encoder", "relative_position_buckets", "FlowUniPCMultistepScheduler", "CausalDiffusionInferencePipeline",
            "ClipVisionShape", "CLIP_VIT_H_14", "CLIP_REDUCED", "clip_param_shapes", "synth_clip_state_dict", "CLIPModel", "CLIPVisionEncoder",
-           "clip_weights", "clip_reference"]
+           "clip_weights", "clip_reference", "WAN_I2V_14B", "WAN_I2V_REDUCED", "i2v_reference"]

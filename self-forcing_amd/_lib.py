@@ -128,6 +128,23 @@ class ForwardArgs(C.Structure):
     ]
 
 
+class I2VLayer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("kvimg_w", "kvimg_b", "norm_k_img_w")]
+
+
+class I2VModel(C.Structure):
+    _fields_ = ([("clip_dim", C.c_int32), ("clip_len", C.c_int32), ("img_eps", C.c_float)]
+                + [(n, C.c_void_p) for n in ("img_ln0_w", "img_ln0_b", "img_fc1_w", "img_fc1_b", "img_fc2_w", "img_fc2_b",
+                                             "img_ln1_w", "img_ln1_b")]
+                + [("layers_host", C.POINTER(I2VLayer))])
+
+
+class I2VArgs(C.Structure):
+    _fields_ = [("clip_feature", C.c_void_p), ("y", C.c_void_p),
+                ("y_bstride", C.c_int64), ("y_cstride", C.c_int64), ("y_fstride", C.c_int64), ("y_channels", C.c_int32),
+                ("kimg_cache_host", C.POINTER(C.c_void_p)), ("vimg_cache_host", C.POINTER(C.c_void_p))]
+
+
 class ConvArgs(C.Structure):
     _fields_ = (
         [(n, C.c_void_p) for n in ("x", "w", "bias", "out", "resid", "out_f32")]
@@ -254,6 +271,7 @@ SIGNATURES = {
     "sf_attention": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _vp]),
     "sf_attention_ex": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp]),
     "sf_attention_fold": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp]),
+    "sf_attention_accum": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp]),
     "sf_cross_fold_scan": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _i, _i, _i, _vp, _vp, _vp]),
     "sf_patchify": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sf_unpatchify_x0": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -264,6 +282,10 @@ SIGNATURES = {
     "sf_dit_forward_pair": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), C.POINTER(ForwardArgs), _vp]),
     "sf_dit_forward_fold": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), _vp, _vp, _vp]),
     "sf_dit_forward_pair_fold": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), C.POINTER(ForwardArgs), _vp, _vp, _vp]),
+    "sf_patchify_i2v": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _vp]),
+    "sf_layernorm_rows": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "sf_dit_i2v_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(I2VModel), _i, _i, _i, _i, _i]),
+    "sf_dit_forward_i2v": (C.c_int, [C.POINTER(Model), C.POINTER(I2VModel), C.POINTER(ForwardArgs), C.POINTER(I2VArgs), _vp, _vp, _vp]),
     "sf_conv_igemm": (C.c_int, [C.POINTER(ConvArgs), _vp]),
     "sf_conv_pick_nt": (C.c_int, [_i]),
     "sf_rmsnorm_silu_cl": (C.c_int, [_vp, _vp, _vp, _i64, _i, _i, _vp]),

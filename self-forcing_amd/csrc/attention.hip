@@ -75,8 +75,11 @@ __device__ __forceinline__ bf16x4 lds_tr_read(const char* p) {
 
 // KIND only gives self-attention (0: keys = the KV cache) and cross-attention (1: keys = the text
 // context) distinct symbols, so per-kernel profiles do not mix a 32760-key launch with a 512-key one.
+// KIND 2 (keys = the i2v image context) is the ACCUMULATE epilogue: out = bf16(float(out) + O / l), the fp32 sum
+// rounded once -- the image attention adds into the buffer the text attention wrote (sf_attention_accum).
 template <int KIND>
 __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
+  constexpr bool ACC = KIND == 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -310,8 +313,9 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) {
         bf16x4 w;
+        if (ACC) w = *reinterpret_cast<const bf16x4*>(op + db * 32 + rg * 8);   // this lane's own 8 bytes: read, add, write
 #pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = (bf16_t)(o_acc[db][4 * rg + j] * inv);
+        for (int j = 0; j < 4; ++j) w[j] = (bf16_t)(ACC ? (float)w[j] + o_acc[db][4 * rg + j] * inv : o_acc[db][4 * rg + j] * inv);
         *reinterpret_cast<bf16x4*>(op + db * 32 + rg * 8) = w;
       }
   }
@@ -349,8 +353,9 @@ constexpr int QT8 = 256;
 constexpr int ATT8_THREADS = 512;
 constexpr int ATT8_LDS = 4 * TILE_B;  // K0 K1 V0 V1 = 64 KiB
 
-template <int KIND>
+template <int KIND>   // KIND 2: the accumulate epilogue, as in attention_kernel
 __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
+  constexpr bool ACC = KIND == 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -650,7 +655,8 @@ __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
   // 16-byte aligned output rows one v_permlane32_swap per dword regroups them: lane l stores the whole even 16-byte group,
   // lane l + 32 the odd one -- 8 x dwordx4 per lane instead of 16 x dwordx2 (the store tail of an attention epilogue is
   // issue-bound: cdna_hip_programming.md T21).  Validity is per query row, i.e. the same for both lanes of a pair.
-  const bool wide = (((uintptr_t)obase | (uintptr_t)(p.o_stride * 2)) & 15) == 0;
+  // (the accumulate epilogue adds in fp32 BEFORE the rounding, i.e. in the lanes' own 8-byte layout: it takes the narrow path)
+  const bool wide = !ACC && (((uintptr_t)obase | (uintptr_t)(p.o_stride * 2)) & 15) == 0;
   if (wide) {
     bf16_t* op = obase + (long)min(qrow, p.Lq - 1) * p.o_stride + 8 * hh;
 #pragma unroll
@@ -677,8 +683,9 @@ __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) {
         bf16x4 w;
+        if (ACC) w = *reinterpret_cast<const bf16x4*>(op + db * 32 + rg * 8);   // this lane's own 8 bytes: read, add, write
 #pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = (bf16_t)(o_acc[db][4 * rg + j] * inv);
+        for (int j = 0; j < 4; ++j) w[j] = (bf16_t)(ACC ? (float)w[j] + o_acc[db][4 * rg + j] * inv : o_acc[db][4 * rg + j] * inv);
         *reinterpret_cast<bf16x4*>(op + db * 32 + rg * 8) = w;
       }
   }
@@ -803,10 +810,11 @@ __global__ __launch_bounds__(256) void attention_r64_kernel(AttP p) {
 
 }  // namespace
 
-extern "C" int sf_attention_fold(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
-                                 int Lk, int64_t q_stride, int64_t q_bstride, int64_t kv_stride,
-                                 int64_t kv_bstride, int64_t o_stride, int64_t o_bstride, int structure,
-                                 const int32_t* keys, const float* log2w, void* stream) {
+// accum: out += the attention (KIND 2 of the W4 / W8 kernels) instead of out = the attention
+static int attention_launch(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
+                            int Lk, int64_t q_stride, int64_t q_bstride, int64_t kv_stride,
+                            int64_t kv_bstride, int64_t o_stride, int64_t o_bstride, int structure,
+                            const int32_t* keys, const float* log2w, bool accum, void* stream) {
   SF_CHECK(q && k && v && out, "sf_attention: null tensor");
   SF_CHECK((keys == nullptr) == (log2w == nullptr), "sf_attention: keys and log2w come together");
   SF_CHECK(B > 0 && H > 0 && Lq > 0 && Lk > 0, "sf_attention: empty problem B=%d H=%d Lq=%d Lk=%d", B, H, Lq, Lk);
@@ -834,8 +842,10 @@ extern "C" int sf_attention_fold(const void* q, const void* k, const void* v, vo
   const bool out16 = ((uintptr_t)out % 16 == 0) && o_stride % 8 == 0 && o_bstride % 8 == 0;
   // (round 3: with its shorter prologue / epilogue the 64-row kernel is ahead of the 8-wave one from 512 keys on --
   // cross-attention, Lk = 512: 21.2 vs 22.1 us at one prompt, 41.7 vs 43.1 at two; Lk = 256: 15.8 vs 14.8)
+  // (accumulate: the hand-scheduled r64 stream has no such epilogue, and the image context's 257 keys are below its range)
+  SF_CHECK(!(accum && structure == SF_ATTN_R64), "sf_attention_accum: the r64 structure has no accumulate epilogue (use auto, w8 or w4)");
   if (structure == SF_ATTN_AUTO)
-    structure = (nwg64 >= 192 && Lk >= 512 && out16) ? SF_ATTN_R64 : nwg8 >= 192 ? SF_ATTN_W8 : SF_ATTN_W4;
+    structure = (!accum && nwg64 >= 192 && Lk >= 512 && out16) ? SF_ATTN_R64 : nwg8 >= 192 ? SF_ATTN_W8 : SF_ATTN_W4;
   if (structure == SF_ATTN_R64) {
     SF_CHECK(out16, "sf_attention: the r64 structure needs 16-byte aligned output rows (out %% 16, o_stride %% 8, o_bstride %% 8)");
     p.q_tiles = (Lq + QT64 - 1) / QT64;
@@ -854,7 +864,9 @@ extern "C" int sf_attention_fold(const void* q, const void* k, const void* v, vo
   }
   if (structure == SF_ATTN_W8) {
     p.q_tiles = (Lq + QT8 - 1) / QT8;
-    if (Lk > 1024)
+    if (accum)
+      hipLaunchKernelGGL(attention_w8_kernel<2>, dim3((unsigned)nwg8), dim3(ATT8_THREADS), ATT8_LDS, (hipStream_t)stream, p);
+    else if (Lk > 1024)
       hipLaunchKernelGGL(attention_w8_kernel<0>, dim3((unsigned)nwg8), dim3(ATT8_THREADS), ATT8_LDS, (hipStream_t)stream, p);
     else
       hipLaunchKernelGGL(attention_w8_kernel<1>, dim3((unsigned)nwg8), dim3(ATT8_THREADS), ATT8_LDS, (hipStream_t)stream, p);
@@ -863,12 +875,29 @@ extern "C" int sf_attention_fold(const void* q, const void* k, const void* v, vo
   }
   const long nwg = (long)p.q_tiles * H * B;
   SF_CHECK(nwg < (1L << 30), "sf_attention: grid too large");
-  if (Lk > 1024)
+  if (accum)
+    hipLaunchKernelGGL(attention_kernel<2>, dim3((unsigned)nwg), dim3(ATT_THREADS), ATT_LDS, (hipStream_t)stream, p);
+  else if (Lk > 1024)
     hipLaunchKernelGGL(attention_kernel<0>, dim3((unsigned)nwg), dim3(ATT_THREADS), ATT_LDS, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(attention_kernel<1>, dim3((unsigned)nwg), dim3(ATT_THREADS), ATT_LDS, (hipStream_t)stream, p);
   SF_HIP_LAUNCH_CHECK("sf_attention");
   return 0;
+}
+
+extern "C" int sf_attention_fold(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
+                                 int Lk, int64_t q_stride, int64_t q_bstride, int64_t kv_stride,
+                                 int64_t kv_bstride, int64_t o_stride, int64_t o_bstride, int structure,
+                                 const int32_t* keys, const float* log2w, void* stream) {
+  return attention_launch(q, k, v, out, B, H, Lq, Lk, q_stride, q_bstride, kv_stride, kv_bstride, o_stride, o_bstride, structure,
+                          keys, log2w, false, stream);
+}
+
+extern "C" int sf_attention_accum(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
+                                  int Lk, int64_t q_stride, int64_t q_bstride, int64_t kv_stride,
+                                  int64_t kv_bstride, int64_t o_stride, int64_t o_bstride, int structure, void* stream) {
+  return attention_launch(q, k, v, out, B, H, Lq, Lk, q_stride, q_bstride, kv_stride, kv_bstride, o_stride, o_bstride, structure,
+                          nullptr, nullptr, true, stream);
 }
 
 extern "C" int sf_attention_ex(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,

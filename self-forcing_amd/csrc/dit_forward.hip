@@ -55,6 +55,28 @@ Work carve(const sf_model* m, void* ws, int B, int F, int lat_h, int lat_w, int 
 
 inline const char* bptr(const void* p, size_t elems) { return (const char*)p + elems * 2; }
 
+// The i2v model type: its weights and this pass's image tensors (both or neither), and the image context's buffers, carved
+// BEHIND the t2v workspace so that nothing in front of them moves.
+struct I2V {
+  const sf_i2v_model* m;
+  const sf_i2v_args* a;
+};
+struct ImgWork {
+  void *t0, *t1, *ctx;   // [B clip_len, clip_dim] x 2 (LayerNorm / Linear ping-pong), [B clip_len, C] x 2 in ctx (fc2 out | normed)
+  size_t total;
+};
+ImgWork carve_img(const sf_model* m, const sf_i2v_model* im, void* ws, size_t base, int B) {
+  const size_t R = (size_t)B * im->clip_len;
+  Carve c(ws);
+  c.off = base;
+  ImgWork w;
+  w.t0 = c.take(R * im->clip_dim * 2);
+  w.t1 = c.take(R * im->clip_dim * 2);
+  w.ctx = c.take(2 * R * (size_t)m->dim * 2);
+  w.total = c.off;
+  return w;
+}
+
 }  // namespace
 
 extern "C" size_t sf_dit_workspace_bytes(const sf_model* model, int batch, int frames, int lat_h, int lat_w, int groups) {
@@ -71,10 +93,24 @@ extern "C" size_t sf_dit_workspace_bytes(const sf_model* model, int batch, int f
 // output element, so the results are bit-identical to separate calls; what changes is M (two passes of 4680 tokens give
 // the GEMMs 9360 rows: 1040-1440 instead of 810-1160 TFLOP/s) and the launch count.
 // cache_only passes must come first; past the LAST layer's K / V write only the remaining passes' rows continue.
-static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, int np, int32_t* cross_keys, float* cross_log2w, void* stream) {
+// `iv` (NULL for a t2v generator: nothing below changes) adds the i2v model type: the 36-channel patch gather, the image
+// context with init_cross, and the image attention accumulated behind every layer's text attention.
+static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, int np, int32_t* cross_keys, float* cross_log2w, void* stream,
+                          const I2V* iv = nullptr) {
   SF_CHECK((cross_keys == nullptr) == (cross_log2w == nullptr), "sf_dit_forward: cross_keys and cross_log2w come together");
   const sf_forward_args* a = ps[0];
   SF_CHECK(m && a, "sf_dit_forward: null argument");
+  if (iv) {
+    SF_CHECK(np == 1, "sf_dit_forward_i2v: the two-pass call is not built for the i2v model type");
+    SF_CHECK(!m->fp8, "sf_dit_forward_i2v: fp8 Linears are not built for the i2v model type");
+    SF_CHECK(iv->m->layers_host && iv->m->clip_len > 0 && iv->m->clip_dim > 0 && iv->m->clip_dim % 64 == 0,
+             "sf_dit_forward_i2v: bad image context shape (clip_len=%d, clip_dim=%d: a positive multiple of 64)", iv->m->clip_len, iv->m->clip_dim);
+    SF_CHECK(iv->a->y, "sf_dit_forward_i2v: y is missing (an i2v generator needs clip_feature and y)");
+    SF_CHECK(m->in_dim >= m->out_dim + iv->a->y_channels && iv->a->y_channels > 0 && (m->in_dim * 4) % 64 == 0,
+             "sf_dit_forward_i2v: %d latent + %d conditioning channels do not fit the padded in_dim %d", m->out_dim, iv->a->y_channels, m->in_dim);
+    SF_CHECK(iv->a->kimg_cache_host && iv->a->vimg_cache_host, "sf_dit_forward_i2v: null image cache table");
+    SF_CHECK(!a->init_cross || iv->a->clip_feature, "sf_dit_forward_i2v: init_cross needs clip_feature");
+  }
   SF_CHECK(m->layers_host && m->num_layers > 0, "sf_dit_forward: model has no layers");
   SF_CHECK(m->dim == m->num_heads * 128, "sf_dit_forward: head_dim must be 128 (dim=%d heads=%d)", m->dim, m->num_heads);
   SF_CHECK(a->batch > 0 && a->frames > 0 && a->groups > 0, "sf_dit_forward: empty input");
@@ -107,7 +143,8 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
   }
   SF_CHECK(a->k_cache_host && a->v_cache_host && a->ck_cache_host && a->cv_cache_host, "sf_dit_forward: null cache table");
   const Work ws = carve(m, a->workspace, np * B, F, a->lat_h, a->lat_w, G);
-  SF_CHECK(a->workspace && a->workspace_bytes >= ws.total, "sf_dit_forward: workspace too small (%zu < %zu)", a->workspace_bytes, ws.total);
+  const size_t ws_need = iv ? carve_img(m, iv->m, nullptr, ws.total, B).total : ws.total;
+  SF_CHECK(a->workspace && a->workspace_bytes >= ws_need, "sf_dit_forward: workspace too small (%zu < %zu)", a->workspace_bytes, ws_need);
   SF_CHECK(!a->init_cross || a->prompt_embeds, "sf_dit_forward: init_cross needs prompt_embeds");
 
   const bool f8 = m->fp8 != 0;
@@ -138,8 +175,12 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
   };
 
   // ---- patch embedding (rows of pass p at [p M, (p + 1) M))
-  for (int p = 0; p < np; ++p)
-    SF_TRY(sf_patchify(ps[p]->noisy, (void*)bptr(ws.cols, (size_t)p * M * Kp), B, F, m->in_dim, a->lat_h, a->lat_w, stream));
+  if (iv)   // x | y | zeros: the K = in_dim * 4 operand (in_dim is the padded 48 of an i2v sf_model)
+    SF_TRY(sf_patchify_i2v(a->noisy, iv->a->y, ws.cols, B, F, m->out_dim, iv->a->y_channels, m->in_dim, a->lat_h, a->lat_w, iv->a->y_bstride,
+                           iv->a->y_cstride, iv->a->y_fstride, stream));
+  else
+    for (int p = 0; p < np; ++p)
+      SF_TRY(sf_patchify(ps[p]->noisy, (void*)bptr(ws.cols, (size_t)p * M * Kp), B, F, m->in_dim, a->lat_h, a->lat_w, stream));
   SF_TRY(Gemm(ws.cols, Kp, m->patch_w, Kp, ws.x, C, Mt, C, Kp).bias(m->patch_b).bf16(stream));
 
   // ---- pose conditioning of the fork: x += pose_proj(add_condition)  (causal_model.py:786-819), per pass
@@ -185,6 +226,26 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
     }
     // how many trailing rows of each layer's and sample's K / V repeat the last one (the prompt's padding): folded into one key
     if (cross_keys) SF_TRY(sf_cross_fold_scan(a->ck_cache_host, a->cv_cache_host, m->num_layers, B, m->text_len, C, cross_keys, cross_log2w, stream));
+    // the image context, img_emb = MLPProj (model.py:469-481): LayerNorm, Linear, erf-GELU, Linear, LayerNorm -> clip_len
+    // tokens per sample, then every layer's k_img (RMS-normed) / v_img beside its text K / V
+    if (iv) {
+      const sf_i2v_model* im = iv->m;
+      const ImgWork iw = carve_img(m, im, a->workspace, ws.total, B);
+      const int R = B * im->clip_len, D = im->clip_dim;
+      void* ctx_raw = iw.ctx;
+      void* ctx_img = (void*)bptr(iw.ctx, (size_t)R * C);
+      SF_TRY(sf_layernorm_rows(iv->a->clip_feature, im->img_ln0_w, im->img_ln0_b, iw.t0, R, D, im->img_eps, stream));
+      SF_TRY(Gemm(iw.t0, D, im->img_fc1_w, D, iw.t1, D, R, D, D).bias(im->img_fc1_b).bf16(stream));
+      SF_TRY(sf_clip_gelu(iw.t1, iw.t1, (int64_t)R * D, stream));
+      SF_TRY(Gemm(iw.t1, D, im->img_fc2_w, D, ctx_raw, C, R, C, D).bias(im->img_fc2_b).bf16(stream));
+      SF_TRY(sf_layernorm_affine(ctx_raw, im->img_ln1_w, im->img_ln1_b, ctx_img, R, C, im->img_eps, stream));
+      for (int l = 0; l < m->num_layers; ++l) {
+        const sf_i2v_layer& il = im->layers_host[l];
+        SF_TRY(Gemm(ctx_img, C, il.kvimg_w, C, iv->a->kimg_cache_host[l], C, R, C, C).bias(il.kvimg_b).bf16(stream));
+        SF_TRY(sf_rmsnorm(iv->a->kimg_cache_host[l], C, il.norm_k_img_w, iv->a->kimg_cache_host[l], C, R, C, m->eps, stream));
+        SF_TRY(Gemm(ctx_img, C, bptr(il.kvimg_w, (size_t)C * C), C, iv->a->vimg_cache_host[l], C, R, C, C).bias(bptr(il.kvimg_b, C)).bf16(stream));
+      }
+    }
   }
 
   // ---- transformer blocks
@@ -231,6 +292,9 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
       SF_TRY(sf_attention_fold(bptr(ws.q, (size_t)p * M * C), a->ck_cache_host[l], a->cv_cache_host[l], (void*)bptr(ws.att, (size_t)p * M * C), B, m->num_heads, L,
                                m->text_len, C, (long)L * C, C, ctx_b, C, (long)L * C, SF_ATTN_AUTO, cross_keys ? cross_keys + (size_t)l * B : nullptr,
                                cross_keys ? cross_log2w + (size_t)l * B : nullptr, stream));
+    if (iv)   // + attn(q, k_img, v_img): added into the text attention's buffer in fp32, rounded once (model.py:254-263)
+      SF_TRY(sf_attention_accum(ws.q, iv->a->kimg_cache_host[l], iv->a->vimg_cache_host[l], ws.att, B, m->num_heads, L, iv->m->clip_len, C, (long)L * C,
+                                C, (long)iv->m->clip_len * C, C, (long)L * C, SF_ATTN_AUTO, stream));
     SF_TRY(lin(Gemm(att, C, lw.co_w, C, x, C, Mr, C, C).bias(lw.co_b).epi(SF_EPI_BIAS_RESID).resid(x, C).fp8w(lq.co_q, lq.co_s, M)));
     // feed forward
     SF_TRY(sf_layernorm_modulate(x, xn, Mr, C, m->eps, bptr(mod, 3 * (size_t)C), bptr(mod, 4 * (size_t)C), bptr(e0r, 3 * (size_t)C),
@@ -265,6 +329,21 @@ extern "C" int sf_dit_forward_fold(const sf_model* m, const sf_forward_args* a, 
   SF_CHECK(m && a, "sf_dit_forward: null argument");
   const sf_forward_args* one[1] = {a};
   return forward_passes(m, one, 1, cross_keys, cross_log2w, stream);
+}
+
+extern "C" size_t sf_dit_i2v_workspace_bytes(const sf_model* model, const sf_i2v_model* i2v_model, int batch, int frames, int lat_h, int lat_w,
+                                             int groups) {
+  const size_t base = sf_dit_workspace_bytes(model, batch, frames, lat_h, lat_w, groups);
+  if (!base || !i2v_model || i2v_model->clip_len <= 0 || i2v_model->clip_dim <= 0) return 0;
+  return carve_img(model, i2v_model, nullptr, base, batch).total;
+}
+
+extern "C" int sf_dit_forward_i2v(const sf_model* m, const sf_i2v_model* im, const sf_forward_args* a, const sf_i2v_args* ia, int32_t* cross_keys,
+                                  float* cross_log2w, void* stream) {
+  SF_CHECK(m && im && a && ia, "sf_dit_forward_i2v: null argument");
+  const sf_forward_args* one[1] = {a};
+  const I2V iv = {im, ia};
+  return forward_passes(m, one, 1, cross_keys, cross_log2w, stream, &iv);
 }
 
 extern "C" int sf_dit_forward_pair_fold(const sf_model* m, const sf_forward_args* context_pass, const sf_forward_args* next_pass,

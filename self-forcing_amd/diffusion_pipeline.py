@@ -17,17 +17,20 @@ What differs:
     (`unipc.py`); timesteps come from the scheduler's host table, so the loop never waits on the device;
   * the constants the reference hard-codes (30 blocks, 1560 tokens per frame, 12x128 heads, 32760-token caches,
     :69-72, :464-487) are derived from the generator's shape and the latent size;
-  * the producing half of the fork's image front end is built: `encode_image` (:151-172) runs the CLIP image encoder
-    (`clip.CLIPModel`, csrc/clip_encoder.hip; injected as `image_encoder=` or loaded lazily from
-    `args.clip_checkpoint_path`) and the VAE encoder and returns `clip_feature` and `y`.  The consuming half -- the i2v
-    branch of the generator (`img_emb`, `k_img` / `v_img`, the 36-channel patch embedding, :305-326) -- is not, so
-    `inference(input_image=...)` still raises;
+  * image conditioning (:318-357): `encode_image` (:151-172) runs the CLIP image encoder (`clip.CLIPModel`,
+    csrc/clip_encoder.hip; injected as `image_encoder=` or loaded lazily from `args.clip_checkpoint_path`) and the VAE
+    encoder and returns `clip_feature` and `y`; a generator of the i2v model type consumes them (`img_emb`, `k_img` /
+    `v_img`, the 36-channel patch embedding).  `inference(input_image=...)` encodes the image once per clip over the
+    whole output timeline, 4 (num_output_frames - 1) + 1 pixel frames, puts `clip_feature` into both condition dicts and
+    hands every pass the frames of `y` at its position in `output` -- the reference hands the whole-clip `y` to every
+    chunk (:355-357), which its `torch.cat([u, v])` (causal_model.py:772) only survives when a chunk is the whole clip.  An
+    i2v generator needs an image; any other generator given one raises NotImplementedError (it has no i2v branch);
   * the pose front end runs on the GPU path (`pose.PoseEmbedder`, csrc/pose_conv.hip): `dwpose_data` [3, F, H, W] with
     `random_ref_dwpose` [H, W, 3] are embedded once per clip with weights loaded lazily from `args.pose_weights_path`
     (`args.pose_weights_strict`, :329-331) or by an injected `pose_embedder=`; the tokens come out token-major, so a
     chunk's `add_condition` is a row range of them (a view; one clip is shared by every sample of the batch).  With
     only one of the two inputs the pose branch is not taken, as in the reference (:336).  The reference-pose map is
-    only ever added to `y` (:346-347), which does not exist without image conditioning, so it is not computed here.
+    only ever added to `y` (:346-347): it is computed (`embed_ref`) when there is an image, and broadcast over time.
     Already-embedded tokens can still be passed as `dwpose_data_emb` [B, C_pose, F_total, h, w], sliced per chunk
     exactly as :386-394 does;
   * the 'dpm++' solver branch (:526-536) is not implemented; the per-step `print`s are dropped.
@@ -165,15 +168,19 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
         main.wait_stream(side)
         return fc, fu
 
-    def _pose_tokens(self, dwpose_data: torch.Tensor):
-        """`dwpose_embedding` over the clip (:337-340) as (tokens [1, F'*h*w, 5120], (F', h, w)); the weights load once."""
+    def _pose_embedder(self):
+        """The injected pose embedder, or the one loaded from args.pose_weights_path on first need (:59-61, :329-331)."""
         if self.pose_embedder is None:
             if self.pose_weights_path is None:
                 raise ValueError("dwpose_data needs pose weights: set args.pose_weights_path or construct the pipeline with pose_embedder=")
             from .pose import PoseEmbedder
             self.pose_embedder = PoseEmbedder(self.pose_weights_path, device=self.device, strict=self.pose_weights_strict)
             self.pose_weights_loaded = True
-        return self.pose_embedder.embed(dwpose_data)
+        return self.pose_embedder
+
+    def _pose_tokens(self, dwpose_data: torch.Tensor):
+        """`dwpose_embedding` over the clip (:337-340) as (tokens [1, F'*h*w, 5120], (F', h, w)); the weights load once."""
+        return self._pose_embedder().embed(dwpose_data)
 
     def _image_encoder(self):
         if self.image_encoder is None:
@@ -222,10 +229,13 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
                   random_ref_dwpose=None, initial_latent: Optional[torch.Tensor] = None, return_latents: bool = False,
                   start_frame_index: Optional[int] = 0, dwpose_data_emb: Optional[torch.Tensor] = None):
         """noise [B, F, C, H, W] -> video in [0, 1] (and the latents)."""
-        if input_image is not None:
-            raise NotImplementedError("input_image: the generator's i2v branch (img_emb, k_img / v_img, the 36-channel patch "
-                                      "embedding) is not built, so the rollout cannot consume an image; encode_image() already "
+        is_i2v = getattr(getattr(getattr(self, "generator", None), "model", None), "model_type", "t2v") == "i2v"
+        if input_image is not None and not is_i2v:
+            raise NotImplementedError("input_image: this generator has no i2v branch (img_emb, k_img / v_img, the 36-channel patch "
+                                      "embedding: model_type 'i2v'), so the rollout cannot consume an image; encode_image() still "
                                       "produces its clip_feature and y")
+        if is_i2v and input_image is None:
+            raise ValueError("an i2v generator needs input_image: every pass takes its clip_feature and y")
         batch_size, num_frames, num_channels, height, width = noise.shape
         if not self.independent_first_frame or (self.independent_first_frame and initial_latent is not None):
             assert num_frames % self.num_frame_per_block == 0
@@ -257,6 +267,22 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
         conditional_dict = dict(self.text_encoder(text_prompts=text_prompts))
         unconditional_dict = dict(self.text_encoder(text_prompts=[self.args.negative_prompt] * len(text_prompts)))
 
+        y_clip = None
+        if is_i2v:
+            # once per clip, over the OUTPUT timeline (context frames included): a pass reads y at its position in `output`
+            image_emb = self.encode_image(input_image, 4 * (num_output_frames - 1) + 1, height * 8, width * 8)
+            y_clip = image_emb["y"]
+            assert y_clip.shape[2] >= num_output_frames, (
+                f"y has {y_clip.shape[2]} latent frames, but the output timeline has {num_output_frames}.")
+            if use_pose:   # the image to be driven by the pose (:341-347); [1, 20, 1, h, w] broadcast over time
+                y_clip = y_clip + self._pose_embedder().embed_ref(random_ref_dwpose).to(y_clip.dtype)
+            for d in (conditional_dict, unconditional_dict):   # (:352-353) one image: the wrapper expands it to the batch
+                d["clip_feature"] = image_emb["clip_feature"]
+
+        def set_y(first_frame: int, n: int) -> None:
+            if y_clip is not None:
+                conditional_dict["y"] = unconditional_dict["y"] = y_clip[:, :, first_frame:first_frame + n]
+
         output = torch.zeros([batch_size, num_output_frames, num_channels, height, width], device=noise.device, dtype=noise.dtype)
 
         # Step 1: caches (:203-231)
@@ -282,6 +308,7 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
                 assert (num_input_frames - 1) % self.num_frame_per_block == 0
                 num_input_blocks = (num_input_frames - 1) // self.num_frame_per_block
                 output[:, :1] = initial_latent[:, :1]
+                set_y(cache_start_frame, 1)
                 self._both(initial_latent[:, :1], conditional_dict, unconditional_dict, timestep,
                            current_start_frame * fs, cache_only=True)
                 current_start_frame += 1
@@ -292,6 +319,7 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
             for _ in range(num_input_blocks):
                 ref = initial_latent[:, cache_start_frame:cache_start_frame + self.num_frame_per_block]
                 output[:, cache_start_frame:cache_start_frame + self.num_frame_per_block] = ref
+                set_y(cache_start_frame, self.num_frame_per_block)
                 self._both(ref, conditional_dict, unconditional_dict, timestep, current_start_frame * fs, cache_only=True)
                 current_start_frame += self.num_frame_per_block
                 cache_start_frame += self.num_frame_per_block
@@ -328,6 +356,7 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
                 conditional_dict.pop("add_condition", None)
                 unconditional_dict.pop("add_condition", None)
 
+            set_y(cache_start_frame, current_num_frames)
             sample_scheduler = self._initialize_sample_scheduler(noise)
             for t in sample_scheduler.timesteps_host.tolist():
                 timestep = torch.full([batch_size, current_num_frames], float(t), device=noise.device, dtype=torch.float32)

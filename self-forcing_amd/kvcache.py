@@ -93,12 +93,25 @@ def reset_kv_indices(kv: List[dict]) -> None:
 
 
 def new_crossattn_cache(shape, n_layers: int, batch_size: int, dtype, device) -> List[dict]:
-    """causal_inference.py:300-312."""
-    return [{
+    """causal_inference.py:300-312.  For an i2v shape every dict also holds the image keys / values "k_img" / "v_img"
+    [B, clip_len, H, D], filled with "k" / "v" by the pass that finds is_init False."""
+    cache = [{
         "k": torch.zeros([batch_size, shape.text_len, shape.num_heads, shape.head_dim], dtype=dtype, device=device),
         "v": torch.zeros([batch_size, shape.text_len, shape.num_heads, shape.head_dim], dtype=dtype, device=device),
         "is_init": False,
     } for _ in range(n_layers)]
+    if getattr(shape, "model_type", "t2v") == "i2v":
+        add_image_cache(cache, shape, dtype, device)
+    return cache
+
+
+def add_image_cache(crossattn_cache: List[dict], shape, dtype, device) -> None:
+    """Give every dict that lacks them the i2v "k_img" / "v_img" tensors (a cache built elsewhere, reference schema)."""
+    batch_size = crossattn_cache[0]["k"].shape[0]
+    for d in crossattn_cache:
+        for name in ("k_img", "v_img"):
+            if name not in d:
+                d[name] = torch.zeros([batch_size, shape.clip_len, shape.num_heads, shape.head_dim], dtype=dtype, device=device)
 
 
 def read_indices(kv_cache: List[dict]):

@@ -17,7 +17,7 @@ import torch
 from . import _lib, fp8 as fp8_recipe, torch_ops
 from .device_model import DeviceModel
 from .kvcache import CachePlan
-from .weights import WanShape, param_shapes
+from .weights import I2V_Y_CHANNELS, WanShape, param_shapes
 
 Tensor = torch.Tensor
 
@@ -55,6 +55,14 @@ class CausalWanModel(DeviceModel):
         self.independent_first_frame = False
         self.fp8 = bool(fp8)
         self.fp8_weights: Dict[str, tuple] = {}
+        self.model_type = shape.model_type
+        if shape.is_i2v:
+            if self.fp8:
+                raise NotImplementedError("fp8=True is not built for the i2v model type (its img_emb / k_img / v_img Linears run in bf16 only)")
+            if shape.in_dim != shape.out_dim + I2V_Y_CHANNELS or shape.clip_dim % 64:
+                raise ValueError(f"i2v model: in_dim must be {shape.out_dim} + {I2V_Y_CHANNELS} and clip_dim a multiple of 64 "
+                                 f"(in_dim={shape.in_dim}, clip_dim={shape.clip_dim})")
+        self.y_channels = I2V_Y_CHANNELS if shape.is_i2v else 0
         self._load(state_dict, sched_sigmas, sched_timesteps)
         self._handle = torch_ops.register_model(self)
 
@@ -82,7 +90,14 @@ class CausalWanModel(DeviceModel):
         m.in_dim, m.out_dim, m.freq_dim, m.text_dim, m.text_len = s.in_dim, s.out_dim, s.freq_dim, s.text_dim, s.text_len
         m.eps = s.eps
         P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        m.patch_w = P(self._dev(sd["patch_embedding.weight"].flatten(1)))
+        pw = sd["patch_embedding.weight"].flatten(1)
+        if s.is_i2v:
+            # 36 channels x 4 = 144 columns: the GEMM's k-tile wants K % 64 == 0, so the weight is zero-padded to 192
+            # columns and the sequencer sees in_dim = 48 (its 12 extra channels are written as zeros by sf_patchify_i2v)
+            kpad = -(-pw.shape[1] // 64) * 64
+            pw = torch.cat([pw, pw.new_zeros(pw.shape[0], kpad - pw.shape[1])], dim=1)
+            m.in_dim = kpad // 4
+        m.patch_w = P(self._dev(pw))
         m.patch_b = P(self._dev(sd["patch_embedding.bias"]))
         for dst, src in (("text0", "text_embedding.0"), ("text2", "text_embedding.2"), ("time0", "time_embedding.0"),
                          ("time2", "time_embedding.2"), ("tproj", "time_projection.1"), ("head", "head.head")):
@@ -136,6 +151,22 @@ class CausalWanModel(DeviceModel):
         if self.fp8:
             self._layers8 = layers8
             m.layers_fp8_host = C.cast(layers8, C.POINTER(_lib.LayerFp8))
+        if s.is_i2v:
+            im = _lib.I2VModel()
+            im.clip_dim, im.clip_len, im.img_eps = s.clip_dim, s.clip_len, 1e-5   # nn.LayerNorm's default eps (model.py:474-477)
+            for dst, src in (("img_ln0", "img_emb.proj.0"), ("img_fc1", "img_emb.proj.1"), ("img_fc2", "img_emb.proj.3"),
+                             ("img_ln1", "img_emb.proj.4")):
+                setattr(im, dst + "_w", P(self._dev(sd[src + ".weight"])))
+                setattr(im, dst + "_b", P(self._dev(sd[src + ".bias"])))
+            ilayers = (_lib.I2VLayer * s.num_layers)()
+            for i in range(s.num_layers):
+                ca = f"blocks.{i}.cross_attn."
+                ilayers[i].kvimg_w = P(self._dev(torch.cat([sd[ca + "k_img.weight"], sd[ca + "v_img.weight"]], 0)))
+                ilayers[i].kvimg_b = P(self._dev(torch.cat([sd[ca + "k_img.bias"], sd[ca + "v_img.bias"]], 0)))
+                ilayers[i].norm_k_img_w = P(self._dev(sd[ca + "norm_k_img.weight"]))
+            self._i2v_layers = ilayers
+            im.layers_host = C.cast(ilayers, C.POINTER(_lib.I2VLayer))
+            self.i2v_cmodel = im
         cos, sin = rope_tables(s.head_dim)
         self.rope_cos = cos.to(self.device)
         self.rope_sin = sin.to(self.device)
@@ -150,22 +181,37 @@ class CausalWanModel(DeviceModel):
     def workspace(self, B: int, F: int, H: int, W: int, G: int) -> Tensor:
         # one workspace per shape AND stream: concurrent rollouts on different HIP streams share the
         # weights but must not share activations
+        if self.shape.is_i2v:
+            return self._stream_bytes((B, F, H, W, G), lambda: _lib.lib().sf_dit_i2v_workspace_bytes(
+                C.byref(self.cmodel), C.byref(self.i2v_cmodel), B, F, H, W, G), zero_is_error="sf_dit_i2v_workspace_bytes")
         return self._stream_bytes((B, F, H, W, G), lambda: _lib.lib().sf_dit_workspace_bytes(C.byref(self.cmodel), B, F, H, W, G))
 
     def forward(self, noisy: Tensor, timestep: Tensor, prompt_embeds: Optional[Tensor], init_cross: bool,
                 k_cache: List[Tensor], v_cache: List[Tensor], ck_cache: List[Tensor], cv_cache: List[Tensor], plan: CachePlan,
                 start_frame: int, evict_scratch: Optional[Tensor] = None, cache_only: bool = False,
                 add_condition: Optional[Tensor] = None, kv_index: Optional[Tensor] = None,
-                cross_fold: Optional[Tuple[Tensor, Tensor]] = None):
+                cross_fold: Optional[Tuple[Tensor, Tensor]] = None, clip_feature: Optional[Tensor] = None, y: Optional[Tensor] = None,
+                kimg_cache: Optional[List[Tensor]] = None, vimg_cache: Optional[List[Tensor]] = None):
         """noisy [B,F,in_dim,H,W] bf16 (contiguous); timestep [B,G] float32|int64 on device; *_cache: per-layer cache
         tensors (mutated in place); kv_index: the shared int64 [L, 2] buffer behind the cache dicts' index tensors (the
         pass ends by setting every row to (plan.global_end, plan.local_end)), or None.  Returns (flow, x0)
         [B,F,out_dim,H,W], or (None, None) with cache_only.
         cross_fold: the cross-attention caches' (keys, log2w) buffers (int32 / float32 [L, B], torch_ops.cross_fold_scan):
         filled by this call with init_cross, read by every layer's cross-attention; None: all text_len keys are attended.
+        i2v model type: noisy carries in_dim - 20 channels; y (bf16 [B or 1, 20, F, H, W], strided) and the per-layer image
+        caches are required, clip_feature (bf16 [B, clip_len, clip_dim]) with init_cross: torch.ops.sf_hip.dit_forward_i2v.
         ONE custom-op call: torch.ops.sf_hip.dit_forward[_fold] -> sf_dit_forward_fold."""
         B, F, Cin, H, W = noisy.shape
         ws = self.workspace(B, F, H, W, timestep.shape[1])
+        if self.shape.is_i2v:
+            if y is None or kimg_cache is None or vimg_cache is None or (init_cross and clip_feature is None):
+                raise ValueError("an i2v model needs clip_feature, y and the image caches")
+            flow, x0 = torch.ops.sf_hip.dit_forward_i2v(
+                self._handle, noisy, timestep, prompt_embeds, clip_feature if init_cross else None, y, add_condition, k_cache, v_cache,
+                ck_cache, cv_cache, kimg_cache, vimg_cache, ws, evict_scratch, bool(init_cross), bool(cache_only), plan.sink, plan.evict,
+                plan.keep, plan.write_start, plan.attn_start, plan.local_end, start_frame, kv_index, plan.global_end,
+                *(cross_fold or (None, None)))
+            return (None, None) if cache_only else (flow, x0)
         op = torch.ops.sf_hip.dit_forward_fold if cross_fold else torch.ops.sf_hip.dit_forward
         flow, x0 = op(
             self._handle, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, ws, evict_scratch,
@@ -180,6 +226,8 @@ class CausalWanModel(DeviceModel):
         """The context pass of chunk k (cache only) + the first denoising pass of chunk k + 1 as ONE call
         (torch.ops.sf_hip.dit_forward_pair -> sf_dit_forward_pair): bit-identical to two `forward` calls, but every
         row-wise kernel and GEMM sees both passes' rows at once.  Returns (flow, x0) of the denoising pass."""
+        if self.shape.is_i2v:
+            raise NotImplementedError("forward_pair is not built for the i2v model type")
         B, F, Cin, H, W = noisy.shape
         ws = self.workspace(2 * B, F, H, W, timestep.shape[1])
         as_list = lambda pl, sf: [pl.sink, pl.evict, pl.keep, pl.write_start, pl.attn_start, pl.local_end, sf]  # noqa: E731

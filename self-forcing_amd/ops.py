@@ -186,6 +186,14 @@ def attention(q: Tensor, k: Tensor, v: Tensor, structure: str = "auto", keys: Op
     return torch.ops.sf_hip.attention(q, k, v, _lib.ATTN_STRUCTURES[structure], keys, log2w)
 
 
+def attention_accum(q: Tensor, k: Tensor, v: Tensor, out: Tensor, structure: str = "auto") -> Tensor:
+    """out += attention(q, k, v), in place: the sum is taken in fp32 in the kernel's epilogue and rounded to bf16 once
+    (sf_attention_accum; the i2v cross-attention's image keys added into the text attention's result).  `structure`:
+    "auto" | "w8" | "w4" ("r64" raises: the hand-scheduled kernel has no accumulate epilogue).  Returns `out`."""
+    torch.ops.sf_hip.attention_accum(q, k, v, out, _lib.ATTN_STRUCTURES[structure])
+    return out
+
+
 def cross_fold_scan(ck_cache, cv_cache) -> tuple:
     """Lists (one entry per layer) of contiguous bf16 [B, Lk, H, 128] K and V slabs -> (keys int32 [L, B], log2w float32
     [L, B]): per layer and sample, `same` = the trailing rows that repeat the last row bit for bit in K and in V;

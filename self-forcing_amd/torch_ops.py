@@ -9,6 +9,8 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
 `model.py` (the fused forward), `vae.py`, `text_encoder.py` route through these.
 
     sf_hip::attention(q, k, v, structure) -> out
+    sf_hip::attention_accum(q, k, v, out!, structure) -> ()         (out += attention: the i2v image keys)
+    sf_hip::dit_forward_i2v(model, noisy, timestep, prompt_embeds?, clip_feature?, y, ..., kimg_cache![], vimg_cache![], ...) -> (flow, x0)
     sf_hip::gemm(a, w, bias?, epilogue, resid?, gate_mod?, gate_e0?, rows_per_group, structure) -> out
     sf_hip::gemm_out(out!, a, w, ...) -> ()                         (caller-provided / aliased output)
     sf_hip::quantize_fp8(x, rows_per_segment) -> (q e4m3fn, scales)  (FP8 linear layers, fp8.py)
@@ -101,6 +103,29 @@ def attention(q: Tensor, k: Tensor, v: Tensor, structure: int = 0, keys: Optiona
 @attention.register_fake
 def _(q, k, v, structure=0, keys=None, log2w=None):
     return q.new_empty(q.shape)
+
+
+@custom_op(f"{NAMESPACE}::attention_accum", mutates_args=("out",))
+def attention_accum(q: Tensor, k: Tensor, v: Tensor, out: Tensor, structure: int = 0) -> None:
+    """out += softmax(q k^T / sqrt(D)) v, summed in fp32 in the kernel's epilogue and rounded once (sf_attention_accum):
+    the image half of the i2v cross-attention added into the text half's buffer.  structure: auto, w8 or w4."""
+    for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        _need_gpu(t, n)
+        if t.dim() != 4 or t.shape[3] != 128 or t.stride(3) != 1 or t.stride(2) != 128:
+            raise ValueError(f"attention_accum: {n} must be [B, L, H, 128] with contiguous heads, got {tuple(t.shape)} {t.stride()}")
+    B, Lq, H, D = q.shape
+    if k.stride() != v.stride() or k.shape != v.shape or k.shape[0] != B or k.shape[2] != H:
+        raise ValueError("attention_accum: k and v must share shape and strides, and batch and heads with q")
+    if out.shape != q.shape:
+        raise ValueError(f"attention_accum: out must have q's shape {tuple(q.shape)}, got {tuple(out.shape)}")
+    _lib.check(_lib.lib().sf_attention_accum(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Lq, k.shape[1],
+                                             q.stride(1), q.stride(0), k.stride(1), k.stride(0), out.stride(1), out.stride(0),
+                                             structure, _stream(q)), "sf_attention_accum")
+
+
+@attention_accum.register_fake
+def _(q, k, v, out, structure=0):
+    return None
 
 
 @custom_op(f"{NAMESPACE}::cross_fold_scan", mutates_args=("keys", "log2w"))
@@ -365,7 +390,7 @@ def _pointer_tables(handle: int, k: Sequence[Tensor], v: Sequence[Tensor], ck: S
 def _forward_args(m, model: int, noisy: Tensor, timestep: Tensor, prompt_embeds: Optional[Tensor], add_condition: Optional[Tensor],
                   k_cache, v_cache, ck_cache, cv_cache, workspace: Tensor, evict_scratch: Optional[Tensor], init_cross: bool,
                   cache_only: bool, sink: int, evict: int, keep: int, write_start: int, attn_start: int, attn_end: int,
-                  start_frame: int, kv_index: Optional[Tensor], global_end: int):
+                  start_frame: int, kv_index: Optional[Tensor], global_end: int, in_channels: Optional[int] = None):
     """Validate one pass's tensors and fill its sf_forward_args; returns (args, flow, x0) with empty outputs for cache_only."""
     _need_gpu(noisy, "noisy")
     _need_gpu(timestep, "timestep", None)
@@ -378,8 +403,12 @@ def _forward_args(m, model: int, noisy: Tensor, timestep: Tensor, prompt_embeds:
         raise ValueError(f"dit_forward: cache lists must have {L} entries")
     B, F, _, H, W = noisy.shape
     sh = m.shape
-    if noisy.shape[2] != sh.in_dim or timestep.shape[0] != B:
-        raise ValueError(f"dit_forward: noisy must carry {sh.in_dim} channels and timestep one row per sample")
+    if in_channels is None:   # (dit_forward_i2v names its own: the latent channels in front of y's)
+        if getattr(sh, "is_i2v", False):
+            raise ValueError("dit_forward: an i2v model runs through dit_forward_i2v (clip_feature and y are required)")
+        in_channels = sh.in_dim
+    if noisy.shape[2] != in_channels or timestep.shape[0] != B:
+        raise ValueError(f"dit_forward: noisy must carry {in_channels} channels and timestep one row per sample")
     cap = k_cache[0].shape[1] if k_cache[0].dim() == 4 else -1
     # the C call writes through these pointers: every cache tensor must really be what the kernels assume (checked when
     # the pointer tables are (re)built, i.e. whenever any cache tensor is new to this model / stream)
@@ -486,6 +515,85 @@ def _dit_forward(model, noisy, timestep, prompt_embeds, add_condition, k_cache, 
     _lib.check(_timed_call(_lib.lib().sf_dit_forward_fold, C.byref(m.cmodel), C.byref(a), _ptr(cross_keys), _ptr(cross_log2w), _stream(noisy)),
                "sf_dit_forward")
     return flow, x0
+
+
+_IMG_TABLES: Dict[tuple, tuple] = {}
+
+
+def _image_tables(handle: int, kimg: Sequence[Tensor], vimg: Sequence[Tensor], want: tuple, device):
+    """The image caches' pointer arrays, kept like `_pointer_tables` keeps the other four: rebuilt -- and every tensor
+    validated (the kernels WRITE through these pointers) -- only when a tensor was rebound or the expected shape changed."""
+    key = (want,) + tuple(t.data_ptr() for t in kimg) + tuple(t.data_ptr() for t in vimg)
+    slot = (handle, torch.cuda.current_stream(device).cuda_stream)
+    hit = _IMG_TABLES.get(slot)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    for name, tensors in (("kimg_cache", kimg), ("vimg_cache", vimg)):
+        for i, t in enumerate(tensors):
+            if not t.is_cuda or t.dtype != torch.bfloat16 or tuple(t.shape) != want or not t.is_contiguous() or t.device != device:
+                raise ValueError(f"dit_forward_i2v: {name}[{i}] must be a contiguous bf16 tensor {want} on {device}, got "
+                                 f"{tuple(t.shape)} {t.dtype} {t.device}")
+    arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])  # noqa: E731
+    tabs = (arr(kimg), arr(vimg))
+    if len(_IMG_TABLES) > 64:
+        _IMG_TABLES.clear()
+    _IMG_TABLES[slot] = (key, tabs)
+    return tabs
+
+
+@custom_op(f"{NAMESPACE}::dit_forward_i2v",
+           mutates_args=("k_cache", "v_cache", "ck_cache", "cv_cache", "kimg_cache", "vimg_cache", "workspace", "evict_scratch", "kv_index",
+                         "cross_keys", "cross_log2w"))
+def dit_forward_i2v(model: int, noisy: Tensor, timestep: Tensor, prompt_embeds: Optional[Tensor], clip_feature: Optional[Tensor], y: Tensor,
+                    add_condition: Optional[Tensor], k_cache: List[Tensor], v_cache: List[Tensor], ck_cache: List[Tensor],
+                    cv_cache: List[Tensor], kimg_cache: List[Tensor], vimg_cache: List[Tensor], workspace: Tensor,
+                    evict_scratch: Optional[Tensor], init_cross: bool, cache_only: bool, sink: int, evict: int, keep: int,
+                    write_start: int, attn_start: int, attn_end: int, start_frame: int, kv_index: Optional[Tensor], global_end: int,
+                    cross_keys: Optional[Tensor] = None, cross_log2w: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """One pass of an i2v generator (sf_dit_forward_i2v): dit_forward[_fold] plus y (bf16 [B or 1, 20, F, H, W], any batch /
+    channel / frame strides over contiguous H x W planes: a frame slice of the clip's y needs no copy) in the patch
+    embedding and the image keys behind every layer's text cross-attention.  clip_feature (bf16 [B, clip_len, clip_dim],
+    contiguous) is read with init_cross only, which fills kimg_cache / vimg_cache ([B, clip_len, H, D] per layer)."""
+    m = _model(model)
+    sh = m.shape
+    if not sh.is_i2v:
+        raise ValueError("dit_forward_i2v: the model is not of the i2v type")
+    if noisy.dim() != 5 or noisy.shape[2] + m.y_channels != sh.in_dim:
+        raise ValueError(f"dit_forward_i2v: noisy must carry {sh.in_dim - m.y_channels} channels ([B, F, C, H, W]), got {tuple(noisy.shape)}")
+    a, flow, x0 = _forward_args(m, model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace,
+                                evict_scratch, init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame,
+                                kv_index, global_end, in_channels=noisy.shape[2])
+    B, F, _, H, W = noisy.shape
+    _need_gpu(y, "y")
+    if y.dim() != 5 or y.shape[0] not in (1, B) or y.shape[1] != m.y_channels or tuple(y.shape[2:]) != (F, H, W) \
+            or y.stride(4) != 1 or y.stride(3) != W:
+        raise ValueError(f"dit_forward_i2v: y must be [{B} or 1, {m.y_channels}, {F}, {H}, {W}] with contiguous H x W planes, got "
+                         f"{tuple(y.shape)} {y.stride()}")
+    ia = _lib.I2VArgs()
+    ia.y, ia.y_channels = y.data_ptr(), m.y_channels
+    ia.y_bstride, ia.y_cstride, ia.y_fstride = (0 if y.shape[0] == 1 else y.stride(0)), y.stride(1), y.stride(2)
+    if init_cross:
+        if clip_feature is None:
+            raise ValueError("dit_forward_i2v: init_cross needs clip_feature")
+        _need_gpu(clip_feature, "clip_feature")
+        if tuple(clip_feature.shape) != (B, sh.clip_len, sh.clip_dim) or not clip_feature.is_contiguous():
+            raise ValueError(f"dit_forward_i2v: clip_feature must be contiguous [{B}, {sh.clip_len}, {sh.clip_dim}], got {tuple(clip_feature.shape)}")
+        ia.clip_feature = clip_feature.data_ptr()
+    if len(kimg_cache) != m.num_layers or len(vimg_cache) != m.num_layers:
+        raise ValueError(f"dit_forward_i2v: image cache lists must have {m.num_layers} entries")
+    want = (B, sh.clip_len, sh.num_heads, sh.head_dim)
+    ia.kimg_cache_host, ia.vimg_cache_host = _image_tables(model, kimg_cache, vimg_cache, want, noisy.device)
+    _fold_pair(cross_keys, cross_log2w, (m.num_layers, B), noisy.device, "dit_forward_i2v")
+    _lib.check(_timed_call(_lib.lib().sf_dit_forward_i2v, C.byref(m.cmodel), C.byref(m.i2v_cmodel), C.byref(a), C.byref(ia), _ptr(cross_keys),
+                           _ptr(cross_log2w), _stream(noisy)), "sf_dit_forward_i2v")
+    return flow, x0
+
+
+@dit_forward_i2v.register_fake
+def _(model, noisy, timestep, prompt_embeds, clip_feature, y, add_condition, k_cache, v_cache, ck_cache, cv_cache, kimg_cache, vimg_cache,
+      workspace, evict_scratch, init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame, kv_index, global_end,
+      cross_keys=None, cross_log2w=None):
+    return _dit_forward_fake(model, noisy, cache_only)
 
 
 @custom_op(f"{NAMESPACE}::dit_forward_pair",
@@ -710,5 +818,5 @@ def _(model, frames, workspace):
     return frames.new_empty((frames.shape[0], s.seq_len, s.dim), dtype=torch.float32)
 
 
-OPS = ("attention", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "vae_encode_frames", "taehv_decode_frames",
+OPS = ("attention", "attention_accum", "dit_forward_i2v", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "vae_encode_frames", "taehv_decode_frames",
        "taehv_encode_frames", "t5_encode", "clip_encode")

@@ -21,8 +21,14 @@ Differences from the reference, all deliberate:
     `quantize_(transformer, Float8DynamicActivationFloat8WeightConfig(granularity=PerTensor()))` (demo.py:277-283) --
     every nn.Linear runs as an e4m3 GEMM with a per-tensor weight scale and a dynamic per-pass activation scale
     (fp8.py, DESIGN.md section 11); off by default, and with it off nothing changes;
-  * the non-cached branches (`kv_cache is None`, classify_mode, clean_x teacher forcing) and the i2v inputs
-    (`clip_feature`, `y`) raise NotImplementedError; the fork's pose tokens (`add_condition`) are supported.
+  * the non-cached branches (`kv_cache is None`, classify_mode, clean_x teacher forcing) raise NotImplementedError; the
+    fork's pose tokens (`add_condition`) are supported;
+  * the i2v model type (`shape.model_type == "i2v"`, e.g. model_name="Wan2.1-I2V-14B"): `clip_feature` [B or 1, 257, clip_dim]
+    and `y` [B or 1, 20, F, H, W] (channel-first, THIS call's frames) are required, as arguments or in `conditional_dict`
+    (utils/wan_wrapper.py:271-274); the image keys / values live in the cross-attention cache dicts as "k_img" / "v_img" and
+    are filled with the text K / V.  The reference's own causal i2v path does not run (its WanI2VCrossAttention takes no
+    `crossattn_cache`): the semantics are those of its bidirectional i2v model, DESIGN.md section 16.  A t2v model given
+    either tensor raises NotImplementedError; `forward_pair` and `fp8=True` are not built for an i2v model.
 """
 from __future__ import annotations
 
@@ -33,7 +39,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from .kvcache import plan_cache_update, read_indices, shared_index_buffer, write_indices
+from .kvcache import add_image_cache, plan_cache_update, read_indices, shared_index_buffer, write_indices
 from .model import CausalWanModel
 from .scheduler import FlowMatchScheduler
 from .weights import (LORA_DEFAULT_TARGETS, NAMED_SHAPES, WanShape, apply_lora_file, load_lora_file, merge_lora, strip_prefix,
@@ -209,7 +215,7 @@ class WanDiffusionWrapper(torch.nn.Module):
     def can_pair(self, conditional_dict: dict) -> bool:
         """`forward_pair` covers the plain text-conditioned rollout (no pose tokens / image conditioning)."""
         return conditional_dict.get("add_condition") is None and conditional_dict.get("clip_feature") is None \
-            and conditional_dict.get("y") is None
+            and conditional_dict.get("y") is None and not self.model.shape.is_i2v
 
     @torch.no_grad()
     def forward_pair(self, context_input: Tensor, context_timestep: Tensor, noisy_image_or_video: Tensor, timestep: Tensor,
@@ -221,6 +227,8 @@ class WanDiffusionWrapper(torch.nn.Module):
         bit as `forward(..., cache_only=True)` followed by `forward(...)`; returns (flow_pred, pred_x0) of the second."""
         mdl = self.model
         shape = mdl.shape
+        if shape.is_i2v:
+            raise NotImplementedError("forward_pair is not built for the i2v model type: run the two passes with forward()")
         xs = []
         for x in (context_input, noisy_image_or_video):
             assert x.dim() == 5 and x.shape[2] == shape.in_dim, "inputs must be [B, F, C, H, W] latents"
@@ -265,16 +273,29 @@ class WanDiffusionWrapper(torch.nn.Module):
             raise NotImplementedError("training-only branches (classify_mode / teacher forcing) are out of scope")
         if add_condition is None:
             add_condition = conditional_dict.get("add_condition")
-        if clip_feature is not None or y is not None \
-                or conditional_dict.get("clip_feature") is not None or conditional_dict.get("y") is not None:
-            raise NotImplementedError("image conditioning (clip_feature, y: the i2v model type) is not implemented in the generator; "
-                                      "CausalDiffusionInferencePipeline.encode_image produces the two tensors")
+        if clip_feature is None:
+            clip_feature = conditional_dict.get("clip_feature")
+        if y is None:
+            y = conditional_dict.get("y")
         mdl = self.model
         shape = mdl.shape
+        if not shape.is_i2v and (clip_feature is not None or y is not None):
+            raise NotImplementedError("image conditioning (clip_feature, y) needs a generator of the i2v model type; this one is "
+                                      f"{shape.model_type} (CausalDiffusionInferencePipeline.encode_image produces the two tensors)")
         x = noisy_image_or_video
         assert x.dim() == 5, "noisy_image_or_video must be [B, F, C, H, W]"
         B, F, Cin, H, W = x.shape
-        assert Cin == shape.in_dim, f"expected {shape.in_dim} latent channels, got {Cin}"
+        if shape.is_i2v:
+            # causal_model.py:767-768: `assert clip_fea is not None and y is not None`
+            assert clip_feature is not None and y is not None, "an i2v generator needs clip_feature and y (arguments or conditional_dict)"
+            assert y.dim() == 5 and Cin + y.shape[1] == shape.in_dim, \
+                f"latent channels {Cin} + y channels {tuple(y.shape)[1:2]} must be in_dim = {shape.in_dim} (y is [B or 1, 20, F, H, W])"
+            assert y.shape[0] in (1, B) and tuple(y.shape[2:]) == (F, H, W), \
+                f"y must cover this call's frames: [{B} or 1, {y.shape[1]}, {F}, {H}, {W}], got {tuple(y.shape)}"
+            assert clip_feature.dim() == 3 and clip_feature.shape[0] in (1, B) and tuple(clip_feature.shape[1:]) == (shape.clip_len, shape.clip_dim), \
+                f"clip_feature must be [{B} or 1, {shape.clip_len}, {shape.clip_dim}], got {tuple(clip_feature.shape)}"
+        else:
+            assert Cin == shape.in_dim, f"expected {shape.in_dim} latent channels, got {Cin}"
         assert len(kv_cache) == mdl.num_layers and len(crossattn_cache) == mdl.num_layers, \
             "cache lists must have one entry per transformer block"
         if current_start is None:
@@ -318,11 +339,20 @@ class WanDiffusionWrapper(torch.nn.Module):
                 raise ValueError(f"add_condition spatial dim {add_condition.shape[1]} doesn't match "
                                  f"x spatial dim {n_new}. Check pose data processing.")
             assert add_condition.shape[2] == mdl.cmodel.pose_dim, "add_condition channel width must match pose_proj"
+        i2v = {}
+        if shape.is_i2v:
+            add_image_cache(crossattn_cache, shape, torch.bfloat16, mdl.device)   # (a cache built elsewhere lacks "k_img" / "v_img")
+            y = y.to(device=mdl.device, dtype=torch.bfloat16)
+            if y.stride(4) != 1 or y.stride(3) != W:    # a frame slice of the clip's y keeps contiguous planes: no copy
+                y = y.contiguous()
+            i2v = dict(y=y, kimg_cache=[c["k_img"] for c in crossattn_cache], vimg_cache=[c["v_img"] for c in crossattn_cache])
+            if init_cross:   # one image for the whole batch is expanded here, once per prompt
+                i2v["clip_feature"] = clip_feature.to(device=mdl.device, dtype=torch.bfloat16).expand(B, -1, -1).contiguous()
         index_buf = shared_index_buffer(kv_cache)
         flow, x0 = mdl.forward(x, t, pe, init_cross, [kv["k"] for kv in kv_cache], [kv["v"] for kv in kv_cache],
                                [c["k"] for c in crossattn_cache], [c["v"] for c in crossattn_cache], plan,
                                current_start // fs, scratch, cache_only=cache_only, add_condition=add_condition,
-                               kv_index=index_buf, cross_fold=self._cross_fold_buffers(crossattn_cache, init_cross))
+                               kv_index=index_buf, cross_fold=self._cross_fold_buffers(crossattn_cache, init_cross), **i2v)
         if init_cross:
             for c in crossattn_cache:
                 c["is_init"] = True

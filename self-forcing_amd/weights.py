@@ -31,6 +31,15 @@ class WanShape:
     eps: float = 1e-6
     local_attn_size: int = -1
     sink_size: int = 0
+    # the i2v model type (causal_model.py:381-398 `model_type`, wan/configs/wan_i2v_14B.py): in_dim = 36 = 16 latent + 20
+    # conditioning channels, img_emb = MLPProj(clip_dim, dim) over clip_len image tokens, k_img / v_img in every block
+    model_type: str = "t2v"
+    clip_dim: int = 1280
+    clip_len: int = 257
+
+    @property
+    def is_i2v(self) -> bool:
+        return self.model_type == "i2v"
 
     @property
     def head_dim(self) -> int:
@@ -52,7 +61,14 @@ WAN_14B = WanShape(dim=5120, ffn_dim=13824, num_heads=40, num_layers=40)
 # reduced shape used by the parity tests / golden fixtures (same head_dim = 128)
 WAN_REDUCED = WanShape(dim=512, ffn_dim=1024, num_heads=4, num_layers=2, text_dim=256)
 
-NAMED_SHAPES = {"Wan2.1-T2V-1.3B": WAN_1_3B, "Wan2.1-T2V-14B": WAN_14B, "reduced": WAN_REDUCED}
+# wan/configs/wan_i2v_14B.py:24-35 (the 14B dims with the 36-channel patch embedding and the CLIP ViT-H/14 context)
+WAN_I2V_14B = WAN_14B.replace(model_type="i2v", in_dim=36)
+# the reduced shape as an i2v model: clip_dim matches clip_weights.CLIP_REDUCED
+WAN_I2V_REDUCED = WAN_REDUCED.replace(model_type="i2v", in_dim=36, clip_dim=320)
+
+NAMED_SHAPES = {"Wan2.1-T2V-1.3B": WAN_1_3B, "Wan2.1-T2V-14B": WAN_14B, "Wan2.1-I2V-14B": WAN_I2V_14B, "reduced": WAN_REDUCED}
+
+I2V_Y_CHANNELS = 20   # 4 mask + 16 latent channels of `y` (causal_diffusion_inference.py:160-175)
 
 
 POSE_DIM = 5120  # UniAnimate pose-embedding width (causal_model.py:493-503)
@@ -92,7 +108,28 @@ def param_shapes(s: WanShape, pose: bool = False) -> Dict[str, Tuple[int, ...]]:
     if pose and C != POSE_DIM:   # appended LAST: the seeded draws of all other tensors do not move
         out["pose_proj.weight"] = (C, POSE_DIM)
         out["pose_proj.bias"] = (C,)
+    if s.is_i2v:   # appended LAST as well (model.py:469-481 MLPProj; :232-237 k_img, v_img, norm_k_img)
+        D = s.clip_dim
+        out["img_emb.proj.0.weight"] = (D,)
+        out["img_emb.proj.0.bias"] = (D,)
+        out["img_emb.proj.1.weight"] = (D, D)
+        out["img_emb.proj.1.bias"] = (D,)
+        out["img_emb.proj.3.weight"] = (C, D)
+        out["img_emb.proj.3.bias"] = (C,)
+        out["img_emb.proj.4.weight"] = (C,)
+        out["img_emb.proj.4.bias"] = (C,)
+        for i in range(s.num_layers):
+            p = f"blocks.{i}.cross_attn."
+            for l in ("k_img", "v_img"):
+                out[p + f"{l}.weight"] = (C, C)
+                out[p + f"{l}.bias"] = (C,)
+            out[p + "norm_k_img.weight"] = (C,)
     return out
+
+
+# the scale vectors of norms: drawn as 1 + N(0, .1) by synth_state_dict.  The two img_emb LayerNorm weights are among them:
+# drawn like biases the image branch all but vanishes from the output and a whole-forward test goes blind to it.
+_NORM_SCALES = ("norm_q.weight", "norm_k.weight", "norm3.weight", "norm_k_img.weight", "img_emb.proj.0.weight", "img_emb.proj.4.weight")
 
 
 def synth_state_dict(s: WanShape, seed: int = 0, dtype=torch.bfloat16,
@@ -112,7 +149,7 @@ def synth_state_dict(s: WanShape, seed: int = 0, dtype=torch.bfloat16,
     for name, shape in param_shapes(s, pose).items():
         if name.endswith("modulation"):
             t = torch.randn(shape, generator=g) * (modulation_gain / math.sqrt(s.dim))
-        elif name.endswith("norm_q.weight") or name.endswith("norm_k.weight") or name.endswith("norm3.weight"):
+        elif name.endswith(_NORM_SCALES):
             t = 1.0 + 0.1 * torch.randn(shape, generator=g)
         elif name.endswith("norm3.bias"):
             t = 0.1 * torch.randn(shape, generator=g)
