@@ -22,7 +22,7 @@ tensor) is given.  A config WITHOUT `denoising_step_list` selects the multi-step
 (`CausalDiffusionInferencePipeline`), as inference.py:62-67 does; it needs `num_train_timestep`, `timestep_shift`,
 `guidance_scale` and `negative_prompt`.
 
-`--pose_path` (multi-step configs only) drives the generation with a pose clip: a `.pt` (dict) or `.npy` (pickled dict)
+`--pose_path` drives the generation with a pose clip, under either pipeline: a `.pt` (dict) or `.npy` (pickled dict)
 holding `dwpose_data` [3, F, H, W] and `random_ref_dwpose` [H, W, 3] in 0..255, embedded on the GPU by `PoseEmbedder`
 with the weights of `--pose_weights_path` (a file with `dwpose_embedding.*` / `randomref_embedding_pose.*` tensors) or
 `--pose_random_init_seed N`.  Rendering skeletons and reading video files are outside this driver.
@@ -35,10 +35,11 @@ first latent frame and draws noise for the `num_output_frames - 1` frames after 
 reference.
 
 `--input_image PATH` is the other image conditioning: the i2v MODEL TYPE (a generator whose shape says so, selected by
-`model_name: Wan2.1-I2V-14B` in the config's `model_kwargs`; multi-step configs only).  The image is resized to the output
-size and handed to `CausalDiffusionInferencePipeline.inference(input_image=...)`, which encodes it with the CLIP image
-encoder (`--clip_path` checkpoint or `--clip_random_init_seed N`) and the VAE encoder (a VAE with encoder weights, as
-for `--i2v`) into the generator's `clip_feature` and `y`.  `--i2v` stays "first frame as initial latent" of a t2v model.
+`model_name: Wan2.1-I2V-14B` in the config's `model_kwargs`), under either pipeline.  The image is resized to the output
+size and handed to the pipeline's `inference(input_image=...)`, which encodes it with the CLIP image encoder (`--clip_path`
+checkpoint or `--clip_random_init_seed N`) and the VAE encoder (the Wan VAE with encoder weights: `--vae_path` or
+`--vae_random_init_seed`) into the generator's `clip_feature` and `y` -- the few-step pipeline chunk by chunk, as the
+rollout needs it.  `--i2v` stays "first frame as initial latent" of a t2v model.
 """
 import argparse
 import glob
@@ -119,7 +120,7 @@ def main():
     ap.add_argument("--random_init_seed", type=int, default=None, help="seeded random weights instead of a checkpoint")
     ap.add_argument("--data_path", required=True, help="one prompt per line; with --i2v a TextImagePairDataset directory")
     ap.add_argument("--i2v", action="store_true", help="image-to-video: encode each image as the first latent frame")
-    ap.add_argument("--input_image", default=None, help="condition an i2v-type generator on this image (multi-step sampler; CLIP + VAE encoder)")
+    ap.add_argument("--input_image", default=None, help="condition an i2v-type generator on this image (CLIP + VAE encoder)")
     ap.add_argument("--clip_path", default=None, help="--input_image: the CLIP image encoder's checkpoint")
     ap.add_argument("--clip_random_init_seed", type=int, default=None, help="--input_image: seeded random CLIP weights instead")
     ap.add_argument("--eval_first_n", type=int, default=0)
@@ -139,7 +140,7 @@ def main():
     ap.add_argument("--taehv_random_init_seed", type=int, default=None, help="seeded random TAEHV decoder weights instead (with --i2v the encoder too)")
     ap.add_argument("--fp8", action="store_true",
                     help="FP8 linear layers in the generator (the reference's enable_fp8 / torchao PerTensor quantisation)")
-    ap.add_argument("--pose_path", default=None, help=".pt / .npy dict with dwpose_data [3, F, H, W] and random_ref_dwpose [H, W, 3] (multi-step sampler)")
+    ap.add_argument("--pose_path", default=None, help=".pt / .npy dict with dwpose_data [3, F, H, W] and random_ref_dwpose [H, W, 3]")
     ap.add_argument("--pose_weights_path", default=None, help="pose embedding weights (dwpose_embedding.* / randomref_embedding_pose.*)")
     ap.add_argument("--pose_random_init_seed", type=int, default=None, help="seeded random pose embedding weights instead")
     ap.add_argument("--video_format", choices=("pt", "mjpeg"), default="pt",
@@ -152,8 +153,9 @@ def main():
     if a.pose_path or a.pose_weights_path or a.pose_random_init_seed is not None:
         if not a.pose_path or (a.pose_weights_path is None) == (a.pose_random_init_seed is None):
             ap.error("pose conditioning needs --pose_path and exactly one of --pose_weights_path / --pose_random_init_seed")
-        if is_few_step(load_config(a.config_path, a.default_config_path)):
-            ap.error("--pose_path needs a multi-step config (one without denoising_step_list): the few-step pipeline takes no pose input")
+        if not os.path.exists(a.pose_path):
+            ap.error(f"--pose_path {a.pose_path}: no such file (a .pt / .npy dict with dwpose_data and random_ref_dwpose; few-step and "
+                     "multi-step configs both take it)")
     if a.input_image:
         if (a.clip_path is None) == (a.clip_random_init_seed is None):
             ap.error("--input_image needs exactly one of --clip_path / --clip_random_init_seed")
@@ -161,8 +163,6 @@ def main():
             ap.error("--input_image needs a VAE with encoder weights: --vae_path or --vae_random_init_seed")
         if a.i2v:
             ap.error("--input_image (the i2v model type) and --i2v (first frame as initial latent) are different paths: pick one")
-        if is_few_step(load_config(a.config_path, a.default_config_path)):
-            ap.error("--input_image needs a multi-step config (one without denoising_step_list): the few-step pipeline takes no image")
     if a.taehv_path and a.taehv_random_init_seed is not None:
         ap.error("--taehv_path and --taehv_random_init_seed are mutually exclusive")
     if (a.taehv_path or a.taehv_random_init_seed is not None) and (a.vae_path or a.vae_random_init_seed is not None):
@@ -191,6 +191,12 @@ def main():
         else:
             ck = torch.load(a.checkpoint_path, map_location="cpu", weights_only=True)
             sd = ck["generator_ema" if a.use_ema else "generator"] if "generator" in ck or "generator_ema" in ck else ck
+        gen = sfa.WanDiffusionWrapper(**kwargs, is_causal=True, state_dict=sd, device=device, fp8=a.fp8)
+    elif a.pose_path and a.random_init_seed is not None and kwargs.get("model_name", "Wan2.1-T2V-1.3B") in sfa.NAMED_SHAPES:
+        # seeded weights with the pose_proj Linear the pose tokens go through.  pose_proj is drawn behind every t2v tensor and
+        # in front of an i2v shape's img_emb / k_img / v_img tensors: a t2v generator's other weights are those of the same
+        # seed without a pose clip, an i2v generator's image-branch weights are not
+        sd = sfa.synth_state_dict(sfa.NAMED_SHAPES[kwargs.get("model_name", "Wan2.1-T2V-1.3B")], seed=a.random_init_seed, pose=True)
         gen = sfa.WanDiffusionWrapper(**kwargs, is_causal=True, state_dict=sd, device=device, fp8=a.fp8)
     else:
         gen = sfa.WanDiffusionWrapper(**kwargs, is_causal=True, random_init_seed=a.random_init_seed, device=device, fp8=a.fp8)
@@ -222,27 +228,28 @@ def main():
     decode = not isinstance(vae, sfa.IdentityVAE)
     jpeg = sfa.JpegEncoder(a.jpeg_quality, a.jpeg_subsampling, device=device) if decode and a.video_format == "mjpeg" else None
     few_step = is_few_step(cfg)        # inference.py:62-67: few-step rollout iff the config has denoising_step_list
+    pose_embedder = None
+    if a.pose_path:
+        weights = a.pose_weights_path if a.pose_weights_path else sfa.synth_pose_state_dict(seed=a.pose_random_init_seed)
+        pose_embedder = sfa.PoseEmbedder(weights, device=device, strict=cfg.get("pose_weights_strict", True))
+        pose_data = load_pose(a.pose_path)
+    image_encoder = input_image = None
+    if a.input_image:
+        if gen.model.model_type != "i2v":
+            raise SystemExit(f"--input_image needs a generator of the i2v model type, this one is {gen.model.model_type!r}")
+        clip_shape = sfa.CLIP_VIT_H_14 if shape.clip_dim == sfa.CLIP_VIT_H_14.dim else sfa.CLIP_REDUCED
+        if a.clip_path:
+            image_encoder = sfa.CLIPModel(device=device, checkpoint_path=a.clip_path, shape=clip_shape)
+        else:
+            image_encoder = sfa.CLIPModel(device=device, state_dict=sfa.synth_clip_state_dict(clip_shape, a.clip_random_init_seed), shape=clip_shape)
+        input_image = load_image(a.input_image, 8 * a.latent_height, 8 * a.latent_width)
     if few_step:
-        pipe = sfa.CausalInferencePipeline(cfg, device, generator=gen, text_encoder=enc, vae=vae)
+        pipe = sfa.CausalInferencePipeline(cfg, device, generator=gen, text_encoder=enc, vae=vae, image_encoder=image_encoder,
+                                           pose_embedder=pose_embedder)
     else:                              # 50-step UniPC sampler with classifier-free guidance
         for key in ("num_train_timestep", "timestep_shift", "guidance_scale", "negative_prompt"):
             if key not in cfg:
                 raise SystemExit(f"config has neither denoising_step_list nor {key}: cannot build a sampler from it")
-        pose_embedder = None
-        if a.pose_path:
-            weights = a.pose_weights_path if a.pose_weights_path else sfa.synth_pose_state_dict(seed=a.pose_random_init_seed)
-            pose_embedder = sfa.PoseEmbedder(weights, device=device, strict=cfg.get("pose_weights_strict", True))
-            pose_data = load_pose(a.pose_path)
-        image_encoder = input_image = None
-        if a.input_image:
-            if gen.model.model_type != "i2v":
-                raise SystemExit(f"--input_image needs a generator of the i2v model type, this one is {gen.model.model_type!r}")
-            clip_shape = sfa.CLIP_VIT_H_14 if shape.clip_dim == sfa.CLIP_VIT_H_14.dim else sfa.CLIP_REDUCED
-            if a.clip_path:
-                image_encoder = sfa.CLIPModel(device=device, checkpoint_path=a.clip_path, shape=clip_shape)
-            else:
-                image_encoder = sfa.CLIPModel(device=device, state_dict=sfa.synth_clip_state_dict(clip_shape, a.clip_random_init_seed), shape=clip_shape)
-            input_image = load_image(a.input_image, 8 * a.latent_height, 8 * a.latent_width)
         pipe = sfa.CausalDiffusionInferencePipeline(cfg, device, generator=gen, text_encoder=enc, vae=vae, pose_embedder=pose_embedder,
                                                     image_encoder=image_encoder)
         if a.sampling_steps:
@@ -262,11 +269,11 @@ def main():
             torch.save(initial[0].cpu(), os.path.join(a.output_folder, f"{idx}.initial_latent.pt"))
         n_noise = a.num_output_frames - (1 if a.i2v else 0)
         noise = torch.randn([a.num_samples, n_noise, 16, a.latent_height, a.latent_width], device=device, dtype=torch.bfloat16)
+        dwpose, ref_pose = pose_data if a.pose_path else (None, None)
         if few_step:
             video, latents = pipe.inference(noise=noise, text_prompts=[prompts[idx]] * a.num_samples, initial_latent=initial,
-                                            return_latents=True)
+                                            return_latents=True, input_image=input_image, dwpose_data=dwpose, random_ref_dwpose=ref_pose)
         else:
-            dwpose, ref_pose = pose_data if a.pose_path else (None, None)
             video, latents = pipe.inference(noise, [prompts[idx]] * a.num_samples, input_image, dwpose, ref_pose, initial_latent=initial,
                                             return_latents=True)
         for s in range(a.num_samples):

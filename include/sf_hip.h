@@ -352,6 +352,16 @@ int sf_patchify_i2v(const void* x, const void* y, void* cols, int B, int F, int 
  * img_emb.proj.0 normalises clip_dim = 1280, which sf_layernorm_affine (C = 512 * {1,2,3,4,5,6,8,10}) cannot hold. */
 int sf_layernorm_rows(const void* x, const void* weight, const void* bias, void* out, int M, int C, float eps, void* stream);
 
+/* A chunk of the conditioning tensor y of an i2v generator, in one launch: y[c][t] (bf16, H x W planes contiguous, channel c
+ * at y + c * y_cstride, frame t at + t * y_fstride elements: a frame range of a longer [C, F, h, w] buffer) =
+ *   c <  mask_channels   1 when first_is_frame0 and t == 0, else 0                  (the "frame is known" mask)
+ *   c >= mask_channels   bf16(latent[t][c - mask_channels])                          latent: fp32 [frames, latent_channels, h, w],
+ *                                                                                    the rows sf_vae_encode_frames writes
+ * and, with ref_map (bf16 [h, w, mask_channels + latent_channels] channels-last, as sf_pose_embed_ref writes it; NULL: none),
+ * bf16(float(that value) + float(ref_map[.][c])): two roundings, what `cat([mask, latent]).to(bf16) + map` computes. */
+int sf_i2v_assemble_y(const void* latent, const void* ref_map, void* y, int frames, int mask_channels, int latent_channels, int h, int w,
+                      int64_t y_cstride, int64_t y_fstride, int first_is_frame0, void* stream);
+
 typedef struct sf_i2v_layer {             /* WanI2VCrossAttention beyond WanT2VCrossAttention */
   const void *kvimg_w, *kvimg_b;          /* [2C, C], [2C]: cross_attn k_img|v_img stacked */
   const void* norm_k_img_w;               /* [C] */

@@ -34,6 +34,7 @@ from .clip import CLIPModel, CLIPVisionEncoder  # noqa: F401
 from . import clip_weights, clip_reference, i2v_reference  # noqa: F401
 from . import unipc  # noqa: F401
 from .diffusion_pipeline import CausalDiffusionInferencePipeline  # noqa: F401
+from .i2v_condition import I2VConditioner  # noqa: F401
 from .unipc import FlowUniPCMultistepScheduler  # noqa: F401
 from . import ops, _lib, torch_ops, text_encoder, distributed  # noqa: F401
 
@@ -49,4 +50,4 @@ __all__ = ["WanShape", "WAN_1_3B", "WAN_14B", "WAN_REDUCED", "NAMED_SHAPES", "sy
            "WanVAEDecoder", "repack_conv", "T5Shape", "UMT5_XXL", "T5_REDUCED", "synth_t5_state_dict", "t5_param_shapes",
            "WanTextEncoder", "UMT5Encoder", "relative_position_buckets", "FlowUniPCMultistepScheduler", "CausalDiffusionInferencePipeline",
            "ClipVisionShape", "CLIP_VIT_H_14", "CLIP_REDUCED", "clip_param_shapes", "synth_clip_state_dict", "CLIPModel", "CLIPVisionEncoder",
-           "clip_weights", "clip_reference", "WAN_I2V_14B", "WAN_I2V_REDUCED", "i2v_reference"]
+           "clip_weights", "clip_reference", "WAN_I2V_14B", "WAN_I2V_REDUCED", "i2v_reference", "I2VConditioner"]

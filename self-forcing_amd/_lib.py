@@ -284,6 +284,7 @@ SIGNATURES = {
     "sf_dit_forward_pair_fold": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), C.POINTER(ForwardArgs), _vp, _vp, _vp]),
     "sf_patchify_i2v": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _vp]),
     "sf_layernorm_rows": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "sf_i2v_assemble_y": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _i, _vp]),
     "sf_dit_i2v_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(I2VModel), _i, _i, _i, _i, _i]),
     "sf_dit_forward_i2v": (C.c_int, [C.POINTER(Model), C.POINTER(I2VModel), C.POINTER(ForwardArgs), C.POINTER(I2VArgs), _vp, _vp, _vp]),
     "sf_conv_igemm": (C.c_int, [C.POINTER(ConvArgs), _vp]),

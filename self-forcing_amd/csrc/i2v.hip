@@ -3,7 +3,10 @@
 //                    sources, written as the K = 192 operand of the patch GEMM (144 columns + zero padding)
 //   layernorm_rows   nn.LayerNorm over any width that is a multiple of 8 (img_emb.proj.0 normalises clip_dim = 1280,
 //                    which the one-wave-per-row kernels of elementwise.hip, built for multiples of 512, cannot hold)
-// Both are HBM-bound and run once per pass (the gather) or once per prompt (the norm).
+//   assemble_y       a chunk of the conditioning tensor y: 4 mask channels + the VAE encoder's 16 fp32 latent channels
+//                    (+ the reference-pose map) -> bf16 [20, f, h, w] through a channel and a frame stride
+// The first two are HBM-bound; they run once per pass (the gather) and once per prompt (the norm).  assemble_y runs once
+// per chunk on a few hundred KB (scalar fp32 reads, a strided gather of the map): not measured against any bound.
 #include "sf_common.h"
 #include "../../include/sf_hip.h"
 
@@ -75,6 +78,41 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const bf16_t* __res
   }
 }
 
+// One thread per 16-byte group of one H x W plane of y.  blockIdx.y = c * f + t names the plane; its groups are counted
+// from the 16-byte boundary at or below the plane's first element (`off` elements in front of it), so every whole group
+// is one aligned bf16x8 store whatever the strides are; the groups that hang over either end of the plane store their
+// elements one by one.  c < mask_ch: the mask (1 in the clip's frame 0); else bf16(latent[t][c - mask_ch]).  With a map
+// ([h*w][C] channels-last bf16): bf16(float(that) + float(map)) -- two roundings, as `y.to(bf16) + map` in torch.
+__global__ __launch_bounds__(256) void assemble_y_kernel(const float* __restrict__ latent, const bf16_t* __restrict__ map, bf16_t* __restrict__ y,
+                                                         int f, int mask_ch, int C, int hw, long y_cstride, long y_fstride, int first_is_frame0) {
+  const int c = blockIdx.y / f, t = blockIdx.y - c * f;
+  bf16_t* plane = y + c * y_cstride + t * y_fstride;
+  const int off = (int)(((uintptr_t)plane >> 1) & 7);
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  const int p0 = g * 8 - off;                     // first element of this group, relative to the plane
+  if (p0 >= hw) return;
+  const float* src = c < mask_ch ? nullptr : latent + ((long)t * (C - mask_ch) + (c - mask_ch)) * hw;
+  const float mask = (first_is_frame0 && t == 0) ? 1.f : 0.f;
+  bf16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int p = p0 + j;
+    bf16_t v = (bf16_t)0.f;
+    if (p >= 0 && p < hw) {
+      v = (bf16_t)(src ? src[p] : mask);
+      if (map) v = (bf16_t)((float)v + (float)map[(long)p * C + c]);
+    }
+    o[j] = v;
+  }
+  if (p0 >= 0 && p0 + 8 <= hw) {
+    *reinterpret_cast<bf16x8*>(plane + p0) = o;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (p0 + j >= 0 && p0 + j < hw) plane[p0 + j] = o[j];
+  }
+}
+
 }  // namespace
 
 extern "C" int sf_patchify_i2v(const void* x, const void* y, void* cols, int B, int F, int x_channels, int y_channels, int pad_channels,
@@ -99,5 +137,24 @@ extern "C" int sf_layernorm_rows(const void* x, const void* weight, const void* 
   hipLaunchKernelGGL(layernorm_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)weight,
                      (const bf16_t*)bias, (bf16_t*)out, M, C, eps);
   SF_HIP_LAUNCH_CHECK("sf_layernorm_rows");
+  return 0;
+}
+
+extern "C" int sf_i2v_assemble_y(const void* latent, const void* ref_map, void* y, int frames, int mask_channels, int latent_channels, int h, int w,
+                                 int64_t y_cstride, int64_t y_fstride, int first_is_frame0, void* stream) {
+  SF_CHECK(latent && y, "sf_i2v_assemble_y: null tensor");
+  SF_CHECK(frames > 0 && mask_channels > 0 && latent_channels > 0 && h > 0 && w > 0,
+           "sf_i2v_assemble_y: non-positive size (frames=%d mask_channels=%d latent_channels=%d h=%d w=%d)", frames, mask_channels, latent_channels, h, w);
+  const int64_t hw = (int64_t)h * w;
+  const int64_t planes = (int64_t)(mask_channels + latent_channels) * frames;
+  SF_CHECK(hw <= (int64_t)1 << 30 && planes <= 65535, "sf_i2v_assemble_y: %lld planes of %lld elements exceed the grid", (long long)planes, (long long)hw);
+  SF_CHECK(y_cstride >= hw && y_fstride >= hw, "sf_i2v_assemble_y: y's strides (channel %lld, frame %lld) are smaller than a plane of %lld",
+           (long long)y_cstride, (long long)y_fstride, (long long)hw);
+  SF_CHECK((uintptr_t)latent % 4 == 0 && (uintptr_t)y % 2 == 0 && (!ref_map || (uintptr_t)ref_map % 2 == 0), "sf_i2v_assemble_y: misaligned tensor");
+  const unsigned groups = (unsigned)((hw + 7 + 7) / 8);   // a plane that starts inside a group spills into one more
+  hipLaunchKernelGGL(assemble_y_kernel, dim3((groups + 255) / 256, (unsigned)planes), dim3(256), 0, (hipStream_t)stream, (const float*)latent,
+                     (const bf16_t*)ref_map, (bf16_t*)y, frames, mask_channels, mask_channels + latent_channels, (int)hw, (long)y_cstride,
+                     (long)y_fstride, first_is_frame0);
+  SF_HIP_LAUNCH_CHECK("sf_i2v_assemble_y");
   return 0;
 }

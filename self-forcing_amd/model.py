@@ -222,10 +222,12 @@ class CausalWanModel(DeviceModel):
     def forward_pair(self, ctx_noisy: Tensor, ctx_timestep: Tensor, noisy: Tensor, timestep: Tensor, k_cache: List[Tensor],
                      v_cache: List[Tensor], ck_cache: List[Tensor], cv_cache: List[Tensor], ctx_plan: CachePlan, plan: CachePlan,
                      ctx_start_frame: int, start_frame: int, evict_scratch: Optional[Tensor] = None, kv_index: Optional[Tensor] = None,
-                     cross_fold: Optional[Tuple[Tensor, Tensor]] = None):
+                     cross_fold: Optional[Tuple[Tensor, Tensor]] = None,
+                     add_conditions: Tuple[Optional[Tensor], Optional[Tensor]] = (None, None)):
         """The context pass of chunk k (cache only) + the first denoising pass of chunk k + 1 as ONE call
         (torch.ops.sf_hip.dit_forward_pair -> sf_dit_forward_pair): bit-identical to two `forward` calls, but every
-        row-wise kernel and GEMM sees both passes' rows at once.  Returns (flow, x0) of the denoising pass."""
+        row-wise kernel and GEMM sees both passes' rows at once.  `add_conditions`: the pose tokens of the context pass and
+        of the denoising pass (each pass adds its own).  Returns (flow, x0) of the denoising pass."""
         if self.shape.is_i2v:
             raise NotImplementedError("forward_pair is not built for the i2v model type")
         B, F, Cin, H, W = noisy.shape
@@ -233,4 +235,4 @@ class CausalWanModel(DeviceModel):
         as_list = lambda pl, sf: [pl.sink, pl.evict, pl.keep, pl.write_start, pl.attn_start, pl.local_end, sf]  # noqa: E731
         return torch.ops.sf_hip.dit_forward_pair(self._handle, ctx_noisy, ctx_timestep, noisy, timestep, k_cache, v_cache, ck_cache, cv_cache,
                                                  ws, evict_scratch, as_list(ctx_plan, ctx_start_frame), as_list(plan, start_frame), kv_index,
-                                                 plan.global_end, *(cross_fold or (None, None)))
+                                                 plan.global_end, *(cross_fold or (None, None)), *add_conditions)

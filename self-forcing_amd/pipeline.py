@@ -1,8 +1,9 @@
 """`CausalInferencePipeline` -- drop-in for pipeline/causal_inference.py of the reference.
 
-Same constructor `(args, device, generator=None, text_encoder=None, vae=None)`, same
-`inference(noise, text_prompts, initial_latent=None, return_latents=False, profile=False,
-low_memory=False)`, same attributes read by the reference's other callers (`kv_cache1`,
+Same constructor `(args, device, generator=None, text_encoder=None, vae=None)` (plus `image_encoder=None,
+pose_embedder=None`), same `inference(noise, text_prompts, initial_latent=None, return_latents=False, profile=False,
+low_memory=False)` (plus the keywords the reference's driver passes to whichever pipeline the config selects,
+inference.py:166-174: `input_image=None, dwpose_data=None, random_ref_dwpose=None`, and `dwpose_data_emb=None`), same attributes read by the reference's other callers (`kv_cache1`,
 `crossattn_cache`, `denoising_step_list`, `scheduler`, `frame_seq_length`, `num_frame_per_block`,
 `num_transformer_blocks`; demo.py:309-404) and the same cache-dict schema.
 
@@ -13,19 +14,32 @@ injected, `WanTextEncoder()` / `WanVAEWrapper()` are built from the reference's 
 checkpoint paths as causal_inference.py:19-23 does (weights-only loads; FileNotFoundError when the
 files are absent -- benchmarks and tests inject the stand-ins of `harness.py` or seeded-weight
 instances instead); the per-step `print` is dropped; `low_memory` is accepted and ignored (288 GB HBM).
+
+Image and pose conditioning (the reference's few-step pipeline takes neither): with an i2v generator
+`input_image` is encoded by the CLIP image encoder once per clip (`clip_feature`) and by the VAE encoder chunk by chunk --
+`y` for chunk k is produced right before chunk k's first pass, on the rollout's stream, by `i2v_condition.I2VConditioner`,
+and reused by the chunk's passes; every pass, warm-up passes included, gets the frames of `y` at its position in the
+output timeline.  `dwpose_data` [3, F, H, W] with `random_ref_dwpose` [H, W, 3] are embedded once per clip
+(`pose.PoseEmbedder`; a chunk's `add_condition` is a row range of the tokens), or already-embedded `dwpose_data_emb`
+[B, C_pose, F, h, w] is sliced per chunk; with an image too, the reference-pose map goes into `y`.  The semantics, checks
+and messages are those of `CausalDiffusionInferencePipeline`.  With none of these arguments nothing changes.
 """
 from __future__ import annotations
 
 from typing import Callable, List, Optional
+
+import logging
 
 import torch
 
 from .kvcache import new_crossattn_cache, new_kv_cache, reset_kv_indices
 from .wan_wrapper import WanDiffusionWrapper
 
+log = logging.getLogger(__name__)
+
 
 class CausalInferencePipeline(torch.nn.Module):
-    def __init__(self, args, device, generator=None, text_encoder=None, vae=None):
+    def __init__(self, args, device, generator=None, text_encoder=None, vae=None, image_encoder=None, pose_embedder=None):
         super().__init__()
         self.device_ = torch.device(device)
         self.generator = WanDiffusionWrapper(**getattr(args, "model_kwargs", {}), is_causal=True, device=device) \
@@ -40,6 +54,15 @@ class CausalInferencePipeline(torch.nn.Module):
             vae = WanVAEWrapper(device=device)
         self.text_encoder = text_encoder
         self.vae = vae
+        # image / pose conditioning: injected, or loaded lazily on first need from args.clip_checkpoint_path /
+        # args.pose_weights_path (as CausalDiffusionInferencePipeline does)
+        self.image_encoder = image_encoder
+        self.clip_checkpoint_path = getattr(args, "clip_checkpoint_path", None)
+        self.pose_embedder = pose_embedder
+        self.pose_weights_path = getattr(args, "pose_weights_path", None)
+        self.pose_weights_strict = getattr(args, "pose_weights_strict", True)
+        self.pose_weights_loaded = pose_embedder is not None
+        self.conditioner = None      # i2v_condition.I2VConditioner, built on the first inference with an image
 
         # causal hyper-parameters (causal_inference.py:25-45)
         self.scheduler = self.generator.get_scheduler()
@@ -85,8 +108,99 @@ class CausalInferencePipeline(torch.nn.Module):
             return self.noise_source(t).to(device=t.device, dtype=t.dtype)
         return torch.randn_like(t)
 
+    # ------------------------------------------------------------------------------------------ image / pose conditioning
+    def _pose_embedder(self):
+        """The injected pose embedder, or the one loaded from args.pose_weights_path on first need."""
+        if self.pose_embedder is None:
+            if self.pose_weights_path is None:
+                raise ValueError("dwpose_data needs pose weights: set args.pose_weights_path or construct the pipeline with pose_embedder=")
+            from .pose import PoseEmbedder
+            self.pose_embedder = PoseEmbedder(self.pose_weights_path, device=self.device_, strict=self.pose_weights_strict)
+            self.pose_weights_loaded = True
+        return self.pose_embedder
+
+    def _image_encoder(self):
+        if self.image_encoder is None:
+            if self.clip_checkpoint_path is None:
+                raise ValueError("input_image needs the CLIP image encoder: set args.clip_checkpoint_path or construct the pipeline "
+                                 "with image_encoder=")
+            from .clip import CLIPModel
+            self.image_encoder = CLIPModel(dtype=torch.bfloat16, device=self.device_, checkpoint_path=self.clip_checkpoint_path)
+        return self.image_encoder
+
+    def _conditioner(self):
+        if self.conditioner is None:
+            from .i2v_condition import I2VConditioner
+            self.conditioner = I2VConditioner(self.vae, self._image_encoder(), device=self.device_)
+        return self.conditioner
+
+    def _conditioning(self, batch_size, num_output_frames, height, width, input_image, dwpose_data, random_ref_dwpose, dwpose_data_emb):
+        """The clip's conditioning beyond the prompt: (entries of the condition dict that hold for the whole clip,
+        chunk_condition(first_frame, n, warm_up=False) -> the entries of the pass(es) over those latent frames), or
+        (None, None) when there is none.  All checks come first, before any work; the image is encoded by CLIP and the
+        pose clip embedded here, once; `y` is produced by `chunk_condition`, in timeline order, one request per chunk."""
+        is_i2v = getattr(getattr(getattr(self, "generator", None), "model", None), "model_type", "t2v") == "i2v"
+        if input_image is not None and not is_i2v:
+            raise NotImplementedError("input_image: this generator has no i2v branch (img_emb, k_img / v_img, the 36-channel patch "
+                                      "embedding: model_type 'i2v'), so the rollout cannot consume an image")
+        if is_i2v and input_image is None:
+            raise ValueError("an i2v generator needs input_image: every pass takes its clip_feature and y")
+        fs = self.frame_seq_length
+        use_pose = dwpose_data is not None and random_ref_dwpose is not None      # both, as the reference (:336)
+        if use_pose:
+            if dwpose_data_emb is not None:
+                raise ValueError("pass either dwpose_data (with random_ref_dwpose) or dwpose_data_emb, not both")
+            if dwpose_data.dim() != 4 or dwpose_data.shape[0] != 3:
+                raise ValueError(f"dwpose_data must be one clip [3, F, H, W] (shared by the batch), got {tuple(dwpose_data.shape)}")
+            from .pose_weights import pose_plan
+            pose_fhw = pose_plan(*dwpose_data.shape[1:])
+            assert pose_fhw[0] == num_output_frames, (
+                f"dwpose_data_emb has {pose_fhw[0]} frames, "
+                f"but expected {num_output_frames} to match the output timeline.")
+            if pose_fhw[1] * pose_fhw[2] != fs:
+                raise ValueError(f"dwpose_data gives {pose_fhw[1]}x{pose_fhw[2]} pose tokens per frame, the latents {height // 2}x{width // 2}. "
+                                 "Check pose data processing.")
+        elif dwpose_data is not None or random_ref_dwpose is not None:
+            log.warning("only one of dwpose_data / random_ref_dwpose was given: the pose branch needs both and is not taken")
+        if dwpose_data_emb is not None:
+            assert dwpose_data_emb.shape[2] == num_output_frames, (
+                f"dwpose_data_emb has {dwpose_data_emb.shape[2]} frames, "
+                f"but expected {num_output_frames} to match the output timeline.")
+        if not (is_i2v or use_pose or dwpose_data_emb is not None):
+            return None, None
+
+        clip_entries = {}
+        cond = None
+        if is_i2v:
+            cond = self._conditioner()
+            if use_pose and getattr(cond, "pose_embedder", None) is None:
+                cond.pose_embedder = self._pose_embedder()      # the image to be driven by the pose: its map goes into y
+            # one image: the wrapper expands clip_feature to the batch
+            clip_entries["clip_feature"] = cond.begin(input_image, height * 8, width * 8, random_ref_dwpose if use_pose else None)
+        pose_tokens = self._pose_embedder().embed(dwpose_data)[0] if use_pose else None      # [1, F'*h*w, 5120], once per clip
+        next_frame = [0]
+
+        def chunk_condition(first_frame: int, n: int, warm_up: bool = False) -> dict:
+            entries = {}
+            if cond is not None:
+                assert first_frame == next_frame[0], f"y is produced in timeline order: frame {next_frame[0]} is next, not {first_frame}"
+                next_frame[0] += n
+                entries["y"] = cond.frames(n)
+            if warm_up:      # the context frames' passes take y only, as in the multi-step pipeline
+                return entries
+            if dwpose_data_emb is not None:
+                entries["add_condition"] = dwpose_data_emb[:, :, first_frame:first_frame + n].permute(0, 2, 3, 4, 1).flatten(1, 3).contiguous()
+            elif pose_tokens is not None:
+                # token-major: the chunk's tokens are a row range, no copy (batch > 1: the one clip, expanded)
+                condition = pose_tokens[:, first_frame * fs:(first_frame + n) * fs]
+                entries["add_condition"] = condition.expand(batch_size, -1, -1).contiguous() if batch_size > 1 else condition
+            return entries
+        return clip_entries, chunk_condition
+
     def inference(self, noise: torch.Tensor, text_prompts: List[str], initial_latent: Optional[torch.Tensor] = None,
-                  return_latents: bool = False, profile: bool = False, low_memory: bool = False):
+                  return_latents: bool = False, profile: bool = False, low_memory: bool = False, input_image=None,
+                  dwpose_data: Optional[torch.Tensor] = None, random_ref_dwpose: Optional[torch.Tensor] = None,
+                  dwpose_data_emb: Optional[torch.Tensor] = None):
         """noise [B, F, C, H, W] -> video in [0, 1] (and the latents)."""
         batch_size, num_frames, num_channels, height, width = noise.shape
         if not self.independent_first_frame or (self.independent_first_frame and initial_latent is not None):
@@ -98,7 +212,11 @@ class CausalInferencePipeline(torch.nn.Module):
         num_input_frames = initial_latent.shape[1] if initial_latent is not None else 0
         num_output_frames = num_frames + num_input_frames
         self.frame_seq_length = (height // 2) * (width // 2)
+        clip_entries, chunk_condition = self._conditioning(batch_size, num_output_frames, height, width, input_image, dwpose_data,
+                                                           random_ref_dwpose, dwpose_data_emb)
         conditional_dict = self.text_encoder(text_prompts=text_prompts)
+        if chunk_condition is not None:
+            conditional_dict = dict(conditional_dict, **clip_entries)
 
         output = torch.zeros([batch_size, num_output_frames, num_channels, height, width], device=noise.device, dtype=noise.dtype)
 
@@ -128,6 +246,8 @@ class CausalInferencePipeline(torch.nn.Module):
                 assert (num_input_frames - 1) % self.num_frame_per_block == 0
                 num_input_blocks = (num_input_frames - 1) // self.num_frame_per_block
                 output[:, :1] = initial_latent[:, :1]
+                if chunk_condition is not None:
+                    conditional_dict.update(chunk_condition(current_start_frame, 1, warm_up=True))
                 gen(noisy_image_or_video=initial_latent[:, :1], conditional_dict=conditional_dict, timestep=timestep,
                     kv_cache=self.kv_cache1, crossattn_cache=self.crossattn_cache,
                     current_start=current_start_frame * self.frame_seq_length, **self._cache_only_kw)
@@ -138,6 +258,8 @@ class CausalInferencePipeline(torch.nn.Module):
             for _ in range(num_input_blocks):
                 ref = initial_latent[:, current_start_frame:current_start_frame + self.num_frame_per_block]
                 output[:, current_start_frame:current_start_frame + self.num_frame_per_block] = ref
+                if chunk_condition is not None:
+                    conditional_dict.update(chunk_condition(current_start_frame, self.num_frame_per_block, warm_up=True))
                 gen(noisy_image_or_video=ref, conditional_dict=conditional_dict, timestep=timestep,
                     kv_cache=self.kv_cache1, crossattn_cache=self.crossattn_cache,
                     current_start=current_start_frame * self.frame_seq_length, **self._cache_only_kw)
@@ -153,7 +275,7 @@ class CausalInferencePipeline(torch.nn.Module):
             all_num_frames = [1] + all_num_frames
         for chunk_idx, start_frame, denoised_pred in self._denoise_chunks(
                 noise, conditional_dict, all_num_frames, current_start_frame, num_input_frames, skip_last_context=False,
-                on_chunk_start=(lambda: block_events.append([ev(), ev()]) or block_events[-1][0].record()) if profile else None,
+                chunk_condition=chunk_condition, on_chunk_start=(lambda: block_events.append([ev(), ev()]) or block_events[-1][0].record()) if profile else None,
                 on_chunk_end=(lambda: block_events[-1][1].record()) if profile else None):
             output[:, start_frame:start_frame + denoised_pred.shape[1]] = denoised_pred
 
@@ -188,18 +310,22 @@ class CausalInferencePipeline(torch.nn.Module):
 
     # ------------------------------------------------------------------------------------------
     def _denoise_chunks(self, noise, conditional_dict, all_num_frames, current_start_frame, num_input_frames,
-                        skip_last_context, on_chunk_start=None, on_chunk_end=None):
+                        skip_last_context, on_chunk_start=None, on_chunk_end=None, chunk_condition=None):
         """The chunk loop of causal_inference.py:176-244 as a generator: yields
         (chunk_index, start_frame, x0 [B, f, C, H, W]) as soon as a chunk's last denoising step is
         enqueued; the context pass that rewrites the chunk's K/V "clean" follows (and is skipped for
-        the final chunk when `skip_last_context`, as demo.py:396 does: nothing reads that update)."""
+        the final chunk when `skip_last_context`, as demo.py:396 does: nothing reads that update).
+        `chunk_condition` (`_conditioning`): asked once per chunk, right before the chunk's first pass, for the chunk's
+        `y` / `add_condition`, which then stay in `conditional_dict` for all of the chunk's passes."""
         gen = self.generator
         batch_size = noise.shape[0]
         # Every timestep tensor of the rollout is built HERE, once: the reference builds `ones([B, f], int64) * t` for each
         # forward and `t_next * ones([B * f], long)` for each re-noise (causal_inference.py:190-216, :228) -- three small
         # launches per step of kernels this library does not own.  One host->device copy of the step list, one broadcast
         # per distinct chunk length; the loop below then launches nothing of torch's but `randn_like` (the reference's
-        # global-RNG re-noise, :208, which must stay) and the caller's copy of the chunk into `output`.
+        # global-RNG re-noise, :208, which must stay) and the caller's copy of the chunk into `output`.  (A chunk's `y` adds
+        # VAE encode calls and sf_i2v_assemble_y, all this library's; one clip's pose tokens are a view.  Only pose tokens for a
+        # batch, or already-embedded ones, are copied by torch once per chunk, as in the multi-step pipeline.)
         steps = self.denoising_step_list.to(noise.device)
         ctx_noise = getattr(self.args, "context_noise", 0)
         tables = {}
@@ -213,13 +339,21 @@ class CausalInferencePipeline(torch.nn.Module):
         # :190-205) and layer l of the second needs only layer l's K / V of the first: a generator that offers `forward_pair`
         # (ours) runs them as ONE call -- bit-identical latents, twice the rows per GEMM (sf_dit_forward_pair).  The re-noise
         # draws keep their order: nothing is drawn between a chunk's last step and the next chunk's first.
+        # Pose tokens differ between the two passes of a pair: only `chunk_condition` knows both chunks'.  A dict that arrives
+        # with its own `add_condition` (the reference's convention) is handed to every pass as it is, unpaired.
         pair_ok = bool(self.pair_context_with_next and self._cache_only_kw and hasattr(gen, "forward_pair")
                        and gen.can_pair(conditional_dict)
+                       and (chunk_condition is not None or conditional_dict.get("add_condition") is None)
                        and batch_size * max(all_num_frames) * self.frame_seq_length <= self.pair_max_rows)
         first_pred = None          # x0 of this chunk's first step when the previous chunk's pair has already computed it
+        next_entries = None        # ... and the chunk's condition entries, which that pair has already asked for
         for chunk_idx, current_num_frames in enumerate(all_num_frames):
             if on_chunk_start is not None:
                 on_chunk_start()
+            if chunk_condition is not None:
+                entries = next_entries if next_entries is not None else chunk_condition(current_start_frame, current_num_frames)
+                next_entries = None
+                conditional_dict.update(entries)
             noisy_input = noise[:, current_start_frame - num_input_frames:
                                 current_start_frame + current_num_frames - num_input_frames]
             start_tok = current_start_frame * self.frame_seq_length
@@ -241,10 +375,15 @@ class CausalInferencePipeline(torch.nn.Module):
             if not (skip_last_context and is_last):
                 if pair_ok and not is_last and all_num_frames[chunk_idx + 1] == current_num_frames:
                     nxt = current_start_frame + current_num_frames
+                    pair_kw = {}
+                    if chunk_condition is not None:      # pose tokens: the context pass takes this chunk's, the paired pass the next chunk's
+                        next_entries = chunk_condition(nxt, current_num_frames)
+                        if "add_condition" in next_entries:
+                            pair_kw["add_conditions"] = (conditional_dict["add_condition"], next_entries["add_condition"])
                     first_pred = gen.forward_pair(denoised_pred, context_timestep,
                                                   noise[:, nxt - num_input_frames:nxt + current_num_frames - num_input_frames], step_ts[0],
                                                   conditional_dict, self.kv_cache1, self.crossattn_cache, start_tok,
-                                                  nxt * self.frame_seq_length)[1]
+                                                  nxt * self.frame_seq_length, **pair_kw)[1]
                 else:
                     gen(noisy_image_or_video=denoised_pred, conditional_dict=conditional_dict, timestep=context_timestep,
                         kv_cache=self.kv_cache1, crossattn_cache=self.crossattn_cache, current_start=start_tok,
@@ -254,7 +393,8 @@ class CausalInferencePipeline(torch.nn.Module):
             current_start_frame += current_num_frames
 
     def stream(self, noise: torch.Tensor, text_prompts: List[str], skip_last_context: bool = True,
-               overlap_decode: bool = False, frame_encoder=None):
+               overlap_decode: bool = False, frame_encoder=None, input_image=None, dwpose_data: Optional[torch.Tensor] = None,
+               random_ref_dwpose: Optional[torch.Tensor] = None, dwpose_data_emb: Optional[torch.Tensor] = None):
         """Chunk-at-a-time generation (the streaming boundary; mirrors the inline loop of the
         reference's demo.py:303-468): yields `(chunk_index, latents [B, f, C, H, W], pixels)` per chunk.
         `pixels` comes from `vae.decode_chunk(latents, chunk_index)` when the injected VAE has a streaming
@@ -268,7 +408,10 @@ class CausalInferencePipeline(torch.nn.Module):
         frame_encoder (a `JpegEncoder`): every chunk's frames are also encoded on the GPU, on the stream that decoded
         them, and the generator yields `(chunk_index, latents, pixels, frames)` with `frames` the chunk's JPEG files
         (B * T of them).  An encoder with value_range (-1, 1) gets the decoder's output (the demo's truncation), one with
-        (0, 1) gets `pixels`.  Without one the 3-tuples are exactly what they were."""
+        (0, 1) gets `pixels`.  Without one the 3-tuples are exactly what they were.
+
+        input_image / dwpose_data / random_ref_dwpose / dwpose_data_emb: as `inference`.  Chunk k's `y` is encoded on the
+        rollout's stream right before chunk k's first pass; nothing is encoded ahead of need."""
         batch_size, num_frames, num_channels, height, width = noise.shape
         if self.independent_first_frame:
             assert (num_frames - 1) % self.num_frame_per_block == 0
@@ -277,7 +420,11 @@ class CausalInferencePipeline(torch.nn.Module):
             assert num_frames % self.num_frame_per_block == 0
             all_num_frames = [self.num_frame_per_block] * (num_frames // self.num_frame_per_block)
         self.frame_seq_length = (height // 2) * (width // 2)
+        clip_entries, chunk_condition = self._conditioning(batch_size, num_frames, height, width, input_image, dwpose_data,
+                                                           random_ref_dwpose, dwpose_data_emb)
         conditional_dict = self.text_encoder(text_prompts=text_prompts)
+        if chunk_condition is not None:
+            conditional_dict = dict(conditional_dict, **clip_entries)
         key = (batch_size, self._cache_tokens(num_frames), noise.device)
         if self.kv_cache1 is None or self._cache_key != key:
             self._initialize_kv_cache(batch_size, noise.dtype, noise.device, cache_tokens=key[1])
@@ -302,7 +449,7 @@ class CausalInferencePipeline(torch.nn.Module):
                 return chunk_idx, x0, decoded[0]
             return chunk_idx, x0, decoded[0], frame_encoder._to_host(*decoded[1])
 
-        chunks = self._denoise_chunks(noise, conditional_dict, all_num_frames, 0, 0, skip_last_context)
+        chunks = self._denoise_chunks(noise, conditional_dict, all_num_frames, 0, 0, skip_last_context, chunk_condition=chunk_condition)
         if not overlap_decode:
             for chunk_idx, start_frame, x0 in chunks:
                 yield finish(chunk_idx, x0, decode(x0, chunk_idx))

@@ -11,6 +11,7 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::attention(q, k, v, structure) -> out
     sf_hip::attention_accum(q, k, v, out!, structure) -> ()         (out += attention: the i2v image keys)
     sf_hip::dit_forward_i2v(model, noisy, timestep, prompt_embeds?, clip_feature?, y, ..., kimg_cache![], vimg_cache![], ...) -> (flow, x0)
+    sf_hip::i2v_assemble_y(latent, y!, first_is_frame0, ref_map?) -> ()   (a chunk of the i2v conditioning tensor y)
     sf_hip::gemm(a, w, bias?, epilogue, resid?, gate_mod?, gate_e0?, rows_per_group, structure) -> out
     sf_hip::gemm_out(out!, a, w, ...) -> ()                         (caller-provided / aliased output)
     sf_hip::quantize_fp8(x, rows_per_segment) -> (q e4m3fn, scales)  (FP8 linear layers, fp8.py)
@@ -20,7 +21,8 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::dit_forward(model, noisy, timestep, prompt_embeds?, add_condition?, k_cache![], v_cache![], ck_cache![],
                         cv_cache![], workspace!, evict_scratch!?, ..., kv_index!?, global_end) -> (flow, x0)
     sf_hip::dit_forward_pair(model, ctx_noisy, ctx_timestep, noisy, timestep, caches![]..., workspace!, evict_scratch!?, ctx_plan[7],
-                             plan[7], kv_index!?, global_end) -> (flow, x0)        (context pass of chunk k + first pass of chunk k + 1)
+                             plan[7], kv_index!?, global_end, ..., ctx_add_condition?, add_condition?) -> (flow, x0)
+                                                                    (context pass of chunk k + first pass of chunk k + 1)
     sf_hip::vae_decode_frames(model, state!, scratch!, z, out!, h, w, window_frames, frame_index, window, history_at) -> ()
     sf_hip::vae_encode_frames(model, state!, scratch!, pixels, out!, H, W, window_frames, chunk_index, window, history_at) -> ()
     sf_hip::taehv_decode_frames(model, state!, scratch!, z, out!, h, w, clamp) -> ()
@@ -596,23 +598,56 @@ def _(model, noisy, timestep, prompt_embeds, clip_feature, y, add_condition, k_c
     return _dit_forward_fake(model, noisy, cache_only)
 
 
+@custom_op(f"{NAMESPACE}::i2v_assemble_y", mutates_args=("y",))
+def i2v_assemble_y(latent: Tensor, y: Tensor, first_is_frame0: bool, ref_map: Optional[Tensor] = None) -> None:
+    """A chunk of an i2v generator's conditioning tensor in one launch (sf_i2v_assemble_y): latent float32 [f, 16, h, w] (the
+    VAE encoder's rows) -> y bf16 [20, f, h, w], any channel / frame strides over contiguous h x w planes (a frame range of a
+    longer buffer): channels 0..3 the mask (1 in the clip's frame 0 when `first_is_frame0`), 4..19 bf16(latent); with
+    ref_map (bf16 [h, w, 20] channels-last, `PoseEmbedder.embed_ref`'s storage) bf16(float(that) + float(map))."""
+    _need_gpu(latent, "latent", torch.float32)
+    _need_gpu(y, "y")
+    if latent.dim() != 4 or not latent.is_contiguous():
+        raise ValueError(f"i2v_assemble_y: latent must be contiguous [f, C, h, w], got {tuple(latent.shape)} {latent.stride()}")
+    f, cl, h, w = latent.shape
+    if y.dim() != 4 or y.shape[0] <= cl or tuple(y.shape[1:]) != (f, h, w) or y.stride(3) != 1 or y.stride(2) != w \
+            or y.stride(1) < h * w or y.stride(0) < h * w or y.device != latent.device:
+        raise ValueError(f"i2v_assemble_y: y must be [mask + {cl}, {f}, {h}, {w}] with contiguous h x w planes on {latent.device}, got "
+                         f"{tuple(y.shape)} {y.stride()}")
+    (n_in, s_in), (n_out, s_out) = sorted(((y.shape[0], y.stride(0)), (f, y.stride(1))), key=lambda d: (d[0] == 1, d[1]))
+    if n_out > 1 and s_out < n_in * s_in:     # the kernel writes every plane: no two may share memory
+        raise ValueError(f"i2v_assemble_y: y's planes overlap (strides {y.stride()})")
+    if ref_map is not None:
+        _need_gpu(ref_map, "ref_map")
+        if tuple(ref_map.shape) != (h, w, y.shape[0]) or not ref_map.is_contiguous() or ref_map.device != latent.device:
+            raise ValueError(f"i2v_assemble_y: ref_map must be contiguous [{h}, {w}, {y.shape[0]}] (channels-last), got {tuple(ref_map.shape)}")
+    _lib.check(_lib.lib().sf_i2v_assemble_y(latent.data_ptr(), _ptr(ref_map), y.data_ptr(), f, y.shape[0] - cl, cl, h, w, y.stride(0), y.stride(1),
+                                            int(first_is_frame0), _stream(latent)), "sf_i2v_assemble_y")
+
+
+@i2v_assemble_y.register_fake
+def _(latent, y, first_is_frame0, ref_map=None):
+    return None   # writes only its mutated argument
+
+
 @custom_op(f"{NAMESPACE}::dit_forward_pair",
            mutates_args=("k_cache", "v_cache", "ck_cache", "cv_cache", "workspace", "evict_scratch", "kv_index"))
 def dit_forward_pair(model: int, ctx_noisy: Tensor, ctx_timestep: Tensor, noisy: Tensor, timestep: Tensor,
                      k_cache: List[Tensor], v_cache: List[Tensor], ck_cache: List[Tensor], cv_cache: List[Tensor],
                      workspace: Tensor, evict_scratch: Optional[Tensor], ctx_plan: List[int], plan: List[int],
                      kv_index: Optional[Tensor], global_end: int, cross_keys: Optional[Tensor] = None,
-                     cross_log2w: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+                     cross_log2w: Optional[Tensor] = None, ctx_add_condition: Optional[Tensor] = None,
+                     add_condition: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """The context pass of one chunk (cache_only) and the first denoising pass of the next in ONE call
     (sf_dit_forward_pair): bit-identical to the two calls, twice the rows per GEMM.  `ctx_plan` / `plan` =
     [sink, evict, keep, write_start, attn_start, attn_end, start_frame] of the two passes; workspace sized for 2 x batch.
-    cross_keys / cross_log2w as in dit_forward (read only).  Returns (flow, x0) of the denoising pass."""
+    cross_keys / cross_log2w as in dit_forward (read only); ctx_add_condition / add_condition: each pass's pose tokens, as
+    dit_forward's add_condition.  Returns (flow, x0) of the denoising pass."""
     m = _model(model)
     if len(ctx_plan) != 7 or len(plan) != 7 or ctx_noisy.shape != noisy.shape or ctx_timestep.shape != timestep.shape:
         raise ValueError("dit_forward_pair: two passes of one shape with 7 plan integers each expected")
-    a0, _, _ = _forward_args(m, model, ctx_noisy, ctx_timestep, None, None, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
+    a0, _, _ = _forward_args(m, model, ctx_noisy, ctx_timestep, None, ctx_add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
                              False, True, *ctx_plan, None, 0)
-    a1, flow, x0 = _forward_args(m, model, noisy, timestep, None, None, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
+    a1, flow, x0 = _forward_args(m, model, noisy, timestep, None, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
                                  False, False, *plan, kv_index, global_end)
     _fold_pair(cross_keys, cross_log2w, (m.num_layers, noisy.shape[0]), noisy.device, "dit_forward_pair")
     _lib.check(_timed_call(_lib.lib().sf_dit_forward_pair_fold, C.byref(m.cmodel), C.byref(a0), C.byref(a1), _ptr(cross_keys), _ptr(cross_log2w),
@@ -622,7 +657,7 @@ def dit_forward_pair(model: int, ctx_noisy: Tensor, ctx_timestep: Tensor, noisy:
 
 @dit_forward_pair.register_fake
 def _(model, ctx_noisy, ctx_timestep, noisy, timestep, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch, ctx_plan, plan,
-      kv_index, global_end, cross_keys=None, cross_log2w=None):
+      kv_index, global_end, cross_keys=None, cross_log2w=None, ctx_add_condition=None, add_condition=None):
     B, F, _, H, W = noisy.shape
     out_dim = _model(model).shape.out_dim
     return noisy.new_empty((B, F, out_dim, H, W)), noisy.new_empty((B, F, out_dim, H, W))
@@ -818,5 +853,5 @@ def _(model, frames, workspace):
     return frames.new_empty((frames.shape[0], s.seq_len, s.dim), dtype=torch.float32)
 
 
-OPS = ("attention", "attention_accum", "dit_forward_i2v", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "vae_encode_frames", "taehv_decode_frames",
+OPS = ("attention", "attention_accum", "dit_forward_i2v", "i2v_assemble_y", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "vae_encode_frames", "taehv_decode_frames",
        "taehv_encode_frames", "t5_encode", "clip_encode")

@@ -6,6 +6,7 @@ Mirrors `utils/wan_wrapper.py:56-117`:
     video = vae.decode_to_pixel(latent, use_cache=False)      # [B, F, 16, h, w] -> [B, 1+4(F-1), 3, 8h, 8w]
     vae.model.clear_cache()                                    # inference.py:183
     latent = vae.encode_to_latent(pixel)                       # [B, 3, T, H, W] -> float32 [B, 1+(T-1)//4, 16, H/8, W/8]
+    z0 = vae.encoder.begin_clip(image); z = vae.encoder.continue_clip(n)   # the clip "image, then zeros", as it is needed
 
 Every kernel is in csrc/ (conv_igemm.hip, vae_elementwise.hip, gemm_bf16.hip); a group of latent frames is ONE C call
 (`sf_vae_decode_frames`), a group of 4-frame chunks likewise (`sf_vae_encode_frames`).  There is no eager/CPU
@@ -34,6 +35,14 @@ class _StreamPos:
         self.fresh = True      # no chunk decoded since the last clear_cache
         self.nframes = 0       # latent frames decoded since then
         self.slot = 0          # ... of them in the current lap of the sliding history windows (sf_vae_decode_frames)
+
+
+class _EncodePos:
+    """Where one encode stream stands since its reset: its size and window slots, chunks encoded, slots taken in this lap."""
+    __slots__ = ("H", "W", "K", "chunks", "slot")
+
+    def __init__(self, H: int, W: int, K: int):
+        self.H, self.W, self.K, self.chunks, self.slot = H, W, K, 0, 0
 
 
 def window_step(slot: int, g: int, K: int):
@@ -217,6 +226,8 @@ class WanVAEEncoder(_VAEWeights):
 
     def __init__(self, shape: VaeShape, state_dict: Dict[str, Tensor], device, frames_per_call: int = 4):
         super().__init__(shape, device, frames_per_call)
+        self._clip: Optional[_EncodePos] = None      # the clip begin_clip started, until another begin_clip or an encode() over the same (H, W, K) histories ends it
+        self._zeros: Dict[tuple, Tensor] = {}        # per (H, W): the zero pixel frames continue_clip feeds
         self._load_encoder(state_dict)
 
     def _load_encoder(self, sd: Dict[str, Tensor]) -> None:
@@ -263,6 +274,21 @@ class WanVAEEncoder(_VAEWeights):
                              "(the kernels address a volume through one 32-bit-ranged buffer descriptor); use fewer frames per call")
         return self._state_scratch((H, W, K), "sf_vae_encode_state_bytes", "sf_vae_encode_scratch_bytes", H, W, K)
 
+    def _reset(self, H: int, W: int, K: int) -> "_EncodePos":
+        state, _ = self._enc_buffers(H, W, K)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(_lib.lib().sf_vae_encode_reset(C.byref(self.cmodel), state.data_ptr(), state.numel(), H, W, K, stream), "sf_vae_encode_reset")
+        return _EncodePos(H, W, K)
+
+    def _encode_group(self, pos: "_EncodePos", pixels: Tensor, out: Tensor) -> None:
+        """The next `out.shape[0]` chunks of the stream at `pos` (the first: one pixel frame; later ones: 4 each) in one C call."""
+        g = out.shape[0]
+        state, scratch = self._enc_buffers(pos.H, pos.W, pos.K)
+        window, history_at = window_step(pos.slot, g, pos.K)
+        torch.ops.sf_hip.vae_encode_frames(self._handle, state, scratch, pixels, out, pos.H, pos.W, pos.K, pos.chunks, window, history_at)
+        pos.slot = window + g
+        pos.chunks += g
+
     def encode(self, x: Tensor) -> Tensor:
         """`WanVAE_.encode` (vae.py:517-543) for one sample: x [3, T, H, W] (bf16 or float32, in [-1, 1]) -> float32
         normalised mu [1 + (T-1)//4, z_dim, H/8, W/8].  Starts from cleared histories; frames past the last whole chunk
@@ -279,21 +305,72 @@ class WanVAEEncoder(_VAEWeights):
         x = x.to(self.device)[:, :1 + 4 * (n - 1)].contiguous()
         # histories for the first frame + up to frames_per_call chunks per call; fewer slots when the input is short
         K = min(self.frames_per_call, max(n - 1, 1)) + 1
-        state, scratch = self._enc_buffers(H, W, K)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(_lib.lib().sf_vae_encode_reset(C.byref(self.cmodel), state.data_ptr(), state.numel(), H, W, K, stream), "sf_vae_encode_reset")
+        if self._clip is not None and (self._clip.H, self._clip.W, self._clip.K) == (H, W, K):
+            self._clip = None                  # a clip of begin_clip with these histories (same size, same window slots) ends here
+        pos = self._reset(H, W, K)
         out = torch.empty(n, self.shape.z_dim, H // sf, W // sf, dtype=torch.float32, device=self.device)
-        i, slot, f0 = 0, 0, 0
-        while i < n:
+        f0 = 0
+        while pos.chunks < n:
+            i = pos.chunks
             g = 1 if i == 0 else min(self.frames_per_call, n - i)
-            window, history_at = window_step(slot, g, K)
             nf = 1 if i == 0 else 4 * g
-            torch.ops.sf_hip.vae_encode_frames(self._handle, state, scratch, x[:, f0:f0 + nf], out[i:i + g], H, W, K, i, window,
-                                               history_at)
-            slot = window + g
+            self._encode_group(pos, x[:, f0:f0 + nf], out[i:i + g])
             f0 += nf
+        return out
+
+    # --- a clip "one image, then zeros" of open length, encoded as it is needed (i2v_condition.py) ---------------
+    def _clip_out(self, out: Optional[Tensor], n: int, H: int, W: int) -> Tensor:
+        sf = self.shape.spatial_factor
+        want = (n, self.shape.z_dim, H // sf, W // sf)
+        if out is None:
+            return torch.empty(want, dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != want or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous float32 tensor {want} on {self.device}, got {tuple(out.shape)} {out.dtype} {out.device}")
+        return out
+
+    def begin_clip(self, image: Tensor, out: Optional[Tensor] = None) -> Tensor:
+        """Start the clip whose first pixel frame is `image` [3, H, W] (bf16 or float32 in [-1, 1]) and whose other frames
+        are zero: cleared histories, then the one-frame call.  Returns latent frame 0, float32 [1, z_dim, H/8, W/8]
+        (written to `out` when given).  `continue_clip` encodes what follows -- the same calls `encode` makes on the whole
+        clip, so the same bits."""
+        if image.dim() != 3 or image.shape[0] != 3:
+            raise ValueError(f"expected an image [3, H, W], got {tuple(image.shape)}")
+        _, H, W = image.shape
+        sf = self.shape.spatial_factor
+        if H % sf or W % sf:
+            raise ValueError(f"begin_clip: height and width must be multiples of {sf}, got {H}x{W}")
+        if image.dtype not in (torch.bfloat16, torch.float32):
+            image = image.float()
+        image = image.to(self.device).unsqueeze(1).contiguous()
+        self._clip = None
+        out = self._clip_out(out, 1, H, W)
+        pos = self._reset(H, W, self.frames_per_call + 1)
+        self._encode_group(pos, image, out)
+        self._clip = pos
+        return out
+
+    def continue_clip(self, n: int, out: Optional[Tensor] = None) -> Tensor:
+        """The next `n` latent frames of the clip `begin_clip` started (4 n zero pixel frames), float32
+        [n, z_dim, H/8, W/8] (written to `out` when given), carrying the histories.  The zeros are one persistent buffer of
+        4 x frames_per_call frames per size: the clip itself never exists in memory."""
+        pos = self._clip
+        if pos is None:
+            raise RuntimeError("continue_clip: no clip in progress (begin_clip starts one; encode() over the same histories ends it)")
+        if n < 1:
+            raise ValueError(f"continue_clip: n must be positive, got {n}")
+        out = self._clip_out(out, n, pos.H, pos.W)
+        zeros = self._zero_frames(pos.H, pos.W)
+        i = 0
+        while i < n:
+            g = min(self.frames_per_call, n - i)
+            self._encode_group(pos, zeros[:, :4 * g], out[i:i + g])
             i += g
         return out
+
+    def _zero_frames(self, H: int, W: int) -> Tensor:
+        if (H, W) not in self._zeros:
+            self._zeros[(H, W)] = torch.zeros(3, 4 * self.frames_per_call, H, W, dtype=torch.bfloat16, device=self.device)
+        return self._zeros[(H, W)]
 
 
 VAE_CHECKPOINT = "wan_models/Wan2.1-T2V-1.3B/Wan2.1_VAE.pth"   # utils/wan_wrapper.py:74

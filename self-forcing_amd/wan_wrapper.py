@@ -28,7 +28,8 @@ Differences from the reference, all deliberate:
     (utils/wan_wrapper.py:271-274); the image keys / values live in the cross-attention cache dicts as "k_img" / "v_img" and
     are filled with the text K / V.  The reference's own causal i2v path does not run (its WanI2VCrossAttention takes no
     `crossattn_cache`): the semantics are those of its bidirectional i2v model, DESIGN.md section 16.  A t2v model given
-    either tensor raises NotImplementedError; `forward_pair` and `fp8=True` are not built for an i2v model.
+    either tensor raises NotImplementedError; `forward_pair` and `fp8=True` are not built for an i2v model (`forward_pair` does
+    take the two passes' pose tokens).
 """
 from __future__ import annotations
 
@@ -213,22 +214,42 @@ class WanDiffusionWrapper(torch.nn.Module):
 
     # --- two passes in one call ------------------------------------------------------------------
     def can_pair(self, conditional_dict: dict) -> bool:
-        """`forward_pair` covers the plain text-conditioned rollout (no pose tokens / image conditioning)."""
-        return conditional_dict.get("add_condition") is None and conditional_dict.get("clip_feature") is None \
-            and conditional_dict.get("y") is None and not self.model.shape.is_i2v
+        """`forward_pair` covers the text-conditioned rollout, with or without pose tokens (which it takes per pass, as
+        `add_conditions=`, never from `conditional_dict`); not the image conditioning of the i2v model type."""
+        return conditional_dict.get("clip_feature") is None and conditional_dict.get("y") is None and not self.model.shape.is_i2v
+
+    def _pose_condition(self, add_condition: Tensor, B: int, n_new: int) -> Tensor:
+        """pose tokens [B, L_pose, 5120]: x += pose_proj(add_condition), the intent of causal_model.py:786-819 (that branch
+        raises in the reference snapshot: parity pinned by the oracle only)"""
+        mdl = self.model
+        if not mdl.accepts_pose:   # (dim == 5120 models need none: their pose_proj is nn.Identity(), :500-501)
+            raise ValueError(f"add_condition needs pose_proj weights in the state dict of a dim-{mdl.shape.dim} model")
+        add_condition = add_condition.to(device=mdl.device, dtype=torch.bfloat16).contiguous()
+        if add_condition.dim() != 3 or add_condition.shape[0] != B or add_condition.shape[1] != n_new:
+            raise ValueError(f"add_condition spatial dim {add_condition.shape[1]} doesn't match "
+                             f"x spatial dim {n_new}. Check pose data processing.")
+        assert add_condition.shape[2] == mdl.cmodel.pose_dim, "add_condition channel width must match pose_proj"
+        return add_condition
 
     @torch.no_grad()
     def forward_pair(self, context_input: Tensor, context_timestep: Tensor, noisy_image_or_video: Tensor, timestep: Tensor,
-                     conditional_dict: dict, kv_cache: List[dict], crossattn_cache: List[dict], context_start: int, current_start: int):
+                     conditional_dict: dict, kv_cache: List[dict], crossattn_cache: List[dict], context_start: int, current_start: int,
+                     add_conditions: Optional[tuple] = None):
         """Extension (no counterpart call in the reference, which runs these back to back, causal_inference.py:226-235 then
         :190-205 of the next chunk): the context pass of one chunk -- `context_input` = its denoised latents at
         `context_timestep`, cache positions from `context_start`, only the KV cache is updated -- and the FIRST denoising
         pass of the next chunk (`noisy_image_or_video`, `timestep`, `current_start`) as one call.  Same results bit for
-        bit as `forward(..., cache_only=True)` followed by `forward(...)`; returns (flow_pred, pred_x0) of the second."""
+        bit as `forward(..., cache_only=True)` followed by `forward(...)`; returns (flow_pred, pred_x0) of the second.
+        `add_conditions`: the two passes' pose tokens (context pass, denoising pass), each as `forward`'s `add_condition`.
+        The passes belong to different chunks, so one `conditional_dict["add_condition"]` cannot serve both: a dict that
+        carries one without `add_conditions` is refused rather than run without the tokens."""
         mdl = self.model
         shape = mdl.shape
         if shape.is_i2v:
             raise NotImplementedError("forward_pair is not built for the i2v model type: run the two passes with forward()")
+        if add_conditions is None and conditional_dict.get("add_condition") is not None:
+            raise ValueError("forward_pair: conditional_dict carries add_condition but the two passes belong to different chunks: pass "
+                             "add_conditions=(context pass tokens, denoising pass tokens), or run the passes with forward()")
         xs = []
         for x in (context_input, noisy_image_or_video):
             assert x.dim() == 5 and x.shape[2] == shape.in_dim, "inputs must be [B, F, C, H, W] latents"
@@ -248,10 +269,15 @@ class WanDiffusionWrapper(torch.nn.Module):
         plan1 = plan_cache_update(plan0.local_end, plan0.global_end, current_start, n_new, cap, mdl.local_attn_size, mdl.sink_size * fs, window)
         scratch = self._eviction_scratch(B, max(plan0.keep, plan1.keep), cap) if plan0.evict > 0 or plan1.evict > 0 else None
         index_buf = shared_index_buffer(kv_cache)
+        poses = (None, None)
+        if add_conditions is not None:
+            assert len(add_conditions) == 2 and all(a is not None for a in add_conditions), \
+                "forward_pair: add_conditions is (context pass tokens, denoising pass tokens)"
+            poses = tuple(self._pose_condition(a, B, n_new) for a in add_conditions)
         flow, x0 = mdl.forward_pair(xs[0], ts[0], xs[1], ts[1], [kv["k"] for kv in kv_cache], [kv["v"] for kv in kv_cache],
                                     [c["k"] for c in crossattn_cache], [c["v"] for c in crossattn_cache], plan0, plan1,
                                     context_start // fs, current_start // fs, scratch, kv_index=index_buf,
-                                    cross_fold=self._cross_fold_buffers(crossattn_cache, False))
+                                    cross_fold=self._cross_fold_buffers(crossattn_cache, False), add_conditions=poses)
         write_indices(kv_cache, plan1.global_end, plan1.local_end, done_by_kernel=index_buf is not None)
         self._pace(mdl.device)
         return flow, x0
@@ -330,15 +356,8 @@ class WanDiffusionWrapper(torch.nn.Module):
                 pe = torch.cat([pe, pe.new_zeros(B, shape.text_len - pe.shape[1], shape.text_dim)], dim=1)
             pe = pe.contiguous()
 
-        if add_condition is not None:   # pose tokens [B, L_pose, 5120]: x += pose_proj(add_condition), the intent of
-            # causal_model.py:786-819 (that branch raises in the reference snapshot: parity pinned by the oracle only)
-            if not mdl.accepts_pose:   # (dim == 5120 models need none: their pose_proj is nn.Identity(), :500-501)
-                raise ValueError(f"add_condition needs pose_proj weights in the state dict of a dim-{shape.dim} model")
-            add_condition = add_condition.to(device=mdl.device, dtype=torch.bfloat16).contiguous()
-            if add_condition.dim() != 3 or add_condition.shape[0] != B or add_condition.shape[1] != n_new:
-                raise ValueError(f"add_condition spatial dim {add_condition.shape[1]} doesn't match "
-                                 f"x spatial dim {n_new}. Check pose data processing.")
-            assert add_condition.shape[2] == mdl.cmodel.pose_dim, "add_condition channel width must match pose_proj"
+        if add_condition is not None:
+            add_condition = self._pose_condition(add_condition, B, n_new)
         i2v = {}
         if shape.is_i2v:
             add_image_cache(crossattn_cache, shape, torch.bfloat16, mdl.device)   # (a cache built elsewhere lacks "k_img" / "v_img")

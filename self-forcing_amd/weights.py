@@ -66,7 +66,8 @@ WAN_I2V_14B = WAN_14B.replace(model_type="i2v", in_dim=36)
 # the reduced shape as an i2v model: clip_dim matches clip_weights.CLIP_REDUCED
 WAN_I2V_REDUCED = WAN_REDUCED.replace(model_type="i2v", in_dim=36, clip_dim=320)
 
-NAMED_SHAPES = {"Wan2.1-T2V-1.3B": WAN_1_3B, "Wan2.1-T2V-14B": WAN_14B, "Wan2.1-I2V-14B": WAN_I2V_14B, "reduced": WAN_REDUCED}
+NAMED_SHAPES = {"Wan2.1-T2V-1.3B": WAN_1_3B, "Wan2.1-T2V-14B": WAN_14B, "Wan2.1-I2V-14B": WAN_I2V_14B, "reduced": WAN_REDUCED,
+                "reduced-i2v": WAN_I2V_REDUCED}
 
 I2V_Y_CHANNELS = 20   # 4 mask + 16 latent channels of `y` (causal_diffusion_inference.py:160-175)
 

@@ -1,0 +1,380 @@
+"""Image and pose conditioning of the few-step pipeline without a GPU: the keyword call of the
+reference's driver, the refusals and assertions shared with the multi-step pipeline, the order in which a clip's `y` is
+asked for, the argument checks of `sf_i2v_assemble_y`, the unchanged ABI, and the call sequence of `WanVAEEncoder.encode`
+beside the resumable calls."""
+import ctypes
+import os
+import re
+from types import SimpleNamespace
+
+import pytest
+import torch
+
+import self_forcing_amd as sfa
+from self_forcing_amd import vae as vae_mod
+from self_forcing_amd import vae_weights as vw
+from self_forcing_amd import weights as wt
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FS = 4 * 6          # tokens per frame of an 8 x 12 latent
+
+
+class Generator:
+    """Stand-in generator that records what every pass is handed."""
+
+    def __init__(self, model_type="t2v", pair=False):
+        self.model = SimpleNamespace(num_layers=2, local_attn_size=-1, sink_size=0, num_frame_per_block=1, model_type=model_type,
+                                     shape=wt.WAN_I2V_REDUCED if model_type == "i2v" else wt.WAN_REDUCED)
+        self.scheduler = sfa.FlowMatchScheduler(shift=5.0, sigma_min=0.0, extra_one_step=True)
+        self.scheduler.set_timesteps(1000, training=True)
+        self.scheduler.add_noise = lambda x0, eps, t: x0 + 0 * eps          # keep it on the CPU
+        self.calls = []
+        if pair:
+            self.can_pair = lambda conditional_dict: True
+            self.forward_pair = self._forward_pair
+
+    def get_scheduler(self):
+        return self.scheduler
+
+    def forward(self, noisy_image_or_video, conditional_dict, timestep, kv_cache, crossattn_cache, current_start, cache_only=False):
+        self.calls.append(SimpleNamespace(start=current_start, frames=noisy_image_or_video.shape[1], cache_only=bool(cache_only),
+                                          y=conditional_dict.get("y"), clip=conditional_dict.get("clip_feature"),
+                                          pose=conditional_dict.get("add_condition")))
+        return noisy_image_or_video, noisy_image_or_video * 0.5
+
+    __call__ = forward
+
+    def _forward_pair(self, context_input, context_timestep, noisy_image_or_video, timestep, conditional_dict, kv_cache, crossattn_cache,
+                      context_start, current_start, add_conditions=None):
+        self.calls.append(SimpleNamespace(start=(context_start, current_start), frames=noisy_image_or_video.shape[1], cache_only=False,
+                                          y=None, clip=None, pose=add_conditions))
+        return noisy_image_or_video, noisy_image_or_video * 0.5
+
+
+class Conditioner:
+    """Stand-in for `I2VConditioner`: frame i of its y is filled with the value i."""
+
+    def __init__(self):
+        self.begun, self.asked, self.position, self.pose_embedder = [], [], 0, None
+
+    def begin(self, image, height, width, random_ref_dwpose=None):
+        self.begun.append((height, width, random_ref_dwpose is not None))
+        self.position = 0
+        return torch.full((1, 257, 320), 3.0)
+
+    def frames(self, n):
+        self.asked.append((self.position, n))
+        y = torch.arange(self.position, self.position + n, dtype=torch.float32).reshape(1, 1, n, 1, 1).expand(1, 20, n, 8, 12)
+        self.position += n
+        return y
+
+
+def pipeline(gen, nfpb=1, iff=False, **kw):
+    args = SimpleNamespace(denoising_step_list=[1000, 750, 500, 250], warp_denoising_step=True, independent_first_frame=iff,
+                           num_frame_per_block=nfpb, context_noise=0)
+    return sfa.CausalInferencePipeline(args, "cpu", generator=gen, text_encoder=lambda text_prompts: {"prompt_embeds": None},
+                                       vae=sfa.IdentityVAE(), **kw)
+
+
+# ------------------------------------------------------------------------------------------ the driver's call
+def test_the_reference_drivers_keyword_call_is_accepted():
+    """inference.py:166-174 calls whichever pipeline the config selects with these keywords."""
+    gen = Generator()
+    pipe = pipeline(gen)
+    sampled_noise, prompts, initial_latent = torch.randn(1, 2, 16, 8, 12), ["p"], None
+    video, latents = pipe.inference(
+        noise=sampled_noise,
+        text_prompts=prompts,
+        return_latents=True,
+        initial_latent=initial_latent,
+        input_image=None,
+        dwpose_data=None,
+        random_ref_dwpose=None,
+    )
+    assert tuple(latents.shape) == (1, 2, 16, 8, 12) and len(gen.calls) == 10
+    assert all(c.y is None and c.clip is None and c.pose is None for c in gen.calls)      # nothing new reaches the generator
+    import inspect
+    params = list(inspect.signature(sfa.CausalInferencePipeline.__init__).parameters)
+    assert params[:6] == ["self", "args", "device", "generator", "text_encoder", "vae"] and params[6:] == ["image_encoder", "pose_embedder"]
+    for fn in (sfa.CausalInferencePipeline.inference, sfa.CausalInferencePipeline.stream):
+        assert {"input_image", "dwpose_data", "random_ref_dwpose", "dwpose_data_emb"} <= set(inspect.signature(fn).parameters)
+
+
+def test_lazy_loading_reads_the_args():
+    a = dict(clip_checkpoint_path="clip.pth", pose_weights_path="pose.pt", pose_weights_strict=False)
+    args = SimpleNamespace(denoising_step_list=[1000], warp_denoising_step=False, independent_first_frame=False, **a)
+    pipe = sfa.CausalInferencePipeline(args, "cpu", generator=Generator(), text_encoder=object(), vae=object())
+    assert (pipe.clip_checkpoint_path, pipe.pose_weights_path, pipe.pose_weights_strict) == ("clip.pth", "pose.pt", False)
+    assert pipe.image_encoder is None and pipe.pose_embedder is None and not pipe.pose_weights_loaded and pipe.conditioner is None
+    bare = pipeline(Generator())
+    with pytest.raises(ValueError, match="pose_weights_path"):
+        bare._pose_embedder()
+    with pytest.raises(ValueError, match="clip_checkpoint_path"):
+        bare._image_encoder()
+
+
+# ------------------------------------------------------------------------------------------ refusals and assertions
+@pytest.mark.parametrize("call", ["inference", "stream"])
+def test_refusals_and_assertions(call, caplog):
+    noise = torch.zeros(1, 2, 16, 8, 12)
+    clip, ref = torch.zeros(3, 9, 64, 96, dtype=torch.uint8), torch.zeros(64, 96, 3, dtype=torch.uint8)
+
+    def run(pipe, noise=noise, **kw):
+        out = getattr(pipe, call)(noise, ["p"], **kw)
+        return list(out) if call == "stream" else out
+
+    with pytest.raises(NotImplementedError, match="i2v branch"):
+        run(pipeline(Generator()), input_image=torch.zeros(3, 64, 96))
+    with pytest.raises(ValueError, match="an i2v generator needs input_image"):
+        run(pipeline(Generator("i2v")))
+    t2v = pipeline(Generator(), pose_embedder=object())
+    with pytest.raises(AssertionError, match="dwpose_data_emb has 3 frames, but expected 2 to match the output timeline."):
+        run(t2v, dwpose_data=clip, random_ref_dwpose=ref)
+    with pytest.raises(ValueError, match="pose tokens per frame"):
+        run(t2v, noise=torch.zeros(1, 3, 16, 16, 12), dwpose_data=clip, random_ref_dwpose=ref)
+    with pytest.raises(ValueError, match="not both"):
+        run(t2v, noise=torch.zeros(1, 3, 16, 8, 12), dwpose_data=clip, random_ref_dwpose=ref, dwpose_data_emb=torch.zeros(1, 5120, 3, 4, 6))
+    with pytest.raises(ValueError, match=r"one clip \[3, F, H, W\]"):
+        run(t2v, dwpose_data=clip[None], random_ref_dwpose=ref)
+    with pytest.raises(AssertionError, match="dwpose_data_emb has 5 frames, but expected 2 to match the output timeline."):
+        run(t2v, dwpose_data_emb=torch.zeros(1, 5120, 5, 4, 6))
+    gen = Generator()
+    with caplog.at_level("WARNING"):
+        run(pipeline(gen), dwpose_data=clip)                   # only one of the two: the pose branch is not taken
+    assert "pose branch" in caplog.text and all(c.pose is None for c in gen.calls)
+
+
+# ------------------------------------------------------------------------------------------ y: once per chunk, in order
+@pytest.mark.parametrize("nfpb,frames,initial,iff", [(1, 3, 0, False), (2, 4, 2, False), (3, 3, 4, True), (3, 4, 0, True)])
+def test_inference_asks_for_each_chunks_y_once_and_in_order(nfpb, frames, initial, iff):
+    gen, cond = Generator("i2v"), Conditioner()
+    pipe = pipeline(gen, nfpb=nfpb, iff=iff)
+    pipe.conditioner = cond
+    init = torch.randn(1, initial, 16, 8, 12) if initial else None
+    pipe.inference(torch.randn(1, frames, 16, 8, 12), ["p"], initial_latent=init, input_image=torch.zeros(3, 64, 96))
+    assert cond.begun == [(64, 96, False)]
+    warm = ([1] if iff and initial else []) + [nfpb] * ((initial - (1 if iff else 0)) // nfpb) if initial else []
+    chunks = ([1] if iff and not initial else []) + [nfpb] * ((frames - (1 if iff and not initial else 0)) // nfpb)
+    want, at = [], 0
+    for n in warm + chunks:
+        want.append((at, n))
+        at += n
+    assert cond.asked == want and cond.asked[0][0] == 0          # every chunk once, in timeline order, from frame 0
+    assert len(gen.calls) == len(warm) + 5 * len(chunks)
+    for c in gen.calls:                                          # every pass sees the frames of y at its position
+        first = c.start // FS
+        assert tuple(c.y.shape) == (1, 20, c.frames, 8, 12) and c.y[0, 0, :, 0, 0].tolist() == list(range(first, first + c.frames))
+        assert c.clip is not None and float(c.clip[0, 0, 0]) == 3.0
+    assert all(c.cache_only for c in gen.calls[:len(warm)])
+
+
+def test_stream_asks_for_y_right_before_each_chunk():
+    gen, cond = Generator("i2v"), Conditioner()
+    pipe = pipeline(gen)
+    pipe.conditioner = cond
+    it = pipe.stream(torch.randn(1, 3, 16, 8, 12), ["p"], skip_last_context=False, input_image=torch.zeros(3, 64, 96))
+    assert cond.asked == []
+    for k in range(3):
+        next(it)
+        assert cond.asked == [(i, 1) for i in range(k + 1)]      # nothing is encoded ahead of need
+    assert list(it) == [] and len(gen.calls) == 15
+    # a second clip on the same pipeline starts again at frame 0
+    list(pipe.stream(torch.randn(1, 2, 16, 8, 12), ["p"], input_image=torch.zeros(3, 64, 96)))
+    assert cond.asked[3:] == [(0, 1), (1, 1)] and len(cond.begun) == 2
+
+
+# ------------------------------------------------------------------------------------------ pose tokens, paired or not
+class Embedder:
+    def embed(self, dwpose_data):
+        f, h, w = sfa.pose_plan(*dwpose_data.shape[1:])
+        return torch.arange(f * h * w, dtype=torch.float32).reshape(1, -1, 1).expand(1, -1, 8), (f, h, w)
+
+    def embed_ref(self, random_ref_dwpose):
+        raise AssertionError("the reference-pose map is only computed when there is an image")
+
+
+@pytest.mark.parametrize("pair", [False, True])
+def test_pose_tokens_are_a_row_range_per_chunk(pair):
+    gen = Generator(pair=pair)
+    pipe = pipeline(gen, pose_embedder=Embedder())
+    clip, ref = torch.zeros(3, 9, 64, 96, dtype=torch.uint8), torch.zeros(64, 96, 3, dtype=torch.uint8)
+    pipe.inference(torch.randn(1, 3, 16, 8, 12), ["p"], dwpose_data=clip, random_ref_dwpose=ref)
+    rows = lambda t: (int(t[0, 0, 0]), int(t[0, -1, 0]) + 1)  # noqa: E731
+    if not pair:
+        assert len(gen.calls) == 15
+        for c in gen.calls:
+            assert rows(c.pose) == (c.start, c.start + FS) and tuple(c.pose.shape) == (1, FS, 8)
+        return
+    # the context pass of chunk k runs with chunk k + 1's first pass: 4 + pair, 3 + pair, 3 + the last context pass
+    pairs = [c for c in gen.calls if isinstance(c.start, tuple)]
+    assert len(gen.calls) == 4 + 1 + 3 + 1 + 3 + 1 and [c.start for c in pairs] == [(0, FS), (FS, 2 * FS)]
+    for c in pairs:                                              # the context pass: chunk k's tokens; the paired pass: chunk k + 1's
+        assert rows(c.pose[0]) == (c.start[0], c.start[0] + FS) and rows(c.pose[1]) == (c.start[1], c.start[1] + FS)
+    for c in gen.calls:
+        if not isinstance(c.start, tuple):
+            assert rows(c.pose) == (c.start, c.start + FS)
+
+
+def test_already_embedded_tokens_are_sliced_per_chunk():
+    gen = Generator()
+    emb = torch.arange(3, dtype=torch.float32).reshape(1, 1, 3, 1, 1).expand(2, 8, 3, 4, 6)
+    pipeline(gen).inference(torch.randn(2, 3, 16, 8, 12), ["p", "p"], dwpose_data_emb=emb)
+    for c in gen.calls:
+        assert tuple(c.pose.shape) == (2, FS, 8) and bool((c.pose == c.start // FS).all())
+
+
+def test_tokens_from_the_callers_dict_are_never_paired_away():
+    """The reference's convention: `add_condition` arrives in the condition dict (here from the text encoder).  Only the
+    caller knows which chunk it belongs to, so every pass gets it, one call per pass -- as before pairs took pose tokens."""
+    gen, tokens = Generator(pair=True), torch.ones(1, FS, 8)
+    args = SimpleNamespace(denoising_step_list=[1000, 750, 500, 250], warp_denoising_step=True, independent_first_frame=False,
+                           num_frame_per_block=1, context_noise=0)
+    pipe = sfa.CausalInferencePipeline(args, "cpu", generator=gen, text_encoder=lambda text_prompts: {"prompt_embeds": None, "add_condition": tokens},
+                                       vae=sfa.IdentityVAE())
+    pipe.inference(torch.randn(1, 3, 16, 8, 12), ["p"])
+    assert len(gen.calls) == 15 and all(not isinstance(c.start, tuple) and c.pose is tokens for c in gen.calls)
+    plain = Generator(pair=True)                               # without tokens the same stand-in is paired
+    pipeline(plain).inference(torch.randn(1, 3, 16, 8, 12), ["p"])
+    assert len(plain.calls) == 13
+    # the wrapper itself refuses a dict with tokens and no per-pass tokens, before it touches anything
+    w = sfa.WanDiffusionWrapper.__new__(sfa.WanDiffusionWrapper)
+    torch.nn.Module.__init__(w)
+    w.model = SimpleNamespace(shape=wt.WAN_REDUCED)
+    x, t = torch.zeros(1, 1, 16, 8, 12), torch.zeros(1, 1)
+    with pytest.raises(ValueError, match="add_conditions="):
+        w.forward_pair(x, t, x, t, {"add_condition": tokens}, [{}] * 2, [{}] * 2, 0, FS)
+
+
+def test_wrapper_pairs_with_pose_tokens_only():
+    w = sfa.WanDiffusionWrapper.__new__(sfa.WanDiffusionWrapper)
+    torch.nn.Module.__init__(w)
+    w.model = SimpleNamespace(shape=wt.WAN_REDUCED)
+    assert w.can_pair({}) and w.can_pair({"add_condition": torch.zeros(1)})
+    assert not w.can_pair({"y": torch.zeros(1)}) and not w.can_pair({"clip_feature": torch.zeros(1)})
+    w.model = SimpleNamespace(shape=wt.WAN_I2V_REDUCED)
+    assert not w.can_pair({"add_condition": torch.zeros(1)})
+    sch = str(torch.ops.sf_hip.dit_forward_pair.default._schema)
+    assert "Tensor? ctx_add_condition=None" in sch and "Tensor? add_condition=None" in sch
+
+
+# ------------------------------------------------------------------------------------------ the new entry point
+def test_assemble_y_rejects_bad_arguments_without_touching_the_gpu():
+    lib = sfa._lib.lib()
+    err = lib.sf_last_error
+    p = 1 << 20       # an aligned non-null address: every call below fails its checks before any launch
+    call = lambda latent=p, ref=None, y=p, f=1, mc=4, lc=16, h=8, w=12, cs=96, fs=96: lib.sf_i2v_assemble_y(  # noqa: E731
+        latent, ref, y, f, mc, lc, h, w, cs, fs, 1, None)
+    assert call(latent=None) != 0 and b"null" in err()
+    assert call(y=None) != 0 and b"null" in err()
+    for kw in ({"f": 0}, {"mc": 0}, {"lc": -1}, {"h": 0}, {"w": -3}):
+        assert call(**kw) != 0 and b"non-positive" in err(), kw
+    assert call(cs=95) != 0 and b"smaller than a plane" in err()
+    assert call(fs=95) != 0 and b"smaller than a plane" in err()
+    assert call(f=4000) != 0 and b"exceed the grid" in err()
+    assert call(latent=p + 2) != 0 and b"misaligned" in err()
+    assert call(y=p + 1) != 0 and b"misaligned" in err()
+    assert call(ref=p + 1) != 0 and b"misaligned" in err()
+    with pytest.raises(ValueError, match="CUDA"):
+        torch.ops.sf_hip.i2v_assemble_y(torch.zeros(1, 16, 8, 12), torch.zeros(20, 1, 8, 12, dtype=torch.bfloat16), True, None)
+
+
+def test_abi_is_unchanged_and_the_entry_point_is_declared():
+    text = open(os.path.join(ROOT, "include", "sf_hip.h")).read()
+    L = sfa._lib
+    assert int(re.search(r"#define SF_HIP_ABI_VERSION (\d+)", text).group(1)) == 10 == L.ABI_VERSION == L.lib().sf_abi_version()
+    nocomment = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    decl = re.search(r"\bsf_i2v_assemble_y\((.*?)\);", nocomment, re.S).group(1)
+    assert len(decl.split(",")) == len(L.SIGNATURES["sf_i2v_assemble_y"][1]) == 12
+    # the structs the generator's calls take keep their layouts
+    assert ctypes.sizeof(L.I2VLayer) == 3 * 8 and ctypes.sizeof(L.I2VModel) == 16 + 9 * 8 and ctypes.sizeof(L.I2VArgs) == 2 * 8 + 3 * 8 + 8 + 2 * 8
+    assert ctypes.sizeof(L.LayerWeights) == 21 * 8 and L.Model.layers_fp8_host.offset == ctypes.sizeof(L.Model) - 8
+    assert L.ForwardArgs.global_end.offset == ctypes.sizeof(L.ForwardArgs) - 8
+    sch = str(torch.ops.sf_hip.i2v_assemble_y.default._schema)
+    assert "Tensor(a1!) y" in sch and "i2v_assemble_y" in sfa.torch_ops.OPS
+
+
+# ------------------------------------------------------------------------------------------ the resumable encode
+class Recorder:
+    """An encoder whose C calls are recorded instead of made."""
+
+    def __init__(self, monkeypatch, frames_per_call=4):
+        self.calls = []
+        enc = sfa.WanVAEEncoder.__new__(sfa.WanVAEEncoder)
+        enc.device, enc.shape, enc.frames_per_call = torch.device("cpu"), vw.VAE_REDUCED, frames_per_call
+        enc._handle, enc.cmodel, enc._clip, enc._zeros = 0, sfa._lib.VaeEncoder(), None, {}
+        enc._enc_buffers = lambda H, W, K: (torch.zeros(8, dtype=torch.uint8), torch.zeros(8, dtype=torch.uint8))
+        monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: SimpleNamespace(cuda_stream=0))
+        lib = SimpleNamespace(sf_vae_encode_reset=lambda m, st, n, H, W, K, stream: self.calls.append(("reset", H, W, K)) or 0)
+        monkeypatch.setattr(vae_mod._lib, "lib", lambda: lib)
+
+        def frames(handle, state, scratch, pixels, out, H, W, K, chunk_index, window, history_at):
+            self.calls.append(("frames", pixels.shape[1], out.shape[0], K, chunk_index, window, history_at, bool((pixels == 0).all())))
+        monkeypatch.setattr(torch.ops.sf_hip, "vae_encode_frames", frames)
+        self.enc = enc
+
+
+def test_encode_makes_the_calls_it_made(monkeypatch):
+    """`encode` for a caller that never uses the resumable calls: one reset, the one-frame call, then groups of up to
+    frames_per_call chunks through the sliding windows -- the loop as it was."""
+    r = Recorder(monkeypatch)
+    x = torch.ones(3, 37, 64, 64)
+    assert tuple(r.enc.encode(x).shape) == (10, 16, 8, 8)
+    assert r.calls == [("reset", 64, 64, 5), ("frames", 1, 1, 5, 0, 0, 0, False), ("frames", 16, 4, 5, 1, 1, 1, False),
+                       ("frames", 16, 4, 5, 5, 0, 5, False), ("frames", 4, 1, 5, 9, 4, 4, False)]
+    r.calls.clear()
+    r.enc.encode(torch.ones(3, 7, 64, 64))                     # a short clip: fewer window slots, the trailing 2 frames dropped
+    assert r.calls == [("reset", 64, 64, 2), ("frames", 1, 1, 2, 0, 0, 0, False), ("frames", 4, 1, 2, 1, 1, 1, False)]
+    assert r.enc._zeros == {} and r.enc._clip is None          # nothing of the resumable path was touched
+
+
+def test_resumable_encode_carries_the_windows(monkeypatch):
+    r = Recorder(monkeypatch)
+    with pytest.raises(RuntimeError, match="no clip in progress"):
+        r.enc.continue_clip(1)
+    assert tuple(r.enc.begin_clip(torch.ones(3, 64, 64)).shape) == (1, 16, 8, 8)
+    assert tuple(r.enc.continue_clip(2).shape) == (2, 16, 8, 8)
+    out = torch.empty(7, 16, 8, 8)
+    assert r.enc.continue_clip(7, out=out) is out
+    # slot 0 | slots 1-2 | 4 chunks do not fit behind slot 3: the lap restarts, histories read at 3 | 3 more: again, histories at 4
+    assert r.calls == [("reset", 64, 64, 5), ("frames", 1, 1, 5, 0, 0, 0, False), ("frames", 8, 2, 5, 1, 1, 1, True),
+                       ("frames", 16, 4, 5, 3, 0, 3, True), ("frames", 12, 3, 5, 7, 0, 4, True)]
+    assert list(r.enc._zeros) == [(64, 64)] and tuple(r.enc._zeros[(64, 64)].shape) == (3, 16, 64, 64)   # 4 x frames_per_call frames, never the clip
+    r.enc.encode(torch.ones(3, 5, 64, 64))                     # a short clip: 2 window slots, histories of its own
+    r.enc.encode(torch.ones(3, 17, 32, 32))                    # ... and another size: neither touches the clip
+    assert tuple(r.enc.continue_clip(1).shape) == (1, 16, 8, 8) and r.calls[-1] == ("frames", 4, 1, 5, 10, 3, 3, True)
+    r.enc.encode(torch.ones(3, 17, 64, 64))                    # the same (H, W, K): the histories are reset, the clip ends
+    with pytest.raises(RuntimeError, match="no clip in progress"):
+        r.enc.continue_clip(1)
+    with pytest.raises(ValueError, match="multiples of 8"):
+        r.enc.begin_clip(torch.ones(3, 60, 64))
+    with pytest.raises(ValueError, match="out must be"):
+        r.enc.begin_clip(torch.ones(3, 64, 64), out=torch.empty(2, 16, 8, 8))
+
+
+def test_conditioner_checks_without_a_gpu():
+    from self_forcing_amd.i2v_condition import I2VConditioner, prepare_image
+    with pytest.raises(NotImplementedError, match="Wan VAE encoder"):
+        I2VConditioner(sfa.IdentityVAE(), object(), device="cpu")
+    with pytest.raises(ValueError, match="multiples of 8"):
+        prepare_image(torch.zeros(3, 60, 96), 60, 96)
+    with pytest.raises(ValueError, match=r"image must be \[1, 3, 64, 96\]"):
+        prepare_image(torch.zeros(3, 64, 64), 64, 96)
+    assert tuple(prepare_image(torch.zeros(1, 3, 64, 96), 64, 96).shape) == (3, 64, 96)
+    from PIL import Image
+    img = prepare_image(Image.new("RGB", (40, 30), (255, 0, 127)), 64, 96)
+    assert tuple(img.shape) == (3, 64, 96) and abs(float(img[0].max()) - 1.0) < 1e-6 and abs(float(img[1].min()) + 1.0) < 1e-6
+    cond = I2VConditioner(SimpleNamespace(encoder=SimpleNamespace(begin_clip=None)), object(), device="cpu")
+    with pytest.raises(RuntimeError, match="before begin"):
+        cond.frames(1)
+
+
+def test_generate_takes_image_and_pose_with_a_few_step_config(tmp_path):
+    """The CLI no longer refuses --input_image / --pose_path under a few-step config: it gets as far as reading its inputs."""
+    import subprocess
+    import sys
+    cfg = os.path.join(ROOT, "configs", "tiny_test_hotpath.yaml")
+    base = [sys.executable, os.path.join(ROOT, "generate.py"), "--config_path", cfg, "--data_path", "d", "--output_folder", str(tmp_path)]
+    r = subprocess.run(base + ["--pose_path", str(tmp_path / "missing.pt"), "--pose_random_init_seed", "0"], capture_output=True, text=True)
+    assert r.returncode != 0 and "no such file" in r.stderr and "needs a multi-step config" not in r.stderr
+    r = subprocess.run(base + ["--input_image", "x.png", "--clip_random_init_seed", "0"], capture_output=True, text=True)
+    assert r.returncode != 0 and "VAE with encoder weights" in r.stderr and "needs a multi-step config" not in r.stderr
