@@ -811,6 +811,25 @@ typedef struct sf_pose_conv_args {
 
 int sf_pose_conv(const sf_pose_conv_args* args, void* stream);
 
+/* The same convolution over a temporal WINDOW of a clip, for embedding a clip piece by piece.  args->x holds the
+ * clip-timeline frames [x_t0, x_t0 + args->T) of the layer's input (x_t0 may be negative: the frames in front of the
+ * clip are never read); the timeline's valid range is [0, t_end): frames < 0 are zero, frames >= t_end are zero when
+ * the clip is `closed` and must not be needed otherwise.  Output frames [t_out0, t_out0 + n_out) are computed (any
+ * start, either parity under temporal stride 2) and output frame t_out0 is written at args->out's start.  Every output
+ * element is formed from the same taps in the same order as in sf_pose_conv, so a window that holds a frame's true
+ * neighbours gives the whole-clip bits; the whole-volume call is the window (0, [0, T) closed, 0, Tout).  Refused: a
+ * window that does not hold every in-range input frame the outputs read (t*stride_t - 1 .. t*stride_t + 1), and a
+ * window or output of 4 GiB or more.  kt = 3 only: (Cin, stride_t, stride_s) in (8|16, 1, 1), (16, 1, 2), (16, 2, 2),
+ * Cout <= 16. */
+typedef struct sf_pose_window {
+  int32_t x_t0;           /* clip-timeline index of x's first frame                                               */
+  int32_t t_end;          /* the timeline's valid range is [0, t_end)                                             */
+  int32_t closed;         /* 1: the clip has ended, frames >= t_end are the zero padding; 0: they must not be read */
+  int32_t t_out0, n_out;  /* output frames [t_out0, t_out0 + n_out)                                               */
+} sf_pose_window;
+
+int sf_pose_conv_window(const sf_pose_conv_args* args, const sf_pose_window* window, void* stream);
+
 /* The input transform (causal_diffusion_inference.py:337-343): pose frames holding 0..255 as uint8 / float32 / bf16
  * (enum sf_pose_dtype), planar [3][F][H][W] (hwc = 0) or one image [H][W][3] (hwc = 1, F = 1), -> bf16
  * [lead + F][H][W][8]: `lead` copies of the first frame in front (3 for the clip, :339), value / 255 (the fp32 quotient
@@ -854,6 +873,37 @@ int sf_pose_embed(const sf_pose_model* model, const void* frames, int dtype, int
  * channels-last (the reference's [1, 20, 1, h, w] is a permuted view). */
 int sf_pose_embed_ref(const sf_pose_model* model, const void* image, int dtype, int H, int W, void* scratch,
                       size_t scratch_bytes, void* out, void* stream);
+
+/* The dwpose stack, resumable: a clip is pushed in pieces of any length and every latent frame comes out as soon as the
+ * pixel frames it depends on are in (latent frame j reads pixel frames 4j-10 .. 4j+4, so it is final once 4j+5 are
+ * known), with the bits sf_pose_embed gives for the whole clip.  The library keeps no state: `state` is a caller-owned
+ * device buffer holding the last two frames of each of the six layer inputs, and the position is `frames_before`.
+ *
+ * Level 0 is the prepared volume (three copies of frame 0, then the pixel frames), level i + 1 the output of
+ * convolution i.  With P pixel frames pushed and the clip open the levels' final frames are P+3, P+2, P+1, P, P-1,
+ * (P-1)/2, (P-1)/4 (all 0 for P = 0); once closed they are the full sizes sf_pose_out_size gives over P + 3 frames.
+ * sf_pose_stream_plan states what a push computes: level l gains frames [first[l], first[l] + count[l]), and convolution
+ * l reads them from a window of 2 + count[l] frames starting at first[l] - 2.  0 on success. */
+#define SF_POSE_LEVELS (SF_POSE_CONVS + 1)
+typedef struct sf_pose_push_plan {
+  int32_t first[SF_POSE_LEVELS], count[SF_POSE_LEVELS];
+} sf_pose_push_plan;
+int sf_pose_stream_plan(int frames_before, int n, int closing, sf_pose_push_plan* plan);
+
+/* Bytes of `state` for H x W frames (two frames per layer input); 0 = malformed arguments. */
+size_t sf_pose_stream_state_bytes(const sf_pose_model* model, int H, int W);
+/* Scratch of a push of up to n_max pixel frames, closing or not: independent of the clip's length.  0 = malformed
+ * arguments or a window of 4 GiB or more. */
+size_t sf_pose_stream_scratch_bytes(const sf_pose_model* model, int n_max, int H, int W);
+
+/* Push n >= 0 new pixel frames [3][n][H][W] (enum sf_pose_dtype) behind the `frames_before` already pushed; `closing`
+ * declares the clip ended after them (n = 0 then flushes the tail; a clip of no frames cannot be closed).  The rows of
+ * the latent frames this push makes final are written token-major at tokens_out ([frames*h*w][pose_dim] bf16, at most
+ * token_rows_capacity rows) and their number of frames at *latent_frames_written; a push that finalises nothing writes
+ * 0 frames.  state: 256-byte aligned, untouched contents on the first push (frames_before = 0). */
+int sf_pose_stream_push(const sf_pose_model* model, void* state, int frames_before, const void* frames, int dtype, int n,
+                        int H, int W, int closing, void* scratch, size_t scratch_bytes, void* tokens_out,
+                        int64_t token_rows_capacity, int32_t* latent_frames_written, void* stream);
 
 /* ==========================================================================================
  * umT5 text encoder (prompt token ids -> prompt embeddings): WanTextEncoder.forward after its tokenizer

@@ -220,6 +220,14 @@ class PoseConvArgs(C.Structure):
                 + [(n, C.c_int32) for n in ("T", "H", "W", "Cin", "Cout", "kt", "stride_t", "stride_s", "ldw", "ldo", "silu")])
 
 
+class PoseWindow(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("x_t0", "t_end", "closed", "t_out0", "n_out")]
+
+
+class PosePushPlan(C.Structure):
+    _fields_ = [("first", C.c_int32 * (POSE_CONVS + 1)), ("count", C.c_int32 * (POSE_CONVS + 1))]
+
+
 class PoseLayer(C.Structure):
     _fields_ = [("w", C.c_void_p), ("bias", C.c_void_p)] + [(n, C.c_int32) for n in ("cin", "cout", "kt", "stride_t", "stride_s", "ldw", "silu")]
 
@@ -318,11 +326,16 @@ SIGNATURES = {
     "sf_taehv_encode_frames": (C.c_int, [C.POINTER(TaehvEncoder), _vp, _sz, _vp, _sz, _vp, _i, _i64, _i, _i, _i, _i, _vp, _vp]),
     "sf_pose_out_size": (C.c_int, [_i, _i, _i]),
     "sf_pose_conv": (C.c_int, [C.POINTER(PoseConvArgs), _vp]),
+    "sf_pose_conv_window": (C.c_int, [C.POINTER(PoseConvArgs), C.POINTER(PoseWindow), _vp]),
     "sf_pose_prepare": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sf_pose_patch_embed": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "sf_pose_scratch_bytes": (C.c_size_t, [C.POINTER(PoseModel), _i, _i, _i]),
     "sf_pose_embed": (C.c_int, [C.POINTER(PoseModel), _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i64, _vp]),
     "sf_pose_embed_ref": (C.c_int, [C.POINTER(PoseModel), _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "sf_pose_stream_plan": (C.c_int, [_i, _i, _i, C.POINTER(PosePushPlan)]),
+    "sf_pose_stream_state_bytes": (C.c_size_t, [C.POINTER(PoseModel), _i, _i]),
+    "sf_pose_stream_scratch_bytes": (C.c_size_t, [C.POINTER(PoseModel), _i, _i, _i]),
+    "sf_pose_stream_push": (C.c_int, [C.POINTER(PoseModel), _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i64, C.POINTER(C.c_int32), _vp]),
     "sf_jpeg_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "sf_jpeg_transform": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sf_jpeg_entropy": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),

@@ -19,6 +19,9 @@
 //     once per workgroup; workgroups are persistent and walk a contiguous run of bricks (w fastest), so the halo shared
 //     by consecutive bricks is still in the L2 of the XCD that read it.
 //   * fp32 accumulation, fp32 bias, SiLU in fp32, one rounding to bf16; 16 lanes x 4 quarters write 512 contiguous bytes.
+// The 3x3x3 layers also run over a temporal WINDOW of a clip (sf_pose_conv_window): x holds a range of the clip's frames,
+// the brick walk starts at any output frame, and every output element is formed from the same taps in the same k order
+// as in the whole-volume call, so a clip embedded piece by piece has the whole clip's bits.
 #include "sf_common.h"
 #include "../../include/sf_hip.h"
 
@@ -57,10 +60,15 @@ struct Geo {
   static_assert((TT * TH) % 4 == 0 && MT % MU == 0, "row tiles divide among the four waves");
 };
 
-template <int CIN, int KT, int ST, int SS, int NB>
-__global__ __launch_bounds__(PTHREADS) void pose_conv_kernel(PConvP p) {
+// The temporal window of sf_pose_conv_window: x holds the clip-timeline frames [x_t0, x_t0 + T); a tap is loaded when its
+// frame lies in [t_lo, t_hi) (the window clipped to the timeline's valid range) and is a literal zero otherwise; the
+// brick walk along t starts at output frame t_out0, which is written at out's start, and p.To counts the frames written.
+struct PWin { int x_t0, t_lo, t_hi, t_out0; };
+
+// WIN = false is the whole-volume kernel: x is the timeline [0, T), the walk starts at output frame 0.
+template <int CIN, int KT, int ST, int SS, int NB, bool WIN>
+__device__ __forceinline__ void pose_conv_body(const PConvP& p, const PWin& pw, char* brick) {
   using G = Geo<CIN, KT, ST, SS>;
-  __shared__ __attribute__((aligned(16))) char brick[G::LDS_BYTES];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -100,7 +108,7 @@ __global__ __launch_bounds__(PTHREADS) void pose_conv_kernel(PConvP p) {
   for (int tile = lid * p.per; tile < tile_end; ++tile) {
     const int tw_i = tile % p.ntw, r0 = tile / p.ntw;
     const int th_i = r0 % p.nth, tt_i = r0 / p.nth;
-    const int t0 = tt_i * G::TT, h0 = th_i * G::TH, w0 = tw_i * TW;
+    const int t0 = (WIN ? pw.t_out0 : 0) + tt_i * G::TT, h0 = th_i * G::TH, w0 = tw_i * TW;
     const int ti0 = t0 * ST - G::PT, hi0 = h0 * SS - 1, wi0 = w0 * SS - 1;
 
     // ---- stage the input brick (zeros outside the volume), four 16-byte pieces per thread in flight
@@ -114,8 +122,10 @@ __global__ __launch_bounds__(PTHREADS) void pose_conv_kernel(PConvP p) {
         const int bh = r % G::BH, bt = r / G::BH;
         const int ti = ti0 + bt, hi = hi0 + bh, wi = wi0 + bw;
         v[j] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        if (i < G::NPIECE && (unsigned)ti < (unsigned)p.T && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W) {
-          const unsigned off = ((unsigned)((ti * p.H + hi) * p.W + wi) * G::PPV + hf) * 16u;   // < 4 GiB: checked by the host
+        const bool t_in = WIN ? (ti >= pw.t_lo && ti < pw.t_hi) : ((unsigned)ti < (unsigned)p.T);
+        const int tx = WIN ? ti - pw.x_t0 : ti;          // the frame's place in x
+        if (i < G::NPIECE && t_in && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W) {
+          const unsigned off = ((unsigned)((tx * p.H + hi) * p.W + wi) * G::PPV + hf) * 16u;   // < 4 GiB: checked by the host
           v[j] = *reinterpret_cast<const bf16x8*>(p.x + off);
         }
       }
@@ -154,7 +164,7 @@ __global__ __launch_bounds__(PTHREADS) void pose_conv_kernel(PConvP p) {
       for (int u = 0; u < G::MU; ++u) {
         const int row = wave * G::MT + mt + u;
         const int tt = row / G::TH, th = row - tt * G::TH;
-        const int t = t0 + tt, h = h0 + th, w = w0 + m16;
+        const int t = t0 + tt - (WIN ? pw.t_out0 : 0), h = h0 + th, w = w0 + m16;   // t: the frame's place in out
         if (t >= p.To || h >= p.Ho || w >= p.Wo) continue;
         const unsigned obase = (unsigned)((t * p.Ho + h) * p.Wo + w) * (unsigned)(p.ldo * 2);
 #pragma unroll
@@ -177,7 +187,19 @@ __global__ __launch_bounds__(PTHREADS) void pose_conv_kernel(PConvP p) {
 }
 
 template <int CIN, int KT, int ST, int SS, int NB>
-int launch(PConvP& p, hipStream_t s) {
+__global__ __launch_bounds__(PTHREADS) void pose_conv_kernel(PConvP p) {
+  __shared__ __attribute__((aligned(16))) char brick[Geo<CIN, KT, ST, SS>::LDS_BYTES];
+  pose_conv_body<CIN, KT, ST, SS, NB, false>(p, PWin{0, 0, 0, 0}, brick);
+}
+
+template <int CIN, int KT, int ST, int SS, int NB>
+__global__ __launch_bounds__(PTHREADS) void pose_conv_window_kernel(PConvP p, PWin pw) {
+  __shared__ __attribute__((aligned(16))) char brick[Geo<CIN, KT, ST, SS>::LDS_BYTES];
+  pose_conv_body<CIN, KT, ST, SS, NB, true>(p, pw, brick);
+}
+
+template <int CIN, int KT, int ST, int SS, int NB>
+int launch(PConvP& p, hipStream_t s, const PWin* pw = nullptr) {
   using G = Geo<CIN, KT, ST, SS>;
   p.ntw = (p.Wo + TW - 1) / TW;
   p.nth = (p.Ho + G::TH - 1) / G::TH;
@@ -188,6 +210,12 @@ int launch(PConvP& p, hipStream_t s) {
   if (nwg >= 8) nwg &= ~7;
   p.per = (p.ntiles + nwg - 1) / nwg;
   nwg = (p.ntiles + p.per - 1) / p.per;                  // no idle workgroups; the XCD remap needs nwg % 8 == 0 and is skipped otherwise
+  if constexpr (KT == 3) {      // the window mode exists for the dwpose stack's layers only
+    if (pw) {
+      hipLaunchKernelGGL((pose_conv_window_kernel<CIN, KT, ST, SS, NB>), dim3(nwg), dim3(PTHREADS), 0, s, p, *pw);
+      return 0;
+    }
+  }
   hipLaunchKernelGGL((pose_conv_kernel<CIN, KT, ST, SS, NB>), dim3(nwg), dim3(PTHREADS), 0, s, p);
   return 0;
 }
@@ -218,32 +246,50 @@ extern "C" int sf_pose_out_size(int n, int kernel, int stride) {
   return kernel == 3 ? (n - 1) / stride + 1 : n >= kernel ? (n - kernel) / stride + 1 : 0;
 }
 
-extern "C" int sf_pose_conv(const sf_pose_conv_args* a, void* stream) {
-  SF_CHECK(a != nullptr, "sf_pose_conv: null args");
-  SF_CHECK(a->x && a->w && a->bias && a->out, "sf_pose_conv: null tensor");
-  SF_CHECK(a->T > 0 && a->H > 0 && a->W > 0, "sf_pose_conv: empty volume %dx%dx%d", a->T, a->H, a->W);
-  SF_CHECK(a->Cin == 8 || a->Cin == 16, "sf_pose_conv: Cin=%d (8 = three channels stored padded, or 16)", a->Cin);
-  SF_CHECK(a->kt == 1 || a->kt == 3, "sf_pose_conv: kt must be 1 or 3, got %d", a->kt);
-  SF_CHECK((a->stride_t == 1 || a->stride_t == 2) && (a->stride_s == 1 || a->stride_s == 2), "sf_pose_conv: strides must be 1 or 2, got t=%d s=%d",
+namespace {
+
+// The argument checks both entry points share, and the kernel parameters of the whole-volume call.
+int conv_setup(const sf_pose_conv_args* a, const char* who, PConvP& p, int& nb) {
+  SF_CHECK(a != nullptr, "%s: null args", who);
+  SF_CHECK(a->x && a->w && a->bias && a->out, "%s: null tensor", who);
+  SF_CHECK(a->T > 0 && a->H > 0 && a->W > 0, "%s: empty volume %dx%dx%d", who, a->T, a->H, a->W);
+  SF_CHECK(a->Cin == 8 || a->Cin == 16, "%s: Cin=%d (8 = three channels stored padded, or 16)", who, a->Cin);
+  SF_CHECK(a->kt == 1 || a->kt == 3, "%s: kt must be 1 or 3, got %d", who, a->kt);
+  SF_CHECK((a->stride_t == 1 || a->stride_t == 2) && (a->stride_s == 1 || a->stride_s == 2), "%s: strides must be 1 or 2, got t=%d s=%d", who,
            a->stride_t, a->stride_s);
-  SF_CHECK(a->kt == 3 || a->stride_t == 1, "sf_pose_conv: kt = 1 goes with temporal stride 1");
-  SF_CHECK(a->Cout > 0 && a->Cout <= 32 && a->Cout % 4 == 0, "sf_pose_conv: Cout=%d (a multiple of 4, at most 32)", a->Cout);
-  const int nb = a->Cout <= 16 ? 1 : 2;
+  SF_CHECK(a->kt == 3 || a->stride_t == 1, "%s: kt = 1 goes with temporal stride 1", who);
+  SF_CHECK(a->Cout > 0 && a->Cout <= 32 && a->Cout % 4 == 0, "%s: Cout=%d (a multiple of 4, at most 32)", who, a->Cout);
+  nb = a->Cout <= 16 ? 1 : 2;
   const int tps = 32 / a->Cin, nk = (a->kt * 9 + tps - 1) / tps;
-  SF_CHECK(a->ldw >= nk * 32 && a->ldw % 8 == 0, "sf_pose_conv: weight row stride %d < padded K %d", a->ldw, nk * 32);
-  SF_CHECK(a->ldo >= a->Cout && a->ldo % 4 == 0, "sf_pose_conv: ldo=%d too small for %d channels or not a multiple of 4", a->ldo, a->Cout);
+  SF_CHECK(a->ldw >= nk * 32 && a->ldw % 8 == 0, "%s: weight row stride %d < padded K %d", who, a->ldw, nk * 32);
+  SF_CHECK(a->ldo >= a->Cout && a->ldo % 4 == 0, "%s: ldo=%d too small for %d channels or not a multiple of 4", who, a->ldo, a->Cout);
   SF_CHECK(((uintptr_t)a->x % 16 == 0) && ((uintptr_t)a->w % 16 == 0) && ((uintptr_t)a->bias % 16 == 0) && ((uintptr_t)a->out % 8 == 0),
-           "sf_pose_conv: misaligned tensor");
-  PConvP p;
+           "%s: misaligned tensor", who);
   p.x = (const char*)a->x; p.w = (const bf16_t*)a->w; p.bias = a->bias; p.out = (char*)a->out;
   p.T = a->T; p.H = a->H; p.W = a->W;
   p.To = a->kt == 3 ? sf_pose_out_size(a->T, 3, a->stride_t) : a->T;
   p.Ho = sf_pose_out_size(a->H, 3, a->stride_s);
   p.Wo = sf_pose_out_size(a->W, 3, a->stride_s);
   p.Cout = a->Cout; p.ldw = a->ldw; p.ldo = a->ldo; p.silu = a->silu ? 1 : 0;
-  const long xb = (long)a->T * a->H * a->W * a->Cin * 2, ob = (long)p.To * p.Ho * p.Wo * a->ldo * 2;
-  SF_CHECK(xb < 0xFFFFFF00L, "sf_pose_conv: input volume of %ld bytes exceeds the 4 GiB the kernel's 32-bit offsets cover", xb);
-  SF_CHECK(ob < 0xFFFFFF00L, "sf_pose_conv: output volume of %ld bytes exceeds the 4 GiB the kernel's 32-bit offsets cover", ob);
+  return 0;
+}
+
+// x holds p.T frames and out p.To frames: both under the 4 GiB of the kernel's 32-bit offsets
+int check_4g(const sf_pose_conv_args* a, const PConvP& p, const char* who) {
+  const long xb = (long)p.T * a->H * a->W * a->Cin * 2, ob = (long)p.To * p.Ho * p.Wo * a->ldo * 2;
+  SF_CHECK(xb < 0xFFFFFF00L, "%s: input volume of %ld bytes exceeds the 4 GiB the kernel's 32-bit offsets cover", who, xb);
+  SF_CHECK(ob < 0xFFFFFF00L, "%s: output volume of %ld bytes exceeds the 4 GiB the kernel's 32-bit offsets cover", who, ob);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int sf_pose_conv(const sf_pose_conv_args* a, void* stream) {
+  const char* who = "sf_pose_conv";
+  PConvP p;
+  int nb = 0;
+  if (const int rc = conv_setup(a, who, p, nb)) return rc;
+  if (const int rc = check_4g(a, p, who)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int key = (a->Cin == 16) * 1000 + a->kt * 100 + a->stride_t * 10 + a->stride_s;
   int rc = -1;
@@ -264,6 +310,56 @@ extern "C" int sf_pose_conv(const sf_pose_conv_args* a, void* stream) {
   SF_CHECK(rc == 0, "sf_pose_conv: no kernel for Cin=%d kt=%d stride (%d, %d) Cout=%d (the pose stacks do not use it)", a->Cin, a->kt, a->stride_t,
            a->stride_s, a->Cout);
   SF_HIP_LAUNCH_CHECK("sf_pose_conv");
+  return 0;
+}
+
+extern "C" int sf_pose_conv_window(const sf_pose_conv_args* a, const sf_pose_window* win, void* stream) {
+  const char* who = "sf_pose_conv_window";
+  PConvP p;
+  int nb = 0;
+  if (const int rc = conv_setup(a, who, p, nb)) return rc;
+  SF_CHECK(win != nullptr, "%s: null window", who);
+  const int st = a->stride_t;
+  const int key = (a->Cin == 16) * 1000 + a->kt * 100 + st * 10 + a->stride_s;
+  SF_CHECK(nb == 1 && (key == 311 || key == 1311 || key == 1312 || key == 1322),
+           "%s: no kernel for Cin=%d kt=%d stride (%d, %d) Cout=%d (the window mode serves the dwpose stack's 3x3x3 layers)", who, a->Cin, a->kt, st,
+           a->stride_s, a->Cout);
+  const int lim = 1 << 28;
+  SF_CHECK(win->t_end > 0 && win->t_end <= lim && win->x_t0 > -lim && win->x_t0 < lim && win->t_out0 >= 0 && win->t_out0 < lim && win->n_out > 0 &&
+               win->n_out < lim,
+           "%s: malformed window (x_t0=%d, timeline [0, %d), outputs %d + %d)", who, win->x_t0, win->t_end, win->t_out0, win->n_out);
+  const int o_lo = win->t_out0, o_hi = win->t_out0 + win->n_out;        // output frames [o_lo, o_hi)
+  // the in-range input frames they read: t*st - 1 .. t*st + 1, clipped to the timeline
+  const int need_lo = o_lo * st - 1 < 0 ? 0 : o_lo * st - 1;
+  int need_hi = (o_hi - 1) * st + 2;                                    // exclusive
+  if (win->closed) {
+    SF_CHECK(o_hi <= sf_pose_out_size(win->t_end, 3, st), "%s: output frames [%d, %d) of a closed timeline of %d frames, which gives %d", who, o_lo,
+             o_hi, win->t_end, sf_pose_out_size(win->t_end, 3, st));
+    if (need_hi > win->t_end) need_hi = win->t_end;                     // frames behind a closed clip are the zero padding
+  } else {
+    SF_CHECK(need_hi <= win->t_end, "%s: output frames [%d, %d) read input frame %d, but the open timeline ends at %d", who, o_lo, o_hi, need_hi - 1,
+             win->t_end);
+  }
+  SF_CHECK(win->x_t0 <= need_lo && need_hi <= win->x_t0 + a->T,
+           "%s: the window holds input frames [%d, %d), output frames [%d, %d) read [%d, %d)", who, win->x_t0, win->x_t0 + a->T, o_lo, o_hi, need_lo,
+           need_hi);
+  p.To = win->n_out;
+  if (const int rc = check_4g(a, p, who)) return rc;
+  PWin pw;
+  pw.x_t0 = win->x_t0;
+  pw.t_lo = win->x_t0 < 0 ? 0 : win->x_t0;
+  pw.t_hi = win->x_t0 + a->T < win->t_end ? win->x_t0 + a->T : win->t_end;
+  pw.t_out0 = win->t_out0;
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  switch (key) {
+    case 311: rc = launch<8, 3, 1, 1, 1>(p, s, &pw); break;
+    case 1311: rc = launch<16, 3, 1, 1, 1>(p, s, &pw); break;
+    case 1312: rc = launch<16, 3, 1, 2, 1>(p, s, &pw); break;
+    default: rc = launch<16, 3, 2, 2, 1>(p, s, &pw); break;
+  }
+  if (rc != 0) return rc;
+  SF_HIP_LAUNCH_CHECK(who);
   return 0;
 }
 

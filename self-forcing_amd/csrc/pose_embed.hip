@@ -7,7 +7,9 @@
 //     patch into a row of [F'*h*w][64], then sf_gemm_bf16 with the bias epilogue -> tokens [F'*h*w][5120], token-major
 //
 // and the reference-pose stack is six sf_pose_conv with kt = 1 on one image.  Everything lives in scratch; the library
-// keeps no state.
+// keeps no state.  The same dwpose stack also runs piece by piece (sf_pose_stream_push, at the end of this file): every
+// layer over a temporal window of its input (sf_pose_conv_window), two frames of history per layer input in a buffer
+// the caller owns, the bits of the whole clip.
 #include "sf_host.h"
 
 namespace {
@@ -182,4 +184,177 @@ extern "C" int sf_pose_embed_ref(const sf_pose_model* model, const void* image, 
   SF_CHECK(scratch_bytes >= b.bytes, "%s: scratch of %zu bytes, %zu needed", who, scratch_bytes, b.bytes);
   SF_TRY(sf_pose_prepare(image, dtype, 1, 1, H, W, 0, b.in, stream));
   return run_stack(model->ref_conv, v, b, out, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ the resumable stack
+// A clip pushed piece by piece.  Level 0 is the prepared volume, level i + 1 the output of convolution i; the temporal
+// strides are the dwpose stack's (1, 1, 1, 1, 2, 2).  A layer's output frame t reads input frames t*st - 1 .. t*st + 1, so
+// with N final input frames of an open clip a stride-1 layer has N - 1 final output frames and a stride-2 layer N / 2;
+// once the clip is closed every level is complete.  A push computes, level by level, the frames between the old and the
+// new frontier; the lowest input frame they read is never more than two behind the input's old frontier, so two frames
+// of history per layer input (the caller's `state`) carry everything, and a window of 2 + new frames holds every tap.
+namespace {
+
+constexpr int POSE_STREAM_ST[SF_POSE_CONVS] = {1, 1, 1, 1, 2, 2};
+constexpr int STREAM_MAX_FRAMES = 1 << 28;
+
+// final frames of every level with P pixel frames known
+void stream_frontier(int P, bool closed, int (&f)[SF_POSE_LEVELS]) {
+  f[0] = P > 0 ? P + 3 : 0;
+  for (int i = 0; i < SF_POSE_CONVS; ++i) {
+    const int n = f[i], st = POSE_STREAM_ST[i];
+    f[i + 1] = n <= 0 ? 0 : closed ? sf_pose_out_size(n, 3, st) : st == 1 ? n - 1 : n / 2;
+  }
+}
+
+// the most frames level l gains in one push of n pixel frames, first, middle or closing (the host test walks it)
+inline int stream_cap(int l, int n) { return l <= 4 ? n + 4 : l == 5 ? (n + 3) / 2 + 2 : (n + 3) / 4 + 2; }
+
+struct StreamGeo {
+  Vol v[SF_POSE_LEVELS];          // T = 1: one frame of each level
+  size_t frame[SF_POSE_LEVELS];   // its bytes
+  int h, w;                       // tokens per latent frame: h x w
+};
+
+int stream_geo(const sf_pose_model* m, int H, int W, StreamGeo& g, const char* who) {
+  SF_TRY(check_model(m, 1, H, W, who));
+  for (int i = 0; i < SF_POSE_CONVS; ++i)
+    SF_CHECK(m->conv[i].stride_t == POSE_STREAM_ST[i], "%s: dwpose layer %d has temporal stride %d, the streamed stack expects %d", who, i,
+             m->conv[i].stride_t, POSE_STREAM_ST[i]);
+  SF_TRY(plan(m->conv, 1, H, W, g.v, 16, who));
+  for (int l = 0; l < SF_POSE_LEVELS; ++l) g.frame[l] = vbytes(g.v[l]);
+  g.h = sf_pose_out_size(g.v[SF_POSE_CONVS].H, 2, 2);
+  g.w = sf_pose_out_size(g.v[SF_POSE_CONVS].W, 2, 2);
+  SF_CHECK(g.h > 0 && g.w > 0, "%s: frames of %dx%d give no tokens", who, H, W);
+  return 0;
+}
+
+struct StreamBufs { char *in, *a, *b, *rows; size_t bytes; };
+
+// windows of 2 + cap frames: level 0 in `in`, odd levels in a, even levels in b (a level's window is dead once the next
+// level's frames are computed and its last two frames are saved); rows: the gathered rows of the token embedding
+int stream_carve(void* scratch, const StreamGeo& g, int n, StreamBufs& r, const char* who) {
+  size_t sa = 0, sb = 0;
+  for (int l = 0; l < SF_POSE_LEVELS; ++l) {
+    const long b = (long)(2 + stream_cap(l, n)) * (long)g.frame[l];
+    SF_CHECK(b < VOL_LIMIT, "%s: a window of %d frames of %dx%d with %d channels is %ld bytes, beyond the 4 GiB the convolution's 32-bit offsets cover; "
+             "push fewer frames at a time", who, 2 + stream_cap(l, n), g.v[l].H, g.v[l].W, g.v[l].C, b);
+    if (l == 0) continue;
+    size_t& s = (l & 1) ? sa : sb;
+    if ((size_t)b > s) s = (size_t)b;
+  }
+  Carve c(scratch);
+  r.in = c.take((size_t)(2 + stream_cap(0, n)) * g.frame[0]);
+  r.a = c.take(sa);
+  r.b = c.take(sb);
+  r.rows = c.take((size_t)stream_cap(SF_POSE_CONVS, n) * g.h * g.w * 64 * 2);
+  r.bytes = c.off;
+  return 0;
+}
+
+inline char* state_of(void* state, const StreamGeo& g, int l) {
+  Carve c(state);
+  char* r = nullptr;
+  for (int i = 0; i <= l; ++i) r = c.take(2 * g.frame[i]);
+  return r;
+}
+
+inline int copy2(char* dst, const char* src, size_t frame_bytes, void* stream) {
+  return sf_hip_ok(hipMemcpyAsync(dst, src, 2 * frame_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream), "sf_pose_stream_push", "history copy");
+}
+
+}  // namespace
+
+extern "C" int sf_pose_stream_plan(int frames_before, int n, int closing, sf_pose_push_plan* out) {
+  const char* who = "sf_pose_stream_plan";
+  SF_CHECK(out != nullptr, "%s: null plan", who);
+  SF_CHECK(frames_before >= 0 && n >= 0 && frames_before <= STREAM_MAX_FRAMES && n <= STREAM_MAX_FRAMES, "%s: frames_before=%d n=%d", who, frames_before, n);
+  SF_CHECK(!closing || frames_before + n > 0, "%s: closing a clip of no frames (frames_before=%d, n=%d)", who, frames_before, n);
+  int f0[SF_POSE_LEVELS], f1[SF_POSE_LEVELS];
+  stream_frontier(frames_before, false, f0);
+  stream_frontier(frames_before + n, closing != 0, f1);
+  for (int l = 0; l < SF_POSE_LEVELS; ++l) {
+    out->first[l] = f0[l];
+    out->count[l] = f1[l] - f0[l];
+  }
+  return 0;
+}
+
+extern "C" size_t sf_pose_stream_state_bytes(const sf_pose_model* model, int H, int W) {
+  StreamGeo g;
+  if (stream_geo(model, H, W, g, "sf_pose_stream_state_bytes") != 0) return 0;
+  Carve c(nullptr);
+  for (int l = 0; l < SF_POSE_CONVS; ++l) c.take(2 * g.frame[l]);
+  return c.off;
+}
+
+extern "C" size_t sf_pose_stream_scratch_bytes(const sf_pose_model* model, int n_max, int H, int W) {
+  const char* who = "sf_pose_stream_scratch_bytes";
+  StreamGeo g;
+  if (stream_geo(model, H, W, g, who) != 0) return 0;
+  if (n_max < 0 || n_max > (1 << 20)) {
+    sf_set_error("%s: n_max=%d", who, n_max);
+    return 0;
+  }
+  StreamBufs b;
+  if (stream_carve(nullptr, g, n_max, b, who) != 0) return 0;
+  return b.bytes;
+}
+
+extern "C" int sf_pose_stream_push(const sf_pose_model* model, void* state, int frames_before, const void* frames, int dtype, int n, int H, int W,
+                                   int closing, void* scratch, size_t scratch_bytes, void* tokens_out, int64_t token_rows_capacity,
+                                   int32_t* latent_frames_written, void* stream) {
+  const char* who = "sf_pose_stream_push";
+  StreamGeo g;
+  SF_TRY(stream_geo(model, H, W, g, who));
+  SF_CHECK(state && scratch && latent_frames_written, "%s: null buffer", who);
+  SF_CHECK(n >= 0 && n <= (1 << 20) && (n == 0 || frames != nullptr), "%s: n=%d frames%s", who, n, frames ? "" : " in a null buffer");
+  SF_CHECK(dtype >= SF_POSE_U8 && dtype <= SF_POSE_BF16, "%s: unknown dtype %d", who, dtype);
+  SF_CHECK((uintptr_t)state % 256 == 0 && (uintptr_t)scratch % 256 == 0, "%s: state and scratch must be 256-byte aligned", who);
+  sf_pose_push_plan pl;
+  SF_CHECK(sf_pose_stream_plan(frames_before, n, closing, &pl) == 0, "%s: frames_before=%d n=%d closing=%d: a clip of no frames cannot be closed, and counts are not negative",
+           who, frames_before, n, closing);
+  StreamBufs b;
+  SF_TRY(stream_carve(scratch, g, n, b, who));
+  SF_CHECK(scratch_bytes >= b.bytes, "%s: scratch of %zu bytes, %zu needed for a push of %d frames", who, scratch_bytes, b.bytes, n);
+  for (int l = 0; l < SF_POSE_LEVELS; ++l)
+    SF_CHECK(pl.count[l] >= 0 && pl.count[l] <= stream_cap(l, n), "%s: level %d gains %d frames, its window is planned for %d", who, l, pl.count[l],
+             stream_cap(l, n));
+  const int m = pl.count[SF_POSE_CONVS];
+  const long rows = (long)m * g.h * g.w;
+  SF_CHECK(token_rows_capacity >= rows, "%s: tokens_out holds %ld rows, this push writes %d x %d x %d = %ld", who, (long)token_rows_capacity, m, g.h, g.w, rows);
+  SF_CHECK(m == 0 || (tokens_out && (uintptr_t)tokens_out % 16 == 0), "%s: tokens_out must be a 16-byte aligned buffer", who);
+  *latent_frames_written = 0;
+  if (n == 0 && !closing) return 0;
+
+  char* win[SF_POSE_LEVELS];
+  for (int l = 0; l < SF_POSE_LEVELS; ++l) win[l] = l == 0 ? b.in : (l & 1) ? b.a : b.b;
+  // level 0: history, then the new frames prepared behind it
+  if (frames_before > 0) SF_TRY(copy2(win[0], state_of(state, g, 0), g.frame[0], stream));
+  if (n > 0) SF_TRY(sf_pose_prepare(frames, dtype, 0, n, H, W, frames_before == 0 ? 3 : 0, win[0] + 2 * g.frame[0], stream));
+  if (!closing) SF_TRY(copy2(state_of(state, g, 0), win[0] + (size_t)pl.count[0] * g.frame[0], g.frame[0], stream));
+  for (int i = 0; i < SF_POSE_CONVS; ++i) {
+    const int l = i + 1;
+    const bool keeps = l < SF_POSE_CONVS;      // the last level feeds the token embedding, not a convolution
+    if (keeps && frames_before > 0) SF_TRY(copy2(win[l], state_of(state, g, l), g.frame[l], stream));
+    if (pl.count[l] > 0) {
+      const sf_pose_layer& L = model->conv[i];
+      sf_pose_conv_args a;
+      memset(&a, 0, sizeof(a));
+      a.x = win[i]; a.w = L.w; a.bias = L.bias; a.out = win[l] + (keeps ? 2 * g.frame[l] : 0);
+      a.T = 2 + pl.count[i]; a.H = g.v[i].H; a.W = g.v[i].W; a.Cin = L.cin; a.Cout = L.cout;
+      a.kt = 3; a.stride_t = L.stride_t; a.stride_s = L.stride_s; a.ldw = L.ldw; a.ldo = 16; a.silu = L.silu;
+      sf_pose_window w;
+      w.x_t0 = pl.first[i] - 2; w.t_end = pl.first[i] + pl.count[i]; w.closed = closing ? 1 : 0;
+      w.t_out0 = pl.first[l]; w.n_out = pl.count[l];
+      SF_TRY(sf_pose_conv_window(&a, &w, stream));
+    }
+    if (keeps && !closing) SF_TRY(copy2(state_of(state, g, l), win[l] + (size_t)pl.count[l] * g.frame[l], g.frame[l], stream));
+  }
+  if (m > 0) {
+    const Vol& v = g.v[SF_POSE_CONVS];
+    SF_TRY(sf_pose_patch_embed(win[SF_POSE_CONVS], m, v.H, v.W, model->embed_w, model->embed_b, model->pose_dim, b.rows, tokens_out, stream));
+  }
+  *latent_frames_written = m;
+  return 0;
 }

@@ -416,6 +416,29 @@ def pose_conv(x: Tensor, w_packed: Tensor, bias: Tensor, cout: int, kt: int = 3,
     return out
 
 
+def pose_conv_window(x: Tensor, w_packed: Tensor, bias: Tensor, cout: int, x_t0: int, t_end: int, closed: bool, t_out0: int, n_out: int,
+                     stride_t: int = 1, stride_s: int = 1, silu: bool = True) -> Tensor:
+    """A 3x3x3 convolution of the dwpose stack over a temporal window (sf_pose_conv_window).  x [T, H, W, Cin] holds the
+    clip-timeline frames [x_t0, x_t0 + T) of a timeline valid on [0, t_end) (`closed`: zero padding behind it).  Returns
+    output frames [t_out0, t_out0 + n_out) as bf16 [n_out, Hout, Wout, cout]: the bits `pose_conv` gives for them on
+    the whole clip."""
+    _bf16(x, "x"), _bf16(w_packed, "w_packed")
+    if not bias.is_cuda or bias.dtype != torch.float32 or bias.numel() != w_packed.shape[0]:
+        raise ValueError("pose_conv_window: bias must be a CUDA float32 tensor padded like the weight rows")
+    if x.dim() != 4 or not x.is_contiguous() or not w_packed.is_contiguous():
+        raise ValueError("pose_conv_window: x must be a contiguous [T, H, W, C] volume")
+    T, H, W, c = x.shape
+    size = lib().sf_pose_out_size
+    out = torch.empty(max(n_out, 0), size(H, 3, stride_s), size(W, 3, stride_s), cout, dtype=torch.bfloat16, device=x.device)
+    a = _lib.PoseConvArgs()
+    a.x, a.w, a.bias, a.out = x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr()
+    a.T, a.H, a.W, a.Cin, a.Cout, a.kt, a.stride_t, a.stride_s = T, H, W, c, cout, 3, stride_t, stride_s
+    a.ldw, a.ldo, a.silu = w_packed.stride(0), cout, int(silu)
+    win = _lib.PoseWindow(x_t0, t_end, int(closed), t_out0, n_out)
+    check(lib().sf_pose_conv_window(a, win, stream_handle()), "sf_pose_conv_window")
+    return out
+
+
 def pose_patch_embed(x: Tensor, w_packed: Tensor, bias: Tensor) -> Tensor:
     """The dwpose stack's last layer (sf_pose_patch_embed).  x [T, H, W, 16] channels-last; w_packed [N, 64] from
     `pose_weights.repack_pose_embed`, bias [N], both bf16.  Returns the tokens bf16 [T * (H//2) * (W//2), N]."""

@@ -134,11 +134,14 @@ class CausalInferencePipeline(torch.nn.Module):
             self.conditioner = I2VConditioner(self.vae, self._image_encoder(), device=self.device_)
         return self.conditioner
 
-    def _conditioning(self, batch_size, num_output_frames, height, width, input_image, dwpose_data, random_ref_dwpose, dwpose_data_emb):
+    def _conditioning(self, batch_size, num_output_frames, height, width, input_image, dwpose_data, random_ref_dwpose, dwpose_data_emb,
+                      pose_feed=None):
         """The clip's conditioning beyond the prompt: (entries of the condition dict that hold for the whole clip,
         chunk_condition(first_frame, n, warm_up=False) -> the entries of the pass(es) over those latent frames), or
         (None, None) when there is none.  All checks come first, before any work; the image is encoded by CLIP and the
-        pose clip embedded here, once; `y` is produced by `chunk_condition`, in timeline order, one request per chunk."""
+        pose clip embedded here, once; `y` is produced by `chunk_condition`, in timeline order, one request per chunk.
+        `pose_feed` (an iterable of [3, n, H, W] pieces, `stream` only) replaces the pose clip: its first piece is taken
+        here for the size check, every further piece when `chunk_condition` needs rows that are not final yet."""
         is_i2v = getattr(getattr(getattr(self, "generator", None), "model", None), "model_type", "t2v") == "i2v"
         if input_image is not None and not is_i2v:
             raise NotImplementedError("input_image: this generator has no i2v branch (img_emb, k_img / v_img, the 36-channel patch "
@@ -146,6 +149,8 @@ class CausalInferencePipeline(torch.nn.Module):
         if is_i2v and input_image is None:
             raise ValueError("an i2v generator needs input_image: every pass takes its clip_feature and y")
         fs = self.frame_seq_length
+        if pose_feed is not None and (dwpose_data is not None or dwpose_data_emb is not None):
+            raise ValueError("pass either pose_feed or a whole pose clip (dwpose_data / dwpose_data_emb), not both")
         use_pose = dwpose_data is not None and random_ref_dwpose is not None      # both, as the reference (:336)
         if use_pose:
             if dwpose_data_emb is not None:
@@ -160,25 +165,59 @@ class CausalInferencePipeline(torch.nn.Module):
             if pose_fhw[1] * pose_fhw[2] != fs:
                 raise ValueError(f"dwpose_data gives {pose_fhw[1]}x{pose_fhw[2]} pose tokens per frame, the latents {height // 2}x{width // 2}. "
                                  "Check pose data processing.")
-        elif dwpose_data is not None or random_ref_dwpose is not None:
+        elif pose_feed is None and (dwpose_data is not None or random_ref_dwpose is not None):
             log.warning("only one of dwpose_data / random_ref_dwpose was given: the pose branch needs both and is not taken")
+        feed, feed_first = None, None
+        if pose_feed is not None:
+            from .pose_weights import POSE_DIM, pose_plan
+            feed = iter(pose_feed)
+            feed_first = next(feed, None)
+            if feed_first is None:
+                raise ValueError("pose_feed is empty: chunk 0 needs its first pose frames")
+            if feed_first.dim() != 4 or feed_first.shape[0] != 3 or feed_first.shape[1] < 1:
+                raise ValueError(f"a pose_feed piece must be [3, n >= 1, H, W] (shared by the batch), got {tuple(feed_first.shape)}")
+            _, ph, pw = pose_plan(1, *feed_first.shape[2:])
+            if ph * pw != fs:
+                raise ValueError(f"dwpose_data gives {ph}x{pw} pose tokens per frame, the latents {height // 2}x{width // 2}. "
+                                 "Check pose data processing.")
         if dwpose_data_emb is not None:
             assert dwpose_data_emb.shape[2] == num_output_frames, (
                 f"dwpose_data_emb has {dwpose_data_emb.shape[2]} frames, "
                 f"but expected {num_output_frames} to match the output timeline.")
-        if not (is_i2v or use_pose or dwpose_data_emb is not None):
+        if not (is_i2v or use_pose or dwpose_data_emb is not None or feed is not None):
             return None, None
 
         clip_entries = {}
         cond = None
         if is_i2v:
             cond = self._conditioner()
-            if use_pose and getattr(cond, "pose_embedder", None) is None:
+            ref_in_y = use_pose or (feed is not None and random_ref_dwpose is not None)
+            if ref_in_y and getattr(cond, "pose_embedder", None) is None:
                 cond.pose_embedder = self._pose_embedder()      # the image to be driven by the pose: its map goes into y
             # one image: the wrapper expands clip_feature to the batch
-            clip_entries["clip_feature"] = cond.begin(input_image, height * 8, width * 8, random_ref_dwpose if use_pose else None)
+            clip_entries["clip_feature"] = cond.begin(input_image, height * 8, width * 8, random_ref_dwpose if ref_in_y else None)
         pose_tokens = self._pose_embedder().embed(dwpose_data)[0] if use_pose else None      # [1, F'*h*w, 5120], once per clip
         next_frame = [0]
+        feed_rows = None
+        if feed is not None:
+            # the clip's rows in one buffer, filled as the feed delivers; a chunk's add_condition stays a row range of it
+            pose_stream = self._pose_embedder().open_stream(*feed_first.shape[2:])
+            pose_tokens = torch.empty(1, num_output_frames * fs, POSE_DIM, dtype=torch.bfloat16, device=pose_stream.embedder.device)
+            pending = [feed_first]
+
+            def feed_rows(first: int, upto: int) -> None:
+                """Pull pieces until latent frames [0, upto) are final (4*upto + 1 pixel frames in) or the feed ends, which
+                closes the clip.  Nothing is pulled ahead of that."""
+                while pose_stream.latent_frames_done < upto and not pose_stream.closed:
+                    piece = pending.pop() if pending else next(feed, None)
+                    row = pose_stream.latent_frames_done * fs
+                    if piece is None:
+                        pose_stream.close(out=pose_tokens, out_row=row)
+                    else:      # frames past 4 F + 1 belong to latent frames the noise does not have
+                        pose_stream.push(piece[:, :4 * num_output_frames + 1 - pose_stream.frames_pushed], out=pose_tokens, out_row=row)
+                if pose_stream.latent_frames_done < upto:
+                    raise ValueError(f"pose_feed ended after {pose_stream.frames_pushed} pose frames: latent frames {first}..{upto - 1} need "
+                                     f"{4 * upto - 3} when the clip ends with them ({4 * upto + 1} when it goes on)")
 
         def chunk_condition(first_frame: int, n: int, warm_up: bool = False) -> dict:
             entries = {}
@@ -191,6 +230,8 @@ class CausalInferencePipeline(torch.nn.Module):
             if dwpose_data_emb is not None:
                 entries["add_condition"] = dwpose_data_emb[:, :, first_frame:first_frame + n].permute(0, 2, 3, 4, 1).flatten(1, 3).contiguous()
             elif pose_tokens is not None:
+                if feed_rows is not None:
+                    feed_rows(first_frame, first_frame + n)
                 # token-major: the chunk's tokens are a row range, no copy (batch > 1: the one clip, expanded)
                 condition = pose_tokens[:, first_frame * fs:(first_frame + n) * fs]
                 entries["add_condition"] = condition.expand(batch_size, -1, -1).contiguous() if batch_size > 1 else condition
@@ -394,7 +435,7 @@ class CausalInferencePipeline(torch.nn.Module):
 
     def stream(self, noise: torch.Tensor, text_prompts: List[str], skip_last_context: bool = True,
                overlap_decode: bool = False, frame_encoder=None, input_image=None, dwpose_data: Optional[torch.Tensor] = None,
-               random_ref_dwpose: Optional[torch.Tensor] = None, dwpose_data_emb: Optional[torch.Tensor] = None):
+               random_ref_dwpose: Optional[torch.Tensor] = None, dwpose_data_emb: Optional[torch.Tensor] = None, pose_feed=None):
         """Chunk-at-a-time generation (the streaming boundary; mirrors the inline loop of the
         reference's demo.py:303-468): yields `(chunk_index, latents [B, f, C, H, W], pixels)` per chunk.
         `pixels` comes from `vae.decode_chunk(latents, chunk_index)` when the injected VAE has a streaming
@@ -411,7 +452,14 @@ class CausalInferencePipeline(torch.nn.Module):
         (0, 1) gets `pixels`.  Without one the 3-tuples are exactly what they were.
 
         input_image / dwpose_data / random_ref_dwpose / dwpose_data_emb: as `inference`.  Chunk k's `y` is encoded on the
-        rollout's stream right before chunk k's first pass; nothing is encoded ahead of need."""
+        rollout's stream right before chunk k's first pass; nothing is encoded ahead of need.
+
+        pose_feed: an iterable of pose pieces [3, n >= 1, H, W] (any lengths) instead of a whole `dwpose_data` clip -- a
+        live source.  It takes the pose branch by itself (`random_ref_dwpose` still only goes into an i2v generator's `y`).
+        Pieces are pulled only when a chunk's rows are not final yet: chunk k of three latent frames needs 12 k + 13 pose
+        frames, one latent frame beyond its own, or the feed's end, which closes the clip (then 4 (f - 1) + 1 frames
+        serve f latent frames, as with `dwpose_data`).  A feed that ends too early is a ValueError.  The latents are the
+        whole clip's, bit for bit (`PoseStream`)."""
         batch_size, num_frames, num_channels, height, width = noise.shape
         if self.independent_first_frame:
             assert (num_frames - 1) % self.num_frame_per_block == 0
@@ -421,7 +469,7 @@ class CausalInferencePipeline(torch.nn.Module):
             all_num_frames = [self.num_frame_per_block] * (num_frames // self.num_frame_per_block)
         self.frame_seq_length = (height // 2) * (width // 2)
         clip_entries, chunk_condition = self._conditioning(batch_size, num_frames, height, width, input_image, dwpose_data,
-                                                           random_ref_dwpose, dwpose_data_emb)
+                                                           random_ref_dwpose, dwpose_data_emb, pose_feed)
         conditional_dict = self.text_encoder(text_prompts=text_prompts)
         if chunk_condition is not None:
             conditional_dict = dict(conditional_dict, **clip_entries)

@@ -7,8 +7,14 @@
     pipe = CausalDiffusionInferencePipeline(args, device, ..., pose_embedder=emb)
     pipe.inference(noise, prompts, None, dwpose_data, random_ref_dwpose)
 
-Every kernel is in csrc/ (pose_conv.hip, pose_embed.hip, gemm_bf16.hip); a clip is ONE C call (`sf_pose_embed`).  The
-tokens come out token-major, which is already the `add_condition` layout: a chunk's tokens are a contiguous row range.
+    stream = emb.open_stream(H, W)                                       # a clip in pieces (a live feed, a long clip)
+    tokens, m = stream.push(frames)                                      # [3, n, H, W] -> the rows of the m latent frames now final
+    tokens, m = stream.close()                                           # the tail, with the clip-end padding
+    tokens, (f, h, w) = emb.embed_long(dwpose_data)                      # `embed` through a stream: clips `embed` refuses
+
+Every kernel is in csrc/ (pose_conv.hip, pose_embed.hip, gemm_bf16.hip); a clip is ONE C call (`sf_pose_embed`), a piece
+of one ONE call too (`sf_pose_stream_push`), and the pieces' rows are the whole clip's, bit for bit.  The tokens come out
+token-major, which is already the `add_condition` layout: a chunk's tokens are a contiguous row range.
 There is no eager/CPU fallback.
 """
 from __future__ import annotations
@@ -20,8 +26,8 @@ import torch
 
 from . import _lib
 from .device_model import DeviceModel
-from .pose_weights import (CIN_STORE, DWPOSE_LAYERS, POSE_DIM, RANDOMREF_DIM, RANDOMREF_LAYERS, pad_pose_bias, pose_plan, ref_plan, repack_pose_conv,
-                           repack_pose_embed, split_pose_state_dict)
+from .pose_weights import (CIN_STORE, DWPOSE_LAYERS, POSE_DIM, RANDOMREF_DIM, RANDOMREF_LAYERS, pad_pose_bias, pose_plan, pose_stream_plan,
+                           ref_plan, repack_pose_conv, repack_pose_embed, split_pose_state_dict)
 
 Tensor = torch.Tensor
 
@@ -127,3 +133,119 @@ class PoseEmbedder(DeviceModel):
         tokens, (f, h, w) = self.embed(dwpose_data)
         emb = tokens.view(tokens.shape[0], f, h, w, POSE_DIM).permute(0, 4, 1, 2, 3)
         return emb, (self.embed_ref(random_ref_dwpose) if random_ref_dwpose is not None else None)
+
+    # --------------------------------------------------------------------------------- a clip in pieces
+    def open_stream(self, H: int, W: int, max_frames_per_push: int = 16) -> "PoseStream":
+        """A resumable `embed` for H x W frames: push the clip in pieces, get every latent frame's rows as soon as the
+        frames it depends on are in.  Each stream owns its history and scratch; any number may be open."""
+        if not self.has_dwpose:
+            raise RuntimeError("the pose weights hold no dwpose_embedding.* tensors")
+        return PoseStream(self, H, W, max_frames_per_push)
+
+    def embed_long(self, dwpose_data: Tensor, frames_per_push: int = 12) -> Tuple[Tensor, Tuple[int, int, int]]:
+        """`embed` through a `PoseStream`, `frames_per_push` frames at a time: the same tokens, bit for bit, with scratch
+        that does not grow with the clip -- for clips whose volumes `embed` refuses (4 GiB: ~145 frames of 720x1280)."""
+        if dwpose_data.dim() == 5:
+            outs = [self.embed_long(d, frames_per_push) for d in dwpose_data]
+            return torch.cat([t for t, _ in outs], dim=0), outs[0][1]
+        if dwpose_data.dim() != 4 or dwpose_data.shape[0] != 3:
+            raise ValueError(f"dwpose_data must be [3, F, H, W], got {tuple(dwpose_data.shape)}")
+        if frames_per_push < 1:
+            raise ValueError(f"frames_per_push must be at least 1, got {frames_per_push}")
+        _, F, H, W = dwpose_data.shape
+        f, h, w = pose_plan(F, H, W)
+        tokens = torch.empty(1, f * h * w, POSE_DIM, dtype=torch.bfloat16, device=self.device)
+        stream = self.open_stream(H, W, frames_per_push)
+        for i in range(0, F, frames_per_push):
+            stream.push(dwpose_data[:, i:i + frames_per_push], out=tokens, out_row=stream.latent_frames_done * h * w)
+        stream.close(out=tokens, out_row=stream.latent_frames_done * h * w)
+        assert stream.latent_frames_done == f
+        return tokens, (f, h, w)
+
+
+class PoseStream:
+    """One clip going through the dwpose stack piece by piece (`PoseEmbedder.open_stream`).  Latent frame j is final
+    once 4j + 5 pixel frames are in; `close` declares the clip ended and flushes the frames that were waiting for
+    neighbours.  The history (two frames per layer input) and the scratch are this stream's own."""
+
+    def __init__(self, embedder: PoseEmbedder, H: int, W: int, max_frames_per_push: int = 16):
+        if max_frames_per_push < 1:
+            raise ValueError(f"max_frames_per_push must be at least 1, got {max_frames_per_push}")
+        self.embedder, self.H, self.W, self.max_frames_per_push = embedder, int(H), int(W), int(max_frames_per_push)
+        _, self.h, self.w = pose_plan(1, self.H, self.W)
+        lib, cm = _lib.lib(), C.byref(embedder.cmodel)
+        nbytes = []
+        for what, n in (("sf_pose_stream_state_bytes", lib.sf_pose_stream_state_bytes(cm, self.H, self.W)),
+                        ("sf_pose_stream_scratch_bytes", lib.sf_pose_stream_scratch_bytes(cm, self.max_frames_per_push, self.H, self.W))):
+            if int(n) == 0:
+                _lib.check(-1, what)
+            nbytes.append(int(n))
+        self._state = torch.empty(nbytes[0], dtype=torch.uint8, device=embedder.device)
+        self._scratch = torch.empty(nbytes[1], dtype=torch.uint8, device=embedder.device)
+        self.frames_pushed = 0
+        self.latent_frames_done = 0
+        self.closed = False
+
+    @property
+    def hw(self) -> Tuple[int, int]:
+        return self.h, self.w
+
+    def _call(self, x: Optional[Tensor], code: int, n: int, closing: bool, dst: Tensor, row: int) -> int:
+        dev = self.embedder.device
+        written = C.c_int32(0)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(_lib.lib().sf_pose_stream_push(C.byref(self.embedder.cmodel), self._state.data_ptr(), self.frames_pushed,
+                                                      x.data_ptr() if x is not None else None, code, n, self.H, self.W, int(closing),
+                                                      self._scratch.data_ptr(), self._scratch.numel(),
+                                                      dst.data_ptr() + row * POSE_DIM * 2, dst.shape[1] - row, C.byref(written), stream),
+                       "sf_pose_stream_push")
+        if x is not None:
+            x.record_stream(torch.cuda.current_stream(dev))
+        self.frames_pushed += n
+        self.latent_frames_done += written.value
+        return written.value
+
+    def _run(self, frames: Optional[Tensor], closing: bool, out: Optional[Tensor], out_row: int) -> Tuple[Tensor, int]:
+        if self.closed:
+            raise RuntimeError("this pose stream is closed: open a new one for the next clip")
+        code, n = 0, 0
+        if frames is not None:
+            if frames.dim() != 4 or frames.shape[0] != 3 or tuple(frames.shape[2:]) != (self.H, self.W):
+                raise ValueError(f"pose frames must be [3, n, {self.H}, {self.W}], got {tuple(frames.shape)}")
+            frames, code = self.embedder._pose_input(frames, "pose frames")
+            n = frames.shape[1]
+        if closing and self.frames_pushed + n == 0:
+            raise ValueError("a pose stream cannot be closed before its first frame")
+        fs = self.h * self.w
+        step = self.max_frames_per_push
+        pieces = [(i, min(step, n - i)) for i in range(0, n, step)] or [(0, 0)]
+        # the rows this call makes final, from the plan alone
+        m = sum(pose_stream_plan(self.frames_pushed + i, k, closing and i + k == n)[1][-1] for i, k in pieces)
+        if out is None:
+            dst, row = torch.empty(1, m * fs, POSE_DIM, dtype=torch.bfloat16, device=self.embedder.device), 0
+        else:
+            if out.dim() != 3 or out.shape[0] != 1 or out.shape[2] != POSE_DIM or out.dtype != torch.bfloat16 or not out.is_contiguous() \
+                    or out.device != self.embedder.device:
+                raise ValueError(f"out must be a contiguous bf16 [1, rows, {POSE_DIM}] tensor on {self.embedder.device}, got {tuple(out.shape)} {out.dtype}")
+            if out_row < 0 or out_row + m * fs > out.shape[1]:
+                raise ValueError(f"out holds {out.shape[1]} rows: {m} latent frames of {fs} rows do not fit at row {out_row}")
+            dst, row = out, out_row
+        first = row
+        for i, k in pieces:
+            x = frames[:, i:i + k].contiguous() if k else None
+            row += self._call(x, code, k, closing and i + k == n, dst, row) * fs
+        assert row - first == m * fs, "the library's plan and pose_weights.pose_stream_plan disagree"
+        self.closed = closing
+        return dst[:, first:row], m
+
+    def push(self, frames: Tensor, out: Optional[Tensor] = None, out_row: int = 0) -> Tuple[Tensor, int]:
+        """frames [3, n, H, W] in 0..255 (uint8 / float / bf16, as `embed`) -> (tokens bf16 [1, m*h*w, 5120], m): the rows
+        of the m latent frames this push made final (m may be 0).  More than `max_frames_per_push` frames are split.
+        With `out` (bf16 [1, rows, 5120]) the rows are written there from row `out_row` and the result is a view of it."""
+        return self._run(frames, False, out, out_row)
+
+    def close(self, out: Optional[Tensor] = None, out_row: int = 0) -> Tuple[Tensor, int]:
+        """Declare the clip ended: the remaining latent frames, which see the zero padding behind the last frame as in
+        `embed`.  Nothing can be pushed afterwards."""
+        return self._run(None, True, out, out_row)

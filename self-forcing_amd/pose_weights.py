@@ -171,6 +171,42 @@ def pose_plan(num_pose_frames: int, H: int, W: int) -> Tuple[int, int, int]:
     return f, h, w
 
 
+# ---------------------------------------------------------------------------------------- a clip in pieces
+# Level 0 is the stack's input (three copies of frame 0, then the pixel frames), level i + 1 the output of Conv3d i.
+# Output frame t of a 3-tap layer with padding 1 reads input frames t*st - 1 .. t*st + 1, so of an OPEN clip a layer with
+# N final input frames has N - 1 (stride 1) or N // 2 (stride 2) final output frames; a closed clip has them all.
+POSE_LEVELS = len(DWPOSE_LAYERS)       # 7: the input and the six 3x3x3 layers' outputs (the last layer is per frame)
+HISTORY_FRAMES = 2                     # frames of each layer input a later piece still reads
+
+
+def pose_stream_frontier(frames_pushed: int, closed: bool = False) -> List[int]:
+    """Final frames of every level once `frames_pushed` pixel frames are known: open, (P+3, P+2, P+1, P, P-1, (P-1)//2,
+    (P-1)//4); closed, the sizes of `pose_layer_volumes`.  All zero without a frame."""
+    f = [frames_pushed + LEAD_FRAMES if frames_pushed > 0 else 0]
+    for _, _, _, k, s, p, _ in DWPOSE_LAYERS[:-1]:
+        n = f[-1]
+        f.append(0 if n <= 0 else _out(n, k[0], s[0], p[0]) if closed else (n - 1 if s[0] == 1 else n // 2))
+    return f
+
+
+def pose_stream_plan(frames_before: int, n: int, closing: bool = False) -> Tuple[List[int], List[int]]:
+    """What a push of `n` pixel frames behind `frames_before` computes (`sf_pose_stream_plan`): (first, count) per level
+    -- level l gains frames [first[l], first[l] + count[l]), and the layer that reads level l gets a window of
+    HISTORY_FRAMES + count[l] frames starting at frame first[l] - HISTORY_FRAMES.  Latent frames made final: count[-1]."""
+    if frames_before < 0 or n < 0:
+        raise ValueError(f"pose_stream_plan: frames_before={frames_before} n={n}")
+    if closing and frames_before + n == 0:
+        raise ValueError("pose_stream_plan: closing a clip of no frames")
+    f0, f1 = pose_stream_frontier(frames_before), pose_stream_frontier(frames_before + n, closing)
+    return f0, [b - a for a, b in zip(f0, f1)]
+
+
+def pose_stream_cap(level: int, n: int) -> int:
+    """The most frames `level` gains in one push of `n` pixel frames, first, middle or closing: what the scratch of
+    `sf_pose_stream_scratch_bytes` is sized for."""
+    return n + 4 if level <= 4 else (n + 3) // 2 + 2 if level == 5 else (n + 3) // 4 + 2
+
+
 def ref_plan(H: int, W: int) -> Tuple[int, int]:
     """(h, w) of the reference-pose map for an H x W image: (480, 832) -> (60, 104)."""
     h, w = H, W
