@@ -43,6 +43,9 @@ __global__ __launch_bounds__(256) void patchify_i2v_kernel(const bf16_t* __restr
 
 // One wave per row, any C % 8 == 0: lane l walks the 16-byte chunks l, l + 64, ...  Mean, then the variance about it,
 // then the output: three passes over a row that stays in the cache (at most a few KiB).
+// The mean is kept as two floats, mean + mean_lo (the fma gives the division's remainder exactly): rounded to one float
+// it is off by up to 2^-25 |mean|, which for a row far from zero (N(1000, 4^2): 3e-5 against deviations of 4) moved
+// x - mean by 1e-5 relative, 20-60 times the rest of the kernel's error wherever xhat w + b cancels.
 __global__ __launch_bounds__(256) void layernorm_rows_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ weight,
                                                              const bf16_t* __restrict__ bias, bf16_t* __restrict__ out, int M, int C, float eps) {
   const int lane = threadIdx.x & 63;
@@ -55,13 +58,15 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const bf16_t* __res
 #pragma unroll
     for (int j = 0; j < 8; ++j) s += (float)t[j];
   }
-  const float mean = wave_sum(s) / (float)C;
+  const float total = wave_sum(s);
+  const float mean = total / (float)C;
+  const float mean_lo = fmaf(-mean, (float)C, total) / (float)C;
   float q = 0.f;
   for (int c = lane * 8; c < C; c += 512) {
     const bf16x8 t = *reinterpret_cast<const bf16x8*>(xr + c);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float d = (float)t[j] - mean;
+      const float d = ((float)t[j] - mean) - mean_lo;
       q += d * d;
     }
   }
@@ -73,7 +78,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const bf16_t* __res
     const bf16x8 bv = *reinterpret_cast<const bf16x8*>(bias + c);
     bf16x8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (bf16_t)(((float)t[j] - mean) * rstd * (float)wv[j] + (float)bv[j]);
+    for (int j = 0; j < 8; ++j) o[j] = (bf16_t)((((float)t[j] - mean) - mean_lo) * rstd * (float)wv[j] + (float)bv[j]);
     *reinterpret_cast<bf16x8*>(orow + c) = o;
   }
 }

@@ -83,7 +83,8 @@ def epi_ref(epi, y, M, N, g, rps_gate):
 SHAPES = [(4680, 4608, 1536), (4680, 1536, 1536), (4680, 8960, 1536), (4680, 1536, 8960),
           (9360, 4608, 1536), (9360, 1536, 1536), (9360, 8960, 1536), (9360, 1536, 8960),
           (3600, 5120, 5120), (3600, 13824, 5120), (1200, 5120, 13824),
-          (1000, 1056, 256), (1560, 1536, 384), (333, 200, 512), (77, 64, 1536), (4680, 64, 1536)]
+          (1000, 1056, 256), (1560, 1536, 384), (333, 200, 512), (77, 64, 1536), (4680, 64, 1536),
+          (333, 204, 512)]      # N % 8 == 4: the direct epilogue and the clamped w_scale read on the fp8 path
 
 
 @pytest.mark.parametrize("M,N,K", SHAPES)

@@ -35,7 +35,7 @@ def opsgold():
 
 # ---------------------------------------------------------------------------------------- GEMM
 @pytest.mark.parametrize("M,N,K", [(1, 128, 64), (72, 64, 64), (200, 256, 128), (257, 384, 1536), (1560, 1536, 512),
-                                   (4680, 512, 1024)])
+                                   (4680, 512, 1024), (130, 132, 64)])    # the last: one k-tile, N % 8 == 4, two column tiles
 @pytest.mark.parametrize("epi", ["bias", "gelu", "resid", "gate_resid"])
 def test_gemm(M, N, K, epi):
     g = torch.Generator().manual_seed(M * 7 + N + K)
