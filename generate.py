@@ -25,7 +25,9 @@ tensor) is given.  A config WITHOUT `denoising_step_list` selects the multi-step
 `--pose_path` drives the generation with a pose clip, under either pipeline: a `.pt` (dict) or `.npy` (pickled dict)
 holding `dwpose_data` [3, F, H, W] and `random_ref_dwpose` [H, W, 3] in 0..255, embedded on the GPU by `PoseEmbedder`
 with the weights of `--pose_weights_path` (a file with `dwpose_embedding.*` / `randomref_embedding_pose.*` tensors) or
-`--pose_random_init_seed N`.  Rendering skeletons and reading video files are outside this driver.
+`--pose_random_init_seed N`.  `--pose_path clip.avi` takes the clip as a Motion-JPEG AVI instead (what `--video_format mjpeg`
+writes, or a skeleton renderer's output), with `--ref_pose_path ref.jpg` as `random_ref_dwpose`: the frames are read by
+`mjpeg.read_avi` and decoded on the GPU by `JpegDecoder`, with no host decode.  Rendering skeletons is outside this driver.
 
 `--i2v` (inference.py:83-90, 136-149) reads `--data_path` as a TextImagePairDataset directory -- one
 `target_crop_info_<ratio>.json` listing `file_name` / `caption` entries, images under `<ratio>/` --, encodes each
@@ -111,6 +113,20 @@ def load_pose(path: str):
     return tuple(torch.as_tensor(d[k]) for k in ("dwpose_data", "random_ref_dwpose"))
 
 
+def load_pose_mjpeg(clip_path: str, ref_path: str, device):
+    """(dwpose_data uint8 [3, F, H, W], random_ref_dwpose uint8 [H, W, 3]) on `device` from an MJPEG AVI and a JPEG file."""
+    decoder = sfa.JpegDecoder(device=device)
+    frames = sfa.mjpeg.read_avi(clip_path)
+    if not frames:
+        raise SystemExit(f"{clip_path}: no video frames (00dc chunks) in the file")
+    with open(ref_path, "rb") as fh:
+        ref = fh.read()
+    try:
+        return decoder.decode(frames, layout="pose"), decoder.decode([ref], layout="hwc")[0]
+    except ValueError as e:
+        raise SystemExit(f"{clip_path} / {ref_path}: {e}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_path", required=True)
@@ -140,7 +156,9 @@ def main():
     ap.add_argument("--taehv_random_init_seed", type=int, default=None, help="seeded random TAEHV decoder weights instead (with --i2v the encoder too)")
     ap.add_argument("--fp8", action="store_true",
                     help="FP8 linear layers in the generator (the reference's enable_fp8 / torchao PerTensor quantisation)")
-    ap.add_argument("--pose_path", default=None, help=".pt / .npy dict with dwpose_data [3, F, H, W] and random_ref_dwpose [H, W, 3]")
+    ap.add_argument("--pose_path", default=None,
+                    help=".pt / .npy dict with dwpose_data [3, F, H, W] and random_ref_dwpose [H, W, 3], or an MJPEG .avi (with --ref_pose_path)")
+    ap.add_argument("--ref_pose_path", default=None, help="--pose_path clip.avi: the JPEG file that is random_ref_dwpose")
     ap.add_argument("--pose_weights_path", default=None, help="pose embedding weights (dwpose_embedding.* / randomref_embedding_pose.*)")
     ap.add_argument("--pose_random_init_seed", type=int, default=None, help="seeded random pose embedding weights instead")
     ap.add_argument("--video_format", choices=("pt", "mjpeg"), default="pt",
@@ -156,6 +174,15 @@ def main():
         if not os.path.exists(a.pose_path):
             ap.error(f"--pose_path {a.pose_path}: no such file (a .pt / .npy dict with dwpose_data and random_ref_dwpose; few-step and "
                      "multi-step configs both take it)")
+        pose_is_mjpeg = a.pose_path.lower().endswith(".avi")
+        if a.ref_pose_path and not pose_is_mjpeg:
+            ap.error("--ref_pose_path goes with an MJPEG --pose_path (.avi); a .pt / .npy dict holds its own random_ref_dwpose")
+        if pose_is_mjpeg and not a.ref_pose_path:
+            ap.error("--pose_path clip.avi needs --ref_pose_path: the JPEG file that is random_ref_dwpose")
+        if pose_is_mjpeg and not os.path.exists(a.ref_pose_path):
+            ap.error(f"--ref_pose_path {a.ref_pose_path}: no such file")
+    elif a.ref_pose_path:
+        ap.error("--ref_pose_path needs --pose_path clip.avi")
     if a.input_image:
         if (a.clip_path is None) == (a.clip_random_init_seed is None):
             ap.error("--input_image needs exactly one of --clip_path / --clip_random_init_seed")
@@ -232,7 +259,7 @@ def main():
     if a.pose_path:
         weights = a.pose_weights_path if a.pose_weights_path else sfa.synth_pose_state_dict(seed=a.pose_random_init_seed)
         pose_embedder = sfa.PoseEmbedder(weights, device=device, strict=cfg.get("pose_weights_strict", True))
-        pose_data = load_pose(a.pose_path)
+        pose_data = load_pose_mjpeg(a.pose_path, a.ref_pose_path, device) if pose_is_mjpeg else load_pose(a.pose_path)
     image_encoder = input_image = None
     if a.input_image:
         if gen.model.model_type != "i2v":

@@ -779,6 +779,65 @@ int sf_jpeg_encode_frames(const void* frames, int dtype, int value_range, int n,
                           size_t out_capacity, int64_t* offsets, int32_t* status, void* stream);
 
 /* ==========================================================================================
+ * JPEG decoder (JFIF files -> pixels): the way back in, for pose frames that arrive as JPEG (a renderer behind a socket,
+ * a webcam, an MJPEG file this project wrote).  Baseline sequential DCT, 8 bit, Huffman, one interleaved scan; Y Cb Cr
+ * with luma sampling 2x2 / 1x1 / 2x1 over 1x1 chroma, or one component; any tables, with or without DRI, any h, w >= 1
+ * (the padding blocks are decoded and cropped).  Four kernels: restart-marker search, entropy decoding (one lane per
+ * restart interval), dequantisation + IDCT, chroma upsampling + colour + output format.  All arithmetic is integer and
+ * exact: X = coef Q, t = Bi^T X Bi with Bi[k][n] = rint(2^13 b(k, n)) in 64 bits, sample = clamp(((t + 2^25) >> 26) + 128),
+ * libjpeg's "fancy" triangle filter for the chroma, 16.16 fixed point for the colour matrix.  The numbers are defined by
+ * self_forcing_amd/jpeg_reference.py (`decode`), which the kernels equal bit for bit.
+ *
+ * The caller reads the files' header segments on the host (the library never parses a file) and uploads ONE buffer:
+ * n table entries of SF_JPEG_DECODE_FILE_BYTES each, then the files' bytes.  A table entry (little endian):
+ *   uint32 scan_off, scan_len     the entropy-coded bytes of the file: upload[scan_off .. scan_off + scan_len)
+ *   uint32 ri, intervals          MCUs per restart interval (the MCU count without DRI), ceil(MCUs / ri)
+ *   uint16 quant[3][64]           per component, natural order
+ *   huff[3][2]                    per component DC, AC: uint16 look[512] ((length << 8) | symbol of the code the next 9
+ *                                 bits start with, 0 = longer), int32 maxcode[18], int32 valoff[18] (T.81 F.2.2.3:
+ *                                 symbol = vals[code + valoff[L]] for the first L with code <= maxcode[L]), uint8 vals[256]
+ *   16 bytes of padding
+ * The kernels trust nothing in it: reads are clamped to the upload, writes to the call's geometry.  A file without DRI
+ * is one interval, so one lane decodes all of it: correct, and slow.
+ * ========================================================================================== */
+
+#define SF_JPEG_DECODE_FILE_BYTES 8960
+/* (the first two as enum sf_jpeg_subsampling) */
+enum sf_jpeg_decode_sampling { SF_JPEG_DEC_420 = 0, SF_JPEG_DEC_444 = 1, SF_JPEG_DEC_422 = 2, SF_JPEG_DEC_GRAY = 3 };
+/* with enum sf_jpeg_dtype: u8 = the decoded samples; f32 / bf16 = u8 / 127.5 - 1, the divide and the subtract each
+ * rounded to fp32, bf16 by round-to-nearest-even */
+enum sf_jpeg_layout {
+  SF_JPEG_HWC = 0,    /* [n][h][w][3]: what the encoder takes as SF_JPEG_U8    */
+  SF_JPEG_POSE = 1,   /* [3][n][h][w]: what sf_pose_embed takes                */
+  SF_JPEG_CHW = 2     /* [n][3][h][w]: what the VAE encoders take              */
+};
+/* bits the kernels OR into status[file] (0 = the file decoded completely) */
+enum sf_jpeg_decode_status {
+  SF_JPEG_DEC_BAD_CODE = 1,       /* a bit pattern that is no Huffman code, or a DC category beyond 11                  */
+  SF_JPEG_DEC_RUN_PAST_63 = 2,    /* a zero run that ends behind the 63rd coefficient                                   */
+  SF_JPEG_DEC_TRUNCATED = 4,      /* a restart interval ended before its blocks did                                     */
+  SF_JPEG_DEC_MARKER_COUNT = 8    /* the scan holds another number of RSTn markers than intervals - 1                   */
+};
+
+/* Workspace for n files of h x w: the coefficients, the component planes, the marker table.  max_intervals = the
+ * largest `intervals` of the call's table entries.  0 = malformed arguments (sf_last_error says which). */
+size_t sf_jpeg_decode_workspace_bytes(int n, int h, int w, int sampling, int max_intervals);
+/* upload -> coef int16 [n][blocks][64]: quantised coefficients, zigzagged, in MCU scan order, the padding MCUs included
+ * (Y00 Y01 Y10 Y11 Cb Cr for 4:2:0, Y Cb Cr for 4:4:4, Y0 Y1 Cb Cr for 4:2:2, raster 8x8 blocks for grayscale).  status
+ * int32 [n], device memory written on `stream`.  `coef` may be the workspace's own (offset 0). */
+int sf_jpeg_decode_entropy(const void* upload, size_t upload_bytes, int n, int h, int w, int sampling, int max_intervals,
+                           void* workspace, size_t workspace_bytes, void* coef, int32_t* status, void* stream);
+/* coef -> out in `layout` / `dtype`.  idct_table: HOST int32 [64], Bi[k * 8 + n] = rint(2^13 b(k, n)) (the caller computes
+ * it, so the kernels and their definition share one source). */
+int sf_jpeg_decode_pixels(const void* coef, const void* upload, size_t upload_bytes, const int32_t* idct_table, int n,
+                          int h, int w, int sampling, void* workspace, size_t workspace_bytes, void* out, int layout,
+                          int dtype, void* stream);
+/* Both steps in one host call. */
+int sf_jpeg_decode_frames(const void* upload, size_t upload_bytes, const int32_t* idct_table, int n, int h, int w,
+                          int sampling, int max_intervals, void* workspace, size_t workspace_bytes, void* out, int layout,
+                          int dtype, int32_t* status, void* stream);
+
+/* ==========================================================================================
  * Pose front end (DWPose frames -> pose tokens): `dwpose_embedding` and `randomref_embedding_pose` of the many-step
  * sampler (pipeline/causal_diffusion_inference.py:87-122) with their input transform (:337-343).  Runs once per clip.
  * Activations are channels-last bf16 volumes [T][H][W][C] with C = 8 (the three input channels, stored padded with

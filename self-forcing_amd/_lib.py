@@ -43,6 +43,12 @@ JPEG_DTYPES = {"uint8": 0, "float32": 1, "bfloat16": 2}
 JPEG_RANGES = {(-1, 1): 0, (0, 1): 1}
 JPEG_STATUS = {1: "an interval outgrew its worst-case slot", 2: "a coefficient is outside the baseline range",
                4: "the files do not fit the output buffer"}
+# enum sf_jpeg_decode_sampling / sf_jpeg_layout / sf_jpeg_decode_status; SF_JPEG_DECODE_FILE_BYTES
+JPEG_DECODE_SAMPLINGS = {"420": 0, "444": 1, "422": 2, "gray": 3}
+JPEG_LAYOUTS = {"hwc": 0, "pose": 1, "chw": 2}
+JPEG_DECODE_STATUS = {1: "a bit pattern that is no Huffman code", 2: "a zero run past the 63rd coefficient", 4: "a truncated restart interval",
+                      8: "a wrong number of restart markers"}
+JPEG_DECODE_FILE_BYTES = 8960
 # enum sf_clip_dtype
 CLIP_DTYPES = {"float32": 0, "bfloat16": 1}
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
@@ -340,6 +346,10 @@ SIGNATURES = {
     "sf_jpeg_transform": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sf_jpeg_entropy": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "sf_jpeg_encode_frames": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "sf_jpeg_decode_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "sf_jpeg_decode_entropy": (C.c_int, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "sf_jpeg_decode_pixels": (C.c_int, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i, _i, _vp]),
+    "sf_jpeg_decode_frames": (C.c_int, [_vp, _sz, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i, _i, _vp, _vp]),
     "sf_embedding_gather": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_t5_softmax_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_mul_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),

@@ -1,5 +1,7 @@
 """Host reference of the JPEG format the GPU encoder writes (csrc/jpeg.hip), in numpy float64, written from ITU-T T.81
-and the JFIF 1.02 note.  It is the oracle of the tests and the documentation of the format; nothing here is fast.
+and the JFIF 1.02 note.  It is the oracle of the tests and the documentation of the format; nothing here is fast.  The
+second half (`parse`, `decode_coefficients`, `decode`) is the definition of the GPU decoder (csrc/jpeg_decode.hip), in
+exact integers; it takes more than the encoder writes (any tables, 4:2:2, grayscale, any size, files without DRI).
 
 The format: baseline sequential JFIF, 8 bit, three components (Y, Cb, Cr; JFIF's full-range BT.601 matrix), 4:2:0 (chroma =
 the 2x2 mean) or 4:4:4, libjpeg's quality scaling of the Annex K quantisation tables, the Annex K Huffman tables, a DRI
@@ -15,6 +17,7 @@ The numbers, stage by stage (the GPU runs the same definition: the truncation in
 """
 from __future__ import annotations
 
+import functools
 from typing import List, Sequence, Tuple
 
 import numpy as np
@@ -270,3 +273,363 @@ def encode(frames_u8: np.ndarray, quality: int = 90, subsampling: str = "420", r
     coef = coefficients(frames_u8, quality, subsampling)
     h, w = frames_u8.shape[1:3]
     return [encode_coefficients(c, h, w, quality, subsampling, restart_interval) for c in coef]
+
+
+# ================================================================================================= decoding
+# The definition of the GPU decoder (csrc/jpeg_decode.hip), in exact integers: `parse` reads a file's header segments,
+# `decode_coefficients` the entropy-coded scan, `decode` the pixels.  Accepted: baseline sequential DCT (SOF0), 8 bit,
+# Huffman, one interleaved scan; Y Cb Cr with luma sampling 1x1 / 2x1 / 2x2 and chroma 1x1, or one component; up to four
+# 8-bit DQT and 4 + 4 DHT tables of any content; with or without DRI; any H, W >= 1 (the padding blocks are decoded and
+# cropped).  Everything else is a ValueError that names the reason.
+#
+#   X       = coef * Q                                 integers, natural order
+#   t       = IDCT_INT^T X IDCT_INT                    exact (64-bit), IDCT_INT[k][n] = rint(2^13 b(k, n))
+#   sample  = clamp(((t + 2^25) >> 26) + 128, 0, 255)  arithmetic shift
+#   chroma  = libjpeg's "fancy" triangle filter over the component's true size, edges replicated
+#   r, g, b = the JFIF matrix in 16.16 fixed point (F(x) = int(x * 65536 + 0.5)), clamped
+#
+# An integer IDCT because a DC-only block is DC * Q / 8 + 128, an exact tie one time in eight: a float evaluation's order
+# would decide those pixels, and a pose frame is mostly such blocks.
+DECODE_SAMPLINGS = {"420": 0, "444": 1, "422": 2, "gray": 3}
+# sampling -> (luma blocks across, down) of one MCU
+_LUMA_BLOCKS = {"420": (2, 2), "444": (1, 1), "422": (2, 1), "gray": (1, 1)}
+IDCT_BITS = 13
+IDCT_INT = np.rint(DCT * (1 << IDCT_BITS)).astype(np.int64)           # [k][n]
+LOOKUP_BITS = 9                                                        # first-level Huffman lookup of the decoder
+
+
+def _fix(x: float) -> int:
+    return int(x * 65536 + 0.5)
+
+
+FIX_CR_R, FIX_CB_G, FIX_CR_G, FIX_CB_B = _fix(1.402), _fix(0.344136286), _fix(0.714136286), _fix(1.772)
+
+_SOF_NAMES = {0xC1: "extended sequential DCT", 0xC2: "progressive DCT", 0xC3: "lossless", 0xC5: "differential sequential DCT",
+              0xC6: "differential progressive DCT", 0xC7: "differential lossless", 0xC9: "arithmetic coding", 0xCA: "arithmetic coding",
+              0xCB: "arithmetic coding", 0xCD: "arithmetic coding", 0xCE: "arithmetic coding", 0xCF: "arithmetic coding"}
+
+
+class JpegInfo:
+    """What `parse` reads from a file's header segments.
+
+    height, width; sampling ("420" / "444" / "422" / "gray"); restart_interval (MCUs, 0 = no DRI); quant: per component the
+    quantiser in natural order (int64 [64]); dc / ac: per component (BITS, HUFFVAL); scan_offset / scan_end: the entropy-coded
+    bytes are file[scan_offset:scan_end] (scan_end = where the EOI marker stands)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def components(self) -> int:
+        return 1 if self.sampling == "gray" else 3
+
+    @property
+    def mcu_grid(self) -> Tuple[int, int]:
+        """(MCUs per row, MCU rows), the padding MCUs included."""
+        bx, by = _LUMA_BLOCKS[self.sampling]
+        return -(-self.width // (8 * bx)), -(-self.height // (8 * by))
+
+    @property
+    def blocks_per_mcu(self) -> int:
+        bx, by = _LUMA_BLOCKS[self.sampling]
+        return bx * by + (0 if self.sampling == "gray" else 2)
+
+    @property
+    def blocks(self) -> int:
+        mx, my = self.mcu_grid
+        return mx * my * self.blocks_per_mcu
+
+    @property
+    def intervals(self) -> int:
+        mx, my = self.mcu_grid
+        return -(-(mx * my) // self.restart_interval) if self.restart_interval else 1
+
+
+def parse(file: bytes) -> JpegInfo:
+    """Read the header segments of one file (nothing of the scan); ValueError for whatever the decoder does not take."""
+    data = bytes(file)
+    if data[:2] != b"\xff\xd8":
+        raise ValueError("not a JPEG file: SOI marker missing")
+    quant, huff, frame, ri, pos = {}, {}, None, 0, 2
+    while True:
+        while pos < len(data) and data[pos] == 0xFF and pos + 1 < len(data) and data[pos + 1] == 0xFF:
+            pos += 1                                                   # fill bytes in front of a marker, T.81 B.1.1.2
+        if pos + 4 > len(data):
+            raise ValueError("SOF / SOS marker missing: the file ends inside its header" if frame is None
+                             else "SOS marker missing: the file ends inside its header")
+        if data[pos] != 0xFF:
+            raise ValueError(f"no marker at byte {pos} of the header")
+        marker, length = data[pos + 1], int.from_bytes(data[pos + 2:pos + 4], "big")
+        if marker == 0xD9:
+            raise ValueError("SOS marker missing: EOI in the header" if frame is not None else "SOF marker missing: EOI in the header")
+        if length < 2 or pos + 2 + length > len(data):
+            raise ValueError(f"segment length {length} of marker 0x{marker:02X} runs past the file")
+        p = data[pos + 4:pos + 2 + length]
+        pos += 2 + length
+        if marker in _SOF_NAMES:
+            raise ValueError(f"{_SOF_NAMES[marker]} (SOF marker 0x{marker:02X}) is not baseline sequential DCT")
+        if marker == 0xC0:
+            if frame is not None:
+                raise ValueError("a second SOF segment")
+            if len(p) < 6 or len(p) != 6 + 3 * p[5]:
+                raise ValueError("malformed SOF segment")
+            if p[0] != 8:
+                raise ValueError(f"{p[0]} bit samples: only 8 bit is baseline")
+            frame = (int.from_bytes(p[1:3], "big"), int.from_bytes(p[3:5], "big"), [(p[6 + 3 * i], p[7 + 3 * i], p[8 + 3 * i]) for i in range(p[5])])
+        elif marker == 0xDB:
+            while p:
+                if p[0] >> 4:
+                    raise ValueError("16-bit DQT table: only 8-bit tables are baseline")
+                if (p[0] & 15) > 3 or len(p) < 65:
+                    raise ValueError("malformed DQT segment")
+                q = np.zeros(64, np.int64)
+                q[ZIGZAG] = np.frombuffer(p[1:65], np.uint8)
+                quant[p[0] & 15] = q
+                p = p[65:]
+        elif marker == 0xC4:
+            while p:
+                if len(p) < 17 or (p[0] >> 4) > 1 or (p[0] & 15) > 3:
+                    raise ValueError("malformed DHT segment")
+                bits = list(p[1:17])
+                if len(p) < 17 + sum(bits) or sum(bits) > 256:
+                    raise ValueError("malformed DHT segment")
+                huff[(p[0] >> 4, p[0] & 15)] = (bits, list(p[17:17 + sum(bits)]))
+                p = p[17 + sum(bits):]
+        elif marker == 0xDD:
+            if len(p) != 2:
+                raise ValueError("malformed DRI segment")
+            ri = int.from_bytes(p, "big")
+        elif marker == 0xDA:
+            break
+        elif not (0xE0 <= marker <= 0xEF or marker == 0xFE):
+            raise ValueError(f"marker 0x{marker:02X} in the header is not supported")
+    if frame is None:
+        raise ValueError("SOF marker missing in front of SOS")
+    h, w, comps = frame
+    if h < 1 or w < 1:
+        raise ValueError(f"frame {h}x{w}: the size must be given in SOF")
+    if len(comps) not in (1, 3):
+        raise ValueError(f"{len(comps)} components: only Y Cb Cr or grayscale")
+    if len(p) < 1 or len(p) != 4 + 2 * p[0]:
+        raise ValueError("malformed SOS segment")
+    if p[0] != len(comps):
+        raise ValueError(f"a scan of {p[0]} of {len(comps)} components: multiple scans are not supported")
+    if tuple(p[-3:]) != (0, 63, 0):
+        raise ValueError("spectral selection / successive approximation in SOS: not baseline")
+    if len(comps) == 1:
+        sampling = "gray"
+    else:
+        hv = [c[1] for c in comps]
+        sampling = {0x11: "444", 0x21: "422", 0x22: "420"}.get(hv[0])
+        if sampling is None or hv[1] != 0x11 or hv[2] != 0x11:
+            raise ValueError("sampling factors " + " ".join(f"{v >> 4}x{v & 15}" for v in hv) + ": only 1x1 / 2x1 / 2x2 luma over 1x1 chroma")
+    q, dc, ac = [], [], []
+    for i, (cid, _, tq) in enumerate(comps):
+        if p[1 + 2 * i] != cid:
+            raise ValueError("the scan's components are not in the frame's order")
+        td, ta = p[2 + 2 * i] >> 4, p[2 + 2 * i] & 15
+        if tq not in quant or (0, td) not in huff or (1, ta) not in huff:
+            raise ValueError(f"component {cid} uses a table the file does not define")
+        q.append(quant[tq])
+        dc.append(huff[(0, td)])
+        ac.append(huff[(1, ta)])
+    for bits, vals in dc + ac:
+        decode_tables(bits, vals)                                      # ValueError for an over-subscribed code
+    end = data.rfind(b"\xff\xd9")
+    if end < pos:
+        raise ValueError("EOI marker missing")
+    return JpegInfo(height=h, width=w, sampling=sampling, restart_interval=ri, quant=q, dc=dc, ac=ac, scan_offset=pos, scan_end=end)
+
+
+def decode_tables(bits: Sequence[int], vals: Sequence[int]) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The decoder's form of one Huffman table (T.81 F.2.2.3): (look uint16 [512], maxcode int32 [18], valoff int32 [18],
+    vals uint8 [256]).  look[next 9 bits] = (length << 8) | symbol for codes of up to 9 bits, 0 for longer ones; a code of
+    length L > 9 is the first L for which the next L bits are <= maxcode[L] (-1: no code of that length), its symbol
+    vals[code + valoff[L]].  The arrays are cached per table: read them, do not write them."""
+    return _decode_tables(tuple(int(b) for b in bits), bytes(bytearray(vals)))
+
+
+@functools.lru_cache(maxsize=256)
+def _decode_tables(bits: tuple, vals: bytes):
+    look = np.zeros(1 << LOOKUP_BITS, np.uint16)
+    maxcode, valoff = np.full(18, -1, np.int32), np.zeros(18, np.int32)
+    table = np.zeros(256, np.uint8)
+    table[:len(vals)] = np.frombuffer(vals, np.uint8)
+    code, k = 0, 0
+    for length in range(1, 17):
+        n = bits[length - 1]
+        if n:
+            if code + n > (1 << length):
+                raise ValueError("a DHT table assigns more codes than its lengths allow")
+            valoff[length] = k - code
+            maxcode[length] = code + n - 1
+            if length <= LOOKUP_BITS:
+                for i in range(n):
+                    lo = (code + i) << (LOOKUP_BITS - length)
+                    look[lo:lo + (1 << (LOOKUP_BITS - length))] = (length << 8) | int(table[k + i])
+            code += n
+            k += n
+        code <<= 1
+    return look, maxcode, valoff, table
+
+
+class _BitReader:
+    """The bits of one restart interval: 0xFF 0x00 unstuffed; zeros behind the end, and `overrun` says they were used."""
+
+    def __init__(self, data: bytes):
+        self.data, self.pos, self.acc, self.n, self.phantom = data.replace(b"\xff\x00", b"\xff"), 0, 0, 0, 0
+
+    def _fill(self, want: int):
+        while self.n < want:
+            if self.pos < len(self.data):
+                byte = self.data[self.pos]
+            else:
+                byte, self.phantom = 0, self.phantom + 8
+            self.pos += 1
+            self.acc = ((self.acc << 8) | byte) & 0xFFFFFFFFFFFF
+            self.n += 8
+
+    def peek(self, length: int) -> int:
+        self._fill(length)
+        return (self.acc >> (self.n - length)) & ((1 << length) - 1)
+
+    def skip(self, length: int):
+        self.n -= length
+
+    def receive(self, size: int) -> int:
+        """T.81 F.2.2.1 EXTEND of the next `size` bits."""
+        if size == 0:
+            return 0
+        v = self.peek(size)
+        self.skip(size)
+        return v if v >> (size - 1) else v - (1 << size) + 1
+
+    @property
+    def overrun(self) -> bool:
+        return self.n < self.phantom
+
+
+def _symbol(br: _BitReader, tables) -> int:
+    look, maxcode, valoff, vals = tables
+    e = int(look[br.peek(LOOKUP_BITS)])
+    if e:
+        br.skip(e >> 8)
+        return e & 255
+    for length in range(LOOKUP_BITS + 1, 17):
+        code = br.peek(length)
+        if code <= maxcode[length]:
+            br.skip(length)
+            return int(vals[(code + int(valoff[length])) & 255])
+    raise ValueError("bad Huffman code in the scan")
+
+
+def block_components(sampling: str) -> List[int]:
+    """The component of each block of one MCU."""
+    bx, by = _LUMA_BLOCKS[sampling]
+    return [0] * (bx * by) + ([] if sampling == "gray" else [1, 2])
+
+
+def decode_coefficients(file: bytes, info: JpegInfo = None) -> np.ndarray:
+    """The scan's quantised coefficients, int16 [blocks, 64], zigzagged, blocks in MCU scan order (Y.. Cb Cr per MCU: the
+    encoder's layout for "420" / "444", Y0 Y1 Cb Cr for "422", raster 8x8 blocks for grayscale), the padding MCUs included."""
+    import re
+    info = info or parse(file)
+    scan = bytes(file)[info.scan_offset:info.scan_end]
+    marks = [m.start() for m in re.finditer(rb"\xff[\xd0-\xd7]", scan)]
+    if len(marks) != info.intervals - 1:
+        raise ValueError(f"{len(marks)} restart markers in the scan, {info.intervals - 1} expected")
+    comps = block_components(info.sampling)
+    bpm = len(comps)
+    mcus = info.blocks // bpm
+    ri = info.restart_interval or mcus
+    dc = [decode_tables(*t) for t in info.dc]
+    ac = [decode_tables(*t) for t in info.ac]
+    out = np.zeros((info.blocks, 64), np.int64)
+    for iv, (a, b) in enumerate(zip([0] + [m + 2 for m in marks], marks + [len(scan)])):
+        br, pred = _BitReader(scan[a:b]), [0, 0, 0]
+        for blk in range(iv * ri * bpm, min((iv + 1) * ri, mcus) * bpm):
+            comp = comps[blk % bpm]
+            size = _symbol(br, dc[comp])
+            if size > 11:
+                raise ValueError("bad Huffman code in the scan: a DC category beyond 11")
+            pred[comp] += br.receive(size)
+            out[blk, 0] = pred[comp]
+            k = 1
+            while k < 64:
+                rs = _symbol(br, ac[comp])
+                run, size = rs >> 4, rs & 15
+                if size == 0:
+                    if run != 15:
+                        break                                          # EOB
+                    k += 16                                            # ZRL
+                    continue
+                k += run
+                if k > 63:
+                    raise ValueError("a zero run past the 63rd coefficient")
+                out[blk, k] = br.receive(size)
+                k += 1
+        if br.overrun:
+            raise ValueError(f"restart interval {iv} is truncated")
+    return out.astype(np.int16)
+
+
+def idct_blocks(coef: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """Zigzagged coefficients [..., 64] and a quantiser (natural order) -> uint8 samples [..., 8, 8] by the integer IDCT."""
+    x = np.zeros(coef.shape, np.int64)
+    x[..., ZIGZAG] = coef.astype(np.int64)
+    x = (x * q.astype(np.int64)).reshape(*coef.shape[:-1], 8, 8)
+    t = np.einsum("kn,...kl,lm->...nm", IDCT_INT, x, IDCT_INT)
+    return np.clip(((t + (1 << (2 * IDCT_BITS - 1))) >> (2 * IDCT_BITS)) + 128, 0, 255).astype(np.uint8)
+
+
+def component_planes(coef: np.ndarray, info: JpegInfo) -> List[np.ndarray]:
+    """The components' sample planes (uint8, padded to whole MCUs) of one file's coefficient buffer."""
+    mx, my = info.mcu_grid
+    bx, by = _LUMA_BLOCKS[info.sampling]
+    c = np.asarray(coef).reshape(my, mx, info.blocks_per_mcu, 64)
+    luma = idct_blocks(c[:, :, :bx * by], info.quant[0]).reshape(my, mx, by, bx, 8, 8)
+    planes = [luma.transpose(0, 2, 4, 1, 3, 5).reshape(my * by * 8, mx * bx * 8)]
+    for i in range(1, info.components):
+        s = idct_blocks(c[:, :, bx * by + i - 1], info.quant[i])       # [my, mx, 8, 8]
+        planes.append(s.transpose(0, 2, 1, 3).reshape(my * 8, mx * 8))
+    return planes
+
+
+def upsample(c: np.ndarray, sampling: str, h: int, w: int) -> np.ndarray:
+    """One chroma plane (padded) -> [h, w] by libjpeg's "fancy" triangle filter over the component's true size."""
+    bx, by = _LUMA_BLOCKS[sampling]
+    ch, cw = -(-h // by), -(-w // bx)
+    c = c[:ch, :cw].astype(np.int64)
+    prev = lambda a, axis: np.concatenate([a.take([0], axis), a.take(range(a.shape[axis] - 1), axis)], axis)          # noqa: E731
+    nxt = lambda a, axis: np.concatenate([a.take(range(1, a.shape[axis]), axis), a.take([-1], axis)], axis)           # noqa: E731
+    if by == 2:
+        t = np.empty((2 * ch, cw), np.int64)
+        t[0::2], t[1::2] = 3 * c + prev(c, 0), 3 * c + nxt(c, 0)
+        out = np.empty((2 * ch, 2 * cw), np.int64)
+        out[:, 0::2], out[:, 1::2] = (3 * t + prev(t, 1) + 8) >> 4, (3 * t + nxt(t, 1) + 7) >> 4
+    elif bx == 2:
+        out = np.empty((ch, 2 * cw), np.int64)
+        out[:, 0::2], out[:, 1::2] = (3 * c + prev(c, 1) + 1) >> 2, (3 * c + nxt(c, 1) + 2) >> 2
+    else:
+        out = c
+    return out[:h, :w]
+
+
+def decode(file: bytes) -> np.ndarray:
+    """One file -> uint8 [H, W, 3]."""
+    info = parse(file)
+    planes = component_planes(decode_coefficients(file, info), info)
+    h, w = info.height, info.width
+    y = planes[0][:h, :w].astype(np.int64)
+    if info.components == 1:
+        return np.repeat(y[..., None], 3, axis=2).astype(np.uint8)
+    cb, cr = (upsample(p, info.sampling, h, w) - 128 for p in planes[1:])
+    r = y + ((FIX_CR_R * cr + 32768) >> 16)
+    g = y + ((-FIX_CB_G * cb - FIX_CR_G * cr + 32768) >> 16)
+    b = y + ((FIX_CB_B * cb + 32768) >> 16)
+    return np.clip(np.stack([r, g, b], -1), 0, 255).astype(np.uint8)
+
+
+def to_float(u8: np.ndarray) -> np.ndarray:
+    """u8 / 127.5 - 1, the divide and the subtract each rounded to fp32: the range the VAE encoders take."""
+    return np.asarray(u8).astype(np.float32) / np.float32(127.5) - np.float32(1)

@@ -538,6 +538,55 @@ def jpeg_encode_frames(frames: Tensor, n: int, h: int, w: int, subsampling: str,
                                       meta[n + 1:].data_ptr(), torch.cuda.current_stream(frames.device).cuda_stream), "sf_jpeg_encode_frames")
 
 
+# -------------------------------------------------------------------------------------- JPEG decoder (csrc/jpeg_decode.hip)
+_IDCT_TABLE = None
+
+
+def _idct_table():
+    """jpeg_reference.IDCT_INT as the host int32 [64] the C side takes: the kernels and their definition share it."""
+    global _IDCT_TABLE
+    if _IDCT_TABLE is None:
+        from . import jpeg_reference as jr
+        _IDCT_TABLE = (C.c_int32 * 64)(*[int(v) for v in jr.IDCT_INT.reshape(-1)])
+    return _IDCT_TABLE
+
+
+def jpeg_decode_workspace_bytes(n: int, h: int, w: int, sampling: str, max_intervals: int) -> int:
+    """Bytes of workspace for n files of h x w (sf_jpeg_decode_workspace_bytes)."""
+    need = lib().sf_jpeg_decode_workspace_bytes(n, h, w, _lib.JPEG_DECODE_SAMPLINGS[sampling], max_intervals)
+    if need == 0:
+        check(-1, "sf_jpeg_decode_workspace_bytes")
+    return need
+
+
+def jpeg_decode_entropy(upload: Tensor, upload_bytes: int, n: int, h: int, w: int, sampling: str, max_intervals: int, workspace: Tensor, coef: Tensor,
+                        status: Tensor) -> Tensor:
+    """upload (uint8: the table block, then the scans) -> coef int16 [n, blocks, 64]; status int32 [n] (sf_jpeg_decode_entropy)."""
+    check(lib().sf_jpeg_decode_entropy(upload.data_ptr(), upload_bytes, n, h, w, _lib.JPEG_DECODE_SAMPLINGS[sampling], max_intervals, workspace.data_ptr(),
+                                       workspace.numel(), coef.data_ptr(), status.data_ptr(), _cur(upload)), "sf_jpeg_decode_entropy")
+    return coef
+
+
+def jpeg_decode_pixels(coef: Tensor, upload: Tensor, upload_bytes: int, n: int, h: int, w: int, sampling: str, workspace: Tensor, out: Tensor,
+                       layout: str) -> Tensor:
+    """coef -> out (uint8 / float32 / bfloat16, already shaped for `layout`) (sf_jpeg_decode_pixels)."""
+    dtype = _lib.JPEG_DTYPES[str(out.dtype).replace("torch.", "")]
+    check(lib().sf_jpeg_decode_pixels(coef.data_ptr(), upload.data_ptr(), upload_bytes, _idct_table(), n, h, w, _lib.JPEG_DECODE_SAMPLINGS[sampling],
+                                      workspace.data_ptr(), workspace.numel(), out.data_ptr(), _lib.JPEG_LAYOUTS[layout], dtype, _cur(upload)),
+          "sf_jpeg_decode_pixels")
+    return out
+
+
+def jpeg_decode_frames(upload: Tensor, upload_bytes: int, n: int, h: int, w: int, sampling: str, max_intervals: int, workspace: Tensor, out: Tensor,
+                       layout: str, status: Tensor) -> Tensor:
+    """Both steps in one host call (sf_jpeg_decode_frames); arguments as `jpeg_decode_entropy` / `jpeg_decode_pixels`."""
+    dtype = _lib.JPEG_DTYPES[str(out.dtype).replace("torch.", "")]
+    check(lib().sf_jpeg_decode_frames(upload.data_ptr(), upload_bytes, _idct_table(), n, h, w, _lib.JPEG_DECODE_SAMPLINGS[sampling], max_intervals,
+                                      workspace.data_ptr(), workspace.numel(), out.data_ptr(), _lib.JPEG_LAYOUTS[layout], dtype, status.data_ptr(),
+                                      _cur(upload)), "sf_jpeg_decode_frames")
+    return out
+
+
 # -------------------------------------------------------------------------------------- CLIP image encoder (csrc/clip_encoder.hip)
 def _cur(t: Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
