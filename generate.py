@@ -27,7 +27,9 @@ holding `dwpose_data` [3, F, H, W] and `random_ref_dwpose` [H, W, 3] in 0..255, 
 with the weights of `--pose_weights_path` (a file with `dwpose_embedding.*` / `randomref_embedding_pose.*` tensors) or
 `--pose_random_init_seed N`.  `--pose_path clip.avi` takes the clip as a Motion-JPEG AVI instead (what `--video_format mjpeg`
 writes, or a skeleton renderer's output), with `--ref_pose_path ref.jpg` as `random_ref_dwpose`: the frames are read by
-`mjpeg.read_avi` and decoded on the GPU by `JpegDecoder`, with no host decode.  Rendering skeletons is outside this driver.
+`mjpeg.read_avi` and decoded on the GPU by `JpegDecoder`, with no host decode.  `--pose_resize stretch|cover` resizes both on
+the GPU to the output size (`FrameResizer`: Pillow's antialiased bilinear, bit for bit), so a clip of any size can drive the
+generation; the default `none` takes them as they are.  Rendering skeletons is outside this driver.
 
 `--i2v` (inference.py:83-90, 136-149) reads `--data_path` as a TextImagePairDataset directory -- one
 `target_crop_info_<ratio>.json` listing `file_name` / `caption` entries, images under `<ratio>/` --, encodes each
@@ -113,8 +115,9 @@ def load_pose(path: str):
     return tuple(torch.as_tensor(d[k]) for k in ("dwpose_data", "random_ref_dwpose"))
 
 
-def load_pose_mjpeg(clip_path: str, ref_path: str, device):
-    """(dwpose_data uint8 [3, F, H, W], random_ref_dwpose uint8 [H, W, 3]) on `device` from an MJPEG AVI and a JPEG file."""
+def load_pose_mjpeg(clip_path: str, ref_path: str, device, size=None, fit: str = "stretch"):
+    """(dwpose_data uint8 [3, F, H, W], random_ref_dwpose uint8 [H, W, 3]) on `device` from an MJPEG AVI and a JPEG file;
+    with `size` both are resized to it on the device (antialiased bilinear, Pillow's bits on the decoded samples)."""
     decoder = sfa.JpegDecoder(device=device)
     frames = sfa.mjpeg.read_avi(clip_path)
     if not frames:
@@ -122,7 +125,7 @@ def load_pose_mjpeg(clip_path: str, ref_path: str, device):
     with open(ref_path, "rb") as fh:
         ref = fh.read()
     try:
-        return decoder.decode(frames, layout="pose"), decoder.decode([ref], layout="hwc")[0]
+        return decoder.decode(frames, layout="pose", size=size, fit=fit), decoder.decode([ref], layout="hwc", size=size, fit=fit)[0]
     except ValueError as e:
         raise SystemExit(f"{clip_path} / {ref_path}: {e}")
 
@@ -159,6 +162,9 @@ def main():
     ap.add_argument("--pose_path", default=None,
                     help=".pt / .npy dict with dwpose_data [3, F, H, W] and random_ref_dwpose [H, W, 3], or an MJPEG .avi (with --ref_pose_path)")
     ap.add_argument("--ref_pose_path", default=None, help="--pose_path clip.avi: the JPEG file that is random_ref_dwpose")
+    ap.add_argument("--pose_resize", choices=("none", "stretch", "cover"), default="none",
+                    help="--pose_path clip.avi: resize the clip and --ref_pose_path on the GPU to the output size (8 x the latent size): stretch, or "
+                         "cover = the largest centred crop with the output's aspect ratio; none: their size must be the output size")
     ap.add_argument("--pose_weights_path", default=None, help="pose embedding weights (dwpose_embedding.* / randomref_embedding_pose.*)")
     ap.add_argument("--pose_random_init_seed", type=int, default=None, help="seeded random pose embedding weights instead")
     ap.add_argument("--video_format", choices=("pt", "mjpeg"), default="pt",
@@ -183,6 +189,8 @@ def main():
             ap.error(f"--ref_pose_path {a.ref_pose_path}: no such file")
     elif a.ref_pose_path:
         ap.error("--ref_pose_path needs --pose_path clip.avi")
+    if a.pose_resize != "none" and not (a.pose_path and a.pose_path.lower().endswith(".avi")):
+        ap.error("--pose_resize goes with an MJPEG --pose_path (.avi); a .pt / .npy dict is taken at the size it has")
     if a.input_image:
         if (a.clip_path is None) == (a.clip_random_init_seed is None):
             ap.error("--input_image needs exactly one of --clip_path / --clip_random_init_seed")
@@ -259,7 +267,11 @@ def main():
     if a.pose_path:
         weights = a.pose_weights_path if a.pose_weights_path else sfa.synth_pose_state_dict(seed=a.pose_random_init_seed)
         pose_embedder = sfa.PoseEmbedder(weights, device=device, strict=cfg.get("pose_weights_strict", True))
-        pose_data = load_pose_mjpeg(a.pose_path, a.ref_pose_path, device) if pose_is_mjpeg else load_pose(a.pose_path)
+        if pose_is_mjpeg:
+            pose_size = None if a.pose_resize == "none" else (8 * a.latent_height, 8 * a.latent_width)
+            pose_data = load_pose_mjpeg(a.pose_path, a.ref_pose_path, device, pose_size, "stretch" if pose_size is None else a.pose_resize)
+        else:
+            pose_data = load_pose(a.pose_path)
     image_encoder = input_image = None
     if a.input_image:
         if gen.model.model_type != "i2v":

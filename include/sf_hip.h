@@ -838,6 +838,42 @@ int sf_jpeg_decode_frames(const void* upload, size_t upload_bytes, const int32_t
                           int dtype, int32_t* status, void* stream);
 
 /* ==========================================================================================
+ * Frame resizer (uint8 frames -> frames of another size): what the reference does on the host with Pillow
+ * (inference.py:84-88, transforms.Resize on a PIL image = antialiased bilinear; causal_diffusion_inference.py:158,
+ * image.resize = bicubic), with Pillow's bits.  Pillow's 8-bit resampler is exact integer arithmetic: per axis a table of
+ * 22-bit fixed-point coefficients, one pass
+ *   out = clamp((2^21 + sum_{x < xmax} px[xmin + x] * coef[x]) >> 22, 0, 255)      (arithmetic shift, int32)
+ * the horizontal pass first, rounded to uint8, then the vertical pass over its result.  The numbers are defined by
+ * self_forcing_amd/resize_reference.py (`coefficients`, `resize`), which the kernel equals bit for bit.
+ *
+ * The caller computes the two tables (the library never does: the double-precision arithmetic has one definition) and
+ * passes them as DEVICE memory, for an axis of `in` pixels (the crop's size) resampled to `out`:
+ *   bounds int32 [out][2]    (xmin, xmax): the first input pixel and the number of taps of output pixel xx, relative to
+ *                            the crop; 0 <= xmin, xmin + xmax <= in, xmax <= ks
+ *   coefs  int32 [out][ks]   ks = sf_resize_kernel_size(in, out, filter) = ceil(support * max(in / out, 1)) * 2 + 1 with
+ *                            support 1 (bilinear) or 2 (bicubic); entries past xmax are not read
+ * An axis that keeps its size takes the table the same arithmetic gives (one weight 1 << 22): no special case.  The
+ * kernel clamps what it reads from the tables to the crop, so a wrong table gives wrong pixels and nothing else.
+ * One fused kernel (a workgroup resamples the input rows of a 16 x 64 output tile horizontally into LDS, then that
+ * vertically); its LDS grows with the reduction, so in / out may be at most SF_RESIZE_MAX_RATIO per axis (any
+ * enlargement is taken); a larger reduction is refused.  The library keeps no state and needs no workspace.
+ * ========================================================================================== */
+
+#define SF_RESIZE_MAX_RATIO 8
+enum sf_resize_filter { SF_RESIZE_BILINEAR = 0, SF_RESIZE_BICUBIC = 1 };
+
+/* Columns of the coefficient table of one axis; 0 = malformed arguments (sf_last_error says which). */
+int sf_resize_kernel_size(int in_size, int out_size, int filter);
+/* frames uint8 in `layout` (enum sf_jpeg_layout, n frames of h x w) -> out in `out_layout` / `out_dtype` (enum
+ * sf_jpeg_dtype: u8 = the samples, f32 / bf16 = u8 / 127.5 - 1 as the decoder converts), n frames of out_h x out_w.
+ * crop: HOST int32 [4] = (top, left, height, width) inside the frame, or NULL for the whole frame: exactly
+ * im.crop(...).resize(...), no tap reaches outside it.  The tables are for crop size -> output size.  frames 4-byte, out
+ * 16-byte aligned. */
+int sf_resize_frames(const void* frames, int layout, int n, int h, int w, const int32_t* crop, const int32_t* bounds_h,
+                     const int32_t* coefs_h, const int32_t* bounds_v, const int32_t* coefs_v, int filter, void* out,
+                     int out_layout, int out_dtype, int out_h, int out_w, void* stream);
+
+/* ==========================================================================================
  * Pose front end (DWPose frames -> pose tokens): `dwpose_embedding` and `randomref_embedding_pose` of the many-step
  * sampler (pipeline/causal_diffusion_inference.py:87-122) with their input transform (:337-343).  Runs once per clip.
  * Activations are channels-last bf16 volumes [T][H][W][C] with C = 8 (the three input channels, stored padded with

@@ -49,6 +49,9 @@ JPEG_LAYOUTS = {"hwc": 0, "pose": 1, "chw": 2}
 JPEG_DECODE_STATUS = {1: "a bit pattern that is no Huffman code", 2: "a zero run past the 63rd coefficient", 4: "a truncated restart interval",
                       8: "a wrong number of restart markers"}
 JPEG_DECODE_FILE_BYTES = 8960
+# enum sf_resize_filter; SF_RESIZE_MAX_RATIO (layouts and output types are the decoder's: JPEG_LAYOUTS, JPEG_DTYPES)
+RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1}
+RESIZE_MAX_RATIO = 8
 # enum sf_clip_dtype
 CLIP_DTYPES = {"float32": 0, "bfloat16": 1}
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
@@ -350,6 +353,8 @@ SIGNATURES = {
     "sf_jpeg_decode_entropy": (C.c_int, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "sf_jpeg_decode_pixels": (C.c_int, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _i, _i, _vp]),
     "sf_jpeg_decode_frames": (C.c_int, [_vp, _sz, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i, _i, _vp, _vp]),
+    "sf_resize_kernel_size": (C.c_int, [_i, _i, _i]),
+    "sf_resize_frames": (C.c_int, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "sf_embedding_gather": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_t5_softmax_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_mul_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),

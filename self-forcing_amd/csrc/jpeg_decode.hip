@@ -17,6 +17,7 @@
 // block count and byte range, every read is clamped to the upload, every write to the call's geometry: a damaged file
 // sets bits of its status word and leaves zeros, it cannot reach another file's memory.
 #include "sf_host.h"
+#include "pixel_format.h"
 
 namespace {
 
@@ -340,28 +341,6 @@ __global__ __launch_bounds__(256) void jpeg_decode_idct_kernel(const int16_t* __
 constexpr int fix16(double x) { return (int)(x * 65536 + 0.5); }
 constexpr int FIX_CR_R = fix16(1.402), FIX_CB_G = fix16(0.344136286), FIX_CR_G = fix16(0.714136286), FIX_CB_B = fix16(1.772);
 
-__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-// u8 / 127.5 - 1, the divide and the subtract each rounded to fp32 (jpeg_reference.to_float)
-__device__ __forceinline__ float to_pm1(int v) {
-#pragma clang fp contract(off)
-  const float q = (float)v / 127.5f;
-  return q - 1.0f;
-}
-
-__device__ __forceinline__ void convert(int v, uint8_t& o) { o = (uint8_t)v; }
-__device__ __forceinline__ void convert(int v, float& o) { o = to_pm1(v); }
-__device__ __forceinline__ void convert(int v, bf16_t& o) { o = f2bf(to_pm1(v)); }
-
-// four values next to each other, 4 sizeof(T)-aligned
-__device__ __forceinline__ void store4(uint8_t* p, const int (&v)[4]) {
-  *(uint32_t*)p = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
-}
-__device__ __forceinline__ void store4(float* p, const int (&v)[4]) { *(f32x4*)p = f32x4{to_pm1(v[0]), to_pm1(v[1]), to_pm1(v[2]), to_pm1(v[3])}; }
-__device__ __forceinline__ void store4(bf16_t* p, const int (&v)[4]) {
-  *(bf16x4*)p = bf16x4{f2bf(to_pm1(v[0])), f2bf(to_pm1(v[1])), f2bf(to_pm1(v[2])), f2bf(to_pm1(v[3]))};
-}
-
 // the chroma plane `p` (rows of `ld`) at output pixels x0 .. x0 + 3 of row y: libjpeg's triangle filter over the
 // component's true size tcw x tch, edges replicated (jpeg_reference.upsample)
 __device__ __forceinline__ void chroma4(const uint8_t* __restrict__ p, int ld, int lbx, int lby, int tcw, int tch, int x0, int y, int (&c)[4]) {
@@ -429,22 +408,7 @@ __global__ __launch_bounds__(256) void jpeg_decode_colour_kernel(const uint8_t* 
     }
   }
   T* o = out + f * sn + (long)y * sy + (long)x0 * sx;
-  if (sx == 1 && (W & 3) == 0) {                                   // planar rows of whole quads
-#pragma unroll
-    for (int c = 0; c < 3; ++c) store4(o + c * sc, rgb[c]);
-  } else if (sizeof(T) == 1 && sx == 3 && sc == 1 && (W & 3) == 0) {         // uint8 [.., W, 3]: twelve bytes
-    uint32_t w[3] = {0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < 12; ++i) w[i >> 2] |= (uint32_t)rgb[i % 3][i / 3] << (8 * (i & 3));
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ((uint32_t*)o)[i] = w[i];
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (x0 + i < W)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) convert(rgb[c][i], o[c * sc + i * sx]);
-  }
+  store_rgb4(o, rgb, x0, W, sc, sx);
 }
 
 int launch_entropy(const char* who, const DecGeometry& g, const void* upload, size_t upload_bytes, int n, int max_intervals, char* ws, void* coef,

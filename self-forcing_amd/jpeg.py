@@ -16,6 +16,7 @@ import torch
 
 from . import _lib, ops
 from . import jpeg_reference as jr
+from . import resize as resize_mod
 
 Tensor = torch.Tensor
 
@@ -166,6 +167,8 @@ class JpegDecoder:
         self._ws: Optional[Tensor] = None
         self._host: Optional[Tensor] = None
         self._dev: Optional[Tensor] = None
+        self._full: Optional[Tensor] = None                        # decode(size=...): the frames at the files' own size
+        self._resizer = None
         self.status: List[int] = []                                # per file of the last call: _lib.JPEG_DECODE_STATUS bits
 
     @staticmethod
@@ -247,16 +250,41 @@ class JpegDecoder:
             self._finish(status, strict)
         return coef
 
-    def decode(self, files: Sequence[bytes], layout: str = "hwc", dtype=torch.uint8, strict: bool = True) -> Tensor:
+    def _decode_resized(self, files: Sequence[bytes], layout: str, dtype, strict: bool, size, filter: str, fit: str) -> Tensor:
+        """`decode` with `size`: the files' own size as uint8 "hwc" into a reused buffer, then the resizer into layout / dtype."""
+        oh, ow = resize_mod.check_arguments(size, filter, dtype, None, fit, "JpegDecoder")
+        files, infos = self._parse(files)
+        n, h, w = len(files), infos[0].height, infos[0].width
+        resize_mod.crop_box(h, w, oh, ow, None, fit)               # the ratio limit, before anything is uploaded
+        with torch.cuda.device(self.device):
+            up, nbytes, info, max_iv = self._upload(files, infos)
+            if self._full is None or self._full.numel() < n * h * w * 3:
+                self._full = torch.empty(n * h * w * 3, dtype=torch.uint8, device=self.device)
+            full = self._full[:n * h * w * 3].view(n, h, w, 3)
+            status = torch.empty(n, dtype=torch.int32, device=self.device)
+            ops.jpeg_decode_frames(up, nbytes, n, h, w, info.sampling, max_iv, self._workspace(n, info, max_iv), full, "hwc", status)
+            if self._resizer is None:
+                self._resizer = resize_mod.FrameResizer(self.device)
+            out = self._resizer.resize(full, (oh, ow), filter, "hwc", layout, dtype, fit=fit)
+            self._finish(status, strict)
+        return out
+
+    def decode(self, files: Sequence[bytes], layout: str = "hwc", dtype=torch.uint8, strict: bool = True, size: Optional[Sequence[int]] = None,
+               filter: str = "bilinear", fit: str = "stretch") -> Tensor:
         """The files' frames.  layout "hwc": [N, H, W, 3] (what `JpegEncoder` takes as uint8); "pose": [3, N, H, W] (what
         `PoseEmbedder.embed` / `PoseStream.push` take); "chw": [N, 3, H, W] (what the VAE encoders take as float).  dtype
         uint8: the samples; float32 / bfloat16: u8 / 127.5 - 1 (each operation rounded to fp32, bf16 to nearest even).
         A damaged file (a truncated scan, a bad code) raises SfHipError naming the file and what is wrong with it; with
-        strict=False the frames are returned anyway (undecoded blocks are grey) and `self.status` holds each file's bits."""
+        strict=False the frames are returned anyway (undecoded blocks are grey) and `self.status` holds each file's bits.
+        size=(H, W): the frames resized on the device to H x W as `FrameResizer.resize` does it (`filter` "bilinear" /
+        "bicubic", `fit` "stretch" / "cover"; Pillow's bits on the decoded samples): they are decoded as uint8 "hwc" into a
+        buffer the decoder keeps, then resampled into `layout` / `dtype`."""
         if layout not in _lib.JPEG_LAYOUTS:
             raise ValueError(f"layout must be 'hwc', 'pose' or 'chw', got {layout!r}")
         if dtype not in _DECODE_DTYPES:
             raise ValueError(f"dtype must be torch.uint8, float32 or bfloat16, got {dtype}")
+        if size is not None:
+            return self._decode_resized(files, layout, dtype, strict, size, filter, fit)
         files, infos = self._parse(files)
         with torch.cuda.device(self.device):
             up, nbytes, info, max_iv = self._upload(files, infos)
@@ -269,17 +297,21 @@ class JpegDecoder:
         return out
 
 
-def pose_feed(files: Sequence[bytes], decoder: JpegDecoder, frames_per_piece: int = 12) -> Iterator[Tensor]:
+def pose_feed(files: Sequence[bytes], decoder: JpegDecoder, frames_per_piece: int = 12, size: Optional[Sequence[int]] = None, filter: str = "bilinear",
+              fit: str = "stretch") -> Iterator[Tensor]:
     """JPEG pose frames as the pieces `CausalInferencePipeline.stream(pose_feed=...)` pulls: uint8 [3, n, H, W], n =
     `frames_per_piece` (the last piece may be shorter), each decoded when it is asked for.  `files` may be any iterable,
-    a live source included."""
+    a live source included.  size=(H, W) resizes every piece on the device (`JpegDecoder.decode(size=, filter=, fit=)`), so
+    the source's frames may have any size."""
     if frames_per_piece < 1:
         raise ValueError(f"frames_per_piece must be >= 1, got {frames_per_piece}")
+    if size is not None:
+        resize_mod.check_arguments(size, filter, torch.uint8, None, fit, "pose_feed")
     piece: List[bytes] = []
     for f in files:
         piece.append(f)
         if len(piece) == frames_per_piece:
-            yield decoder.decode(piece, layout="pose")
+            yield decoder.decode(piece, layout="pose", size=size, filter=filter, fit=fit)
             piece = []
     if piece:
-        yield decoder.decode(piece, layout="pose")
+        yield decoder.decode(piece, layout="pose", size=size, filter=filter, fit=fit)

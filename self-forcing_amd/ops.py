@@ -587,6 +587,27 @@ def jpeg_decode_frames(upload: Tensor, upload_bytes: int, n: int, h: int, w: int
     return out
 
 
+# -------------------------------------------------------------------------------------- frame resizer (csrc/resize.hip)
+def resize_kernel_size(in_size: int, out_size: int, filter: str) -> int:
+    """Columns of one axis' coefficient table (sf_resize_kernel_size); equals resize_reference.kernel_size."""
+    ks = lib().sf_resize_kernel_size(in_size, out_size, _lib.RESIZE_FILTERS[filter])
+    if ks == 0:
+        check(-1, "sf_resize_kernel_size")
+    return ks
+
+
+def resize_frames(frames: Tensor, tables_h, tables_v, filter: str, layout: str = "hwc", out_layout: str = "hwc", dtype=torch.uint8, crop=None,
+                  out: Optional[Tensor] = None) -> Tensor:
+    """uint8 frames in `layout` -> resized frames in `out_layout` / `dtype` (torch.ops.sf_hip.resize_frames over sf_resize_frames).
+    tables_h / tables_v: (bounds, coefs) device int32 tensors of `resize_reference.coefficients` for the crop's width -> the
+    output's and its height -> the output's; crop = (top, left, height, width) or None."""
+    crop = None if crop is None else [int(v) for v in crop]
+    if out is not None:
+        torch.ops.sf_hip.resize_frames_out(out, frames, tables_h[0], tables_h[1], tables_v[0], tables_v[1], filter, layout, out_layout, crop)
+        return out
+    return torch.ops.sf_hip.resize_frames(frames, tables_h[0], tables_h[1], tables_v[0], tables_v[1], filter, layout, out_layout, dtype, crop)
+
+
 # -------------------------------------------------------------------------------------- CLIP image encoder (csrc/clip_encoder.hip)
 def _cur(t: Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream

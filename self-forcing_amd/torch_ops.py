@@ -29,6 +29,8 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::taehv_encode_frames(model, state!, scratch!, pixels, out!, H, W, lead) -> ()
     sf_hip::t5_encode(model, ids, mask, buckets, workspace!) -> out
     sf_hip::clip_encode(model, frames, workspace!) -> out
+    sf_hip::resize_frames(frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, dtype, crop?) -> out
+    sf_hip::resize_frames_out(out!, frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, crop?) -> ()
 
 Models (weights + C descriptors) are Python objects that own device memory; operators take an integer HANDLE from
 `register_model` (a constant to a tracer).  There is no CPU implementation: CPU tensors raise.
@@ -853,5 +855,90 @@ def _(model, frames, workspace):
     return frames.new_empty((frames.shape[0], s.seq_len, s.dim), dtype=torch.float32)
 
 
+# ------------------------------------------------------------------------------------------ frame resizer
+_RESIZE_DTYPES = {torch.uint8: "uint8", torch.float32: "float32", torch.bfloat16: "bfloat16"}
+
+
+def _frame_shape(layout: str, n: int, h: int, w: int) -> Tuple[int, int, int, int]:
+    if layout not in _lib.JPEG_LAYOUTS:
+        raise ValueError(f"layout must be 'hwc', 'pose' or 'chw', got {layout!r}")
+    return {"hwc": (n, h, w, 3), "pose": (3, n, h, w), "chw": (n, 3, h, w)}[layout]
+
+
+def _frame_geometry(frames: Tensor, layout: str) -> Tuple[int, int, int]:
+    """(n, h, w) of a uint8 frame tensor in `layout`."""
+    if layout not in _lib.JPEG_LAYOUTS:
+        raise ValueError(f"layout must be 'hwc', 'pose' or 'chw', got {layout!r}")
+    if frames.dim() != 4 or frames.shape[{"hwc": 3, "pose": 0, "chw": 1}[layout]] != 3:
+        raise ValueError(f"resize_frames: frames in layout {layout!r} must be {'[N, H, W, 3]' if layout == 'hwc' else '[3, N, H, W]' if layout == 'pose' else '[N, 3, H, W]'}, "
+                         f"got {tuple(frames.shape)}")
+    dims = {"hwc": (0, 1, 2), "pose": (1, 2, 3), "chw": (0, 2, 3)}[layout]
+    return tuple(int(frames.shape[d]) for d in dims)
+
+
+def _resize_launch(out: Tensor, frames: Tensor, bounds_h: Tensor, coefs_h: Tensor, bounds_v: Tensor, coefs_v: Tensor, filter: str, layout: str,
+                   out_layout: str, crop: Optional[Sequence[int]]) -> None:
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"resize_frames: frames must be uint8, got {frames.dtype}")
+    n, h, w = _frame_geometry(frames, layout)
+    if filter not in _lib.RESIZE_FILTERS:
+        raise ValueError(f"filter must be 'bilinear' or 'bicubic', got {filter!r}")
+    if out.dtype not in _RESIZE_DTYPES:
+        raise ValueError(f"dtype must be torch.uint8, float32 or bfloat16, got {out.dtype}")
+    if out_layout not in _lib.JPEG_LAYOUTS or out.dim() != 4:
+        raise ValueError(f"resize_frames: out must be a 4-d tensor in layout 'hwc', 'pose' or 'chw', got {out_layout!r} {tuple(out.shape)}")
+    on, oh, ow = _frame_geometry(out, out_layout)
+    if on != n:
+        raise ValueError(f"resize_frames: out holds {on} frames, frames {n}")
+    _need_gpu(frames, "frames", torch.uint8), _need_gpu(out, "out", None)
+    if not frames.is_contiguous() or not out.is_contiguous() or frames.data_ptr() % 4 or out.data_ptr() % 16:
+        raise ValueError("resize_frames: frames and out must be contiguous, frames 4-byte and out 16-byte aligned")
+    ch, cw = (h, w) if crop is None else (int(crop[2]), int(crop[3]))
+    lib = _lib.lib()
+    fcode = _lib.RESIZE_FILTERS[filter]
+    for name, b, k, size_in, size_out in (("horizontal", bounds_h, coefs_h, cw, ow), ("vertical", bounds_v, coefs_v, ch, oh)):
+        ks = lib.sf_resize_kernel_size(size_in, size_out, fcode)
+        if ks == 0:
+            _lib.check(-1, "sf_resize_kernel_size")
+        for t in (b, k):
+            _need_gpu(t, f"the {name} table", torch.int32)
+        if tuple(b.shape) != (size_out, 2) or tuple(k.shape) != (size_out, ks) or not b.is_contiguous() or not k.is_contiguous():
+            raise ValueError(f"resize_frames: the {name} table must be bounds [{size_out}, 2] and coefs [{size_out}, {ks}] for {size_in} -> {size_out} {filter}, "
+                             f"got {tuple(b.shape)} and {tuple(k.shape)}")
+    ccrop = None if crop is None else (C.c_int32 * 4)(*[int(v) for v in crop])
+    _lib.check(lib.sf_resize_frames(frames.data_ptr(), _lib.JPEG_LAYOUTS[layout], n, h, w, ccrop, bounds_h.data_ptr(), coefs_h.data_ptr(), bounds_v.data_ptr(),
+                                    coefs_v.data_ptr(), fcode, out.data_ptr(), _lib.JPEG_LAYOUTS[out_layout], _lib.JPEG_DTYPES[_RESIZE_DTYPES[out.dtype]], oh, ow,
+                                    _stream(frames)), "sf_resize_frames")
+
+
+@custom_op(f"{NAMESPACE}::resize_frames", mutates_args=())
+def resize_frames(frames: Tensor, bounds_h: Tensor, coefs_h: Tensor, bounds_v: Tensor, coefs_v: Tensor, filter: str, layout: str, out_layout: str,
+                  dtype: torch.dtype, crop: Optional[List[int]] = None) -> Tensor:
+    """uint8 frames in `layout` -> frames of bounds_v.shape[0] x bounds_h.shape[0] in `out_layout` / `dtype`, with Pillow's bits
+    (sf_resize_frames).  The tables are `resize_reference.coefficients` of the two axes, on the device."""
+    n, _, _ = _frame_geometry(frames, layout)
+    out = torch.empty(_frame_shape(out_layout, n, bounds_v.shape[0], bounds_h.shape[0]), dtype=dtype, device=frames.device)
+    _resize_launch(out, frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, crop)
+    return out
+
+
+@resize_frames.register_fake
+def _(frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, dtype, crop=None):
+    n, _, _ = _frame_geometry(frames, layout)
+    return frames.new_empty(_frame_shape(out_layout, n, bounds_v.shape[0], bounds_h.shape[0]), dtype=dtype)
+
+
+@custom_op(f"{NAMESPACE}::resize_frames_out", mutates_args=("out",))
+def resize_frames_out(out: Tensor, frames: Tensor, bounds_h: Tensor, coefs_h: Tensor, bounds_v: Tensor, coefs_v: Tensor, filter: str, layout: str,
+                      out_layout: str, crop: Optional[List[int]] = None) -> None:
+    """`resize_frames` into a caller's tensor (its shape gives the output size, its dtype the output type)."""
+    _resize_launch(out, frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, crop)
+
+
+@resize_frames_out.register_fake
+def _(out, frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, crop=None):
+    return None
+
+
 OPS = ("attention", "attention_accum", "dit_forward_i2v", "i2v_assemble_y", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "vae_encode_frames", "taehv_decode_frames",
-       "taehv_encode_frames", "t5_encode", "clip_encode")
+       "taehv_encode_frames", "t5_encode", "clip_encode", "resize_frames", "resize_frames_out")
