@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SF_HIP_ABI_VERSION 10
+#define SF_HIP_ABI_VERSION 11
 
 int sf_abi_version(void);
 const char* sf_last_error(void);
@@ -152,38 +152,34 @@ int sf_kv_evict(void* cache, int B, int64_t cache_tokens, int row_elems, int sin
  * (causal_model.py:230-234) and for T5 cross-attention (model.py:189).
  *   q   [B, Lq, H, D]  with token stride q_stride (elements) and batch stride q_bstride
  *   k,v [B, Lk, H, D]  with token stride kv_stride and batch stride kv_bstride
- *   out [B, Lq, H, D]  token stride o_stride, batch stride o_bstride */
-int sf_attention(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq, int Lk,
-                 int64_t q_stride, int64_t q_bstride, int64_t kv_stride, int64_t kv_bstride,
-                 int64_t o_stride, int64_t o_bstride, void* stream);
-
-/* The same with the kernel structure named by the caller instead of picked from the shape (tests and A/B timing;
- * every structure computes every shape): SF_ATTN_R64 = 64 query rows per wave, one wave per SIMD, hand-scheduled
- * (256 rows per workgroup); SF_ATTN_W8 = 8-wave anti-phase workgroups of 256 rows; SF_ATTN_W4 = 4-wave workgroups of
- * 128 rows.  sf_attention == sf_attention_ex(..., SF_ATTN_AUTO, stream). */
+ *   out [B, Lq, H, D]  token stride o_stride, batch stride o_bstride
+ * structure: SF_ATTN_AUTO picks from the shape (on Lk, not on the folded key counts); the others name the kernel
+ *   (tests and A/B timing; every structure computes every shape): SF_ATTN_R64 = 64 query rows per wave, one wave per
+ *   SIMD, hand-scheduled (256 rows per workgroup); SF_ATTN_W8 = 8-wave anti-phase workgroups of 256 rows; SF_ATTN_W4 =
+ *   4-wave workgroups of 128 rows.
+ * accumulate: out = bf16(float(out) + attention), the sum taken in fp32 in the kernel's epilogue and rounded once.  The
+ *   i2v cross-attention (model.py:240-266) is o(attn(q, k, v) + attn(q, k_img, v_img)): the image attention accumulates
+ *   into the buffer the text attention wrote, with no third buffer and no elementwise pass.  An epilogue variant of the
+ *   SF_ATTN_W8 and SF_ATTN_W4 structures: SF_ATTN_AUTO picks between those two, SF_ATTN_R64 is an error.  Every query
+ *   row of `out` must hold a finite value on entry.
+ * keys / log2w (DEVICE arrays, int32 [B] / float [B], as sf_cross_fold_scan writes them; read by the kernels only): a key
+ *   slab whose trailing rows repeat (a prompt's padding keys).  Sample b attends only rows [0, keys[b]) and log2w[b] is
+ *   added to the exp2-domain score of row keys[b] - 1, which so stands for 2^log2w[b] identical rows.  Both NULL: every
+ *   row.  Not built together with accumulate (an error). */
 enum sf_attn_structure { SF_ATTN_AUTO = 0, SF_ATTN_R64 = 1, SF_ATTN_W8 = 2, SF_ATTN_W4 = 3 };
-int sf_attention_ex(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq, int Lk,
-                    int64_t q_stride, int64_t q_bstride, int64_t kv_stride, int64_t kv_bstride,
-                    int64_t o_stride, int64_t o_bstride, int structure, void* stream);
 
-/* The same over a key slab whose trailing rows repeat (a prompt's padding keys): sample b attends only rows
- * [0, keys[b]) and log2w[b] is added to the exp2-domain score of row keys[b] - 1, which so stands for 2^log2w[b]
- * identical rows.  `keys` (int32 [B]) and `log2w` (float [B]) are DEVICE arrays as sf_cross_fold_scan writes them, read
- * by the kernels only; both NULL: every row, exactly sf_attention_ex.  SF_ATTN_AUTO decides on Lk, not on the counts. */
-int sf_attention_fold(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq, int Lk,
-                      int64_t q_stride, int64_t q_bstride, int64_t kv_stride, int64_t kv_bstride,
-                      int64_t o_stride, int64_t o_bstride, int structure, const int32_t* keys, const float* log2w,
-                      void* stream);
+typedef struct sf_attention_args {
+  const void *q, *k, *v;
+  void* out;
+  int32_t B, H, Lq, Lk;
+  int64_t q_stride, q_bstride, kv_stride, kv_bstride, o_stride, o_bstride;
+  int32_t structure;          /* enum sf_attn_structure */
+  int32_t accumulate;         /* 1: out += attention */
+  const int32_t* keys;        /* both or neither */
+  const float* log2w;
+} sf_attention_args;
 
-/* sf_attention_ex that ADDS into `out` instead of overwriting it: out = bf16(float(out) + softmax(q k^T / sqrt(D)) v), the
- * sum taken in fp32 in the kernel's epilogue and rounded once.  The i2v cross-attention (model.py:240-266) is
- * o(attn(q, k, v) + attn(q, k_img, v_img)): the image attention accumulates into the buffer the text attention wrote,
- * with no third buffer and no elementwise pass.  A compile-time epilogue variant of the SF_ATTN_W8 and SF_ATTN_W4
- * structures; SF_ATTN_AUTO picks between those two, SF_ATTN_R64 is an error (the hand-scheduled stream has no such
- * epilogue).  Every query row of `out` must hold a finite value on entry. */
-int sf_attention_accum(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq, int Lk,
-                       int64_t q_stride, int64_t q_bstride, int64_t kv_stride, int64_t kv_bstride,
-                       int64_t o_stride, int64_t o_bstride, int structure, void* stream);
+int sf_attention(const sf_attention_args* args, void* stream);
 
 /* Per layer l and sample b of the cross-attention caches ck / cv (HOST arrays [layers] of device pointers, each
  * [B, text_len, row_elems] bf16): same = the number of trailing rows that equal the last row bit for bit in BOTH caches;
@@ -308,28 +304,6 @@ typedef struct sf_forward_args {
   int64_t global_end;                     /* current_start + F*h*w (only written to kv_index_out) */
 } sf_forward_args;
 
-size_t sf_dit_workspace_bytes(const sf_model* model, int batch, int frames, int lat_h, int lat_w,
-                              int groups);
-int sf_dit_forward(const sf_model* model, const sf_forward_args* args, void* stream);
-/* Two passes of the rollout in ONE call: the context pass of chunk k (`context_pass`, cache_only = 1: it rewrites the
- * chunk's K / V "clean", causal_inference.py:226-235) and the first denoising pass of chunk k + 1 (`next_pass`,
- * :190-205), which the reference runs back to back.  Layer l of the second needs only layer l's K / V of the first, so
- * the two run layer by layer as one batch of 2 x batch samples through every row-wise kernel and GEMM (twice the rows
- * per GEMM) and one after the other through the cache (eviction, K / V write, attention).  Results are bit-identical to
- * two sf_dit_forward calls.  Both argument structs must name the same caches, latent geometry, batch and groups, and the
- * same workspace, sized sf_dit_workspace_bytes(model, 2 * batch, ...); neither may have init_cross set;
- * `next_pass->kv_index_out` (if any) receives the final indices. */
-int sf_dit_forward_pair(const sf_model* model, const sf_forward_args* context_pass, const sf_forward_args* next_pass,
-                        void* stream);
-/* The two calls above with the cross-attention padding folded: `cross_keys` (int32) and `cross_log2w` (float) are device
- * arrays [num_layers][batch] that belong to the cross-attention caches.  A pass with init_cross fills them
- * (sf_cross_fold_scan) behind the caches; every pass hands layer l's slices to its cross-attention (sf_attention_fold).
- * Caches filled by anything else need one sf_cross_fold_scan first.  Both NULL: sf_dit_forward / sf_dit_forward_pair. */
-int sf_dit_forward_fold(const sf_model* model, const sf_forward_args* args, int32_t* cross_keys, float* cross_log2w,
-                        void* stream);
-int sf_dit_forward_pair_fold(const sf_model* model, const sf_forward_args* context_pass, const sf_forward_args* next_pass,
-                             const int32_t* cross_keys, const float* cross_log2w, void* stream);
-
 /* ------------------------------------------------------------------------------------------
  * The i2v model type (CausalWanModel(model_type='i2v', in_dim=36), causal_model.py:767-775, :844-846; WanI2VCrossAttention
  * and MLPProj, model.py:222-266, :469-481).  Everything i2v travels in the structs below, beside an sf_model /
@@ -386,16 +360,36 @@ typedef struct sf_i2v_args {
   void* const* vimg_cache_host;           /*   written with init_cross, read by every pass                              */
 } sf_i2v_args;
 
-/* sf_dit_workspace_bytes plus the image context's buffers (the workspace an i2v pass needs). */
-size_t sf_dit_i2v_workspace_bytes(const sf_model* model, const sf_i2v_model* i2v_model, int batch, int frames, int lat_h,
-                                  int lat_w, int groups);
-/* One pass of an i2v generator: sf_dit_forward_fold (cross_keys / cross_log2w both NULL: no folding of the text keys)
- * with the 36-channel patch embedding and, behind every layer's text cross-attention, sf_attention_accum over the
- * clip_len image keys.  With init_cross the image context and every layer's k_img / v_img are computed beside the text
- * K / V; cache_only and the rolling window behave as in sf_dit_forward.  Not built: the two-pass call and fp8 Linears
- * (model->fp8 != 0 is an error). */
-int sf_dit_forward_i2v(const sf_model* model, const sf_i2v_model* i2v_model, const sf_forward_args* args, const sf_i2v_args* i2v_args,
-                       int32_t* cross_keys, float* cross_log2w, void* stream);
+/* One call of the denoiser: one pass, or two passes of the rollout.
+ * Two passes are the context pass of chunk k (passes[0], cache_only = 1: it rewrites the chunk's K / V "clean",
+ * causal_inference.py:226-235) and the first denoising pass of chunk k + 1 (passes[1], :190-205), which the reference
+ * runs back to back.  Layer l of the second needs only layer l's K / V of the first, so the two run layer by layer as one
+ * batch of 2 x batch samples through every row-wise kernel and GEMM (twice the rows per GEMM) and one after the other
+ * through the cache (eviction, K / V write, attention): bit-identical to two one-pass calls.  Both passes must name the
+ * same caches, latent geometry, batch and groups, and the same workspace, sized for 2 x batch; neither may have
+ * init_cross set; passes[1]->kv_index_out (if any) receives the final indices.
+ * cross_keys (int32) / cross_log2w (float): device arrays [num_layers][batch] that belong to the cross-attention caches,
+ * folding the prompt's padding keys.  A pass with init_cross fills them (sf_cross_fold_scan) behind the caches; every
+ * pass hands layer l's slices to its cross-attention.  Caches filled by anything else need one sf_cross_fold_scan first.
+ * Both NULL: every text key is attended.
+ * i2v_model / i2v_args: an i2v generator's weights and this pass's image tensors: the 36-channel patch embedding and,
+ * behind every layer's text cross-attention, the accumulating attention over the clip_len image keys.  With init_cross
+ * the image context and every layer's k_img / v_img are computed beside the text K / V.  Not built: two passes and fp8
+ * Linears (model->fp8 != 0) of an i2v generator; both are errors. */
+typedef struct sf_forward_call {
+  const sf_forward_args* passes[2];       /* cache_only passes first */
+  int32_t n_passes;                       /* 1 or 2 */
+  int32_t* cross_keys;                    /* both or neither; written only by a pass with init_cross */
+  float* cross_log2w;
+  const sf_i2v_model* i2v_model;          /* both or neither; NULL: a t2v generator */
+  const sf_i2v_args* i2v_args;
+} sf_forward_call;
+
+int sf_dit_forward(const sf_model* model, const sf_forward_call* call, void* stream);
+/* Bytes of sf_forward_args.workspace for one pass of `batch` samples (two passes: 2 x batch); with i2v_model (NULL: a
+ * t2v generator) the image context's buffers behind them.  0 for a bad shape. */
+size_t sf_dit_workspace_bytes(const sf_model* model, const sf_i2v_model* i2v_model, int batch, int frames, int lat_h, int lat_w,
+                              int groups);
 
 /* ==========================================================================================
  * Wan VAE decode (latents -> pixels): WanVAEWrapper.decode_to_pixel -> WanVAE_.decode /

@@ -21,7 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("SF_HIP_LIB") or os.path.join(CSRC, "libsf_hip.so")   # SF_HIP_LIB: alternate builds (kernel ablation timing)
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 FP8_AMAX_PARTS = 1024   # SF_FP8_AMAX_PARTS: scratch floats per segment behind the scales of sf_quantize_fp8
 
 # epilogue codes (enum sf_epilogue)
@@ -72,6 +72,13 @@ class GemmArgs(C.Structure):
         ("a_bstride", C.c_int64), ("w_bstride", C.c_int64), ("o_bstride", C.c_int64), ("r_bstride", C.c_int64),
         ("structure", C.c_int32),
     ]
+
+
+class AttentionArgs(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("q", "k", "v", "out")]
+                + [(n, C.c_int32) for n in ("B", "H", "Lq", "Lk")]
+                + [(n, C.c_int64) for n in ("q_stride", "q_bstride", "kv_stride", "kv_bstride", "o_stride", "o_bstride")]
+                + [("structure", C.c_int32), ("accumulate", C.c_int32), ("keys", C.c_void_p), ("log2w", C.c_void_p)])
 
 
 class LayerWeights(C.Structure):
@@ -152,6 +159,11 @@ class I2VArgs(C.Structure):
     _fields_ = [("clip_feature", C.c_void_p), ("y", C.c_void_p),
                 ("y_bstride", C.c_int64), ("y_cstride", C.c_int64), ("y_fstride", C.c_int64), ("y_channels", C.c_int32),
                 ("kimg_cache_host", C.POINTER(C.c_void_p)), ("vimg_cache_host", C.POINTER(C.c_void_p))]
+
+
+class ForwardCall(C.Structure):
+    _fields_ = [("passes", C.POINTER(ForwardArgs) * 2), ("n_passes", C.c_int32), ("cross_keys", C.c_void_p), ("cross_log2w", C.c_void_p),
+                ("i2v_model", C.POINTER(I2VModel)), ("i2v_args", C.POINTER(I2VArgs))]
 
 
 class ConvArgs(C.Structure):
@@ -285,25 +297,17 @@ SIGNATURES = {
     "sf_qkv_norm_rope_cache": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64,
                                          _i, _i, _f, _vp]),
     "sf_kv_evict": (C.c_int, [_vp, _i, _i64, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "sf_attention": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _vp]),
-    "sf_attention_ex": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp]),
-    "sf_attention_fold": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp, _vp, _vp]),
-    "sf_attention_accum": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp]),
+    "sf_attention": (C.c_int, [C.POINTER(AttentionArgs), _vp]),
     "sf_cross_fold_scan": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _i, _i, _i, _vp, _vp, _vp]),
     "sf_patchify": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sf_unpatchify_x0": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "sf_add_noise": (C.c_int, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i64, _vp]),
     "sf_lincomb_bf16": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_float), _i, _i64, _vp]),
-    "sf_dit_workspace_bytes": (C.c_size_t, [C.POINTER(Model), _i, _i, _i, _i, _i]),
-    "sf_dit_forward": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), _vp]),
-    "sf_dit_forward_pair": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), C.POINTER(ForwardArgs), _vp]),
-    "sf_dit_forward_fold": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), _vp, _vp, _vp]),
-    "sf_dit_forward_pair_fold": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardArgs), C.POINTER(ForwardArgs), _vp, _vp, _vp]),
+    "sf_dit_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(I2VModel), _i, _i, _i, _i, _i]),
+    "sf_dit_forward": (C.c_int, [C.POINTER(Model), C.POINTER(ForwardCall), _vp]),
     "sf_patchify_i2v": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _vp]),
     "sf_layernorm_rows": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "sf_i2v_assemble_y": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _i, _vp]),
-    "sf_dit_i2v_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(I2VModel), _i, _i, _i, _i, _i]),
-    "sf_dit_forward_i2v": (C.c_int, [C.POINTER(Model), C.POINTER(I2VModel), C.POINTER(ForwardArgs), C.POINTER(I2VArgs), _vp, _vp, _vp]),
     "sf_conv_igemm": (C.c_int, [C.POINTER(ConvArgs), _vp]),
     "sf_conv_pick_nt": (C.c_int, [_i]),
     "sf_rmsnorm_silu_cl": (C.c_int, [_vp, _vp, _vp, _i64, _i, _i, _vp]),

@@ -76,7 +76,7 @@ __device__ __forceinline__ bf16x4 lds_tr_read(const char* p) {
 // KIND only gives self-attention (0: keys = the KV cache) and cross-attention (1: keys = the text
 // context) distinct symbols, so per-kernel profiles do not mix a 32760-key launch with a 512-key one.
 // KIND 2 (keys = the i2v image context) is the ACCUMULATE epilogue: out = bf16(float(out) + O / l), the fp32 sum
-// rounded once -- the image attention adds into the buffer the text attention wrote (sf_attention_accum).
+// rounded once -- the image attention adds into the buffer the text attention wrote (sf_attention_args.accumulate).
 template <int KIND>
 __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
   constexpr bool ACC = KIND == 2;
@@ -843,7 +843,7 @@ static int attention_launch(const void* q, const void* k, const void* v, void* o
   // (round 3: with its shorter prologue / epilogue the 64-row kernel is ahead of the 8-wave one from 512 keys on --
   // cross-attention, Lk = 512: 21.2 vs 22.1 us at one prompt, 41.7 vs 43.1 at two; Lk = 256: 15.8 vs 14.8)
   // (accumulate: the hand-scheduled r64 stream has no such epilogue, and the image context's 257 keys are below its range)
-  SF_CHECK(!(accum && structure == SF_ATTN_R64), "sf_attention_accum: the r64 structure has no accumulate epilogue (use auto, w8 or w4)");
+  SF_CHECK(!(accum && structure == SF_ATTN_R64), "sf_attention: the r64 structure has no accumulate epilogue (use auto, w8 or w4)");
   if (structure == SF_ATTN_AUTO)
     structure = (!accum && nwg64 >= 192 && Lk >= 512 && out16) ? SF_ATTN_R64 : nwg8 >= 192 ? SF_ATTN_W8 : SF_ATTN_W4;
   if (structure == SF_ATTN_R64) {
@@ -885,31 +885,9 @@ static int attention_launch(const void* q, const void* k, const void* v, void* o
   return 0;
 }
 
-extern "C" int sf_attention_fold(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
-                                 int Lk, int64_t q_stride, int64_t q_bstride, int64_t kv_stride,
-                                 int64_t kv_bstride, int64_t o_stride, int64_t o_bstride, int structure,
-                                 const int32_t* keys, const float* log2w, void* stream) {
-  return attention_launch(q, k, v, out, B, H, Lq, Lk, q_stride, q_bstride, kv_stride, kv_bstride, o_stride, o_bstride, structure,
-                          keys, log2w, false, stream);
-}
-
-extern "C" int sf_attention_accum(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
-                                  int Lk, int64_t q_stride, int64_t q_bstride, int64_t kv_stride,
-                                  int64_t kv_bstride, int64_t o_stride, int64_t o_bstride, int structure, void* stream) {
-  return attention_launch(q, k, v, out, B, H, Lq, Lk, q_stride, q_bstride, kv_stride, kv_bstride, o_stride, o_bstride, structure,
-                          nullptr, nullptr, true, stream);
-}
-
-extern "C" int sf_attention_ex(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
-                               int Lk, int64_t q_stride, int64_t q_bstride, int64_t kv_stride,
-                               int64_t kv_bstride, int64_t o_stride, int64_t o_bstride, int structure, void* stream) {
-  return sf_attention_fold(q, k, v, out, B, H, Lq, Lk, q_stride, q_bstride, kv_stride, kv_bstride, o_stride, o_bstride,
-                           structure, nullptr, nullptr, stream);
-}
-
-extern "C" int sf_attention(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
-                            int Lk, int64_t q_stride, int64_t q_bstride, int64_t kv_stride,
-                            int64_t kv_bstride, int64_t o_stride, int64_t o_bstride, void* stream) {
-  return sf_attention_ex(q, k, v, out, B, H, Lq, Lk, q_stride, q_bstride, kv_stride, kv_bstride, o_stride, o_bstride,
-                         SF_ATTN_AUTO, stream);
+extern "C" int sf_attention(const sf_attention_args* a, void* stream) {
+  SF_CHECK(a, "sf_attention: null argument struct");
+  SF_CHECK(!(a->accumulate && a->keys), "sf_attention: accumulate together with keys / log2w is not built");
+  return attention_launch(a->q, a->k, a->v, a->out, a->B, a->H, a->Lq, a->Lk, a->q_stride, a->q_bstride, a->kv_stride, a->kv_bstride,
+                          a->o_stride, a->o_bstride, a->structure, a->keys, a->log2w, a->accumulate != 0, stream);
 }

@@ -55,12 +55,7 @@ Work carve(const sf_model* m, void* ws, int B, int F, int lat_h, int lat_w, int 
 
 inline const char* bptr(const void* p, size_t elems) { return (const char*)p + elems * 2; }
 
-// The i2v model type: its weights and this pass's image tensors (both or neither), and the image context's buffers, carved
-// BEHIND the t2v workspace so that nothing in front of them moves.
-struct I2V {
-  const sf_i2v_model* m;
-  const sf_i2v_args* a;
-};
+// The i2v model type's image context buffers, carved BEHIND the t2v workspace so that nothing in front of them moves.
 struct ImgWork {
   void *t0, *t1, *ctx;   // [B clip_len, clip_dim] x 2 (LayerNorm / Linear ping-pong), [B clip_len, C] x 2 in ctx (fc2 out | normed)
   size_t total;
@@ -79,13 +74,17 @@ ImgWork carve_img(const sf_model* m, const sf_i2v_model* im, void* ws, size_t ba
 
 }  // namespace
 
-extern "C" size_t sf_dit_workspace_bytes(const sf_model* model, int batch, int frames, int lat_h, int lat_w, int groups) {
+extern "C" size_t sf_dit_workspace_bytes(const sf_model* model, const sf_i2v_model* i2v_model, int batch, int frames, int lat_h, int lat_w,
+                                         int groups) {
   if (!model || batch <= 0 || frames <= 0 || lat_h <= 0 || lat_w <= 0 || groups <= 0) return 0;
-  return carve(model, nullptr, batch, frames, lat_h, lat_w, groups).total;
+  const size_t base = carve(model, nullptr, batch, frames, lat_h, lat_w, groups).total;
+  if (!i2v_model) return base;
+  if (!base || i2v_model->clip_len <= 0 || i2v_model->clip_dim <= 0) return 0;
+  return carve_img(model, i2v_model, nullptr, base, batch).total;
 }
 
 // ------------------------------------------------------------------------------------------
-// The pass sequencer.  `np` passes (1, or 2 for sf_dit_forward_pair) over the SAME model, caches and latent geometry run
+// The pass sequencer.  `np` passes (1 or 2) over the SAME model, caches and latent geometry run
 // as ONE batch of np * B samples through everything that is row-wise -- patch embedding, time MLPs, norms, all ten GEMMs
 // of a layer, the head -- and one after the other through what touches the KV cache (eviction, K / V write, attention:
 // pass p + 1's write and eviction must not be visible to pass p's attention, exactly as when the passes run as separate
@@ -93,23 +92,33 @@ extern "C" size_t sf_dit_workspace_bytes(const sf_model* model, int batch, int f
 // output element, so the results are bit-identical to separate calls; what changes is M (two passes of 4680 tokens give
 // the GEMMs 9360 rows: 1040-1440 instead of 810-1160 TFLOP/s) and the launch count.
 // cache_only passes must come first; past the LAST layer's K / V write only the remaining passes' rows continue.
-// `iv` (NULL for a t2v generator: nothing below changes) adds the i2v model type: the 36-channel patch gather, the image
-// context with init_cross, and the image attention accumulated behind every layer's text attention.
-static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, int np, int32_t* cross_keys, float* cross_log2w, void* stream,
-                          const I2V* iv = nullptr) {
-  SF_CHECK((cross_keys == nullptr) == (cross_log2w == nullptr), "sf_dit_forward: cross_keys and cross_log2w come together");
+// `im` / `ia` (NULL for a t2v generator: nothing below changes) add the i2v model type: the 36-channel patch gather, the
+// image context with init_cross, and the image attention accumulated behind every layer's text attention.
+extern "C" int sf_dit_forward(const sf_model* m, const sf_forward_call* call, void* stream) {
+  SF_CHECK(m && call, "sf_dit_forward: null argument");
+  const sf_forward_args* const* ps = call->passes;
+  const int np = call->n_passes;
+  SF_CHECK(np == 1 || np == 2, "sf_dit_forward: one or two passes per call (n_passes=%d)", np);
   const sf_forward_args* a = ps[0];
-  SF_CHECK(m && a, "sf_dit_forward: null argument");
-  if (iv) {
-    SF_CHECK(np == 1, "sf_dit_forward_i2v: the two-pass call is not built for the i2v model type");
-    SF_CHECK(!m->fp8, "sf_dit_forward_i2v: fp8 Linears are not built for the i2v model type");
-    SF_CHECK(iv->m->layers_host && iv->m->clip_len > 0 && iv->m->clip_dim > 0 && iv->m->clip_dim % 64 == 0,
-             "sf_dit_forward_i2v: bad image context shape (clip_len=%d, clip_dim=%d: a positive multiple of 64)", iv->m->clip_len, iv->m->clip_dim);
-    SF_CHECK(iv->a->y, "sf_dit_forward_i2v: y is missing (an i2v generator needs clip_feature and y)");
-    SF_CHECK(m->in_dim >= m->out_dim + iv->a->y_channels && iv->a->y_channels > 0 && (m->in_dim * 4) % 64 == 0,
-             "sf_dit_forward_i2v: %d latent + %d conditioning channels do not fit the padded in_dim %d", m->out_dim, iv->a->y_channels, m->in_dim);
-    SF_CHECK(iv->a->kimg_cache_host && iv->a->vimg_cache_host, "sf_dit_forward_i2v: null image cache table");
-    SF_CHECK(!a->init_cross || iv->a->clip_feature, "sf_dit_forward_i2v: init_cross needs clip_feature");
+  SF_CHECK(a && ps[np - 1], "sf_dit_forward: null argument");
+  SF_CHECK(ps[np - 1]->workspace == a->workspace && ps[np - 1]->workspace_bytes == a->workspace_bytes,
+           "sf_dit_forward: both passes name the same workspace (sized for 2 x batch)");
+  int32_t* const cross_keys = call->cross_keys;
+  float* const cross_log2w = call->cross_log2w;
+  SF_CHECK((cross_keys == nullptr) == (cross_log2w == nullptr), "sf_dit_forward: cross_keys and cross_log2w come together");
+  const sf_i2v_model* const im = call->i2v_model;
+  const sf_i2v_args* const ia = call->i2v_args;
+  SF_CHECK((im == nullptr) == (ia == nullptr), "sf_dit_forward: null argument (i2v_model and i2v_args come together)");
+  if (im) {
+    SF_CHECK(np == 1, "sf_dit_forward: the two-pass call is not built for the i2v model type");
+    SF_CHECK(!m->fp8, "sf_dit_forward: fp8 Linears are not built for the i2v model type");
+    SF_CHECK(im->layers_host && im->clip_len > 0 && im->clip_dim > 0 && im->clip_dim % 64 == 0,
+             "sf_dit_forward: bad image context shape (clip_len=%d, clip_dim=%d: a positive multiple of 64)", im->clip_len, im->clip_dim);
+    SF_CHECK(ia->y, "sf_dit_forward: y is missing (an i2v generator needs clip_feature and y)");
+    SF_CHECK(m->in_dim >= m->out_dim + ia->y_channels && ia->y_channels > 0 && (m->in_dim * 4) % 64 == 0,
+             "sf_dit_forward: %d latent + %d conditioning channels do not fit the padded in_dim %d", m->out_dim, ia->y_channels, m->in_dim);
+    SF_CHECK(ia->kimg_cache_host && ia->vimg_cache_host, "sf_dit_forward: null image cache table");
+    SF_CHECK(!a->init_cross || ia->clip_feature, "sf_dit_forward: init_cross needs clip_feature");
   }
   SF_CHECK(m->layers_host && m->num_layers > 0, "sf_dit_forward: model has no layers");
   SF_CHECK(m->dim == m->num_heads * 128, "sf_dit_forward: head_dim must be 128 (dim=%d heads=%d)", m->dim, m->num_heads);
@@ -137,13 +146,13 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
              "sf_dit_forward: KV cache overflow: write_start=%d + %d new tokens > capacity %lld", q->write_start, L, (long long)q->cache_tokens);
     SF_CHECK(q->write_start + L == q->attn_end, "sf_dit_forward: the new tokens must end the attention window");
     if (q->evict > 0) SF_CHECK(q->evict_scratch && q->keep >= 0, "sf_dit_forward: eviction needs evict_scratch");
-    SF_CHECK(np == 1 || !q->init_cross, "sf_dit_forward_pair: the cross-attention cache must be initialised by an earlier single pass");
+    SF_CHECK(np == 1 || !q->init_cross, "sf_dit_forward: the cross-attention cache must be initialised by an earlier single pass");
     if (!q->cache_only && first_full == np) first_full = p;
-    SF_CHECK(!(q->cache_only && first_full != np), "sf_dit_forward_pair: cache_only passes must come first");
+    SF_CHECK(!(q->cache_only && first_full != np), "sf_dit_forward: cache_only passes must come first");
   }
   SF_CHECK(a->k_cache_host && a->v_cache_host && a->ck_cache_host && a->cv_cache_host, "sf_dit_forward: null cache table");
   const Work ws = carve(m, a->workspace, np * B, F, a->lat_h, a->lat_w, G);
-  const size_t ws_need = iv ? carve_img(m, iv->m, nullptr, ws.total, B).total : ws.total;
+  const size_t ws_need = im ? carve_img(m, im, nullptr, ws.total, B).total : ws.total;
   SF_CHECK(a->workspace && a->workspace_bytes >= ws_need, "sf_dit_forward: workspace too small (%zu < %zu)", a->workspace_bytes, ws_need);
   SF_CHECK(!a->init_cross || a->prompt_embeds, "sf_dit_forward: init_cross needs prompt_embeds");
 
@@ -175,9 +184,9 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
   };
 
   // ---- patch embedding (rows of pass p at [p M, (p + 1) M))
-  if (iv)   // x | y | zeros: the K = in_dim * 4 operand (in_dim is the padded 48 of an i2v sf_model)
-    SF_TRY(sf_patchify_i2v(a->noisy, iv->a->y, ws.cols, B, F, m->out_dim, iv->a->y_channels, m->in_dim, a->lat_h, a->lat_w, iv->a->y_bstride,
-                           iv->a->y_cstride, iv->a->y_fstride, stream));
+  if (im)   // x | y | zeros: the K = in_dim * 4 operand (in_dim is the padded 48 of an i2v sf_model)
+    SF_TRY(sf_patchify_i2v(a->noisy, ia->y, ws.cols, B, F, m->out_dim, ia->y_channels, m->in_dim, a->lat_h, a->lat_w, ia->y_bstride,
+                           ia->y_cstride, ia->y_fstride, stream));
   else
     for (int p = 0; p < np; ++p)
       SF_TRY(sf_patchify(ps[p]->noisy, (void*)bptr(ws.cols, (size_t)p * M * Kp), B, F, m->in_dim, a->lat_h, a->lat_w, stream));
@@ -228,22 +237,21 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
     if (cross_keys) SF_TRY(sf_cross_fold_scan(a->ck_cache_host, a->cv_cache_host, m->num_layers, B, m->text_len, C, cross_keys, cross_log2w, stream));
     // the image context, img_emb = MLPProj (model.py:469-481): LayerNorm, Linear, erf-GELU, Linear, LayerNorm -> clip_len
     // tokens per sample, then every layer's k_img (RMS-normed) / v_img beside its text K / V
-    if (iv) {
-      const sf_i2v_model* im = iv->m;
+    if (im) {
       const ImgWork iw = carve_img(m, im, a->workspace, ws.total, B);
       const int R = B * im->clip_len, D = im->clip_dim;
       void* ctx_raw = iw.ctx;
       void* ctx_img = (void*)bptr(iw.ctx, (size_t)R * C);
-      SF_TRY(sf_layernorm_rows(iv->a->clip_feature, im->img_ln0_w, im->img_ln0_b, iw.t0, R, D, im->img_eps, stream));
+      SF_TRY(sf_layernorm_rows(ia->clip_feature, im->img_ln0_w, im->img_ln0_b, iw.t0, R, D, im->img_eps, stream));
       SF_TRY(Gemm(iw.t0, D, im->img_fc1_w, D, iw.t1, D, R, D, D).bias(im->img_fc1_b).bf16(stream));
       SF_TRY(sf_clip_gelu(iw.t1, iw.t1, (int64_t)R * D, stream));
       SF_TRY(Gemm(iw.t1, D, im->img_fc2_w, D, ctx_raw, C, R, C, D).bias(im->img_fc2_b).bf16(stream));
       SF_TRY(sf_layernorm_affine(ctx_raw, im->img_ln1_w, im->img_ln1_b, ctx_img, R, C, im->img_eps, stream));
       for (int l = 0; l < m->num_layers; ++l) {
         const sf_i2v_layer& il = im->layers_host[l];
-        SF_TRY(Gemm(ctx_img, C, il.kvimg_w, C, iv->a->kimg_cache_host[l], C, R, C, C).bias(il.kvimg_b).bf16(stream));
-        SF_TRY(sf_rmsnorm(iv->a->kimg_cache_host[l], C, il.norm_k_img_w, iv->a->kimg_cache_host[l], C, R, C, m->eps, stream));
-        SF_TRY(Gemm(ctx_img, C, bptr(il.kvimg_w, (size_t)C * C), C, iv->a->vimg_cache_host[l], C, R, C, C).bias(bptr(il.kvimg_b, C)).bf16(stream));
+        SF_TRY(Gemm(ctx_img, C, il.kvimg_w, C, ia->kimg_cache_host[l], C, R, C, C).bias(il.kvimg_b).bf16(stream));
+        SF_TRY(sf_rmsnorm(ia->kimg_cache_host[l], C, il.norm_k_img_w, ia->kimg_cache_host[l], C, R, C, m->eps, stream));
+        SF_TRY(Gemm(ctx_img, C, bptr(il.kvimg_w, (size_t)C * C), C, ia->vimg_cache_host[l], C, R, C, C).bias(bptr(il.kvimg_b, C)).bf16(stream));
       }
     }
   }
@@ -268,8 +276,8 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
       SF_TRY(sf_qkv_norm_rope_cache(bptr(ws.qkv, roff * 3 * C), lw.norm_q_w, lw.norm_k_w, (void*)bptr(ws.q, roff * C), q->k_cache_host[l], q->v_cache_host[l],
                                     m->rope_cos, m->rope_sin, B, F, h, w, C, m->num_heads, q->cache_tokens, q->write_start, q->start_frame, m->eps, stream));
       if (q->cache_only && last_layer) continue;            // nothing downstream of this K/V write is read
-      SF_TRY(sf_attention(bptr(ws.q, roff * C), bptr(q->k_cache_host[l], (size_t)q->attn_start * C), bptr(q->v_cache_host[l], (size_t)q->attn_start * C),
-                          (void*)bptr(ws.att, roff * C), B, m->num_heads, L, q->attn_end - q->attn_start, C, (long)L * C, C, cache_b, C, (long)L * C, stream));
+      SF_TRY(Attention(bptr(ws.q, roff * C), C, (long)L * C, bptr(q->k_cache_host[l], (size_t)q->attn_start * C), bptr(q->v_cache_host[l], (size_t)q->attn_start * C),
+                       C, cache_b, (void*)bptr(ws.att, roff * C), C, (long)L * C, B, m->num_heads, L, q->attn_end - q->attn_start).run(stream));
     }
     // rows that go on: all of them, except behind the last layer's K / V write, where the cache_only passes are done
     const int p0 = last_layer ? first_full : 0;
@@ -289,12 +297,12 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
     SF_TRY(lin(Gemm(xn, C, lw.cq_w, C, qb, C, Mr, C, C).bias(lw.cq_b).fp8w(lq.cq_q, lq.cq_s, M)));
     SF_TRY(sf_rmsnorm(qb, C, lw.cnorm_q_w, qb, C, Mr, C, m->eps, stream));
     for (int p = p0; p < np; ++p)                            // every pass reads the same text K / V: one launch per pass
-      SF_TRY(sf_attention_fold(bptr(ws.q, (size_t)p * M * C), a->ck_cache_host[l], a->cv_cache_host[l], (void*)bptr(ws.att, (size_t)p * M * C), B, m->num_heads, L,
-                               m->text_len, C, (long)L * C, C, ctx_b, C, (long)L * C, SF_ATTN_AUTO, cross_keys ? cross_keys + (size_t)l * B : nullptr,
-                               cross_keys ? cross_log2w + (size_t)l * B : nullptr, stream));
-    if (iv)   // + attn(q, k_img, v_img): added into the text attention's buffer in fp32, rounded once (model.py:254-263)
-      SF_TRY(sf_attention_accum(ws.q, iv->a->kimg_cache_host[l], iv->a->vimg_cache_host[l], ws.att, B, m->num_heads, L, iv->m->clip_len, C, (long)L * C,
-                                C, (long)iv->m->clip_len * C, C, (long)L * C, SF_ATTN_AUTO, stream));
+      SF_TRY(Attention(bptr(ws.q, (size_t)p * M * C), C, (long)L * C, a->ck_cache_host[l], a->cv_cache_host[l], C, ctx_b, (void*)bptr(ws.att, (size_t)p * M * C), C,
+                       (long)L * C, B, m->num_heads, L, m->text_len)
+                 .fold(cross_keys ? cross_keys + (size_t)l * B : nullptr, cross_keys ? cross_log2w + (size_t)l * B : nullptr).run(stream));
+    if (im)   // + attn(q, k_img, v_img): added into the text attention's buffer in fp32, rounded once (model.py:254-263)
+      SF_TRY(Attention(ws.q, C, (long)L * C, ia->kimg_cache_host[l], ia->vimg_cache_host[l], C, (long)im->clip_len * C, ws.att, C, (long)L * C, B, m->num_heads, L,
+                       im->clip_len).accum().run(stream));
     SF_TRY(lin(Gemm(att, C, lw.co_w, C, x, C, Mr, C, C).bias(lw.co_b).epi(SF_EPI_BIAS_RESID).resid(x, C).fp8w(lq.co_q, lq.co_s, M)));
     // feed forward
     SF_TRY(sf_layernorm_modulate(x, xn, Mr, C, m->eps, bptr(mod, 3 * (size_t)C), bptr(mod, 4 * (size_t)C), bptr(e0r, 3 * (size_t)C),
@@ -317,44 +325,4 @@ static int forward_passes(const sf_model* m, const sf_forward_args* const* ps, i
                               ps[p]->flow_out, ps[p]->x0_out, B, F, G, m->out_dim, a->lat_h, a->lat_w, stream));
   }
   return finish_indices();
-}
-
-extern "C" int sf_dit_forward(const sf_model* m, const sf_forward_args* a, void* stream) {
-  SF_CHECK(m && a, "sf_dit_forward: null argument");
-  const sf_forward_args* one[1] = {a};
-  return forward_passes(m, one, 1, nullptr, nullptr, stream);
-}
-
-extern "C" int sf_dit_forward_fold(const sf_model* m, const sf_forward_args* a, int32_t* cross_keys, float* cross_log2w, void* stream) {
-  SF_CHECK(m && a, "sf_dit_forward: null argument");
-  const sf_forward_args* one[1] = {a};
-  return forward_passes(m, one, 1, cross_keys, cross_log2w, stream);
-}
-
-extern "C" size_t sf_dit_i2v_workspace_bytes(const sf_model* model, const sf_i2v_model* i2v_model, int batch, int frames, int lat_h, int lat_w,
-                                             int groups) {
-  const size_t base = sf_dit_workspace_bytes(model, batch, frames, lat_h, lat_w, groups);
-  if (!base || !i2v_model || i2v_model->clip_len <= 0 || i2v_model->clip_dim <= 0) return 0;
-  return carve_img(model, i2v_model, nullptr, base, batch).total;
-}
-
-extern "C" int sf_dit_forward_i2v(const sf_model* m, const sf_i2v_model* im, const sf_forward_args* a, const sf_i2v_args* ia, int32_t* cross_keys,
-                                  float* cross_log2w, void* stream) {
-  SF_CHECK(m && im && a && ia, "sf_dit_forward_i2v: null argument");
-  const sf_forward_args* one[1] = {a};
-  const I2V iv = {im, ia};
-  return forward_passes(m, one, 1, cross_keys, cross_log2w, stream, &iv);
-}
-
-extern "C" int sf_dit_forward_pair_fold(const sf_model* m, const sf_forward_args* context_pass, const sf_forward_args* next_pass,
-                                        const int32_t* cross_keys, const float* cross_log2w, void* stream) {
-  SF_CHECK(m && context_pass && next_pass, "sf_dit_forward_pair: null argument");
-  SF_CHECK(context_pass->workspace == next_pass->workspace && context_pass->workspace_bytes == next_pass->workspace_bytes,
-           "sf_dit_forward_pair: both passes name the same workspace (sized for 2 x batch)");
-  const sf_forward_args* two[2] = {context_pass, next_pass};
-  return forward_passes(m, two, 2, const_cast<int32_t*>(cross_keys), const_cast<float*>(cross_log2w), stream);   // (written only with init_cross)
-}
-
-extern "C" int sf_dit_forward_pair(const sf_model* m, const sf_forward_args* context_pass, const sf_forward_args* next_pass, void* stream) {
-  return sf_dit_forward_pair_fold(m, context_pass, next_pass, nullptr, nullptr, stream);
 }

@@ -71,3 +71,23 @@ struct Gemm {
     return sf_gemm_fp8(&q, a_scale, rows_per_segment, w_scale, stream);
   }
 };
+
+// One sf_attention call, in the same style: each operand with its token and batch stride, then the problem size;
+// everything optional is named:
+//   Attention(q, q_stride, q_bstride, k, v, kv_stride, kv_bstride, out, o_stride, o_bstride, B, H, Lq, Lk).fold(keys, log2w).run(stream)
+struct Attention {
+  sf_attention_args a;
+  Attention(const void* q, long q_stride, long q_bstride, const void* k, const void* v, long kv_stride, long kv_bstride, void* out,
+            long o_stride, long o_bstride, int B, int H, int Lq, int Lk) {
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.q_stride = q_stride; a.q_bstride = q_bstride;
+    a.k = k; a.v = v; a.kv_stride = kv_stride; a.kv_bstride = kv_bstride;
+    a.out = out; a.o_stride = o_stride; a.o_bstride = o_bstride;
+    a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk;
+    a.structure = SF_ATTN_AUTO;
+  }
+  Attention& structure(int s) { a.structure = s; return *this; }
+  Attention& accum() { a.accumulate = 1; return *this; }                  // out += the attention
+  Attention& fold(const int32_t* keys, const float* log2w) { a.keys = keys; a.log2w = log2w; return *this; }
+  int run(void* stream) const { return sf_attention(&a, stream); }
+};

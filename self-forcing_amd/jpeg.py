@@ -17,6 +17,7 @@ import torch
 from . import _lib, ops
 from . import jpeg_reference as jr
 from . import resize as resize_mod
+from .torch_ops import _dtype_name
 
 Tensor = torch.Tensor
 
@@ -55,7 +56,7 @@ class JpegEncoder:
     def _prepare(self, frames: Tensor):
         if not isinstance(frames, Tensor) or not frames.is_cuda:
             raise ValueError("JpegEncoder: expected a CUDA/ROCm tensor (the HIP path has no CPU fallback)")
-        name = str(frames.dtype).replace("torch.", "")
+        name = _dtype_name(frames)
         if name not in _lib.JPEG_DTYPES:
             raise ValueError(f"JpegEncoder: frames must be float32, bfloat16 or uint8, got {frames.dtype}")
         if frames.dim() not in (4, 5):

@@ -181,10 +181,9 @@ class CausalWanModel(DeviceModel):
     def workspace(self, B: int, F: int, H: int, W: int, G: int) -> Tensor:
         # one workspace per shape AND stream: concurrent rollouts on different HIP streams share the
         # weights but must not share activations
-        if self.shape.is_i2v:
-            return self._stream_bytes((B, F, H, W, G), lambda: _lib.lib().sf_dit_i2v_workspace_bytes(
-                C.byref(self.cmodel), C.byref(self.i2v_cmodel), B, F, H, W, G), zero_is_error="sf_dit_i2v_workspace_bytes")
-        return self._stream_bytes((B, F, H, W, G), lambda: _lib.lib().sf_dit_workspace_bytes(C.byref(self.cmodel), B, F, H, W, G))
+        i2v = C.byref(self.i2v_cmodel) if self.shape.is_i2v else None
+        return self._stream_bytes((B, F, H, W, G), lambda: _lib.lib().sf_dit_workspace_bytes(C.byref(self.cmodel), i2v, B, F, H, W, G),
+                                  zero_is_error="sf_dit_workspace_bytes" if i2v else None)
 
     def forward(self, noisy: Tensor, timestep: Tensor, prompt_embeds: Optional[Tensor], init_cross: bool,
                 k_cache: List[Tensor], v_cache: List[Tensor], ck_cache: List[Tensor], cv_cache: List[Tensor], plan: CachePlan,
@@ -200,7 +199,7 @@ class CausalWanModel(DeviceModel):
         filled by this call with init_cross, read by every layer's cross-attention; None: all text_len keys are attended.
         i2v model type: noisy carries in_dim - 20 channels; y (bf16 [B or 1, 20, F, H, W], strided) and the per-layer image
         caches are required, clip_feature (bf16 [B, clip_len, clip_dim]) with init_cross: torch.ops.sf_hip.dit_forward_i2v.
-        ONE custom-op call: torch.ops.sf_hip.dit_forward[_fold] -> sf_dit_forward_fold."""
+        ONE custom-op call: torch.ops.sf_hip.dit_forward -> sf_dit_forward."""
         B, F, Cin, H, W = noisy.shape
         ws = self.workspace(B, F, H, W, timestep.shape[1])
         if self.shape.is_i2v:
@@ -212,11 +211,10 @@ class CausalWanModel(DeviceModel):
                 plan.keep, plan.write_start, plan.attn_start, plan.local_end, start_frame, kv_index, plan.global_end,
                 *(cross_fold or (None, None)))
             return (None, None) if cache_only else (flow, x0)
-        op = torch.ops.sf_hip.dit_forward_fold if cross_fold else torch.ops.sf_hip.dit_forward
-        flow, x0 = op(
+        flow, x0 = torch.ops.sf_hip.dit_forward(
             self._handle, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, ws, evict_scratch,
             bool(init_cross), bool(cache_only), plan.sink, plan.evict, plan.keep, plan.write_start, plan.attn_start, plan.local_end,
-            start_frame, kv_index, plan.global_end, *(cross_fold or ()))
+            start_frame, kv_index, plan.global_end, *(cross_fold or (None, None)))
         return (None, None) if cache_only else (flow, x0)
 
     def forward_pair(self, ctx_noisy: Tensor, ctx_timestep: Tensor, noisy: Tensor, timestep: Tensor, k_cache: List[Tensor],
@@ -225,7 +223,7 @@ class CausalWanModel(DeviceModel):
                      cross_fold: Optional[Tuple[Tensor, Tensor]] = None,
                      add_conditions: Tuple[Optional[Tensor], Optional[Tensor]] = (None, None)):
         """The context pass of chunk k (cache only) + the first denoising pass of chunk k + 1 as ONE call
-        (torch.ops.sf_hip.dit_forward_pair -> sf_dit_forward_pair): bit-identical to two `forward` calls, but every
+        (torch.ops.sf_hip.dit_forward_pair -> sf_dit_forward with two passes): bit-identical to two `forward` calls, but every
         row-wise kernel and GEMM sees both passes' rows at once.  `add_conditions`: the pose tokens of the context pass and
         of the denoising pass (each pass adds its own).  Returns (flow, x0) of the denoising pass."""
         if self.shape.is_i2v:

@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from . import torch_ops  # noqa: F401  (registers torch.ops.sf_hip.*)
+from .torch_ops import _dtype_name, _ptr, _stream
 from ._lib import (ACT_GELU, ACT_NONE, ACT_SILU, CONV_BIAS, CONV_BIAS_CLAMP_F32, CONV_BIAS_RESID, EPI_BIAS,
                    EPI_BIAS_GATE_RESID, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_F32, ConvArgs, GemmArgs, check, lib)
 
@@ -25,7 +26,7 @@ _ACT = {None: ACT_NONE, "none": ACT_NONE, "silu": ACT_SILU, "gelu": ACT_GELU}
 
 
 def stream_handle() -> int:
-    return torch.cuda.current_stream().cuda_stream
+    return _stream()
 
 
 def _bf16(t: Tensor, name: str) -> Tensor:
@@ -45,10 +46,6 @@ def _rows(t: Tensor, name: str, dtype=torch.bfloat16) -> Tensor:
     if t.dim() != 2 or t.stride(1) != 1:
         raise ValueError(f"{name}: expected a 2-D tensor with contiguous rows, got shape {tuple(t.shape)} strides {t.stride()}")
     return t
-
-
-def _ptr(t: Optional[Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
 
 
 def _timestep(t: Tensor):
@@ -77,7 +74,7 @@ def small_linear(x: Tensor, w: Tensor, bias: Optional[Tensor], act_in=None, act_
     N = w.shape[0]
     out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
     check(lib().sf_small_linear(x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K,
-                                _ACT[act_in], _ACT[act_out], stream_handle()), "sf_small_linear")
+                                _ACT[act_in], _ACT[act_out], _stream(x)), "sf_small_linear")
     return out
 
 
@@ -110,14 +107,14 @@ def small_linear_fp8(x: Tensor, w_q: Tensor, w_scale: Tensor, bias: Optional[Ten
     w_scale = (w_scale.reshape(1).expand(N) if w_scale.numel() == 1 else w_scale).float().contiguous()
     out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
     check(lib().sf_small_linear_fp8(x.data_ptr(), w_q.data_ptr(), w_scale.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K,
-                                    rows_per_segment or M, _ACT[act_in], _ACT[act_out], stream_handle()), "sf_small_linear_fp8")
+                                    rows_per_segment or M, _ACT[act_in], _ACT[act_out], _stream(x)), "sf_small_linear_fp8")
     return out
 
 
 def sinusoid_embedding(t: Tensor, dim: int) -> Tensor:
     tt, is64 = _timestep(t.flatten())
     out = torch.empty(tt.numel(), dim, dtype=torch.bfloat16, device=t.device)
-    check(lib().sf_sinusoid_embedding(tt.data_ptr(), is64, out.data_ptr(), tt.numel(), dim, stream_handle()),
+    check(lib().sf_sinusoid_embedding(tt.data_ptr(), is64, out.data_ptr(), tt.numel(), dim, _stream(t)),
           "sf_sinusoid_embedding")
     return out
 
@@ -133,7 +130,7 @@ def layernorm_modulate(x: Tensor, mod_shift: Tensor, mod_scale: Tensor, e0_shift
     out = torch.empty_like(x)
     check(lib().sf_layernorm_modulate(x.data_ptr(), out.data_ptr(), M, Cc, eps, mod_shift.data_ptr(), mod_scale.data_ptr(),
                                       e0_shift.data_ptr(), e0_scale.data_ptr(), e0_shift.stride(0), rows_per_group,
-                                      stream_handle()), "sf_layernorm_modulate")
+                                      _stream(x)), "sf_layernorm_modulate")
     return out
 
 
@@ -141,7 +138,7 @@ def layernorm_affine(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-6)
     x = _rows(x, "x").contiguous()
     out = torch.empty_like(x)
     check(lib().sf_layernorm_affine(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1],
-                                    eps, stream_handle()), "sf_layernorm_affine")
+                                    eps, _stream(x)), "sf_layernorm_affine")
     return out
 
 
@@ -150,7 +147,7 @@ def rmsnorm(x: Tensor, weight: Tensor, eps: float = 1e-6, out: Optional[Tensor] 
     if out is None:
         out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     check(lib().sf_rmsnorm(x.data_ptr(), x.stride(0), weight.data_ptr(), out.data_ptr(), out.stride(0), x.shape[0], x.shape[1],
-                           eps, stream_handle()), "sf_rmsnorm")
+                           eps, _stream(x)), "sf_rmsnorm")
     return out
 
 
@@ -167,14 +164,14 @@ def qkv_norm_rope_cache(qkv: Tensor, norm_q_w: Tensor, norm_k_w: Tensor, k_cache
     q = torch.empty(qkv.shape[0], Cc, dtype=torch.bfloat16, device=qkv.device)
     check(lib().sf_qkv_norm_rope_cache(qkv.data_ptr(), norm_q_w.data_ptr(), norm_k_w.data_ptr(), q.data_ptr(), k_cache.data_ptr(),
                                        v_cache.data_ptr(), rope_cos.data_ptr(), rope_sin.data_ptr(), B, f, h, w, Cc, H, S,
-                                       write_start, start_frame, eps, stream_handle()), "sf_qkv_norm_rope_cache")
+                                       write_start, start_frame, eps, _stream(qkv)), "sf_qkv_norm_rope_cache")
     return q
 
 
 def kv_evict(cache: Tensor, sink: int, evict: int, keep: int, scratch: Tensor) -> None:
     B, S, H, D = cache.shape
     check(lib().sf_kv_evict(cache.data_ptr(), B, S, H * D, sink, evict, keep, scratch.data_ptr(),
-                            scratch.numel() * scratch.element_size(), stream_handle()), "sf_kv_evict")
+                            scratch.numel() * scratch.element_size(), _stream(cache)), "sf_kv_evict")
 
 
 def attention(q: Tensor, k: Tensor, v: Tensor, structure: str = "auto", keys: Optional[Tensor] = None,
@@ -188,7 +185,7 @@ def attention(q: Tensor, k: Tensor, v: Tensor, structure: str = "auto", keys: Op
 
 def attention_accum(q: Tensor, k: Tensor, v: Tensor, out: Tensor, structure: str = "auto") -> Tensor:
     """out += attention(q, k, v), in place: the sum is taken in fp32 in the kernel's epilogue and rounded to bf16 once
-    (sf_attention_accum; the i2v cross-attention's image keys added into the text attention's result).  `structure`:
+    (sf_attention_args.accumulate; the i2v cross-attention's image keys added into the text attention's result).  `structure`:
     "auto" | "w8" | "w4" ("r64" raises: the hand-scheduled kernel has no accumulate epilogue).  Returns `out`."""
     torch.ops.sf_hip.attention_accum(q, k, v, out, _lib.ATTN_STRUCTURES[structure])
     return out
@@ -210,7 +207,7 @@ def patchify(x: Tensor) -> Tensor:
     x = _bf16(x, "x").contiguous()
     B, F, Cin, H, W = x.shape
     out = torch.empty(B * F * (H // 2) * (W // 2), Cin * 4, dtype=torch.bfloat16, device=x.device)
-    check(lib().sf_patchify(x.data_ptr(), out.data_ptr(), B, F, Cin, H, W, stream_handle()), "sf_patchify")
+    check(lib().sf_patchify(x.data_ptr(), out.data_ptr(), B, F, Cin, H, W, _stream(x)), "sf_patchify")
     return out
 
 
@@ -224,7 +221,7 @@ def unpatchify_x0(head_out: Tensor, xt: Tensor, timestep: Tensor, sigmas: Tensor
     x0 = torch.empty_like(xt)
     check(lib().sf_unpatchify_x0(_rows(head_out, "head_out").contiguous().data_ptr(), xt.data_ptr(), tt.data_ptr(), is64,
                                  sigmas.data_ptr(), timesteps.data_ptr(), sigmas.numel(), flow.data_ptr(), x0.data_ptr(),
-                                 B, F, G, Cout, H, W, stream_handle()), "sf_unpatchify_x0")
+                                 B, F, G, Cout, H, W, _stream(xt)), "sf_unpatchify_x0")
     return flow, x0
 
 
@@ -294,7 +291,7 @@ def conv_igemm(x: Tensor, w_packed: Tensor, bias: Tensor, kernel, t_out: int, up
             if tuple(resid.shape) != tuple(out.shape) or not resid.is_contiguous():
                 raise ValueError("conv_igemm: resid must match the output volume")
             a.resid, a.ldr, a.epilogue = resid.data_ptr(), cout, CONV_BIAS_RESID
-    check(lib().sf_conv_igemm(a, stream_handle()), "sf_conv_igemm")
+    check(lib().sf_conv_igemm(a, _stream(x)), "sf_conv_igemm")
     return out
 
 
@@ -334,7 +331,7 @@ def taehv_conv(x: Tensor, w_packed: Tensor, bias: Optional[Tensor], kt: int, t_o
             if tuple(resid.shape) != tuple(out.shape) or not resid.is_contiguous():
                 raise ValueError("taehv_conv: resid must match the output volume")
             a.resid, a.ldr = resid.data_ptr(), cout
-    check(lib().sf_taehv_conv(a, stream_handle()), "sf_taehv_conv")
+    check(lib().sf_taehv_conv(a, _stream(x)), "sf_taehv_conv")
     return out
 
 
@@ -351,8 +348,8 @@ def taehv_encode_stem(pixels: Tensor, w_packed: Tensor, bias: Tensor, lead: int 
         raise ValueError("taehv_encode_stem: w_packed [64, 32] and bias [64] expected")
     _, T, H, W = pixels.shape
     out = torch.empty(lead + T, H, W, 64, dtype=torch.bfloat16, device=pixels.device)
-    check(lib().sf_taehv_encode_stem(pixels.data_ptr(), _lib.TAEHV_PIXEL_DTYPES[str(pixels.dtype).replace("torch.", "")], pixels.stride(0), H, W,
-                                     lead + T, lead, w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), stream_handle()), "sf_taehv_encode_stem")
+    check(lib().sf_taehv_encode_stem(pixels.data_ptr(), _lib.TAEHV_PIXEL_DTYPES[_dtype_name(pixels)], pixels.stride(0), H, W,
+                                     lead + T, lead, w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), _stream(pixels)), "sf_taehv_encode_stem")
     return out
 
 
@@ -369,7 +366,7 @@ def taehv_down_conv(x: Tensor, w_packed: Tensor, kt: int) -> Tensor:
     a = _lib.TaehvDownConvArgs()
     a.x, a.w, a.out = x.data_ptr(), w_packed.data_ptr(), out.data_ptr()
     a.Tout, a.H, a.W, a.Cin, a.Cout, a.kt, a.ldw, a.ldo = tin // kt, hin // 2, win // 2, c, cout, kt, w_packed.stride(0), cout
-    check(lib().sf_taehv_down_conv(a, stream_handle()), "sf_taehv_down_conv")
+    check(lib().sf_taehv_down_conv(a, _stream(x)), "sf_taehv_down_conv")
     return out
 
 
@@ -379,7 +376,7 @@ def pose_prepare(src: Tensor, lead: int = 3, hwc: bool = False) -> Tensor:
     front, value / 255, channels 3..7 zero."""
     if not src.is_cuda:
         raise ValueError("pose_prepare: expected a CUDA/ROCm tensor (the HIP path has no CPU fallback)")
-    name = str(src.dtype).replace("torch.", "")
+    name = _dtype_name(src)
     if name not in _lib.POSE_DTYPES:
         raise ValueError(f"pose_prepare: pose data must be uint8, float32 or bfloat16, got {src.dtype}")
     if hwc:
@@ -392,7 +389,7 @@ def pose_prepare(src: Tensor, lead: int = 3, hwc: bool = False) -> Tensor:
         F, H, W = src.shape[1:]
     src = src.contiguous()
     out = torch.empty(lead + F, H, W, 8, dtype=torch.bfloat16, device=src.device)
-    check(lib().sf_pose_prepare(src.data_ptr(), _lib.POSE_DTYPES[name], int(hwc), F, H, W, lead, out.data_ptr(), stream_handle()), "sf_pose_prepare")
+    check(lib().sf_pose_prepare(src.data_ptr(), _lib.POSE_DTYPES[name], int(hwc), F, H, W, lead, out.data_ptr(), _stream(src)), "sf_pose_prepare")
     return out
 
 
@@ -412,7 +409,7 @@ def pose_conv(x: Tensor, w_packed: Tensor, bias: Tensor, cout: int, kt: int = 3,
     a.x, a.w, a.bias, a.out = x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr()
     a.T, a.H, a.W, a.Cin, a.Cout, a.kt, a.stride_t, a.stride_s = T, H, W, c, cout, kt, stride_t, stride_s
     a.ldw, a.ldo, a.silu = w_packed.stride(0), cout, int(silu)
-    check(lib().sf_pose_conv(a, stream_handle()), "sf_pose_conv")
+    check(lib().sf_pose_conv(a, _stream(x)), "sf_pose_conv")
     return out
 
 
@@ -435,7 +432,7 @@ def pose_conv_window(x: Tensor, w_packed: Tensor, bias: Tensor, cout: int, x_t0:
     a.T, a.H, a.W, a.Cin, a.Cout, a.kt, a.stride_t, a.stride_s = T, H, W, c, cout, 3, stride_t, stride_s
     a.ldw, a.ldo, a.silu = w_packed.stride(0), cout, int(silu)
     win = _lib.PoseWindow(x_t0, t_end, int(closed), t_out0, n_out)
-    check(lib().sf_pose_conv_window(a, win, stream_handle()), "sf_pose_conv_window")
+    check(lib().sf_pose_conv_window(a, win, _stream(x)), "sf_pose_conv_window")
     return out
 
 
@@ -450,7 +447,7 @@ def pose_patch_embed(x: Tensor, w_packed: Tensor, bias: Tensor) -> Tensor:
     rows = torch.empty(n, 64, dtype=torch.bfloat16, device=x.device)
     out = torch.empty(n, w_packed.shape[0], dtype=torch.bfloat16, device=x.device)
     check(lib().sf_pose_patch_embed(x.data_ptr(), T, H, W, w_packed.data_ptr(), bias.data_ptr(), w_packed.shape[0], rows.data_ptr(), out.data_ptr(),
-                                    stream_handle()), "sf_pose_patch_embed")
+                                    _stream(x)), "sf_pose_patch_embed")
     return out
 
 
@@ -461,7 +458,7 @@ def rmsnorm_silu_cl(x: Tensor, gamma: Tensor, silu: bool = True) -> Tensor:
         raise ValueError("rmsnorm_silu_cl: x must be contiguous")
     out = torch.empty_like(x)
     c = x.shape[-1]
-    check(lib().sf_rmsnorm_silu_cl(x.data_ptr(), gamma.data_ptr(), out.data_ptr(), x.numel() // c, c, int(silu), stream_handle()),
+    check(lib().sf_rmsnorm_silu_cl(x.data_ptr(), gamma.data_ptr(), out.data_ptr(), x.numel() // c, c, int(silu), _stream(x)),
           "sf_rmsnorm_silu_cl")
     return out
 
@@ -473,7 +470,7 @@ def softmax_rows(s: Tensor, scale: float, cols_padded: Optional[int] = None) -> 
     rows, cols = s.shape
     cp = cols_padded or cols
     out = torch.empty(rows, cp, dtype=torch.bfloat16, device=s.device)
-    check(lib().sf_softmax_rows(s.data_ptr(), s.stride(0), out.data_ptr(), cp, rows, cols, cp, float(scale), stream_handle()),
+    check(lib().sf_softmax_rows(s.data_ptr(), s.stride(0), out.data_ptr(), cp, rows, cols, cp, float(scale), _stream(s)),
           "sf_softmax_rows")
     return out
 
@@ -488,7 +485,7 @@ def probe_mfma(operands: Tensor, sink: Tensor, shape: str = "32x32x16", iters: i
         raise ValueError("probe_mfma: operands >= 4096 bf16 and a CUDA float32 sink of workgroups * 256 elements expected")
     fl = C.c_double(0.0)
     check(lib().sf_probe_mfma({"32x32x16": 0, "16x16x32": 1}[shape], iters, workgroups, operands.data_ptr(), sink.data_ptr(),
-                              C.byref(fl), stream_handle()), "sf_probe_mfma")
+                              C.byref(fl), _stream(operands)), "sf_probe_mfma")
     return fl.value
 
 
@@ -499,7 +496,7 @@ def probe_copy(src: Tensor, dst: Tensor) -> int:
     nbytes = src.numel() * src.element_size()
     if nbytes != dst.numel() * dst.element_size() or nbytes % 16:
         raise ValueError("probe_copy: src and dst must hold the same number of bytes, a multiple of 16")
-    check(lib().sf_probe_copy(src.data_ptr(), dst.data_ptr(), nbytes, stream_handle()), "sf_probe_copy")
+    check(lib().sf_probe_copy(src.data_ptr(), dst.data_ptr(), nbytes, _stream(src)), "sf_probe_copy")
     return nbytes
 
 
@@ -514,9 +511,9 @@ def jpeg_workspace_bytes(n: int, h: int, w: int, subsampling: str, restart_inter
 
 def jpeg_transform(frames: Tensor, coef: Tensor, n: int, h: int, w: int, subsampling: str, quality: int, value_range=(-1, 1)) -> Tensor:
     """frames (contiguous float32 / bfloat16 [n, 3, h, w] or uint8 [n, h, w, 3]) -> coef int16 [n, blocks, 64] (sf_jpeg_transform)."""
-    dtype = _lib.JPEG_DTYPES[str(frames.dtype).replace("torch.", "")]
+    dtype = _lib.JPEG_DTYPES[_dtype_name(frames)]
     check(lib().sf_jpeg_transform(frames.data_ptr(), dtype, _lib.JPEG_RANGES[tuple(value_range)], n, h, w, _lib.JPEG_SUBSAMPLINGS[subsampling],
-                                  quality, coef.data_ptr(), torch.cuda.current_stream(frames.device).cuda_stream), "sf_jpeg_transform")
+                                  quality, coef.data_ptr(), _stream(frames)), "sf_jpeg_transform")
     return coef
 
 
@@ -526,16 +523,16 @@ def jpeg_entropy(coef: Tensor, n: int, h: int, w: int, subsampling: str, quality
     (sf_jpeg_entropy)."""
     check(lib().sf_jpeg_entropy(coef.data_ptr(), n, h, w, _lib.JPEG_SUBSAMPLINGS[subsampling], quality, restart_interval, workspace.data_ptr(),
                                 workspace.numel(), out.data_ptr(), out.numel(), meta.data_ptr(), meta[n + 1:].data_ptr(),
-                                torch.cuda.current_stream(coef.device).cuda_stream), "sf_jpeg_entropy")
+                                _stream(coef)), "sf_jpeg_entropy")
 
 
 def jpeg_encode_frames(frames: Tensor, n: int, h: int, w: int, subsampling: str, quality: int, restart_interval: int, value_range, workspace: Tensor,
                        out: Tensor, meta: Tensor) -> None:
     """Both steps in one host call (sf_jpeg_encode_frames); arguments as `jpeg_transform` / `jpeg_entropy`."""
-    dtype = _lib.JPEG_DTYPES[str(frames.dtype).replace("torch.", "")]
+    dtype = _lib.JPEG_DTYPES[_dtype_name(frames)]
     check(lib().sf_jpeg_encode_frames(frames.data_ptr(), dtype, _lib.JPEG_RANGES[tuple(value_range)], n, h, w, _lib.JPEG_SUBSAMPLINGS[subsampling],
                                       quality, restart_interval, workspace.data_ptr(), workspace.numel(), out.data_ptr(), out.numel(), meta.data_ptr(),
-                                      meta[n + 1:].data_ptr(), torch.cuda.current_stream(frames.device).cuda_stream), "sf_jpeg_encode_frames")
+                                      meta[n + 1:].data_ptr(), _stream(frames)), "sf_jpeg_encode_frames")
 
 
 # -------------------------------------------------------------------------------------- JPEG decoder (csrc/jpeg_decode.hip)
@@ -563,16 +560,16 @@ def jpeg_decode_entropy(upload: Tensor, upload_bytes: int, n: int, h: int, w: in
                         status: Tensor) -> Tensor:
     """upload (uint8: the table block, then the scans) -> coef int16 [n, blocks, 64]; status int32 [n] (sf_jpeg_decode_entropy)."""
     check(lib().sf_jpeg_decode_entropy(upload.data_ptr(), upload_bytes, n, h, w, _lib.JPEG_DECODE_SAMPLINGS[sampling], max_intervals, workspace.data_ptr(),
-                                       workspace.numel(), coef.data_ptr(), status.data_ptr(), _cur(upload)), "sf_jpeg_decode_entropy")
+                                       workspace.numel(), coef.data_ptr(), status.data_ptr(), _stream(upload)), "sf_jpeg_decode_entropy")
     return coef
 
 
 def jpeg_decode_pixels(coef: Tensor, upload: Tensor, upload_bytes: int, n: int, h: int, w: int, sampling: str, workspace: Tensor, out: Tensor,
                        layout: str) -> Tensor:
     """coef -> out (uint8 / float32 / bfloat16, already shaped for `layout`) (sf_jpeg_decode_pixels)."""
-    dtype = _lib.JPEG_DTYPES[str(out.dtype).replace("torch.", "")]
+    dtype = _lib.JPEG_DTYPES[_dtype_name(out)]
     check(lib().sf_jpeg_decode_pixels(coef.data_ptr(), upload.data_ptr(), upload_bytes, _idct_table(), n, h, w, _lib.JPEG_DECODE_SAMPLINGS[sampling],
-                                      workspace.data_ptr(), workspace.numel(), out.data_ptr(), _lib.JPEG_LAYOUTS[layout], dtype, _cur(upload)),
+                                      workspace.data_ptr(), workspace.numel(), out.data_ptr(), _lib.JPEG_LAYOUTS[layout], dtype, _stream(upload)),
           "sf_jpeg_decode_pixels")
     return out
 
@@ -580,10 +577,10 @@ def jpeg_decode_pixels(coef: Tensor, upload: Tensor, upload_bytes: int, n: int, 
 def jpeg_decode_frames(upload: Tensor, upload_bytes: int, n: int, h: int, w: int, sampling: str, max_intervals: int, workspace: Tensor, out: Tensor,
                        layout: str, status: Tensor) -> Tensor:
     """Both steps in one host call (sf_jpeg_decode_frames); arguments as `jpeg_decode_entropy` / `jpeg_decode_pixels`."""
-    dtype = _lib.JPEG_DTYPES[str(out.dtype).replace("torch.", "")]
+    dtype = _lib.JPEG_DTYPES[_dtype_name(out)]
     check(lib().sf_jpeg_decode_frames(upload.data_ptr(), upload_bytes, _idct_table(), n, h, w, _lib.JPEG_DECODE_SAMPLINGS[sampling], max_intervals,
                                       workspace.data_ptr(), workspace.numel(), out.data_ptr(), _lib.JPEG_LAYOUTS[layout], dtype, status.data_ptr(),
-                                      _cur(upload)), "sf_jpeg_decode_frames")
+                                      _stream(upload)), "sf_jpeg_decode_frames")
     return out
 
 
@@ -609,10 +606,6 @@ def resize_frames(frames: Tensor, tables_h, tables_v, filter: str, layout: str =
 
 
 # -------------------------------------------------------------------------------------- CLIP image encoder (csrc/clip_encoder.hip)
-def _cur(t: Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def clip_preprocess(frames: Tensor, image_size: int = 224, patch: int = 14, kp: Optional[int] = None) -> Tensor:
     """frames [n, 3, H, W] float32 / bfloat16 in [-1, 1] -> bf16 patch rows [n * (image_size/patch)^2, kp] (sf_clip_preprocess)."""
     if not frames.is_cuda or frames.dim() != 4 or frames.shape[1] != 3 or not frames.is_contiguous():
@@ -620,8 +613,8 @@ def clip_preprocess(frames: Tensor, image_size: int = 224, patch: int = 14, kp: 
     kp = (3 * patch * patch + 63) // 64 * 64 if kp is None else kp
     n, _, H, W = frames.shape
     rows = torch.empty(n * (image_size // patch) ** 2, kp, dtype=torch.bfloat16, device=frames.device)
-    check(lib().sf_clip_preprocess(frames.data_ptr(), _lib.CLIP_DTYPES[str(frames.dtype).replace("torch.", "")], n, H, W, image_size, patch, kp,
-                                   rows.data_ptr(), _cur(frames)), "sf_clip_preprocess")
+    check(lib().sf_clip_preprocess(frames.data_ptr(), _lib.CLIP_DTYPES[_dtype_name(frames)], n, H, W, image_size, patch, kp,
+                                   rows.data_ptr(), _stream(frames)), "sf_clip_preprocess")
     return rows
 
 
@@ -633,7 +626,7 @@ def clip_embed_norm(patch_out: Tensor, cls: Tensor, pos: Tensor, pre_w: Tensor, 
     x32 = torch.empty(n, P + 1, dim, dtype=torch.float32, device=patch_out.device)
     xn = torch.empty(n, P + 1, dim, dtype=torch.bfloat16, device=patch_out.device) if ln_w is not None else None
     check(lib().sf_clip_embed_norm(patch_out.data_ptr(), cls.data_ptr(), pos.data_ptr(), pre_w.data_ptr(), pre_b.data_ptr(), _ptr(ln_w), _ptr(ln_b),
-                                   x32.data_ptr(), _ptr(xn), n, P, dim, eps, _cur(patch_out)), "sf_clip_embed_norm")
+                                   x32.data_ptr(), _ptr(xn), n, P, dim, eps, _stream(patch_out)), "sf_clip_embed_norm")
     return x32, xn
 
 
@@ -646,7 +639,7 @@ def clip_add_layernorm(x32: Tensor, y: Tensor, ln_w: Optional[Tensor] = None, ln
         raise ValueError("clip_add_layernorm: contiguous CUDA float32 x32 [rows, dim] and bf16 y of the same shape expected")
     if ln_w is not None and xn is None:
         xn = torch.empty_like(y)
-    check(lib().sf_clip_add_layernorm(x32.data_ptr(), y.data_ptr(), _ptr(ln_w), _ptr(ln_b), _ptr(xn), x32.shape[0], x32.shape[1], eps, _cur(x32)),
+    check(lib().sf_clip_add_layernorm(x32.data_ptr(), y.data_ptr(), _ptr(ln_w), _ptr(ln_b), _ptr(xn), x32.shape[0], x32.shape[1], eps, _stream(x32)),
           "sf_clip_add_layernorm")
     return xn if ln_w is not None else None
 
@@ -659,7 +652,7 @@ def clip_attention(qkv: Tensor, out: Optional[Tensor] = None) -> Tensor:
     n, L, _, H, _ = qkv.shape
     if out is None:
         out = torch.empty(n, L, H * 80, dtype=torch.bfloat16, device=qkv.device)
-    check(lib().sf_clip_attention(qkv.data_ptr(), out.data_ptr(), n, L, H, _cur(qkv)), "sf_clip_attention")
+    check(lib().sf_clip_attention(qkv.data_ptr(), out.data_ptr(), n, L, H, _stream(qkv)), "sf_clip_attention")
     return out
 
 
@@ -667,5 +660,5 @@ def clip_gelu(x: Tensor) -> Tensor:
     """nn.GELU() (erf form) of a bf16 tensor, evaluated in fp32 (sf_clip_gelu)."""
     _bf16(x, "x")
     out = torch.empty_like(x)
-    check(lib().sf_clip_gelu(x.data_ptr(), out.data_ptr(), x.numel(), _cur(x)), "sf_clip_gelu")
+    check(lib().sf_clip_gelu(x.data_ptr(), out.data_ptr(), x.numel(), _stream(x)), "sf_clip_gelu")
     return out

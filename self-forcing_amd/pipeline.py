@@ -378,7 +378,7 @@ class CausalInferencePipeline(torch.nn.Module):
         n_steps = steps.shape[0]
         # A chunk's context pass and the next chunk's first denoising pass run back to back in the reference (:226-235, then
         # :190-205) and layer l of the second needs only layer l's K / V of the first: a generator that offers `forward_pair`
-        # (ours) runs them as ONE call -- bit-identical latents, twice the rows per GEMM (sf_dit_forward_pair).  The re-noise
+        # (ours) runs them as ONE call -- bit-identical latents, twice the rows per GEMM (the two-pass sf_dit_forward).  The re-noise
         # draws keep their order: nothing is drawn between a chunk's last step and the next chunk's first.
         # Pose tokens differ between the two passes of a pair: only `chunk_condition` knows both chunks'.  A dict that arrives
         # with its own `add_condition` (the reference's convention) is handed to every pass as it is, unpaired.

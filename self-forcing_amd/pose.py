@@ -26,6 +26,7 @@ import torch
 
 from . import _lib
 from .device_model import DeviceModel
+from .torch_ops import _dtype_name
 from .pose_weights import (CIN_STORE, DWPOSE_LAYERS, POSE_DIM, RANDOMREF_DIM, RANDOMREF_LAYERS, pad_pose_bias, pose_plan, pose_stream_plan,
                            ref_plan, repack_pose_conv, repack_pose_embed, split_pose_state_dict)
 
@@ -80,7 +81,7 @@ class PoseEmbedder(DeviceModel):
         return self._stream_bytes((num_frames, H, W), lambda: self.scratch_bytes(num_frames, H, W), keep_one=True)
 
     def _pose_input(self, x: Tensor, what: str) -> Tuple[Tensor, int]:
-        name = str(x.dtype).replace("torch.", "")
+        name = _dtype_name(x)
         if name not in _lib.POSE_DTYPES:
             if not x.is_floating_point():
                 raise ValueError(f"{what}: pose data must be uint8 or floating point holding 0..255, got {x.dtype}")

@@ -19,7 +19,7 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::lincomb(tensors[], coefs[]) -> out ;  sf_hip::lincomb_out(out!, tensors[], coefs[]) -> ()
     sf_hip::add_noise(x0, eps, timestep, sigmas, timesteps) -> out
     sf_hip::dit_forward(model, noisy, timestep, prompt_embeds?, add_condition?, k_cache![], v_cache![], ck_cache![],
-                        cv_cache![], workspace!, evict_scratch!?, ..., kv_index!?, global_end) -> (flow, x0)
+                        cv_cache![], workspace!, evict_scratch!?, ..., kv_index!?, global_end, cross_keys!?, cross_log2w!?) -> (flow, x0)
     sf_hip::dit_forward_pair(model, ctx_noisy, ctx_timestep, noisy, timestep, caches![]..., workspace!, evict_scratch!?, ctx_plan[7],
                              plan[7], kv_index!?, global_end, ..., ctx_add_condition?, add_condition?) -> (flow, x0)
                                                                     (context pass of chunk k + first pass of chunk k + 1)
@@ -68,8 +68,14 @@ def _model(handle: int):
         raise RuntimeError(f"sf_hip: model handle {handle} is not registered (or its owner was freed)") from None
 
 
-def _stream(t: Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
+def _stream(t: Optional[Tensor] = None) -> int:
+    """The current HIP stream of t's device (of the current device without a tensor)."""
+    return torch.cuda.current_stream(None if t is None else t.device).cuda_stream
+
+
+def _dtype_name(t: Tensor) -> str:
+    """'bfloat16' for torch.bfloat16: the keys of the `_lib.*_DTYPES` tables."""
+    return str(t.dtype).replace("torch.", "")
 
 
 def _need_gpu(t: Tensor, name: str, dtype=torch.bfloat16) -> None:
@@ -77,6 +83,13 @@ def _need_gpu(t: Tensor, name: str, dtype=torch.bfloat16) -> None:
         raise ValueError(f"{name}: expected a CUDA/ROCm tensor (the HIP path has no CPU fallback)")
     if dtype is not None and t.dtype != dtype:
         raise ValueError(f"{name}: expected {dtype}, got {t.dtype}")
+
+
+def _need_bytes(op: str, **buffers: Optional[Tensor]) -> None:
+    """State / scratch / workspace blocks: their element counts are passed on as BYTE counts."""
+    for name, t in buffers.items():
+        if t is not None and (not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous()):
+            raise ValueError(f"{op}: {name} must be a contiguous CUDA uint8 tensor")
 
 
 def _ptr(t: Optional[Tensor]) -> Optional[int]:
@@ -88,7 +101,7 @@ def _ptr(t: Optional[Tensor]) -> Optional[int]:
 def attention(q: Tensor, k: Tensor, v: Tensor, structure: int = 0, keys: Optional[Tensor] = None,
               log2w: Optional[Tensor] = None) -> Tensor:
     """softmax(q k^T / sqrt(D)) v.  `keys` (int32 [B]) / `log2w` (float32 [B]), both or neither: sample b attends only its
-    first keys[b] key rows and the last of them counts 2^log2w[b] times (sf_attention_fold; see cross_fold_scan)."""
+    first keys[b] key rows and the last of them counts 2^log2w[b] times (sf_attention_args.keys; see cross_fold_scan)."""
     for n, t in (("q", q), ("k", k), ("v", v)):
         _need_gpu(t, n)
         if t.dim() != 4 or t.shape[3] != 128 or t.stride(3) != 1 or t.stride(2) != 128:
@@ -98,10 +111,16 @@ def attention(q: Tensor, k: Tensor, v: Tensor, structure: int = 0, keys: Optiona
         raise ValueError("attention: k and v must share shape and strides")
     _fold_pair(keys, log2w, (B,), q.device, "attention")
     out = torch.empty(B, Lq, H, D, dtype=torch.bfloat16, device=q.device)
-    _lib.check(_lib.lib().sf_attention_fold(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Lq, k.shape[1],
-                                            q.stride(1), q.stride(0), k.stride(1), k.stride(0), out.stride(1), out.stride(0),
-                                            structure, _ptr(keys), _ptr(log2w), _stream(q)), "sf_attention")
+    _attention_launch(q, k, v, out, structure, keys=_ptr(keys), log2w=_ptr(log2w))
     return out
+
+
+def _attention_launch(q: Tensor, k: Tensor, v: Tensor, out: Tensor, structure: int, **named) -> None:
+    """One sf_attention call on validated [B, L, H, 128] tensors; `named`: accumulate / keys / log2w of sf_attention_args."""
+    a = _lib.AttentionArgs(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), out=out.data_ptr(), B=q.shape[0], H=q.shape[2], Lq=q.shape[1],
+                           Lk=k.shape[1], q_stride=q.stride(1), q_bstride=q.stride(0), kv_stride=k.stride(1), kv_bstride=k.stride(0),
+                           o_stride=out.stride(1), o_bstride=out.stride(0), structure=structure, **named)
+    _lib.check(_lib.lib().sf_attention(a, _stream(q)), "sf_attention")
 
 
 @attention.register_fake
@@ -111,7 +130,7 @@ def _(q, k, v, structure=0, keys=None, log2w=None):
 
 @custom_op(f"{NAMESPACE}::attention_accum", mutates_args=("out",))
 def attention_accum(q: Tensor, k: Tensor, v: Tensor, out: Tensor, structure: int = 0) -> None:
-    """out += softmax(q k^T / sqrt(D)) v, summed in fp32 in the kernel's epilogue and rounded once (sf_attention_accum):
+    """out += softmax(q k^T / sqrt(D)) v, summed in fp32 in the kernel's epilogue and rounded once (sf_attention_args.accumulate):
     the image half of the i2v cross-attention added into the text half's buffer.  structure: auto, w8 or w4."""
     for n, t in (("q", q), ("k", k), ("v", v), ("out", out)):
         _need_gpu(t, n)
@@ -122,9 +141,7 @@ def attention_accum(q: Tensor, k: Tensor, v: Tensor, out: Tensor, structure: int
         raise ValueError("attention_accum: k and v must share shape and strides, and batch and heads with q")
     if out.shape != q.shape:
         raise ValueError(f"attention_accum: out must have q's shape {tuple(q.shape)}, got {tuple(out.shape)}")
-    _lib.check(_lib.lib().sf_attention_accum(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Lq, k.shape[1],
-                                             q.stride(1), q.stride(0), k.stride(1), k.stride(0), out.stride(1), out.stride(0),
-                                             structure, _stream(q)), "sf_attention_accum")
+    _attention_launch(q, k, v, out, structure, accumulate=1)
 
 
 @attention_accum.register_fake
@@ -171,6 +188,27 @@ def _fold_pair(keys: Optional[Tensor], log2w: Optional[Tensor], shape: tuple, de
 
 
 # ------------------------------------------------------------------------------------------ GEMM
+def _gemm_args(out: Tensor, a: Tensor, w: Tensor, bias, epilogue: int, resid, gate_mod, gate_e0, rows_per_group: int,
+               structure: int) -> "_lib.GemmArgs":
+    """sf_gemm_args of out [M, N] = a [M, K] . w [N, K]^T (shapes checked by the caller); the optional bf16 operands are
+    checked for device and dtype here."""
+    g = _lib.GemmArgs()
+    g.a, g.w, g.bias, g.out = a.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr()
+    g.M, g.K = a.shape
+    g.N = w.shape[0]
+    g.lda, g.ldw, g.ldo = a.stride(0), w.stride(0), out.stride(0)
+    g.epilogue, g.rows_per_group, g.structure = epilogue, rows_per_group, structure
+    for name, t in (("bias", bias), ("resid", resid), ("gate_mod", gate_mod), ("gate_e0", gate_e0)):
+        if t is not None:
+            _need_gpu(t, name)
+    if resid is not None:
+        g.resid, g.ldr = resid.data_ptr(), resid.stride(0)
+    g.gate_mod = _ptr(gate_mod)
+    if gate_e0 is not None:
+        g.gate_e0, g.gate_group_stride = gate_e0.data_ptr(), gate_e0.stride(0)
+    return g
+
+
 def _gemm_launch(out: Tensor, a: Tensor, w: Tensor, bias, epilogue: int, resid, gate_mod, gate_e0, rows_per_group: int,
                  structure: int) -> None:
     for n, t in (("a", a), ("w", w)):
@@ -185,20 +223,7 @@ def _gemm_launch(out: Tensor, a: Tensor, w: Tensor, bias, epilogue: int, resid, 
     _need_gpu(out, "out", want)
     if out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (M, N):
         raise ValueError(f"gemm: out must be [{M},{N}] with contiguous rows, got {tuple(out.shape)} {out.stride()}")
-    g = _lib.GemmArgs()
-    g.a, g.w, g.bias, g.out = a.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr()
-    g.M, g.N, g.K = M, N, K
-    g.lda, g.ldw, g.ldo = a.stride(0), w.stride(0), out.stride(0)
-    g.epilogue, g.rows_per_group, g.structure = epilogue, rows_per_group, structure
-    if resid is not None:
-        _need_gpu(resid, "resid")
-        g.resid, g.ldr = resid.data_ptr(), resid.stride(0)
-    if gate_mod is not None:
-        _need_gpu(gate_mod, "gate_mod")
-        g.gate_mod = gate_mod.data_ptr()
-    if gate_e0 is not None:
-        _need_gpu(gate_e0, "gate_e0")
-        g.gate_e0, g.gate_group_stride = gate_e0.data_ptr(), gate_e0.stride(0)
+    g = _gemm_args(out, a, w, bias, epilogue, resid, gate_mod, gate_e0, rows_per_group, structure)
     _lib.check(_lib.lib().sf_gemm_bf16(g, _stream(a)), "sf_gemm_bf16")
 
 
@@ -265,22 +290,7 @@ def gemm_fp8(a: Tensor, a_scale: Tensor, rows_per_segment: int, w: Tensor, w_sca
         if t.dim() != 1 or t.numel() != size or not t.is_contiguous():
             raise ValueError(f"gemm_fp8: {n} must be a contiguous fp32 vector of {size}, got {tuple(t.shape)}")
     out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
-    g = _lib.GemmArgs()
-    g.a, g.w, g.bias, g.out = a.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr()
-    g.M, g.N, g.K = M, N, K
-    g.lda, g.ldw, g.ldo = a.stride(0), w.stride(0), out.stride(0)
-    g.epilogue, g.rows_per_group, g.structure = epilogue, rows_per_group, structure
-    if bias is not None:
-        _need_gpu(bias, "bias")
-    if resid is not None:
-        _need_gpu(resid, "resid")
-        g.resid, g.ldr = resid.data_ptr(), resid.stride(0)
-    if gate_mod is not None:
-        _need_gpu(gate_mod, "gate_mod")
-        g.gate_mod = gate_mod.data_ptr()
-    if gate_e0 is not None:
-        _need_gpu(gate_e0, "gate_e0")
-        g.gate_e0, g.gate_group_stride = gate_e0.data_ptr(), gate_e0.stride(0)
+    g = _gemm_args(out, a, w, bias, epilogue, resid, gate_mod, gate_e0, rows_per_group, structure)
     _lib.check(_lib.lib().sf_gemm_fp8(g, a_scale.data_ptr(), rows_per_segment, w_scale.data_ptr(), _stream(a)), "sf_gemm_fp8")
     return out
 
@@ -346,7 +356,7 @@ def _(x0, eps, timestep, sigmas, timesteps):
 
 
 # ------------------------------------------------------------------------------------------ fused DiT forward
-_TABLES: Dict[int, tuple] = {}
+_TABLES: Dict[str, Dict[tuple, tuple]] = {}    # per operator: {(model handle, stream): (key, pointer arrays)}
 
 # Host time spent INSIDE sf_dit_forward (the C call that enqueues the ~430 launches of a pass), per calling thread:
 # {thread id: [calls, wall seconds, CPU seconds of the thread]}.  Wall time includes waiting for room in the stream's
@@ -367,27 +377,26 @@ def host_enqueue_stats(reset: bool = False):
     return calls, wall, cpu, n
 
 
-def _pointer_tables(handle: int, k: Sequence[Tensor], v: Sequence[Tensor], ck: Sequence[Tensor], cv: Sequence[Tensor],
-                    want_kv: tuple, want_cross: tuple, device):
-    """Per-layer cache pointer arrays for the C call; rebuilt -- and every tensor validated (bf16, contiguous, the
-    expected [B, S, H, D] on the call's device: the kernels WRITE through these pointers) -- only when a cache tensor
-    was re-allocated / rebound or the expected shape changed."""
-    key = (want_kv, want_cross) + tuple(t.data_ptr() for t in k) + tuple(t.data_ptr() for t in v) + tuple(t.data_ptr() for t in ck) \
-        + tuple(t.data_ptr() for t in cv)
+def _cache_tables(slot_kind: str, handle: int, named_lists, device):
+    """Per-layer cache pointer arrays for the C call, one per (name, tensors, expected shape) of `named_lists`; rebuilt --
+    and every tensor validated (bf16, contiguous, the expected [B, S, H, D] on the call's device: the kernels WRITE
+    through these pointers) -- only when a cache tensor was re-allocated / rebound or the expected shape changed.
+    `slot_kind` names the operator (in the messages); each operator keeps its own tables, at most 64 of them."""
+    key = tuple(want for _, _, want in named_lists) + tuple(t.data_ptr() for _, ts, _ in named_lists for t in ts)
+    tables = _TABLES.setdefault(slot_kind, {})
     slot = (handle, torch.cuda.current_stream(device).cuda_stream)
-    hit = _TABLES.get(slot)
+    hit = tables.get(slot)
     if hit is not None and hit[0] == key:
         return hit[1]
-    for name, tensors, want in (("k_cache", k, want_kv), ("v_cache", v, want_kv), ("ck_cache", ck, want_cross), ("cv_cache", cv, want_cross)):
+    for name, tensors, want in named_lists:
         for i, t in enumerate(tensors):
             if not t.is_cuda or t.dtype != torch.bfloat16 or tuple(t.shape) != want or not t.is_contiguous() or t.device != device:
-                raise ValueError(f"dit_forward: {name}[{i}] must be a contiguous bf16 tensor {want} on {device}, got "
+                raise ValueError(f"{slot_kind}: {name}[{i}] must be a contiguous bf16 tensor {want} on {device}, got "
                                  f"{tuple(t.shape)} {t.dtype} {t.device}")
-    arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])  # noqa: E731
-    tabs = (arr(k), arr(v), arr(ck), arr(cv))
-    if len(_TABLES) > 64:
-        _TABLES.clear()
-    _TABLES[slot] = (key, tabs)
+    tabs = tuple((C.c_void_p * len(ts))(*[t.data_ptr() for t in ts]) for _, ts, _ in named_lists)
+    if len(tables) > 64:
+        tables.clear()
+    tables[slot] = (key, tabs)
     return tabs
 
 
@@ -431,11 +440,10 @@ def _forward_args(m, model: int, noisy: Tensor, timestep: Tensor, prompt_embeds:
         _need_gpu(add_condition, "add_condition")
         if add_condition.dim() != 3 or add_condition.shape[:2] != (B, n_new) or not add_condition.is_contiguous():
             raise ValueError(f"dit_forward: add_condition must be contiguous [{B}, {n_new}, pose_dim], got {tuple(add_condition.shape)}")
-    if not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise ValueError("dit_forward: workspace must be a contiguous CUDA uint8 tensor")
-    if evict_scratch is not None and (not evict_scratch.is_cuda or evict_scratch.dtype != torch.uint8 or not evict_scratch.is_contiguous()):
-        raise ValueError("dit_forward: evict_scratch must be a contiguous CUDA uint8 tensor")
-    k_ptrs, v_ptrs, ck_ptrs, cv_ptrs = _pointer_tables(model, k_cache, v_cache, ck_cache, cv_cache, want_kv, want_cross, noisy.device)
+    _need_bytes("dit_forward", workspace=workspace, evict_scratch=evict_scratch)
+    k_ptrs, v_ptrs, ck_ptrs, cv_ptrs = _cache_tables("dit_forward", model, (("k_cache", k_cache, want_kv), ("v_cache", v_cache, want_kv),
+                                                                            ("ck_cache", ck_cache, want_cross), ("cv_cache", cv_cache, want_cross)),
+                                                     noisy.device)
     a = _lib.ForwardArgs()
     a.batch, a.frames, a.lat_h, a.lat_w, a.groups = B, F, H, W, timestep.shape[1]
     a.noisy, a.timestep = noisy.data_ptr(), timestep.data_ptr()
@@ -465,84 +473,49 @@ def _forward_args(m, model: int, noisy: Tensor, timestep: Tensor, prompt_embeds:
     return a, flow, x0
 
 
-def _timed_call(fn, *args) -> int:
-    """The C call, with its wall and CPU time booked to the calling thread (HOST_ENQUEUE)."""
+def _forward_call(m, passes, cross_keys: Optional[Tensor], cross_log2w: Optional[Tensor], stream: int, i2v_args=None) -> None:
+    """sf_dit_forward over one or two filled sf_forward_args, with its wall and CPU time booked to the calling thread
+    (HOST_ENQUEUE)."""
+    call = _lib.ForwardCall()
+    for i, a in enumerate(passes):
+        call.passes[i] = C.pointer(a)
+    call.n_passes = len(passes)
+    call.cross_keys, call.cross_log2w = _ptr(cross_keys), _ptr(cross_log2w)
+    if i2v_args is not None:
+        call.i2v_model, call.i2v_args = C.pointer(m.i2v_cmodel), C.pointer(i2v_args)
+    fn = _lib.lib().sf_dit_forward
     t0, c0 = time.perf_counter(), time.thread_time()
-    rc = fn(*args)
+    rc = fn(C.byref(m.cmodel), C.byref(call), stream)
     dt, dc = time.perf_counter() - t0, time.thread_time() - c0
     rec = HOST_ENQUEUE.setdefault(threading.get_ident(), [0, 0.0, 0.0])
     rec[0] += 1
     rec[1] += dt
     rec[2] += dc
-    return rc
+    _lib.check(rc, "sf_dit_forward")
 
 
 @custom_op(f"{NAMESPACE}::dit_forward",
-           mutates_args=("k_cache", "v_cache", "ck_cache", "cv_cache", "workspace", "evict_scratch", "kv_index"))
+           mutates_args=("k_cache", "v_cache", "ck_cache", "cv_cache", "workspace", "evict_scratch", "kv_index", "cross_keys", "cross_log2w"))
 def dit_forward(model: int, noisy: Tensor, timestep: Tensor, prompt_embeds: Optional[Tensor], add_condition: Optional[Tensor],
                 k_cache: List[Tensor], v_cache: List[Tensor], ck_cache: List[Tensor], cv_cache: List[Tensor],
                 workspace: Tensor, evict_scratch: Optional[Tensor], init_cross: bool, cache_only: bool, sink: int, evict: int,
                 keep: int, write_start: int, attn_start: int, attn_end: int, start_frame: int,
-                kv_index: Optional[Tensor], global_end: int) -> Tuple[Tensor, Tensor]:
+                kv_index: Optional[Tensor], global_end: int, cross_keys: Optional[Tensor],
+                cross_log2w: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
     """One denoiser pass (CausalWanModel._forward_inference + flow -> x0, sf_dit_forward).  Writes the new K/V rows
     into k_cache / v_cache (and, with init_cross, the text K/V into ck_cache / cv_cache); returns (flow, x0), or two
     empty tensors with cache_only.  kv_index (optional, int64 [num_layers, 2]): every row <- (global_end, attn_end),
-    the cache dicts' index tensors when they are views of one buffer."""
-    return _dit_forward(model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
-                        init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame, kv_index, global_end,
-                        None, None)
-
-
-@custom_op(f"{NAMESPACE}::dit_forward_fold",
-           mutates_args=("k_cache", "v_cache", "ck_cache", "cv_cache", "workspace", "evict_scratch", "kv_index", "cross_keys", "cross_log2w"))
-def dit_forward_fold(model: int, noisy: Tensor, timestep: Tensor, prompt_embeds: Optional[Tensor], add_condition: Optional[Tensor],
-                     k_cache: List[Tensor], v_cache: List[Tensor], ck_cache: List[Tensor], cv_cache: List[Tensor],
-                     workspace: Tensor, evict_scratch: Optional[Tensor], init_cross: bool, cache_only: bool, sink: int, evict: int,
-                     keep: int, write_start: int, attn_start: int, attn_end: int, start_frame: int,
-                     kv_index: Optional[Tensor], global_end: int, cross_keys: Tensor, cross_log2w: Tensor) -> Tuple[Tensor, Tensor]:
-    """dit_forward with the cross-attention padding folded (sf_dit_forward_fold): cross_keys / cross_log2w (int32 / float32
-    [num_layers, B]) are the cross-attention caches' folded key counts (cross_fold_scan), written with init_cross and
-    read by every layer's cross-attention."""
-    return _dit_forward(model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
-                        init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame, kv_index, global_end,
-                        cross_keys, cross_log2w)
-
-
-def _dit_forward(model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
-                 init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame, kv_index, global_end,
-                 cross_keys, cross_log2w):
+    the cache dicts' index tensors when they are views of one buffer.  cross_keys / cross_log2w (int32 / float32
+    [num_layers, B], both or neither): the cross-attention caches' folded key counts (cross_fold_scan), written with
+    init_cross and read by every layer's cross-attention; None: every text key is attended.  (No default: torch drops a
+    trailing argument left at its default before it bumps the version counters of the mutated ones, and then fails.)"""
     m = _model(model)
     a, flow, x0 = _forward_args(m, model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace,
                                 evict_scratch, init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame,
                                 kv_index, global_end)
     _fold_pair(cross_keys, cross_log2w, (m.num_layers, noisy.shape[0]), noisy.device, "dit_forward")
-    _lib.check(_timed_call(_lib.lib().sf_dit_forward_fold, C.byref(m.cmodel), C.byref(a), _ptr(cross_keys), _ptr(cross_log2w), _stream(noisy)),
-               "sf_dit_forward")
+    _forward_call(m, (a,), cross_keys, cross_log2w, _stream(noisy))
     return flow, x0
-
-
-_IMG_TABLES: Dict[tuple, tuple] = {}
-
-
-def _image_tables(handle: int, kimg: Sequence[Tensor], vimg: Sequence[Tensor], want: tuple, device):
-    """The image caches' pointer arrays, kept like `_pointer_tables` keeps the other four: rebuilt -- and every tensor
-    validated (the kernels WRITE through these pointers) -- only when a tensor was rebound or the expected shape changed."""
-    key = (want,) + tuple(t.data_ptr() for t in kimg) + tuple(t.data_ptr() for t in vimg)
-    slot = (handle, torch.cuda.current_stream(device).cuda_stream)
-    hit = _IMG_TABLES.get(slot)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    for name, tensors in (("kimg_cache", kimg), ("vimg_cache", vimg)):
-        for i, t in enumerate(tensors):
-            if not t.is_cuda or t.dtype != torch.bfloat16 or tuple(t.shape) != want or not t.is_contiguous() or t.device != device:
-                raise ValueError(f"dit_forward_i2v: {name}[{i}] must be a contiguous bf16 tensor {want} on {device}, got "
-                                 f"{tuple(t.shape)} {t.dtype} {t.device}")
-    arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])  # noqa: E731
-    tabs = (arr(kimg), arr(vimg))
-    if len(_IMG_TABLES) > 64:
-        _IMG_TABLES.clear()
-    _IMG_TABLES[slot] = (key, tabs)
-    return tabs
 
 
 @custom_op(f"{NAMESPACE}::dit_forward_i2v",
@@ -554,7 +527,7 @@ def dit_forward_i2v(model: int, noisy: Tensor, timestep: Tensor, prompt_embeds: 
                     evict_scratch: Optional[Tensor], init_cross: bool, cache_only: bool, sink: int, evict: int, keep: int,
                     write_start: int, attn_start: int, attn_end: int, start_frame: int, kv_index: Optional[Tensor], global_end: int,
                     cross_keys: Optional[Tensor] = None, cross_log2w: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
-    """One pass of an i2v generator (sf_dit_forward_i2v): dit_forward[_fold] plus y (bf16 [B or 1, 20, F, H, W], any batch /
+    """One pass of an i2v generator (sf_dit_forward with sf_i2v_args): dit_forward plus y (bf16 [B or 1, 20, F, H, W], any batch /
     channel / frame strides over contiguous H x W planes: a frame slice of the clip's y needs no copy) in the patch
     embedding and the image keys behind every layer's text cross-attention.  clip_feature (bf16 [B, clip_len, clip_dim],
     contiguous) is read with init_cross only, which fills kimg_cache / vimg_cache ([B, clip_len, H, D] per layer)."""
@@ -586,10 +559,10 @@ def dit_forward_i2v(model: int, noisy: Tensor, timestep: Tensor, prompt_embeds: 
     if len(kimg_cache) != m.num_layers or len(vimg_cache) != m.num_layers:
         raise ValueError(f"dit_forward_i2v: image cache lists must have {m.num_layers} entries")
     want = (B, sh.clip_len, sh.num_heads, sh.head_dim)
-    ia.kimg_cache_host, ia.vimg_cache_host = _image_tables(model, kimg_cache, vimg_cache, want, noisy.device)
+    ia.kimg_cache_host, ia.vimg_cache_host = _cache_tables("dit_forward_i2v", model, (("kimg_cache", kimg_cache, want), ("vimg_cache", vimg_cache, want)),
+                                                           noisy.device)
     _fold_pair(cross_keys, cross_log2w, (m.num_layers, B), noisy.device, "dit_forward_i2v")
-    _lib.check(_timed_call(_lib.lib().sf_dit_forward_i2v, C.byref(m.cmodel), C.byref(m.i2v_cmodel), C.byref(a), C.byref(ia), _ptr(cross_keys),
-                           _ptr(cross_log2w), _stream(noisy)), "sf_dit_forward_i2v")
+    _forward_call(m, (a,), cross_keys, cross_log2w, _stream(noisy), i2v_args=ia)
     return flow, x0
 
 
@@ -640,7 +613,7 @@ def dit_forward_pair(model: int, ctx_noisy: Tensor, ctx_timestep: Tensor, noisy:
                      cross_log2w: Optional[Tensor] = None, ctx_add_condition: Optional[Tensor] = None,
                      add_condition: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """The context pass of one chunk (cache_only) and the first denoising pass of the next in ONE call
-    (sf_dit_forward_pair): bit-identical to the two calls, twice the rows per GEMM.  `ctx_plan` / `plan` =
+    (sf_dit_forward with two passes): bit-identical to the two calls, twice the rows per GEMM.  `ctx_plan` / `plan` =
     [sink, evict, keep, write_start, attn_start, attn_end, start_frame] of the two passes; workspace sized for 2 x batch.
     cross_keys / cross_log2w as in dit_forward (read only); ctx_add_condition / add_condition: each pass's pose tokens, as
     dit_forward's add_condition.  Returns (flow, x0) of the denoising pass."""
@@ -652,8 +625,7 @@ def dit_forward_pair(model: int, ctx_noisy: Tensor, ctx_timestep: Tensor, noisy:
     a1, flow, x0 = _forward_args(m, model, noisy, timestep, None, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
                                  False, False, *plan, kv_index, global_end)
     _fold_pair(cross_keys, cross_log2w, (m.num_layers, noisy.shape[0]), noisy.device, "dit_forward_pair")
-    _lib.check(_timed_call(_lib.lib().sf_dit_forward_pair_fold, C.byref(m.cmodel), C.byref(a0), C.byref(a1), _ptr(cross_keys), _ptr(cross_log2w),
-                           _stream(noisy)), "sf_dit_forward_pair")
+    _forward_call(m, (a0, a1), cross_keys, cross_log2w, _stream(noisy))
     return flow, x0
 
 
@@ -665,16 +637,10 @@ def _(model, ctx_noisy, ctx_timestep, noisy, timestep, k_cache, v_cache, ck_cach
     return noisy.new_empty((B, F, out_dim, H, W)), noisy.new_empty((B, F, out_dim, H, W))
 
 
-@dit_forward_fold.register_fake
+@dit_forward.register_fake
 def _(model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
       init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame, kv_index, global_end,
       cross_keys, cross_log2w):
-    return _dit_forward_fake(model, noisy, cache_only)
-
-
-@dit_forward.register_fake
-def _(model, noisy, timestep, prompt_embeds, add_condition, k_cache, v_cache, ck_cache, cv_cache, workspace, evict_scratch,
-      init_cross, cache_only, sink, evict, keep, write_start, attn_start, attn_end, start_frame, kv_index, global_end):
     return _dit_forward_fake(model, noisy, cache_only)
 
 
@@ -701,9 +667,7 @@ def vae_decode_frames(model: int, state: Tensor, scratch: Tensor, z: Tensor, out
         raise ValueError("vae_decode_frames: contiguous z [F, z_dim, h, w] and out expected")
     if tuple(z.shape[1:]) != (m.shape.z_dim, h, w):
         raise ValueError(f"vae_decode_frames: z must be [F, {m.shape.z_dim}, {h}, {w}], got {tuple(z.shape)}")
-    for name, t in (("state", state), ("scratch", scratch)):       # their element counts are passed on as BYTE counts
-        if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError(f"vae_decode_frames: {name} must be a contiguous CUDA uint8 tensor")
+    _need_bytes("vae_decode_frames", state=state, scratch=scratch)
     sf_, tf_ = m.shape.spatial_factor, m.shape.temporal_factor
     frames = 1 if frame_index == 0 else tf_ * z.shape[0]
     if frame_index == 0 and z.shape[0] != 1:
@@ -730,9 +694,7 @@ def taehv_decode_frames(model: int, state: Tensor, scratch: Tensor, z: Tensor, o
     zc = m.cmodel.z_dim
     if tuple(z.shape[1:]) != (zc, h, w):
         raise ValueError(f"taehv_decode_frames: z must be [F, {zc}, {h}, {w}], got {tuple(z.shape)}")
-    for name, t in (("state", state), ("scratch", scratch)):       # their element counts are passed on as BYTE counts
-        if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError(f"taehv_decode_frames: {name} must be a contiguous CUDA uint8 tensor")
+    _need_bytes("taehv_decode_frames", state=state, scratch=scratch)
     need = 4 * z.shape[0] * 3 * (8 * h) * (8 * w)
     if out.numel() < need:
         raise ValueError(f"taehv_decode_frames: out holds {out.numel()} floats, {4 * z.shape[0]} frames of 3 x {8 * h} x {8 * w} need {need}")
@@ -755,9 +717,7 @@ def vae_encode_frames(model: int, state: Tensor, scratch: Tensor, pixels: Tensor
         raise ValueError(f"vae_encode_frames: pixels must be bf16 or float32, got {pixels.dtype}")
     if pixels.dim() != 4 or pixels.shape[0] != 3 or tuple(pixels.shape[2:]) != (H, W) or not pixels[0].is_contiguous():
         raise ValueError(f"vae_encode_frames: pixels must be [3, T, {H}, {W}] with contiguous frames, got {tuple(pixels.shape)}")
-    for name, t in (("state", state), ("scratch", scratch)):       # their element counts are passed on as BYTE counts
-        if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError(f"vae_encode_frames: {name} must be a contiguous CUDA uint8 tensor")
+    _need_bytes("vae_encode_frames", state=state, scratch=scratch)
     T = pixels.shape[1]
     if chunk_index == 0:
         if T != 1:
@@ -794,9 +754,7 @@ def taehv_encode_frames(model: int, state: Tensor, scratch: Tensor, pixels: Tens
         raise ValueError(f"taehv_encode_frames: pixels must be bf16 or float32, got {pixels.dtype}")
     if pixels.dim() != 4 or pixels.shape[0] != 3 or pixels.shape[1] < 1 or tuple(pixels.shape[2:]) != (H, W) or not pixels[0].is_contiguous():
         raise ValueError(f"taehv_encode_frames: pixels must be [3, T, {H}, {W}] with contiguous frames, got {tuple(pixels.shape)}")
-    for name, t in (("state", state), ("scratch", scratch)):       # their element counts are passed on as BYTE counts
-        if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError(f"taehv_encode_frames: {name} must be a contiguous CUDA uint8 tensor")
+    _need_bytes("taehv_encode_frames", state=state, scratch=scratch)
     n = lead + pixels.shape[1]
     if not 0 <= lead <= 3 or n % 4:
         raise ValueError(f"taehv_encode_frames: lead={lead} + {pixels.shape[1]} pixel frames is not a whole number of 4-frame groups")
@@ -804,7 +762,7 @@ def taehv_encode_frames(model: int, state: Tensor, scratch: Tensor, pixels: Tens
     if tuple(out.shape) != (n // 4, zc, H // 8, W // 8) or not out.is_contiguous():
         raise ValueError(f"taehv_encode_frames: out must be contiguous [{n // 4}, {zc}, {H // 8}, {W // 8}], got {tuple(out.shape)}")
     _lib.check(_lib.lib().sf_taehv_encode_frames(C.byref(m.cmodel), state.data_ptr(), state.numel(), scratch.data_ptr(), scratch.numel(),
-                                                 pixels.data_ptr(), _lib.TAEHV_PIXEL_DTYPES[str(pixels.dtype).replace("torch.", "")],
+                                                 pixels.data_ptr(), _lib.TAEHV_PIXEL_DTYPES[_dtype_name(pixels)],
                                                  pixels.stride(0), H, W, n, lead, out.data_ptr(), _stream(pixels)),
                "sf_taehv_encode_frames")
 
@@ -844,7 +802,7 @@ def clip_encode(model: int, frames: Tensor, workspace: Tensor) -> Tensor:
         raise ValueError(f"clip_encode: frames must be contiguous [n, 3, H, W], got {tuple(frames.shape)}")
     n, _, H, W = frames.shape
     out = torch.empty(n, m.shape.seq_len, m.shape.dim, dtype=torch.float32, device=frames.device)
-    _lib.check(_lib.lib().sf_clip_encode(C.byref(m.cmodel), frames.data_ptr(), _lib.CLIP_DTYPES[str(frames.dtype).split(".")[-1]], n, H, W,
+    _lib.check(_lib.lib().sf_clip_encode(C.byref(m.cmodel), frames.data_ptr(), _lib.CLIP_DTYPES[_dtype_name(frames)], n, H, W,
                                          out.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(frames)), "sf_clip_encode")
     return out
 
@@ -940,5 +898,5 @@ def _(out, frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_lay
     return None
 
 
-OPS = ("attention", "attention_accum", "dit_forward_i2v", "i2v_assemble_y", "gemm", "gemm_out", "lincomb", "lincomb_out", "add_noise", "dit_forward", "dit_forward_pair", "vae_decode_frames", "vae_encode_frames", "taehv_decode_frames",
-       "taehv_encode_frames", "t5_encode", "clip_encode", "resize_frames", "resize_frames_out")
+# every operator this module registered, by its name under torch.ops.sf_hip
+OPS = tuple(op._name for op in list(globals().values()) if isinstance(op, torch.library.CustomOpDef))

@@ -199,32 +199,14 @@ def test_c_entry_points_reject_bad_arguments_without_touching_the_gpu():
         enc.workspace_bytes(0)
 
 
-def _struct_fields(text, name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    out = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            decl = re.sub(r"^(const\s+)?(struct\s+)?\w+\s*", "", decl)
-            out += [re.sub(r"[\s*]", "", d) for d in decl.split(",")]
-    return out
-
-
 def test_ctypes_mirror_matches_the_header():
+    """(Field names and argument counts against the header: test_host_logic.test_ctypes_mirror_matches_the_header.)"""
     text = open(os.path.join(ROOT, "include", "sf_hip.h")).read()
-    assert [f[0] for f in sfa._lib.ClipLayer._fields_] == _struct_fields(text, "sf_clip_layer")
-    assert [f[0] for f in sfa._lib.ClipModel._fields_] == _struct_fields(text, "sf_clip_model")
     assert ctypes.sizeof(sfa._lib.ClipLayer) == 12 * 8 and ctypes.sizeof(sfa._lib.ClipModel) == 32 + 6 * 8
     assert sfa._lib.ClipModel.patch_w.offset == 32 and sfa._lib.ClipModel.eps.offset == 24
     enum = re.search(r"enum sf_clip_dtype \{(.*?)\}", text).group(1)
     assert re.sub(r"\s", "", enum) == "SF_CLIP_F32=0,SF_CLIP_BF16=1" and sfa._lib.CLIP_DTYPES == {"float32": 0, "bfloat16": 1}
-    nocomment = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in ("sf_clip_preprocess", "sf_clip_embed_norm", "sf_clip_add_layernorm", "sf_clip_attention", "sf_clip_gelu", "sf_clip_workspace_bytes",
-                 "sf_clip_encode"):
-        decl = re.search(r"\b%s\((.*?)\);" % name, nocomment, re.S).group(1)
-        assert len(decl.split(",")) == len(sfa._lib.SIGNATURES[name][1]), name
-    assert int(re.search(r"#define SF_HIP_ABI_VERSION (\d+)", text).group(1)) == 10      # entry points are only added
+    assert int(re.search(r"#define SF_HIP_ABI_VERSION (\d+)", text).group(1)) == 11
     assert "clip_encode" in sfa.torch_ops.OPS and "Tensor(a2!) workspace" in str(torch.ops.sf_hip.clip_encode.default._schema)
 
 

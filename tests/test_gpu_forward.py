@@ -417,7 +417,7 @@ def test_add_condition_identity_projection_on_dim_5120_models():
 
 @pytest.mark.parametrize("nfpb,frames,las,sink,batch", [(2, 6, -1, 0, 1), (1, 7, 3, 1, 1), (3, 6, -1, 0, 2), (1, 5, 2, 0, 2)])
 def test_pairing_the_context_pass_with_the_next_chunks_first_pass_is_bit_identical(sd_reduced, nfpb, frames, las, sink, batch):
-    """`sf_dit_forward_pair`: a chunk's context pass and the next chunk's first denoising pass as ONE call (twice the rows per
+    """`sf_dit_forward` with two passes: a chunk's context pass and the next chunk's first denoising pass as ONE call (twice the rows per
     GEMM) against the reference's order, one call per pass: the same latents, the same K / V in every layer's cache and the
     same cache indices, bit for bit -- global cache, rolling window with eviction in the paired pass, batch 1 and 2."""
     g = torch.Generator().manual_seed(91 + frames)

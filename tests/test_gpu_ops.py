@@ -476,8 +476,9 @@ def test_torch_ops_bit_identical_to_the_ctypes_path():
     q, k, v = bf((1, 300, 2, 128), g).to(DEV), bf((1, 1000, 2, 128), g).to(DEV), bf((1, 1000, 2, 128), g).to(DEV)
     stream = torch.cuda.current_stream().cuda_stream
     direct = torch.empty_like(q)
-    _lib.check(_lib.lib().sf_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), direct.data_ptr(), 1, 2, 300, 1000, 256, 300 * 256,
-                                       256, 1000 * 256, 256, 300 * 256, stream))
+    aa = _lib.AttentionArgs(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), out=direct.data_ptr(), B=1, H=2, Lq=300, Lk=1000, q_stride=256,
+                            q_bstride=300 * 256, kv_stride=256, kv_bstride=1000 * 256, o_stride=256, o_bstride=300 * 256)
+    _lib.check(_lib.lib().sf_attention(aa, stream))
     assert torch.equal(torch.ops.sf_hip.attention(q, k, v), direct)
     assert torch.equal(ops.attention(q, k, v), direct)
 

@@ -151,19 +151,84 @@ def test_library_exports_every_declared_symbol():
     assert handle.sf_abi_version() == sfa._lib.ABI_VERSION
 
 
+def _header_structs(text):
+    """{struct name: [field names]} of every `typedef struct sf_* { ... } sf_*;` of the header."""
+    out = {}
+    for name, body in re.findall(r"typedef struct (sf_\w+) \{(.*?)\} \1;", text, re.S):
+        fields = []
+        for decl in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";"):
+            decl = re.sub(r"^(const\s+)?(struct\s+)?\w+\s*", "", decl.strip())      # drop the type
+            fields += [re.sub(r"[\s*]|\bconst\b|\[.*", "", d) for d in decl.split(",") if d.strip()]
+        out[name] = fields
+    return out
+
+
+def test_ctypes_mirror_matches_the_header():
+    """Every struct of include/sf_hip.h has a ctypes.Structure in `_lib` (sf_vae_resblock <-> VaeResBlock) with the same
+    field names in the same order, and the other way round; every entry of `_lib.SIGNATURES` has as many arguments as its
+    declaration, each a pointer where the header has one and else the scalar type of the header's width.
+    (Sizes and offsets are pinned per feature, beside the tests of the code that fills the structs.)"""
+    text = open(os.path.join(ROOT, "include", "sf_hip.h")).read()
+    structs = _header_structs(text)
+    mirrors = {n.lower(): c for n, c in vars(sfa._lib).items() if isinstance(c, type) and issubclass(c, ctypes.Structure)}
+    assert sorted(n[3:].replace("_", "") for n in structs) == sorted(mirrors), "a struct without its mirror, or a mirror without its struct"
+    for name, fields in structs.items():
+        assert [f[0] for f in mirrors[name[3:].replace("_", "")]._fields_] == fields, name
+    nocomment = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+               "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+    for name, (_, argtypes) in sfa._lib.SIGNATURES.items():
+        decl = re.search(r"\b%s\(([^;]*?)\);" % name, nocomment, re.S).group(1).strip()
+        args = [] if decl == "void" else [a.strip() for a in decl.split(",")]
+        assert len(args) == len(argtypes), name
+        # ... and of the same kind: a pointer where the header has one, else the scalar of the header's width
+        for arg, got in zip(args, argtypes):
+            if "*" in arg:
+                assert got in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(got, ctypes._Pointer), (name, arg, got)
+            else:
+                assert got is scalars[re.sub(r"\bconst\b", "", arg).split()[0]], (name, arg, got)
+    # the two argument structs of ABI 11, by hand from the header (LP64)
+    L = sfa._lib
+    assert ctypes.sizeof(L.AttentionArgs) == 4 * 8 + 4 * 4 + 6 * 8 + 2 * 4 + 2 * 8 == 120 and L.AttentionArgs.log2w.offset == 112
+    assert L.AttentionArgs.q_stride.offset == 48 and L.AttentionArgs.structure.offset == 96 and L.AttentionArgs.keys.offset == 104
+    assert ctypes.sizeof(L.ForwardCall) == 2 * 8 + 4 + 4 + 4 * 8 == 56 and L.ForwardCall.i2v_args.offset == 48
+    assert L.ForwardCall.n_passes.offset == 16 and L.ForwardCall.cross_keys.offset == 24
+
+
+def _attention_args(**over):
+    """A well-formed sf_attention_args over an aligned non-null address: every call fails its checks before any launch."""
+    p = 1 << 20
+    a = sfa._lib.AttentionArgs(q=p, k=p, v=p, out=p, B=1, H=2, Lq=72, Lk=257, q_stride=256, q_bstride=72 * 256, kv_stride=256,
+                               kv_bstride=257 * 256, o_stride=256, o_bstride=72 * 256)
+    for k, v in over.items():
+        setattr(a, k, v)
+    return a
+
+
 def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
     lib = sfa._lib.lib()
+    err = lib.sf_last_error
     assert lib.sf_gemm_bf16(None, None) != 0
-    assert b"null" in lib.sf_last_error()
+    assert b"null" in err()
     g = sfa._lib.GemmArgs()
     g.M, g.N, g.K = 4, 8, 100
-    assert lib.sf_gemm_bf16(g, None) != 0 and b"K=100" in lib.sf_last_error()
-    assert lib.sf_attention(None, None, None, None, 1, 1, 1, 1, 128, 128, 128, 128, 128, 128, None) != 0
-    # the two-pass call: null arguments, and two passes that do not name the same workspace
-    assert lib.sf_dit_forward_pair(None, None, None, None) != 0 and b"null" in lib.sf_last_error()
+    assert lib.sf_gemm_bf16(g, None) != 0 and b"K=100" in err()
+    # attention: a null struct, a null tensor, and the combinations the struct can name but no kernel computes
+    assert lib.sf_attention(None, None) != 0 and b"null" in err()
+    assert lib.sf_attention(_attention_args(q=None), None) != 0 and b"null" in err()
+    assert lib.sf_attention(_attention_args(structure=7), None) != 0 and b"unknown structure" in err()
+    assert lib.sf_attention(_attention_args(keys=1 << 20), None) != 0 and b"keys and log2w come together" in err()
+    assert lib.sf_attention(_attention_args(accumulate=1, keys=1 << 20, log2w=1 << 20), None) != 0 and b"accumulate" in err() and b"keys" in err()
+    # the forward: null arguments, and two passes that do not name the same workspace
+    assert lib.sf_dit_forward(None, None, None) != 0 and b"null" in err()
     m, a0, a1 = sfa._lib.Model(), sfa._lib.ForwardArgs(), sfa._lib.ForwardArgs()
+    assert lib.sf_dit_forward(m, sfa._lib.ForwardCall(n_passes=1), None) != 0 and b"null" in err()
     a0.workspace, a1.workspace = 16, 32
-    assert lib.sf_dit_forward_pair(m, a0, a1, None) != 0 and b"same workspace" in lib.sf_last_error()
+    two = sfa._lib.ForwardCall(n_passes=2)
+    two.passes[0], two.passes[1] = ctypes.pointer(a0), ctypes.pointer(a1)
+    assert lib.sf_dit_forward(m, two, None) != 0 and b"same workspace" in err()
+    two.n_passes = 3
+    assert lib.sf_dit_forward(m, two, None) != 0 and b"n_passes=3" in err()
     assert lib.sf_probe_copy(None, None, 64, None) != 0 and lib.sf_probe_mfma(0, 0, 0, None, None, None, None) != 0
 
 
@@ -461,10 +526,11 @@ def test_torch_custom_ops_have_fake_implementations():
         assert tuple(n.shape) == (3, 16, 8, 8)
         caches = [[e(1, 48, 4, 128) for _ in range(2)] for _ in range(2)] + [[e(1, 512, 4, 128) for _ in range(2)] for _ in range(2)]
         flow, x0 = torch.ops.sf_hip.dit_forward(h, e(1, 2, 16, 8, 12), e(1, 2, dt=torch.float32), None, None, *caches,
-                                                e(1024, dt=torch.uint8), None, False, False, 0, 0, 0, 0, 0, 48, 0, None, 0)
+                                                e(1024, dt=torch.uint8), None, False, False, 0, 0, 0, 0, 0, 48, 0, None, 0, None, None)
         assert tuple(flow.shape) == (1, 2, 16, 8, 12) and tuple(x0.shape) == (1, 2, 16, 8, 12)
         flow, x0 = torch.ops.sf_hip.dit_forward(h, e(1, 2, 16, 8, 12), e(1, 2, dt=torch.float32), None, None, *caches,
-                                                e(1024, dt=torch.uint8), None, False, True, 0, 0, 0, 0, 0, 48, 0, e(2, 2, dt=torch.int64), 24)
+                                                e(1024, dt=torch.uint8), None, False, True, 0, 0, 0, 0, 0, 48, 0, e(2, 2, dt=torch.int64), 24,
+                                                e(2, 1, dt=torch.int32), e(2, 1, dt=torch.float32))
         assert flow.numel() == 0
         t = torch.ops.sf_hip.t5_encode(h, e(2, 512, dt=torch.int64), e(2, 512, dt=torch.int64), e(1023, dt=torch.int32), e(64, dt=torch.uint8))
         assert tuple(t.shape) == (2, 512, 4096) and t.dtype == torch.bfloat16

@@ -118,30 +118,13 @@ def test_fixture_sees_the_image_branch(gold, restated):
 
 
 # ------------------------------------------------------------------------------------------ C ABI
-def _struct_fields(text, name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    out = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            decl = re.sub(r"^(const\s+)?(struct\s+)?\w+\s*", "", decl)
-            out += [re.sub(r"[\s*]|const", "", d) for d in decl.split(",")]
-    return out
-
-
 def test_ctypes_mirrors_match_the_header():
+    """(Field names and argument counts against the header: test_host_logic.test_ctypes_mirror_matches_the_header.)"""
     text = open(os.path.join(ROOT, "include", "sf_hip.h")).read()
     L = sfa._lib
-    for cls, name in ((L.I2VLayer, "sf_i2v_layer"), (L.I2VModel, "sf_i2v_model"), (L.I2VArgs, "sf_i2v_args")):
-        assert [f[0] for f in cls._fields_] == _struct_fields(text, name), name
     assert ctypes.sizeof(L.I2VLayer) == 3 * 8 and ctypes.sizeof(L.I2VModel) == 16 + 9 * 8 and ctypes.sizeof(L.I2VArgs) == 2 * 8 + 3 * 8 + 8 + 2 * 8
     assert L.I2VModel.img_ln0_w.offset == 16 and L.I2VArgs.kimg_cache_host.offset == 48
-    nocomment = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in ("sf_attention_accum", "sf_patchify_i2v", "sf_layernorm_rows", "sf_dit_i2v_workspace_bytes", "sf_dit_forward_i2v"):
-        decl = re.search(r"\b%s\((.*?)\);" % name, nocomment, re.S).group(1)
-        assert len(decl.split(",")) == len(L.SIGNATURES[name][1]), name
-    assert int(re.search(r"#define SF_HIP_ABI_VERSION (\d+)", text).group(1)) == 10 == L.ABI_VERSION == L.lib().sf_abi_version()
+    assert int(re.search(r"#define SF_HIP_ABI_VERSION (\d+)", text).group(1)) == 11 == L.ABI_VERSION == L.lib().sf_abi_version()
     # the t2v structs keep their layout: everything i2v travels beside them
     assert ctypes.sizeof(L.LayerWeights) == 21 * 8 and L.Model.layers_fp8_host.offset == ctypes.sizeof(L.Model) - 8
     sch = str(torch.ops.sf_hip.attention_accum.default._schema)
@@ -154,10 +137,13 @@ def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
     lib = sfa._lib.lib()
     err = lib.sf_last_error
     p = 1 << 20       # an aligned non-null address: every call below fails its checks before any launch
-    att = lambda structure: lib.sf_attention_accum(p, p, p, p, 1, 2, 72, 257, 256, 72 * 256, 256, 257 * 256, 256, 72 * 256, structure, None)  # noqa: E731
+    def att(structure, out=p):
+        a = sfa._lib.AttentionArgs(q=p, k=p, v=p, out=out, B=1, H=2, Lq=72, Lk=257, q_stride=256, q_bstride=72 * 256, kv_stride=256,
+                                   kv_bstride=257 * 256, o_stride=256, o_bstride=72 * 256, structure=structure, accumulate=1)
+        return lib.sf_attention(a, None)
     assert att(sfa._lib.ATTN_STRUCTURES["r64"]) != 0 and b"r64" in err() and b"accumulate" in err()
     assert att(7) != 0 and b"unknown structure" in err()
-    assert lib.sf_attention_accum(p, p, p, None, 1, 2, 72, 257, 256, 72 * 256, 256, 257 * 256, 256, 72 * 256, 0, None) != 0 and b"null" in err()
+    assert att(0, out=None) != 0 and b"null" in err()
     assert lib.sf_patchify_i2v(p, None, p, 1, 1, 16, 20, 48, 8, 12, 0, 96, 96, None) != 0 and b"bad arguments" in err()
     assert lib.sf_patchify_i2v(p, p, p, 1, 1, 16, 20, 48, 7, 12, 0, 84, 84, None) != 0 and b"must be even" in err()
     assert lib.sf_patchify_i2v(p, p, p, 1, 1, 16, 20, 32, 8, 12, 0, 96, 96, None) != 0 and b"do not fit" in err()
@@ -166,20 +152,29 @@ def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
     assert lib.sf_layernorm_rows(p, None, p, p, 4, 320, 1e-5, None) != 0 and b"null" in err()
 
     m, im, a, ia = sfa._lib.Model(), sfa._lib.I2VModel(), sfa._lib.ForwardArgs(), sfa._lib.I2VArgs()
-    assert lib.sf_dit_forward_i2v(None, im, a, ia, None, None, None) != 0 and b"null" in err()
-    assert lib.sf_dit_i2v_workspace_bytes(m, im, 1, 1, 8, 12, 1) == 0
+    call = sfa._lib.ForwardCall(n_passes=1, i2v_model=ctypes.pointer(im), i2v_args=ctypes.pointer(ia))
+    call.passes[0] = ctypes.pointer(a)
+    forward = lambda: lib.sf_dit_forward(m, call, None)  # noqa: E731
+    assert lib.sf_dit_forward(None, call, None) != 0 and b"null" in err()
+    call.i2v_args = None
+    assert forward() != 0 and b"null" in err()            # the model's half without the pass's
+    call.i2v_args = ctypes.pointer(ia)
+    assert lib.sf_dit_workspace_bytes(m, im, 1, 1, 8, 12, 1) == 0
     layers = (sfa._lib.I2VLayer * 2)()
     im.layers_host, im.clip_len, im.clip_dim = ctypes.cast(layers, ctypes.POINTER(sfa._lib.I2VLayer)), 257, 320
     m.dim, m.num_heads, m.num_layers, m.in_dim, m.out_dim = 512, 4, 2, 48, 16
-    assert lib.sf_dit_forward_i2v(m, im, a, ia, None, None, None) != 0 and b"y is missing" in err()
+    assert forward() != 0 and b"y is missing" in err()
     ia.y, ia.y_channels = p, 40
-    assert lib.sf_dit_forward_i2v(m, im, a, ia, None, None, None) != 0 and b"do not fit" in err()
+    assert forward() != 0 and b"do not fit" in err()
     ia.y_channels = 20
-    assert lib.sf_dit_forward_i2v(m, im, a, ia, None, None, None) != 0 and b"image cache" in err()
+    assert forward() != 0 and b"image cache" in err()
     m.fp8 = 1
-    assert lib.sf_dit_forward_i2v(m, im, a, ia, None, None, None) != 0 and b"fp8" in err()
+    assert forward() != 0 and b"fp8" in err()
     m.fp8, im.clip_dim = 0, 300
-    assert lib.sf_dit_forward_i2v(m, im, a, ia, None, None, None) != 0 and b"multiple of 64" in err()
+    assert forward() != 0 and b"multiple of 64" in err()
+    im.clip_dim, call.n_passes = 320, 2
+    call.passes[1] = ctypes.pointer(a)
+    assert forward() != 0 and b"two-pass call is not built" in err()
     with pytest.raises(ValueError, match="CUDA"):
         z = torch.zeros(1, 4, 1, 128, dtype=torch.bfloat16)
         sfa.ops.attention_accum(z, z, z, z.clone())

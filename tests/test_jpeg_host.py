@@ -279,7 +279,7 @@ def test_c_entry_points_reject_bad_arguments_without_touching_the_gpu():
 
 
 def test_python_mirror_matches_the_header():
-    """The enum values and argument counts `_lib.py` uses are those include/sf_hip.h declares."""
+    """The enum values `_lib.py` uses are those include/sf_hip.h declares (argument counts: test_host_logic)."""
     text = open(os.path.join(ROOT, "include", "sf_hip.h")).read()
     enum = lambda name: int(re.search(name + r" = (\d+)", text).group(1))                        # noqa: E731
     assert sfa._lib.JPEG_SUBSAMPLINGS == {"420": enum("SF_JPEG_420"), "444": enum("SF_JPEG_444")}
@@ -287,8 +287,6 @@ def test_python_mirror_matches_the_header():
     assert sfa._lib.JPEG_RANGES == {(-1, 1): enum("SF_JPEG_RANGE_PM1"), (0, 1): enum("SF_JPEG_RANGE_01")}
     assert sorted(sfa._lib.JPEG_STATUS) == [enum("SF_JPEG_SLOT_OVERFLOW"), enum("SF_JPEG_COEF_RANGE"), enum("SF_JPEG_OUT_OVERFLOW")]
     for name in ("sf_jpeg_workspace_bytes", "sf_jpeg_transform", "sf_jpeg_entropy", "sf_jpeg_encode_frames"):
-        decl = re.search(r"\b" + name + r"\(([^;]*?)\);", text, re.S).group(1)
-        assert len(decl.split(",")) == len(sfa._lib.SIGNATURES[name][1]), name
         getattr(sfa._lib.lib(), name)
     assert (sfa.jpeg_reference.SUBSAMPLINGS == sfa._lib.JPEG_SUBSAMPLINGS)
 

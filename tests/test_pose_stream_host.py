@@ -216,7 +216,7 @@ def test_stream_entry_points_reject_bad_arguments_without_touching_the_gpu(model
     assert push(before=4, n=5, closing=1, cap=2 * 24) != 0 and b"writes 3 x 4 x 6 = 72" in err()
     assert push(H=8, W=8) != 0 and b"no tokens" in err()
     assert n_out.value == -1                                               # nothing was written on a refusal
-    assert lib.sf_abi_version() == 10 == sfa._lib.ABI_VERSION
+    assert lib.sf_abi_version() == 11 == sfa._lib.ABI_VERSION
 
 
 def test_python_stream_checks_without_a_gpu(model):

@@ -183,7 +183,7 @@ def test_c_entry_points_reject_bad_arguments_without_touching_the_gpu():
     assert lib.sf_taehv_encode_reset(m, 4096, state - 1, 480, 832, None) != 0 and b"state of" in lib.sf_last_error()
     m.down[2].kt = 2
     assert lib.sf_taehv_encode_state_bytes(m, 480, 832) == 0 and b"pool 4 frames" in lib.sf_last_error()
-    assert lib.sf_abi_version() == 10
+    assert lib.sf_abi_version() == 11
     assert ctypes.sizeof(sfa._lib.TaehvDownConvArgs) == 3 * 8 + 8 * 4 and ctypes.sizeof(sfa._lib.TaehvEncoder) == (1 + 3 + 27 + 1) * 32
     assert sfa._lib.TAEHV_EPILOGUES["latent_f32"] == 5 and sfa._lib.TAEHV_EPILOGUES["head_f32"] == 4
 

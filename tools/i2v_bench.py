@@ -7,7 +7,7 @@ each call; median and all samples):
   the same seed, attending 4680 keys (the first chunk) and 32760 keys (the last chunk of a 21-frame cache);
 * the same pass with `init_cross` (the once-per-prompt work: text K / V for both, plus img_emb and k_img / v_img for i2v);
   the image context's cost is the difference of the two differences;
-* `sf_attention_accum` over 257 keys against `sf_attention` at the same shape (4680 queries, 12 heads).
+* `ops.attention_accum` over 257 keys against `ops.attention` at the same shape (4680 queries, 12 heads).
 
     python tools/i2v_bench.py [--iters 7] [--warmup 2] [--out profiles/i2v_bench.json]
 """

@@ -12,6 +12,8 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+from self_forcing_amd import _lib  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("names", nargs="+")
 ap.add_argument("--lk", default="4680,18720,32760")
@@ -25,8 +27,7 @@ a = ap.parse_args()
 libs = {}
 for n in a.names:
     h = C.CDLL(os.path.join(ROOT, "tools", "probes", "abl", f"libattn_{n}.so"))
-    h.sf_attention_ex.restype = C.c_int
-    h.sf_attention_ex.argtypes = [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_int64] * 6 + [C.c_int, C.c_void_p]
+    h.sf_attention.restype, h.sf_attention.argtypes = _lib.SIGNATURES["sf_attention"]
     h.sf_last_error.restype = C.c_char_p
     libs[n] = h
 
@@ -43,8 +44,10 @@ st = torch.cuda.current_stream().cuda_stream
 
 def launch(n, lk):
     kk, vv, o = k[:, :lk], v[:, :lk], outs[n]
-    rc = libs[n].sf_attention_ex(q.data_ptr(), kk.data_ptr(), vv.data_ptr(), o.data_ptr(), B, H, N, lk, q.stride(1), q.stride(0),
-                                 kk.stride(1), kk.stride(0), o.stride(1), o.stride(0), 1, st)
+    args = _lib.AttentionArgs(q=q.data_ptr(), k=kk.data_ptr(), v=vv.data_ptr(), out=o.data_ptr(), B=B, H=H, Lq=N, Lk=lk, q_stride=q.stride(1),
+                              q_bstride=q.stride(0), kv_stride=kk.stride(1), kv_bstride=kk.stride(0), o_stride=o.stride(1), o_bstride=o.stride(0),
+                              structure=_lib.ATTN_STRUCTURES["r64"])
+    rc = libs[n].sf_attention(args, st)
     assert rc == 0, libs[n].sf_last_error()
 
 
