@@ -13,7 +13,8 @@
  *   - every tensor is bf16 (uint16 storage) unless stated; row-major; strides in ELEMENTS;
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*; NULL = default
  *     stream), allocates nothing, never synchronises, reads no environment variables and keeps no
- *     state between calls (apart from registering a kernel's LDS size with the runtime on first use);
+ *     state between calls (apart from a per-device record that a kernel's LDS cap has been registered with
+ *     the runtime, kept lock-free, so any thread may make a kernel's first call on any device);
  *   - return 0 on success, negative on error; `sf_last_error()` gives a thread-local message.
  */
 #ifndef SF_HIP_H

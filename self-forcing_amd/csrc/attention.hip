@@ -824,6 +824,7 @@ static int attention_launch(const void* q, const void* k, const void* v, void* o
            "sf_attention: misaligned tensor");
   SF_CHECK(((long)(Lk - 1) * kv_stride + 128) * 2 < (1L << 31), "sf_attention: one (batch, head) K/V slab must span < 2 GiB");
   SF_CHECK(structure >= SF_ATTN_AUTO && structure <= SF_ATTN_W4, "sf_attention: unknown structure %d", structure);
+  const hipStream_t s = (hipStream_t)stream;
   AttP p;
   p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)out;
   p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk;
@@ -849,40 +850,23 @@ static int attention_launch(const void* q, const void* k, const void* v, void* o
   if (structure == SF_ATTN_R64) {
     SF_CHECK(out16, "sf_attention: the r64 structure needs 16-byte aligned output rows (out %% 16, o_stride %% 8, o_bstride %% 8)");
     p.q_tiles = (Lq + QT64 - 1) / QT64;
-    static bool attr = false;   // one-time registration of the kernels' LDS size (idempotent; no other state is kept)
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_r64_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, ATT64_LDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_r64_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, ATT64_LDS);
-      attr = true;
-    }
-    if (Lk > 1024)
-      hipLaunchKernelGGL(attention_r64_kernel<0>, dim3((unsigned)nwg64), dim3(256), ATT64_LDS, (hipStream_t)stream, p);
-    else
-      hipLaunchKernelGGL(attention_r64_kernel<1>, dim3((unsigned)nwg64), dim3(256), ATT64_LDS, (hipStream_t)stream, p);
-    SF_HIP_LAUNCH_CHECK("sf_attention");
-    return 0;
+    const dim3 grid((unsigned)nwg64), block(256);
+    if (Lk > 1024) return sf_launch<&attention_r64_kernel<0>, ATT64_LDS>("sf_attention", grid, block, ATT64_LDS, s, p);
+    return sf_launch<&attention_r64_kernel<1>, ATT64_LDS>("sf_attention", grid, block, ATT64_LDS, s, p);
   }
   if (structure == SF_ATTN_W8) {
     p.q_tiles = (Lq + QT8 - 1) / QT8;
-    if (accum)
-      hipLaunchKernelGGL(attention_w8_kernel<2>, dim3((unsigned)nwg8), dim3(ATT8_THREADS), ATT8_LDS, (hipStream_t)stream, p);
-    else if (Lk > 1024)
-      hipLaunchKernelGGL(attention_w8_kernel<0>, dim3((unsigned)nwg8), dim3(ATT8_THREADS), ATT8_LDS, (hipStream_t)stream, p);
-    else
-      hipLaunchKernelGGL(attention_w8_kernel<1>, dim3((unsigned)nwg8), dim3(ATT8_THREADS), ATT8_LDS, (hipStream_t)stream, p);
-    SF_HIP_LAUNCH_CHECK("sf_attention");
-    return 0;
+    const dim3 grid((unsigned)nwg8), block(ATT8_THREADS);
+    if (accum) return sf_launch<&attention_w8_kernel<2>>("sf_attention", grid, block, ATT8_LDS, s, p);
+    if (Lk > 1024) return sf_launch<&attention_w8_kernel<0>>("sf_attention", grid, block, ATT8_LDS, s, p);
+    return sf_launch<&attention_w8_kernel<1>>("sf_attention", grid, block, ATT8_LDS, s, p);
   }
   const long nwg = (long)p.q_tiles * H * B;
   SF_CHECK(nwg < (1L << 30), "sf_attention: grid too large");
-  if (accum)
-    hipLaunchKernelGGL(attention_kernel<2>, dim3((unsigned)nwg), dim3(ATT_THREADS), ATT_LDS, (hipStream_t)stream, p);
-  else if (Lk > 1024)
-    hipLaunchKernelGGL(attention_kernel<0>, dim3((unsigned)nwg), dim3(ATT_THREADS), ATT_LDS, (hipStream_t)stream, p);
-  else
-    hipLaunchKernelGGL(attention_kernel<1>, dim3((unsigned)nwg), dim3(ATT_THREADS), ATT_LDS, (hipStream_t)stream, p);
-  SF_HIP_LAUNCH_CHECK("sf_attention");
-  return 0;
+  const dim3 grid((unsigned)nwg), block(ATT_THREADS);
+  if (accum) return sf_launch<&attention_kernel<2>>("sf_attention", grid, block, ATT_LDS, s, p);
+  if (Lk > 1024) return sf_launch<&attention_kernel<0>>("sf_attention", grid, block, ATT_LDS, s, p);
+  return sf_launch<&attention_kernel<1>>("sf_attention", grid, block, ATT_LDS, s, p);
 }
 
 extern "C" int sf_attention(const sf_attention_args* a, void* stream) {

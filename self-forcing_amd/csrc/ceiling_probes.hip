@@ -62,10 +62,9 @@ extern "C" int sf_probe_mfma(int shape, int iters, int workgroups, const void* o
            shape, iters, workgroups);
   hipStream_t st = (hipStream_t)stream;
   if (shape == 0)
-    hipLaunchKernelGGL(probe_mfma_kernel<0>, dim3(workgroups), dim3(256), 0, st, (const bf16x8*)operands, sink, iters);
+    SF_TRY(sf_launch<&probe_mfma_kernel<0>>("sf_probe_mfma", dim3(workgroups), dim3(256), 0, st, (const bf16x8*)operands, sink, iters));
   else
-    hipLaunchKernelGGL(probe_mfma_kernel<1>, dim3(workgroups), dim3(256), 0, st, (const bf16x8*)operands, sink, iters);
-  SF_HIP_LAUNCH_CHECK("sf_probe_mfma");
+    SF_TRY(sf_launch<&probe_mfma_kernel<1>>("sf_probe_mfma", dim3(workgroups), dim3(256), 0, st, (const bf16x8*)operands, sink, iters));
   // 4 waves per workgroup; per iteration 32 x (32x32x16) or 64 x (16x16x32) MFMAs = 32 x 32768 flop either way
   if (flops_out) *flops_out = (double)workgroups * 4.0 * (double)iters * 32.0 * 32768.0;
   return 0;
@@ -74,7 +73,6 @@ extern "C" int sf_probe_mfma(int shape, int iters, int workgroups, const void* o
 extern "C" int sf_probe_copy(const void* src, void* dst, size_t bytes, void* stream) {
   SF_CHECK(src && dst && bytes >= 16 && bytes % 16 == 0, "sf_probe_copy: null pointer or byte count %zu not a multiple of 16", bytes);
   SF_CHECK(((uintptr_t)src | (uintptr_t)dst) % 16 == 0, "sf_probe_copy: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(probe_copy_kernel, dim3(256 * 16), dim3(256), 0, (hipStream_t)stream, (const u32x4*)src, (u32x4*)dst, (int64_t)(bytes / 16));
-  SF_HIP_LAUNCH_CHECK("sf_probe_copy");
-  return 0;
+  return sf_launch<&probe_copy_kernel>("sf_probe_copy", dim3(256 * 16), dim3(256), 0, (hipStream_t)stream, (const u32x4*)src, (u32x4*)dst,
+                                       (int64_t)(bytes / 16));
 }

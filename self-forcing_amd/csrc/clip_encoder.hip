@@ -367,11 +367,10 @@ extern "C" int sf_clip_preprocess(const void* frames, int dtype, int n, int H, i
   const float sy = (float)H / (float)image_size, sx = (float)W / (float)image_size;
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   if (dtype == SF_CLIP_F32)
-    hipLaunchKernelGGL(clip_preprocess_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)frames, (bf16_t*)rows, total, H, W, image_size, patch, kp, sy, sx);
-  else
-    hipLaunchKernelGGL(clip_preprocess_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)frames, (bf16_t*)rows, total, H, W, image_size, patch, kp, sy, sx);
-  SF_HIP_LAUNCH_CHECK("sf_clip_preprocess");
-  return 0;
+    return sf_launch<&clip_preprocess_kernel<float>>("sf_clip_preprocess", grid, block, 0, (hipStream_t)stream, (const float*)frames, (bf16_t*)rows, total, H,
+                                                     W, image_size, patch, kp, sy, sx);
+  return sf_launch<&clip_preprocess_kernel<bf16_t>>("sf_clip_preprocess", grid, block, 0, (hipStream_t)stream, (const bf16_t*)frames, (bf16_t*)rows, total, H,
+                                                    W, image_size, patch, kp, sy, sx);
 }
 
 extern "C" int sf_clip_embed_norm(const void* patch_out, const float* cls, const float* pos, const float* pre_w, const float* pre_b, const float* ln_w,
@@ -382,10 +381,8 @@ extern "C" int sf_clip_embed_norm(const void* patch_out, const float* cls, const
   SF_CHECK((long)n * (P + 1) < (1L << 31), "sf_clip_embed_norm: too many rows");
   SF_CHECK(aligned16(cls) && aligned16(pos) && aligned16(pre_w) && aligned16(pre_b) && aligned16(ln_w) && aligned16(ln_b) && aligned16(x32) &&
                ((uintptr_t)patch_out & 7) == 0 && ((uintptr_t)xn & 7) == 0, "sf_clip_embed_norm: misaligned tensor");
-  hipLaunchKernelGGL(clip_embed_norm_kernel, dim3(n * (P + 1)), dim3(256), (size_t)dim * 4, (hipStream_t)stream, (const bf16_t*)patch_out, cls, pos, pre_w, pre_b,
-                     ln_w, ln_b, x32, (bf16_t*)xn, P, dim, eps);
-  SF_HIP_LAUNCH_CHECK("sf_clip_embed_norm");
-  return 0;
+  return sf_launch<&clip_embed_norm_kernel>("sf_clip_embed_norm", dim3(n * (P + 1)), dim3(256), (size_t)dim * 4, (hipStream_t)stream, (const bf16_t*)patch_out,
+                                            cls, pos, pre_w, pre_b, ln_w, ln_b, x32, (bf16_t*)xn, P, dim, eps);
 }
 
 extern "C" int sf_clip_add_layernorm(float* x32, const void* y, const float* ln_w, const float* ln_b, void* xn, int rows, int dim, float eps, void* stream) {
@@ -393,9 +390,8 @@ extern "C" int sf_clip_add_layernorm(float* x32, const void* y, const float* ln_
   SF_CHECK(ln_w == nullptr || (ln_b && xn), "sf_clip_add_layernorm: ln_w needs ln_b and xn");
   SF_CHECK(rows > 0 && dim > 0 && dim % 4 == 0 && dim <= CLIP_MAX_DIM, "sf_clip_add_layernorm: rows=%d dim=%d (dim a multiple of 4, at most %d)", rows, dim, CLIP_MAX_DIM);
   SF_CHECK(aligned16(x32) && aligned16(ln_w) && aligned16(ln_b) && ((uintptr_t)y & 7) == 0 && ((uintptr_t)xn & 7) == 0, "sf_clip_add_layernorm: misaligned tensor");
-  hipLaunchKernelGGL(clip_add_layernorm_kernel, dim3(rows), dim3(256), (size_t)dim * 4, (hipStream_t)stream, x32, (const bf16_t*)y, ln_w, ln_b, (bf16_t*)xn, dim, eps);
-  SF_HIP_LAUNCH_CHECK("sf_clip_add_layernorm");
-  return 0;
+  return sf_launch<&clip_add_layernorm_kernel>("sf_clip_add_layernorm", dim3(rows), dim3(256), (size_t)dim * 4, (hipStream_t)stream, x32, (const bf16_t*)y,
+                                               ln_w, ln_b, (bf16_t*)xn, dim, eps);
 }
 
 extern "C" int sf_clip_attention(const void* qkv, void* out, int n, int L, int H, void* stream) {
@@ -406,13 +402,9 @@ extern "C" int sf_clip_attention(const void* qkv, void* out, int n, int L, int H
   SF_CHECK((long)n * L * 3 * H * CLIP_D < (1L << 40), "sf_clip_attention: tensor too large");
   const int Lp = (L + 31) & ~31;
   const int lds = (Lp * CLIP_KS + CLIP_D * (Lp + 8)) * 2;
-  constexpr int max_lp = (CLIP_MAX_L + 31) & ~31;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&clip_attention_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (max_lp * CLIP_KS + CLIP_D * (max_lp + 8)) * 2);
-  hipLaunchKernelGGL(clip_attention_kernel, dim3((L + 63) / 64, H, n), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, L, H, Lp,
-                     1.4426950408889634f / sqrtf((float)CLIP_D));
-  SF_HIP_LAUNCH_CHECK("sf_clip_attention");
-  return 0;
+  constexpr int max_lp = (CLIP_MAX_L + 31) & ~31, lds_cap = (max_lp * CLIP_KS + CLIP_D * (max_lp + 8)) * 2;   // the kernel's cap: lds at CLIP_MAX_L
+  return sf_launch<&clip_attention_kernel, lds_cap>("sf_clip_attention", dim3((L + 63) / 64, H, n), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)qkv,
+                                                    (bf16_t*)out, L, H, Lp, 1.4426950408889634f / sqrtf((float)CLIP_D));
 }
 
 extern "C" int sf_clip_gelu(const void* x, void* out, int64_t count, void* stream) {
@@ -420,9 +412,8 @@ extern "C" int sf_clip_gelu(const void* x, void* out, int64_t count, void* strea
   SF_CHECK(aligned16(x) && aligned16(out), "sf_clip_gelu: misaligned tensor");
   const long n8 = count / 8;
   SF_CHECK((n8 + 255) / 256 < (1L << 31), "sf_clip_gelu: count=%lld is too large for one launch", (long long)count);
-  hipLaunchKernelGGL(clip_gelu_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)x, (bf16x8*)out, n8);
-  SF_HIP_LAUNCH_CHECK("sf_clip_gelu");
-  return 0;
+  return sf_launch<&clip_gelu_kernel>("sf_clip_gelu", dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)x, (bf16x8*)out,
+                                      n8);
 }
 
 extern "C" size_t sf_clip_workspace_bytes(const sf_clip_model* m, int n) {

@@ -349,34 +349,20 @@ int launch_halo(const HaloP& p, int tiles, int epi, hipStream_t s) {
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static_assert(256 * (64 * NT + 16) + 1024 <= LDS, "epilogue staging + norm factors fit the k-loop's LDS");
   static_assert(NT == 3 || NT == 6, "bf16 epilogues: 96 or 192 columns per tile");
-  static bool done = false;   // one-time registration of the kernels' LDS size (idempotent)
-  if (!done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<NT, TPC, SF_CONV_BIAS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<NT, TPC, SF_CONV_BIAS_RESID>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    done = true;
-  }
   if (epi == SF_CONV_BIAS)
-    hipLaunchKernelGGL((conv_halo_kernel<NT, TPC, SF_CONV_BIAS>), dim3(tiles), dim3(HALO_THREADS), LDS, s, p);
-  else
-    hipLaunchKernelGGL((conv_halo_kernel<NT, TPC, SF_CONV_BIAS_RESID>), dim3(tiles), dim3(HALO_THREADS), LDS, s, p);
-  return 0;
+    return sf_launch<&conv_halo_kernel<NT, TPC, SF_CONV_BIAS>, LDS>("sf_conv_igemm", dim3(tiles), dim3(HALO_THREADS), LDS, s, p);
+  return sf_launch<&conv_halo_kernel<NT, TPC, SF_CONV_BIAS_RESID>, LDS>("sf_conv_igemm", dim3(tiles), dim3(HALO_THREADS), LDS, s, p);
 }
 
 int launch_halo_head(const HaloP& p, int tiles, hipStream_t s) {   // NT = 1: 32 columns, Cout <= 4 of them real
   constexpr int LDS = PLANE_RING * PLANE_SLOT + 3 * 3 * 32 * 64 + 8 * 1024;
-  static bool done = false;
-  if (!done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<1, 3, SF_CONV_BIAS_CLAMP_F32>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    done = true;
-  }
-  hipLaunchKernelGGL((conv_halo_kernel<1, 3, SF_CONV_BIAS_CLAMP_F32>), dim3(tiles), dim3(HALO_THREADS), LDS, s, p);
-  return 0;
+  return sf_launch<&conv_halo_kernel<1, 3, SF_CONV_BIAS_CLAMP_F32>, LDS>("sf_conv_igemm", dim3(tiles), dim3(HALO_THREADS), LDS, s, p);
 }
 
 }  // namespace
 
 // Returns 1 when the problem is outside this kernel's domain (the caller then uses conv_igemm; with a fused norm
-// output that is an error the caller reports), 0 after a launch, negative on error.  Domain: 3 x 3 spatial taps (kt 1 or 3), Cin % 32 == 0, Cout a multiple of 96 or of 192, bf16
+// output that is an error the caller reports), 0 after a launch, negative after a launch that failed (the error is set).  Domain: 3 x 3 spatial taps (kt 1 or 3), Cin % 32 == 0, Cout a multiple of 96 or of 192, bf16
 // output with bias / bias + residual, no channel -> frame interleave.
 __attribute__((visibility("hidden"))) int sf_conv_halo_launch(const sf_conv_args* a, void* stream) {
   if (a->stride_hw > 1 || a->stride_t > 1) return 1;   // strided gathers (the encoder's downsampling): implicit GEMM only
@@ -396,8 +382,7 @@ __attribute__((visibility("hidden"))) int sf_conv_halo_launch(const sf_conv_args
     p.x_bytes = (unsigned)xbh;
     const long th = (long)a->Tout * p.patches_h * p.patches_w;
     if (th >= (1L << 30)) return 1;
-    launch_halo_head(p, (int)th, (hipStream_t)stream);
-    return 0;
+    return launch_halo_head(p, (int)th, (hipStream_t)stream);
   }
   if (a->epilogue != SF_CONV_BIAS && a->epilogue != SF_CONV_BIAS_RESID) return 1;
   if ((a->Cout & 7) != 0 || (a->out && (a->ldo & 7) != 0)) return 1;
@@ -426,7 +411,6 @@ __attribute__((visibility("hidden"))) int sf_conv_halo_launch(const sf_conv_args
   p.x_bytes = (unsigned)xb;
   const long tiles = (long)a->Tout * p.patches_h * p.patches_w * p.tiles_n;
   if (tiles >= (1L << 30)) return 1;
-  if (nt == 3) launch_halo<3, 3>(p, (int)tiles, a->epilogue, (hipStream_t)stream);
-  else launch_halo<6, 1>(p, (int)tiles, a->epilogue, (hipStream_t)stream);
-  return 0;
+  if (nt == 3) return launch_halo<3, 3>(p, (int)tiles, a->epilogue, (hipStream_t)stream);
+  return launch_halo<6, 1>(p, (int)tiles, a->epilogue, (hipStream_t)stream);
 }

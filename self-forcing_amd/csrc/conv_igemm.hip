@@ -140,22 +140,12 @@ template <int NT>
 int launch_nt(const ConvP& p, int epi, hipStream_t s) {
   constexpr int LDS = igemm::lds_bytes(NT);
   const dim3 grid(p.tiles_m * p.tiles_n), block(igemm::THREADS);
-  if (LDS > 64 * 1024) {   // above the default dynamic-LDS limit: opt in once per kernel
-    static bool done = false;
-    if (!done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<NT, SF_CONV_BIAS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<NT, SF_CONV_BIAS_RESID>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<NT, SF_CONV_BIAS_CLAMP_F32>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      done = true;
-    }
+  switch (epi) {   // (LDS is above the 64 KiB an unregistered kernel may use at NT = 6 only)
+    case SF_CONV_BIAS: return sf_launch<&conv_igemm_kernel<NT, SF_CONV_BIAS>, LDS>("sf_conv_igemm", grid, block, LDS, s, p);
+    case SF_CONV_BIAS_RESID: return sf_launch<&conv_igemm_kernel<NT, SF_CONV_BIAS_RESID>, LDS>("sf_conv_igemm", grid, block, LDS, s, p);
+    case SF_CONV_BIAS_CLAMP_F32: return sf_launch<&conv_igemm_kernel<NT, SF_CONV_BIAS_CLAMP_F32>, LDS>("sf_conv_igemm", grid, block, LDS, s, p);
+    default: SF_CHECK(false, "sf_conv_igemm: unknown epilogue %d", epi);
   }
-  switch (epi) {
-    case SF_CONV_BIAS: hipLaunchKernelGGL((conv_igemm_kernel<NT, SF_CONV_BIAS>), grid, block, LDS, s, p); break;
-    case SF_CONV_BIAS_RESID: hipLaunchKernelGGL((conv_igemm_kernel<NT, SF_CONV_BIAS_RESID>), grid, block, LDS, s, p); break;
-    case SF_CONV_BIAS_CLAMP_F32: hipLaunchKernelGGL((conv_igemm_kernel<NT, SF_CONV_BIAS_CLAMP_F32>), grid, block, LDS, s, p); break;
-    default: return -1;
-  }
-  return 0;
 }
 
 }  // namespace
@@ -218,13 +208,9 @@ extern "C" int sf_conv_igemm(const sf_conv_args* a, void* stream) {
     // 3 x 3 convolutions with 96 k / 192 k output channels: the halo-tile kernel (the A operand staged once per
     // (channel slice, frame) instead of once per tap), conv_halo.hip
     const int rc = sf_conv_halo_launch(a, stream);
-    SF_CHECK(rc >= 0, "sf_conv_igemm: halo kernel failed");
-    SF_CHECK(rc == 0 || (a->structure == SF_CONV_AUTO && !a->norm_out), "sf_conv_igemm: the halo structure needs 3x3 spatial taps, "
+    if (rc <= 0) return rc;   // launched, or the launch failed
+    SF_CHECK(a->structure == SF_CONV_AUTO && !a->norm_out, "sf_conv_igemm: the halo structure needs 3x3 spatial taps, "
              "Cout %% 96 == 0 (a fused norm output: Cout 96 or 192), H, W >= 16, a bf16 bias / bias + residual epilogue and no interleave");
-    if (rc == 0) {
-      SF_HIP_LAUNCH_CHECK("sf_conv_igemm");
-      return 0;
-    }
   }
   ConvP p;
   p.x = (const bf16_t*)a->x; p.w = (const bf16_t*)a->w; p.bias = (const bf16_t*)a->bias;
@@ -245,15 +231,11 @@ extern "C" int sf_conv_igemm(const sf_conv_args* a, void* stream) {
   p.tiles_m = (p.M + igemm::BM - 1) / igemm::BM;
   p.tiles_n = (a->Cout + 32 * nt - 1) / (32 * nt);
   hipStream_t s = (hipStream_t)stream;
-  int rc = 0;
   switch (nt) {
-    case 1: rc = launch_nt<1>(p, a->epilogue, s); break;
-    case 2: rc = launch_nt<2>(p, a->epilogue, s); break;
-    case 3: rc = launch_nt<3>(p, a->epilogue, s); break;
-    case 4: rc = launch_nt<4>(p, a->epilogue, s); break;
-    default: rc = launch_nt<6>(p, a->epilogue, s); break;
+    case 1: return launch_nt<1>(p, a->epilogue, s);
+    case 2: return launch_nt<2>(p, a->epilogue, s);
+    case 3: return launch_nt<3>(p, a->epilogue, s);
+    case 4: return launch_nt<4>(p, a->epilogue, s);
+    default: return launch_nt<6>(p, a->epilogue, s);
   }
-  SF_CHECK(rc == 0, "sf_conv_igemm: unknown epilogue %d", a->epilogue);
-  SF_HIP_LAUNCH_CHECK("sf_conv_igemm");
-  return 0;
 }

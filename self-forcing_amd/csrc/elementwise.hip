@@ -373,16 +373,15 @@ __global__ __launch_bounds__(256) void sinusoid_kernel(const void* __restrict__ 
 
 template <int MODE>
 int launch_layernorm(const bf16_t* x, bf16_t* out, int M, int C, float eps, const bf16_t* p0, const bf16_t* p1,
-                     const bf16_t* e0s, const bf16_t* e0c, long gs, int rpg, hipStream_t s) {
+                     const bf16_t* e0s, const bf16_t* e0c, long gs, int rpg, const char* name, hipStream_t s) {
   const dim3 block(64);
   switch (C / 512) {
 #define SF_LN_CASE(N) \
-  case N: hipLaunchKernelGGL((layernorm_kernel<N, MODE>), dim3((M + LnRows<N>::value - 1) / LnRows<N>::value), block, 0, s, x, out, M, C, eps, p0, p1, e0s, e0c, gs, rpg); break;
+  case N: return sf_launch<&layernorm_kernel<N, MODE>>(name, dim3((M + LnRows<N>::value - 1) / LnRows<N>::value), block, 0, s, x, out, M, C, eps, p0, p1, e0s, e0c, gs, rpg);
     SF_LN_CASE(1) SF_LN_CASE(2) SF_LN_CASE(3) SF_LN_CASE(4) SF_LN_CASE(5) SF_LN_CASE(6) SF_LN_CASE(8) SF_LN_CASE(10)
 #undef SF_LN_CASE
-    default: sf_set_error("layernorm: unsupported channel count %d", C); return -1;
+    default: SF_CHECK(false, "%s: unsupported channel count %d", name, C);
   }
-  return 0;
 }
 
 bool channels_ok(int C) {
@@ -399,23 +398,17 @@ extern "C" int sf_layernorm_modulate(const void* x, void* out, int M, int C, flo
   SF_CHECK(x && out && mod_shift && mod_scale && e0_shift && e0_scale, "sf_layernorm_modulate: null tensor");
   SF_CHECK(M > 0 && channels_ok(C), "sf_layernorm_modulate: unsupported shape M=%d C=%d (C must be 512*{1,2,3,4,5,6,8,10})", M, C);
   SF_CHECK(rows_per_group > 0 && e0_group_stride % 8 == 0, "sf_layernorm_modulate: bad group layout");
-  if (launch_layernorm<0>((const bf16_t*)x, (bf16_t*)out, M, C, eps, (const bf16_t*)mod_shift, (const bf16_t*)mod_scale,
-                          (const bf16_t*)e0_shift, (const bf16_t*)e0_scale, e0_group_stride, rows_per_group,
-                          (hipStream_t)stream) != 0)
-    return -1;
-  SF_HIP_LAUNCH_CHECK("sf_layernorm_modulate");
-  return 0;
+  return launch_layernorm<0>((const bf16_t*)x, (bf16_t*)out, M, C, eps, (const bf16_t*)mod_shift, (const bf16_t*)mod_scale,
+                             (const bf16_t*)e0_shift, (const bf16_t*)e0_scale, e0_group_stride, rows_per_group,
+                             "sf_layernorm_modulate", (hipStream_t)stream);
 }
 
 extern "C" int sf_layernorm_affine(const void* x, const void* weight, const void* bias, void* out, int M, int C,
                                    float eps, void* stream) {
   SF_CHECK(x && out && weight && bias, "sf_layernorm_affine: null tensor");
   SF_CHECK(M > 0 && channels_ok(C), "sf_layernorm_affine: unsupported shape M=%d C=%d", M, C);
-  if (launch_layernorm<1>((const bf16_t*)x, (bf16_t*)out, M, C, eps, (const bf16_t*)weight, (const bf16_t*)bias, nullptr,
-                          nullptr, 0, 1, (hipStream_t)stream) != 0)
-    return -1;
-  SF_HIP_LAUNCH_CHECK("sf_layernorm_affine");
-  return 0;
+  return launch_layernorm<1>((const bf16_t*)x, (bf16_t*)out, M, C, eps, (const bf16_t*)weight, (const bf16_t*)bias, nullptr,
+                             nullptr, 0, 1, "sf_layernorm_affine", (hipStream_t)stream);
 }
 
 extern "C" int sf_rmsnorm(const void* x, int ldx, const void* weight, void* out, int ldo, int M, int C, float eps,
@@ -426,12 +419,11 @@ extern "C" int sf_rmsnorm(const void* x, int ldx, const void* weight, void* out,
   hipStream_t s = (hipStream_t)stream;
   switch (C / 512) {
 #define SF_RMS_CASE(N) \
-  case N: hipLaunchKernelGGL((rmsnorm_kernel<N>), grid, block, 0, s, (const bf16_t*)x, ldx, (const bf16_t*)weight, (bf16_t*)out, ldo, M, C, eps); break;
+  case N: return sf_launch<&rmsnorm_kernel<N>>("sf_rmsnorm", grid, block, 0, s, (const bf16_t*)x, ldx, (const bf16_t*)weight, (bf16_t*)out, ldo, M, C, eps);
     SF_RMS_CASE(1) SF_RMS_CASE(2) SF_RMS_CASE(3) SF_RMS_CASE(4) SF_RMS_CASE(5) SF_RMS_CASE(6) SF_RMS_CASE(8) SF_RMS_CASE(10)
 #undef SF_RMS_CASE
+    default: SF_CHECK(false, "sf_rmsnorm: unsupported channel count %d", C);
   }
-  SF_HIP_LAUNCH_CHECK("sf_rmsnorm");
-  return 0;
 }
 
 extern "C" int sf_qkv_norm_rope_cache(const void* qkv, const void* norm_q_w, const void* norm_k_w, void* q_out,
@@ -451,15 +443,14 @@ extern "C" int sf_qkv_norm_rope_cache(const void* qkv, const void* norm_q_w, con
   // column split of the reference's freqs (causal_model.py:32): c = 64 -> (22, 21, 21)
   const int c = 64, c1 = c / 3, c0 = c - 2 * c1;
   switch (C / 512) {
-#define SF_QKV_CASE(N)                                                                                                   \
-  case N: hipLaunchKernelGGL((qkv_norm_rope_cache_kernel<N>), grid, block, 0, s, (const bf16_t*)qkv, (const bf16_t*)norm_q_w, \
-                             (const bf16_t*)norm_k_w, (bf16_t*)q_out, (bf16_t*)k_cache, (bf16_t*)v_cache, rope_cos, rope_sin,  \
-                             rows, L, h, w, C, (long)cache_tokens, write_start, start_frame, eps, c0, c1); break;
+#define SF_QKV_CASE(N)                                                                                                                         \
+  case N: return sf_launch<&qkv_norm_rope_cache_kernel<N>>("sf_qkv_norm_rope_cache", grid, block, 0, s, (const bf16_t*)qkv, (const bf16_t*)norm_q_w, \
+                             (const bf16_t*)norm_k_w, (bf16_t*)q_out, (bf16_t*)k_cache, (bf16_t*)v_cache, rope_cos, rope_sin,                    \
+                             rows, L, h, w, C, (long)cache_tokens, write_start, start_frame, eps, c0, c1);
     SF_QKV_CASE(1) SF_QKV_CASE(2) SF_QKV_CASE(3) SF_QKV_CASE(4) SF_QKV_CASE(5) SF_QKV_CASE(6) SF_QKV_CASE(8) SF_QKV_CASE(10)
 #undef SF_QKV_CASE
+    default: SF_CHECK(false, "sf_qkv_norm_rope_cache: unsupported channel count %d", C);
   }
-  SF_HIP_LAUNCH_CHECK("sf_qkv_norm_rope_cache");
-  return 0;
 }
 
 extern "C" int sf_kv_evict(void* cache, int B, int64_t cache_tokens, int row_elems, int sink, int evict, int keep,
@@ -477,10 +468,8 @@ extern "C" int sf_kv_evict(void* cache, int B, int64_t cache_tokens, int row_ele
   hipStream_t s = (hipStream_t)stream;
   // the source and destination windows overlap and workgroups run in no defined order:
   // go through a scratch buffer (cache -> scratch -> cache)
-  hipLaunchKernelGGL(copy_rows_kernel, grid, block, 0, s, base + (long)(sink + evict) * row_b, bstride, (char*)scratch, bytes, bytes);
-  hipLaunchKernelGGL(copy_rows_kernel, grid, block, 0, s, (const char*)scratch, bytes, base + (long)sink * row_b, bstride, bytes);
-  SF_HIP_LAUNCH_CHECK("sf_kv_evict");
-  return 0;
+  SF_TRY(sf_launch<&copy_rows_kernel>("sf_kv_evict", grid, block, 0, s, base + (long)(sink + evict) * row_b, bstride, (char*)scratch, bytes, bytes));
+  return sf_launch<&copy_rows_kernel>("sf_kv_evict", grid, block, 0, s, (const char*)scratch, bytes, base + (long)sink * row_b, bstride, bytes);
 }
 
 extern "C" int sf_patchify(const void* x, void* cols, int B, int F, int Cin, int H, int W, void* stream) {
@@ -488,9 +477,7 @@ extern "C" int sf_patchify(const void* x, void* cols, int B, int F, int Cin, int
   SF_CHECK(H % 2 == 0 && W % 2 == 0, "sf_patchify: latent H=%d W=%d must be even (patch 2x2)", H, W);
   const long total = (long)B * F * (H / 2) * (W / 2) * Cin;
   const int gx = (int)min((long)4096, (total + 255) / 256);
-  hipLaunchKernelGGL(patchify_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)cols, total, Cin, H, W);
-  SF_HIP_LAUNCH_CHECK("sf_patchify");
-  return 0;
+  return sf_launch<&patchify_kernel>("sf_patchify", dim3(gx), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)cols, total, Cin, H, W);
 }
 
 extern "C" int sf_unpatchify_x0(const void* head_out, const void* xt, const void* timestep, int t_is_int64,
@@ -501,10 +488,8 @@ extern "C" int sf_unpatchify_x0(const void* head_out, const void* xt, const void
   SF_CHECK(H % 2 == 0 && W % 2 == 0 && n_table > 0, "sf_unpatchify_x0: bad shape");
   const int total = Cout * H * (W / 2);
   const dim3 grid(min(64, (total + 255) / 256), B * F), block(256);
-  hipLaunchKernelGGL(unpatchify_x0_kernel, grid, block, 0, (hipStream_t)stream, (const bf16_t*)head_out, (const bf16_t*)xt, timestep,
-                     t_is_int64, sigmas, timesteps, n_table, (bf16_t*)flow, (bf16_t*)x0, F, groups, Cout, H, W);
-  SF_HIP_LAUNCH_CHECK("sf_unpatchify_x0");
-  return 0;
+  return sf_launch<&unpatchify_x0_kernel>("sf_unpatchify_x0", grid, block, 0, (hipStream_t)stream, (const bf16_t*)head_out, (const bf16_t*)xt, timestep,
+                                          t_is_int64, sigmas, timesteps, n_table, (bf16_t*)flow, (bf16_t*)x0, F, groups, Cout, H, W);
 }
 
 extern "C" int sf_add_noise(const void* x0, const void* eps, const void* timestep, int t_is_int64, const float* sigmas,
@@ -512,10 +497,8 @@ extern "C" int sf_add_noise(const void* x0, const void* eps, const void* timeste
   SF_CHECK(x0 && eps && timestep && sigmas && timesteps && out, "sf_add_noise: null tensor");
   SF_CHECK(n_outer > 0 && inner > 0 && inner % 8 == 0 && n_table > 0, "sf_add_noise: bad shape (inner must be a multiple of 8)");
   const dim3 grid((unsigned)min((long)64, (long)((inner / 8 + 255) / 256)), n_outer), block(256);
-  hipLaunchKernelGGL(add_noise_kernel, grid, block, 0, (hipStream_t)stream, (const bf16_t*)x0, (const bf16_t*)eps, timestep, t_is_int64,
-                     sigmas, timesteps, n_table, (bf16_t*)out, (long)inner);
-  SF_HIP_LAUNCH_CHECK("sf_add_noise");
-  return 0;
+  return sf_launch<&add_noise_kernel>("sf_add_noise", grid, block, 0, (hipStream_t)stream, (const bf16_t*)x0, (const bf16_t*)eps, timestep, t_is_int64, sigmas,
+                                      timesteps, n_table, (bf16_t*)out, (long)inner);
 }
 
 extern "C" int sf_lincomb_bf16(void* out, const void* const* xs, const float* coefs, int n_terms, int64_t n, void* stream) {
@@ -533,15 +516,13 @@ extern "C" int sf_lincomb_bf16(void* out, const void* const* xs, const float* co
   p.n_terms = n_terms;
   const dim3 grid((unsigned)min((long)2048, (p.n8 + 255) / 256)), block(256);
   switch (n_terms) {
-    case 1: hipLaunchKernelGGL(lincomb_kernel<1>, grid, block, 0, (hipStream_t)stream, p); break;
-    case 2: hipLaunchKernelGGL(lincomb_kernel<2>, grid, block, 0, (hipStream_t)stream, p); break;
-    case 3: hipLaunchKernelGGL(lincomb_kernel<3>, grid, block, 0, (hipStream_t)stream, p); break;
-    case 4: hipLaunchKernelGGL(lincomb_kernel<4>, grid, block, 0, (hipStream_t)stream, p); break;
-    case 5: hipLaunchKernelGGL(lincomb_kernel<5>, grid, block, 0, (hipStream_t)stream, p); break;
-    default: hipLaunchKernelGGL(lincomb_kernel<6>, grid, block, 0, (hipStream_t)stream, p); break;
+    case 1: return sf_launch<&lincomb_kernel<1>>("sf_lincomb_bf16", grid, block, 0, (hipStream_t)stream, p);
+    case 2: return sf_launch<&lincomb_kernel<2>>("sf_lincomb_bf16", grid, block, 0, (hipStream_t)stream, p);
+    case 3: return sf_launch<&lincomb_kernel<3>>("sf_lincomb_bf16", grid, block, 0, (hipStream_t)stream, p);
+    case 4: return sf_launch<&lincomb_kernel<4>>("sf_lincomb_bf16", grid, block, 0, (hipStream_t)stream, p);
+    case 5: return sf_launch<&lincomb_kernel<5>>("sf_lincomb_bf16", grid, block, 0, (hipStream_t)stream, p);
+    default: return sf_launch<&lincomb_kernel<6>>("sf_lincomb_bf16", grid, block, 0, (hipStream_t)stream, p);
   }
-  SF_HIP_LAUNCH_CHECK("sf_lincomb_bf16");
-  return 0;
 }
 
 // the cache dicts' index tensors (causal_model.py:235-236), all layers at once: buf int64 [layers][2] <- (global_end, local_end)
@@ -551,18 +532,15 @@ __global__ void kv_index_kernel(long long* __restrict__ buf, int layers, long lo
 }
 // (library-internal: called by sf_dit_forward only)
 __attribute__((visibility("hidden"))) int sf_internal_write_kv_indices(void* buf, int layers, int64_t global_end, int64_t local_end, void* stream) {
-  hipLaunchKernelGGL(kv_index_kernel, dim3((2 * layers + 63) / 64), dim3(64), 0, (hipStream_t)stream, (long long*)buf, layers,
-                     (long long)global_end, (long long)local_end);
-  SF_HIP_LAUNCH_CHECK("kv_index_kernel");
-  return 0;
+  return sf_launch<&kv_index_kernel>("kv_index_kernel", dim3((2 * layers + 63) / 64), dim3(64), 0, (hipStream_t)stream, (long long*)buf, layers,
+                                     (long long)global_end, (long long)local_end);
 }
 
 extern "C" int sf_sinusoid_embedding(const void* t, int t_is_int64, void* out, int n, int dim, void* stream) {
   SF_CHECK(t && out && n > 0 && dim > 0 && dim % 2 == 0, "sf_sinusoid_embedding: bad arguments");
   const int total = n * (dim / 2);
-  hipLaunchKernelGGL(sinusoid_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, t_is_int64, (bf16_t*)out, n, dim);
-  SF_HIP_LAUNCH_CHECK("sf_sinusoid_embedding");
-  return 0;
+  return sf_launch<&sinusoid_kernel>("sf_sinusoid_embedding", dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, t_is_int64, (bf16_t*)out, n,
+                                     dim);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -610,15 +588,13 @@ extern "C" int sf_cross_fold_scan(const void* const* ck_cache_host, const void* 
            layers, B, text_len, row_elems);
   hipStream_t s = (hipStream_t)stream;
   const int n = layers * B;
-  hipLaunchKernelGGL(fold_reset_kernel, dim3((n + 255) / 256), dim3(256), 0, s, keys, n);
+  SF_TRY(sf_launch<&fold_reset_kernel>("sf_cross_fold_scan", dim3((n + 255) / 256), dim3(256), 0, s, keys, n));
   if (text_len > 1)
     for (int l = 0; l < layers; ++l) {
       SF_CHECK(ck_cache_host[l] && cv_cache_host[l], "sf_cross_fold_scan: null cache of layer %d", l);
       SF_CHECK(((uintptr_t)ck_cache_host[l] | (uintptr_t)cv_cache_host[l]) % 16 == 0, "sf_cross_fold_scan: misaligned cache of layer %d", l);
-      hipLaunchKernelGGL(fold_scan_kernel, dim3((text_len - 1 + 3) / 4, B), dim3(256), 0, s, (const uint4*)ck_cache_host[l],
-                         (const uint4*)cv_cache_host[l], text_len, row_elems / 8, keys + (size_t)l * B);
+      SF_TRY(sf_launch<&fold_scan_kernel>("sf_cross_fold_scan", dim3((text_len - 1 + 3) / 4, B), dim3(256), 0, s, (const uint4*)ck_cache_host[l],
+                                          (const uint4*)cv_cache_host[l], text_len, row_elems / 8, keys + (size_t)l * B));
     }
-  hipLaunchKernelGGL(fold_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, s, keys, log2w, n, text_len);
-  SF_HIP_LAUNCH_CHECK("sf_cross_fold_scan");
-  return 0;
+  return sf_launch<&fold_finish_kernel>("sf_cross_fold_scan", dim3((n + 255) / 256), dim3(256), 0, s, keys, log2w, n, text_len);
 }

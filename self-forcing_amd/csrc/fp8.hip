@@ -192,11 +192,9 @@ extern "C" int sf_quantize_fp8(const void* x, int ldx, int M, int K, int rows_pe
   const int parts = (int)std::min<long>(PARTS, std::max<long>(1, (chunks + 2 * QT - 1) / (2 * QT)));
   float* partial = scale_out + segs;
   const dim3 grid(parts, segs);
-  hipLaunchKernelGGL(fp8_amax_kernel, grid, dim3(QT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, M, K, rows_per_segment, parts, partial);
-  hipLaunchKernelGGL(fp8_quantize_kernel, grid, dim3(QT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, M, K, rows_per_segment, parts,
-                     (const float*)partial, (uint8_t*)q_out, scale_out);
-  SF_HIP_LAUNCH_CHECK("sf_quantize_fp8");
-  return 0;
+  SF_TRY(sf_launch<&fp8_amax_kernel>("sf_quantize_fp8", grid, dim3(QT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, M, K, rows_per_segment, parts, partial));
+  return sf_launch<&fp8_quantize_kernel>("sf_quantize_fp8", grid, dim3(QT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, M, K, rows_per_segment, parts,
+                                         (const float*)partial, (uint8_t*)q_out, scale_out);
 }
 
 extern "C" int sf_small_linear_fp8(const void* x, const void* w_q, const float* w_scale, const void* bias, void* out, int M, int N,
@@ -207,16 +205,11 @@ extern "C" int sf_small_linear_fp8(const void* x, const void* w_q, const float* 
   SF_CHECK(act_in >= 0 && act_in <= 2 && act_out >= 0 && act_out <= 2, "sf_small_linear_fp8: bad activation code");
   SF_CHECK((uintptr_t)x % 2 == 0 && (uintptr_t)w_q % 8 == 0, "sf_small_linear_fp8: misaligned tensor");
   const size_t lds = 64 * sizeof(float) + (size_t)SLF_MB * K * 2;
-  SF_CHECK(lds <= 160 * 1024, "sf_small_linear_fp8: K=%d too large for the LDS activation stage", K);
-  static int attr_lds = 0;   // one-time registration of the largest LDS size asked for (idempotent)
-  if ((int)lds > attr_lds && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_linear_fp8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_lds = (int)lds;
-  }
+  constexpr int LDS_CAP = 160 * 1024;   // the kernel's cap: the most any admitted K asks for
+  SF_CHECK(lds <= LDS_CAP, "sf_small_linear_fp8: K=%d too large for the LDS activation stage", K);
   const int waves = (N + SLF_NPW - 1) / SLF_NPW;
   const dim3 grid((waves + SLF_THREADS / 64 - 1) / (SLF_THREADS / 64));
-  hipLaunchKernelGGL(small_linear_fp8_kernel, grid, dim3(SLF_THREADS), lds, (hipStream_t)stream, (const bf16_t*)x, (const uint8_t*)w_q,
-                     w_scale, (const bf16_t*)bias, (bf16_t*)out, M, N, K, rows_per_segment, act_in, act_out);
-  SF_HIP_LAUNCH_CHECK("sf_small_linear_fp8");
-  return 0;
+  return sf_launch<&small_linear_fp8_kernel, LDS_CAP>("sf_small_linear_fp8", grid, dim3(SLF_THREADS), lds, (hipStream_t)stream, (const bf16_t*)x,
+                                                      (const uint8_t*)w_q, w_scale, (const bf16_t*)bias, (bf16_t*)out, M, N, K, rows_per_segment, act_in,
+                                                      act_out);
 }

@@ -759,51 +759,39 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp2_kernel(GemmP p) {
 }
 
 template <int EPI, bool F8>
-int launch_pp2(GemmP& p, hipStream_t s) {
-  static bool attr = false;   // one-time registration of the kernel's LDS size (idempotent)
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp2_kernel<EPI, F8>), hipFuncAttributeMaxDynamicSharedMemorySize, PP2_LDS);
-    attr = true;
-  }
+int launch_pp2(GemmP& p, const char* name, hipStream_t s) {
   p.tiles_m = (p.M + 127) / 128;
   p.tiles_n = (p.N + 255) / 256;
-  hipLaunchKernelGGL((gemm_pp2_kernel<EPI, F8>), dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), PP2_LDS, s, p);
-  return 0;
+  return sf_launch<&gemm_pp2_kernel<EPI, F8>, PP2_LDS>(name, dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), PP2_LDS, s, p);
 }
 
 template <bool F8>
-int launch_pp2_epi(GemmP& p, int epilogue, hipStream_t s) {
+int launch_pp2_epi(GemmP& p, int epilogue, const char* name, hipStream_t s) {
   switch (epilogue) {
-    case SF_EPI_BIAS: return launch_pp2<SF_EPI_BIAS, F8>(p, s);
-    case SF_EPI_BIAS_GELU: return launch_pp2<SF_EPI_BIAS_GELU, F8>(p, s);
-    case SF_EPI_BIAS_RESID: return launch_pp2<SF_EPI_BIAS_RESID, F8>(p, s);
-    case SF_EPI_BIAS_GATE_RESID: return launch_pp2<SF_EPI_BIAS_GATE_RESID, F8>(p, s);
-    default: return -1;
+    case SF_EPI_BIAS: return launch_pp2<SF_EPI_BIAS, F8>(p, name, s);
+    case SF_EPI_BIAS_GELU: return launch_pp2<SF_EPI_BIAS_GELU, F8>(p, name, s);
+    case SF_EPI_BIAS_RESID: return launch_pp2<SF_EPI_BIAS_RESID, F8>(p, name, s);
+    case SF_EPI_BIAS_GATE_RESID: return launch_pp2<SF_EPI_BIAS_GATE_RESID, F8>(p, name, s);
+    default: SF_CHECK(false, "%s: unknown epilogue %d", name, epilogue);
   }
 }
 
 template <int EPI, int MT, bool F8>
-int launch_pp(GemmP& p, hipStream_t s) {
+int launch_pp(GemmP& p, const char* name, hipStream_t s) {
   using Cfg = PPCfg<MT>;
-  static bool attr = false;   // one-time registration of the kernel's LDS size (idempotent)
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<EPI, MT, F8>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    attr = true;
-  }
   p.tiles_m = (p.M + Cfg::BM - 1) / Cfg::BM;
   p.tiles_n = (p.N + 255) / 256;
-  hipLaunchKernelGGL((gemm_pp_kernel<EPI, MT, F8>), dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), Cfg::LDS, s, p);
-  return 0;
+  return sf_launch<&gemm_pp_kernel<EPI, MT, F8>, Cfg::LDS>(name, dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), Cfg::LDS, s, p);
 }
 
 template <int MT, bool F8>
-int launch_pp_epi(GemmP& p, int epilogue, hipStream_t s) {
+int launch_pp_epi(GemmP& p, int epilogue, const char* name, hipStream_t s) {
   switch (epilogue) {
-    case SF_EPI_BIAS: return launch_pp<SF_EPI_BIAS, MT, F8>(p, s);
-    case SF_EPI_BIAS_GELU: return launch_pp<SF_EPI_BIAS_GELU, MT, F8>(p, s);
-    case SF_EPI_BIAS_RESID: return launch_pp<SF_EPI_BIAS_RESID, MT, F8>(p, s);
-    case SF_EPI_BIAS_GATE_RESID: return launch_pp<SF_EPI_BIAS_GATE_RESID, MT, F8>(p, s);
-    default: return -1;
+    case SF_EPI_BIAS: return launch_pp<SF_EPI_BIAS, MT, F8>(p, name, s);
+    case SF_EPI_BIAS_GELU: return launch_pp<SF_EPI_BIAS_GELU, MT, F8>(p, name, s);
+    case SF_EPI_BIAS_RESID: return launch_pp<SF_EPI_BIAS_RESID, MT, F8>(p, name, s);
+    case SF_EPI_BIAS_GATE_RESID: return launch_pp<SF_EPI_BIAS_GATE_RESID, MT, F8>(p, name, s);
+    default: SF_CHECK(false, "%s: unknown epilogue %d", name, epilogue);
   }
 }
 
@@ -854,36 +842,29 @@ int run_gemm(const sf_gemm_args* a, GemmP& p, const char* name, hipStream_t s) {
   }
   const bool is_pp = st == SF_GEMM_PP256 || st == SF_GEMM_PP224 || st == SF_GEMM_PP192 || st == SF_GEMM_PP128;
   if (is_pp && !pp_ok) st = SF_GEMM_T128;
-  else if (is_pp) {
-    const int rc = st == SF_GEMM_PP256 ? launch_pp_epi<8, F8>(p, a->epilogue, s)
-                 : st == SF_GEMM_PP224 ? launch_pp_epi<7, F8>(p, a->epilogue, s)
-                 : st == SF_GEMM_PP192 ? launch_pp_epi<6, F8>(p, a->epilogue, s) : launch_pp2_epi<F8>(p, a->epilogue, s);
-    SF_CHECK(rc == 0, "%s: unknown epilogue %d", name, a->epilogue);
-    SF_HIP_LAUNCH_CHECK(name);
-    return 0;
-  }
+  else if (is_pp)
+    return st == SF_GEMM_PP256 ? launch_pp_epi<8, F8>(p, a->epilogue, name, s)
+         : st == SF_GEMM_PP224 ? launch_pp_epi<7, F8>(p, a->epilogue, name, s)
+         : st == SF_GEMM_PP192 ? launch_pp_epi<6, F8>(p, a->epilogue, name, s) : launch_pp2_epi<F8>(p, a->epilogue, name, s);
   const int batch = a->batch > 1 ? a->batch : 1;
   p.a_bs = a->a_bstride; p.w_bs = a->w_bstride; p.o_bs = a->o_bstride; p.r_bs = a->r_bstride;
   SF_CHECK(batch == 1 || (a->a_bstride % 8 == 0 && a->w_bstride % 8 == 0 && a->o_bstride % 4 == 0 && a->r_bstride % 4 == 0),
            "%s: batch strides must keep 16-byte (operands) / 8-byte (output) alignment", name);
   const dim3 grid(p.tiles_m * p.tiles_n, batch), block(GEMM_THREADS);
   switch (a->epilogue) {
-    case SF_EPI_BIAS: hipLaunchKernelGGL((gemm_bf16_kernel<SF_EPI_BIAS, F8>), grid, block, GEMM_LDS, s, p); break;
-    case SF_EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_bf16_kernel<SF_EPI_BIAS_GELU, F8>), grid, block, GEMM_LDS, s, p); break;
-    case SF_EPI_BIAS_RESID: hipLaunchKernelGGL((gemm_bf16_kernel<SF_EPI_BIAS_RESID, F8>), grid, block, GEMM_LDS, s, p); break;
-    case SF_EPI_BIAS_GATE_RESID: hipLaunchKernelGGL((gemm_bf16_kernel<SF_EPI_BIAS_GATE_RESID, F8>), grid, block, GEMM_LDS, s, p); break;
+    case SF_EPI_BIAS: return sf_launch<&gemm_bf16_kernel<SF_EPI_BIAS, F8>>(name, grid, block, GEMM_LDS, s, p);
+    case SF_EPI_BIAS_GELU: return sf_launch<&gemm_bf16_kernel<SF_EPI_BIAS_GELU, F8>>(name, grid, block, GEMM_LDS, s, p);
+    case SF_EPI_BIAS_RESID: return sf_launch<&gemm_bf16_kernel<SF_EPI_BIAS_RESID, F8>>(name, grid, block, GEMM_LDS, s, p);
+    case SF_EPI_BIAS_GATE_RESID: return sf_launch<&gemm_bf16_kernel<SF_EPI_BIAS_GATE_RESID, F8>>(name, grid, block, GEMM_LDS, s, p);
     case SF_EPI_F32:
       if constexpr (F8) {
         SF_CHECK(false, "%s: the raw fp32 epilogue is bf16-only", name);
       } else {
         SF_CHECK((uintptr_t)a->out % 16 == 0, "%s: fp32 output must be 16-byte aligned", name);
-        hipLaunchKernelGGL((gemm_bf16_kernel<SF_EPI_F32, false>), grid, block, GEMM_LDS, s, p);
+        return sf_launch<&gemm_bf16_kernel<SF_EPI_F32, false>>(name, grid, block, GEMM_LDS, s, p);
       }
-      break;
     default: SF_CHECK(false, "%s: unknown epilogue %d", name, a->epilogue);
   }
-  SF_HIP_LAUNCH_CHECK(name);
-  return 0;
 }
 
 void fill_params(const sf_gemm_args* a, GemmP& p, int unit) {   // unit: operand elements per 2-byte unit (1 bf16, 2 fp8)

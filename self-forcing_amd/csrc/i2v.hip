@@ -129,20 +129,16 @@ extern "C" int sf_patchify_i2v(const void* x, const void* y, void* cols, int B, 
   SF_CHECK(y_bstride >= 0 && y_cstride >= (int64_t)H * W && y_fstride >= (int64_t)H * W, "sf_patchify_i2v: y's frames must be contiguous H x W planes");
   const long total = (long)B * F * (H / 2) * (W / 2) * pad_channels;
   const int gx = (int)min((long)4096, (total + 255) / 256);
-  hipLaunchKernelGGL(patchify_i2v_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)y, (bf16_t*)cols, total, F,
-                     x_channels, y_channels, pad_channels, H, W, (long)y_bstride, (long)y_cstride, (long)y_fstride);
-  SF_HIP_LAUNCH_CHECK("sf_patchify_i2v");
-  return 0;
+  return sf_launch<&patchify_i2v_kernel>("sf_patchify_i2v", dim3(gx), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)y, (bf16_t*)cols,
+                                         total, F, x_channels, y_channels, pad_channels, H, W, (long)y_bstride, (long)y_cstride, (long)y_fstride);
 }
 
 extern "C" int sf_layernorm_rows(const void* x, const void* weight, const void* bias, void* out, int M, int C, float eps, void* stream) {
   SF_CHECK(x && weight && bias && out, "sf_layernorm_rows: null tensor");
   SF_CHECK(M > 0 && C > 0 && C % 8 == 0, "sf_layernorm_rows: unsupported shape M=%d C=%d (C must be a multiple of 8)", M, C);
   SF_CHECK(((uintptr_t)x | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)out) % 16 == 0, "sf_layernorm_rows: misaligned tensor");
-  hipLaunchKernelGGL(layernorm_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)weight,
-                     (const bf16_t*)bias, (bf16_t*)out, M, C, eps);
-  SF_HIP_LAUNCH_CHECK("sf_layernorm_rows");
-  return 0;
+  return sf_launch<&layernorm_rows_kernel>("sf_layernorm_rows", dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                                           (const bf16_t*)weight, (const bf16_t*)bias, (bf16_t*)out, M, C, eps);
 }
 
 extern "C" int sf_i2v_assemble_y(const void* latent, const void* ref_map, void* y, int frames, int mask_channels, int latent_channels, int h, int w,
@@ -157,9 +153,7 @@ extern "C" int sf_i2v_assemble_y(const void* latent, const void* ref_map, void* 
            (long long)y_cstride, (long long)y_fstride, (long long)hw);
   SF_CHECK((uintptr_t)latent % 4 == 0 && (uintptr_t)y % 2 == 0 && (!ref_map || (uintptr_t)ref_map % 2 == 0), "sf_i2v_assemble_y: misaligned tensor");
   const unsigned groups = (unsigned)((hw + 7 + 7) / 8);   // a plane that starts inside a group spills into one more
-  hipLaunchKernelGGL(assemble_y_kernel, dim3((groups + 255) / 256, (unsigned)planes), dim3(256), 0, (hipStream_t)stream, (const float*)latent,
-                     (const bf16_t*)ref_map, (bf16_t*)y, frames, mask_channels, mask_channels + latent_channels, (int)hw, (long)y_cstride,
-                     (long)y_fstride, first_is_frame0);
-  SF_HIP_LAUNCH_CHECK("sf_i2v_assemble_y");
-  return 0;
+  return sf_launch<&assemble_y_kernel>("sf_i2v_assemble_y", dim3((groups + 255) / 256, (unsigned)planes), dim3(256), 0, (hipStream_t)stream,
+                                       (const float*)latent, (const bf16_t*)ref_map, (bf16_t*)y, frames, mask_channels, mask_channels + latent_channels,
+                                       (int)hw, (long)y_cstride, (long)y_fstride, first_is_frame0);
 }

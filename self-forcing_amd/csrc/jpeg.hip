@@ -535,19 +535,16 @@ extern "C" int sf_jpeg_transform(const void* frames, int dtype, int value_range,
   hipStream_t s = (hipStream_t)stream;
   const int r01 = value_range == SF_JPEG_RANGE_01;
 #define SF_JPEG_LAUNCH(T, SUB) \
-  hipLaunchKernelGGL((jpeg_transform_kernel<T, SUB>), grid, block, 0, s, (const T*)frames, (int16_t*)coef, qt, h, w, r01, g.mcus_x, g.blocks)
+  return sf_launch<&jpeg_transform_kernel<T, SUB>>(who, grid, block, 0, s, (const T*)frames, (int16_t*)coef, qt, h, w, r01, g.mcus_x, g.blocks)
   if (subsampling == SF_JPEG_420) {
     if (dtype == SF_JPEG_U8) SF_JPEG_LAUNCH(uint8_t, true);
-    else if (dtype == SF_JPEG_F32) SF_JPEG_LAUNCH(float, true);
-    else SF_JPEG_LAUNCH(bf16_t, true);
-  } else {
-    if (dtype == SF_JPEG_U8) SF_JPEG_LAUNCH(uint8_t, false);
-    else if (dtype == SF_JPEG_F32) SF_JPEG_LAUNCH(float, false);
-    else SF_JPEG_LAUNCH(bf16_t, false);
+    if (dtype == SF_JPEG_F32) SF_JPEG_LAUNCH(float, true);
+    SF_JPEG_LAUNCH(bf16_t, true);
   }
+  if (dtype == SF_JPEG_U8) SF_JPEG_LAUNCH(uint8_t, false);
+  if (dtype == SF_JPEG_F32) SF_JPEG_LAUNCH(float, false);
+  SF_JPEG_LAUNCH(bf16_t, false);
 #undef SF_JPEG_LAUNCH
-  SF_HIP_LAUNCH_CHECK(who);
-  return 0;
 }
 
 extern "C" int sf_jpeg_entropy(const void* coef, int n, int h, int w, int subsampling, int quality, int restart_interval, void* workspace,
@@ -580,17 +577,12 @@ extern "C" int sf_jpeg_entropy(const void* coef, int n, int h, int w, int subsam
   hipStream_t s = (hipStream_t)stream;
   SF_TRY(sf_hip_ok(hipMemsetAsync(status, 0, 4, s), who, "clearing the status word"));
   const dim3 per_interval((unsigned)g.intervals, (unsigned)n);
-  hipLaunchKernelGGL(jpeg_entropy_kernel, per_interval, dim3(64), 0, s, (const int16_t*)coef, slots, lens, (int*)status, ht, g.bpm, g.mcus, restart_interval,
-                     g.blocks, (unsigned)g.slot_bytes);
-  SF_HIP_LAUNCH_CHECK(who);
-  hipLaunchKernelGGL(jpeg_scan_intervals_kernel, dim3((unsigned)n), dim3(256), 0, s, lens, ipos, fsize, g.intervals, (int)hd.len);
-  SF_HIP_LAUNCH_CHECK(who);
-  hipLaunchKernelGGL(jpeg_scan_frames_kernel, dim3(1), dim3(256), 0, s, fsize, offsets, n, (int64_t)out_capacity, (int*)status);
-  SF_HIP_LAUNCH_CHECK(who);
-  hipLaunchKernelGGL(jpeg_pack_kernel, per_interval, dim3(256), 0, s, slots, lens, ipos, offsets, (uint8_t*)out, hd, (unsigned)g.slot_bytes,
-                     (int64_t)out_capacity);
-  SF_HIP_LAUNCH_CHECK(who);
-  return 0;
+  SF_TRY(sf_launch<&jpeg_entropy_kernel>(who, per_interval, dim3(64), 0, s, (const int16_t*)coef, slots, lens, (int*)status, ht, g.bpm, g.mcus,
+                                         restart_interval, g.blocks, (unsigned)g.slot_bytes));
+  SF_TRY(sf_launch<&jpeg_scan_intervals_kernel>(who, dim3((unsigned)n), dim3(256), 0, s, lens, ipos, fsize, g.intervals, (int)hd.len));
+  SF_TRY(sf_launch<&jpeg_scan_frames_kernel>(who, dim3(1), dim3(256), 0, s, fsize, offsets, n, (int64_t)out_capacity, (int*)status));
+  return sf_launch<&jpeg_pack_kernel>(who, per_interval, dim3(256), 0, s, slots, lens, ipos, offsets, (uint8_t*)out, hd, (unsigned)g.slot_bytes,
+                                      (int64_t)out_capacity);
 }
 
 extern "C" int sf_jpeg_encode_frames(const void* frames, int dtype, int value_range, int n, int h, int w, int subsampling, int quality,

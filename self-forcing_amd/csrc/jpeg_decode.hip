@@ -417,13 +417,10 @@ int launch_entropy(const char* who, const DecGeometry& g, const void* upload, si
   uint32_t* counts = (uint32_t*)(ws + g.counts_off);
   SF_TRY(sf_hip_ok(hipMemsetAsync(status, 0, (size_t)n * 4, s), who, "clearing the status words"));
   SF_TRY(sf_hip_ok(hipMemsetAsync(coef, 0, (size_t)n * g.blocks * 128, s), who, "clearing the coefficients"));
-  hipLaunchKernelGGL(jpeg_decode_marks_kernel, dim3((unsigned)n), dim3(256), 0, s, (const uint8_t*)upload, (uint32_t)upload_bytes, marks, counts, status,
-                     max_intervals);
-  SF_HIP_LAUNCH_CHECK(who);
-  hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3((unsigned)((max_intervals + 63) / 64), (unsigned)n), dim3(64), 0, s, (const uint8_t*)upload,
-                     (uint32_t)upload_bytes, marks, counts, (int16_t*)coef, status, max_intervals, g.bpm, g.mcus, g.blocks);
-  SF_HIP_LAUNCH_CHECK(who);
-  return 0;
+  SF_TRY(sf_launch<&jpeg_decode_marks_kernel>(who, dim3((unsigned)n), dim3(256), 0, s, (const uint8_t*)upload, (uint32_t)upload_bytes, marks, counts, status,
+                                              max_intervals));
+  return sf_launch<&jpeg_decode_entropy_kernel>(who, dim3((unsigned)((max_intervals + 63) / 64), (unsigned)n), dim3(64), 0, s, (const uint8_t*)upload,
+                                                (uint32_t)upload_bytes, marks, counts, (int16_t*)coef, status, max_intervals, g.bpm, g.mcus, g.blocks);
 }
 
 }  // namespace
@@ -468,24 +465,21 @@ extern "C" int sf_jpeg_decode_pixels(const void* coef, const void* upload, size_
   char* ws = (char*)workspace;
   uint8_t *py = (uint8_t*)(ws + g.plane_off[0]), *pcb = (uint8_t*)(ws + g.plane_off[1]), *pcr = (uint8_t*)(ws + g.plane_off[2]);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(jpeg_decode_idct_kernel, dim3((unsigned)((g.blocks + 31) / 32), (unsigned)n), dim3(256), 0, s, (const int16_t*)coef, (const uint8_t*)upload, py,
-                     pcb, pcr, tab, g.bpm, g.lbx, g.mcus_x, g.blocks, g.yw, g.yh, g.cw, g.ch);
-  SF_HIP_LAUNCH_CHECK(who);
+  SF_TRY(sf_launch<&jpeg_decode_idct_kernel>(who, dim3((unsigned)((g.blocks + 31) / 32), (unsigned)n), dim3(256), 0, s, (const int16_t*)coef,
+                                             (const uint8_t*)upload, py, pcb, pcr, tab, g.bpm, g.lbx, g.mcus_x, g.blocks, g.yw, g.yh, g.cw, g.ch));
   const long hw = (long)h * w;
   long sn, sc, sy, sx;
   if (layout == SF_JPEG_HWC) sn = 3 * hw, sc = 1, sy = 3L * w, sx = 3;
   else if (layout == SF_JPEG_POSE) sn = hw, sc = (long)n * hw, sy = w, sx = 1;
   else sn = 3 * hw, sc = hw, sy = w, sx = 1;
   const dim3 grid((unsigned)(((w + 3) / 4 + 63) / 64), (unsigned)((h + 3) / 4), (unsigned)n), block(64, 4);
-#define SF_JPEG_DEC_LAUNCH(T)                                                                                                                              \
-  hipLaunchKernelGGL((jpeg_decode_colour_kernel<T>), grid, block, 0, s, py, pcb, pcr, (T*)out, h, w, g.comps, g.lbx, g.lby, g.yw, g.yh, g.cw, g.ch, g.tcw, \
-                     g.tch, sn, sc, sy, sx)
+#define SF_JPEG_DEC_LAUNCH(T)                                                                                                                          \
+  return sf_launch<&jpeg_decode_colour_kernel<T>>(who, grid, block, 0, s, py, pcb, pcr, (T*)out, h, w, g.comps, g.lbx, g.lby, g.yw, g.yh, g.cw, g.ch, \
+                                                  g.tcw, g.tch, sn, sc, sy, sx)
   if (dtype == SF_JPEG_U8) SF_JPEG_DEC_LAUNCH(uint8_t);
-  else if (dtype == SF_JPEG_F32) SF_JPEG_DEC_LAUNCH(float);
-  else SF_JPEG_DEC_LAUNCH(bf16_t);
+  if (dtype == SF_JPEG_F32) SF_JPEG_DEC_LAUNCH(float);
+  SF_JPEG_DEC_LAUNCH(bf16_t);
 #undef SF_JPEG_DEC_LAUNCH
-  SF_HIP_LAUNCH_CHECK(who);
-  return 0;
 }
 
 extern "C" int sf_jpeg_decode_frames(const void* upload, size_t upload_bytes, const int32_t* idct_table, int n, int h, int w, int sampling, int max_intervals,

@@ -199,25 +199,21 @@ __global__ __launch_bounds__(PTHREADS) void pose_conv_window_kernel(PConvP p, PW
 }
 
 template <int CIN, int KT, int ST, int SS, int NB>
-int launch(PConvP& p, hipStream_t s, const PWin* pw = nullptr) {
+int launch(PConvP& p, const char* who, hipStream_t s, const PWin* pw = nullptr) {
   using G = Geo<CIN, KT, ST, SS>;
   p.ntw = (p.Wo + TW - 1) / TW;
   p.nth = (p.Ho + G::TH - 1) / G::TH;
   const long ntiles = (long)p.ntw * p.nth * ((p.To + G::TT - 1) / G::TT);
-  SF_CHECK(ntiles < (1L << 30), "sf_pose_conv: too many output bricks");
+  SF_CHECK(ntiles < (1L << 30), "%s: too many output bricks", who);
   p.ntiles = (int)ntiles;
   int nwg = p.ntiles < 1024 ? p.ntiles : 1024;          // 4 persistent workgroups per CU
   if (nwg >= 8) nwg &= ~7;
   p.per = (p.ntiles + nwg - 1) / nwg;
   nwg = (p.ntiles + p.per - 1) / p.per;                  // no idle workgroups; the XCD remap needs nwg % 8 == 0 and is skipped otherwise
   if constexpr (KT == 3) {      // the window mode exists for the dwpose stack's layers only
-    if (pw) {
-      hipLaunchKernelGGL((pose_conv_window_kernel<CIN, KT, ST, SS, NB>), dim3(nwg), dim3(PTHREADS), 0, s, p, *pw);
-      return 0;
-    }
+    if (pw) return sf_launch<&pose_conv_window_kernel<CIN, KT, ST, SS, NB>>(who, dim3(nwg), dim3(PTHREADS), 0, s, p, *pw);
   }
-  hipLaunchKernelGGL((pose_conv_kernel<CIN, KT, ST, SS, NB>), dim3(nwg), dim3(PTHREADS), 0, s, p);
-  return 0;
+  return sf_launch<&pose_conv_kernel<CIN, KT, ST, SS, NB>>(who, dim3(nwg), dim3(PTHREADS), 0, s, p);
 }
 
 // pose frames / the reference pose image -> channels-last bf16 with 8 stored channels (3 real), `lead` copies of the
@@ -292,25 +288,22 @@ extern "C" int sf_pose_conv(const sf_pose_conv_args* a, void* stream) {
   if (const int rc = check_4g(a, p, who)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int key = (a->Cin == 16) * 1000 + a->kt * 100 + a->stride_t * 10 + a->stride_s;
-  int rc = -1;
   if (nb == 1) {
     switch (key) {
-      case 311: rc = launch<8, 3, 1, 1, 1>(p, s); break;
-      case 1311: rc = launch<16, 3, 1, 1, 1>(p, s); break;
-      case 1312: rc = launch<16, 3, 1, 2, 1>(p, s); break;
-      case 1322: rc = launch<16, 3, 2, 2, 1>(p, s); break;
-      case 111: rc = launch<8, 1, 1, 1, 1>(p, s); break;
-      case 1111: rc = launch<16, 1, 1, 1, 1>(p, s); break;
-      case 1112: rc = launch<16, 1, 1, 2, 1>(p, s); break;
+      case 311: return launch<8, 3, 1, 1, 1>(p, who, s);
+      case 1311: return launch<16, 3, 1, 1, 1>(p, who, s);
+      case 1312: return launch<16, 3, 1, 2, 1>(p, who, s);
+      case 1322: return launch<16, 3, 2, 2, 1>(p, who, s);
+      case 111: return launch<8, 1, 1, 1, 1>(p, who, s);
+      case 1111: return launch<16, 1, 1, 1, 1>(p, who, s);
+      case 1112: return launch<16, 1, 1, 2, 1>(p, who, s);
       default: break;
     }
   } else if (key == 1112) {
-    rc = launch<16, 1, 1, 2, 2>(p, s);
+    return launch<16, 1, 1, 2, 2>(p, who, s);
   }
-  SF_CHECK(rc == 0, "sf_pose_conv: no kernel for Cin=%d kt=%d stride (%d, %d) Cout=%d (the pose stacks do not use it)", a->Cin, a->kt, a->stride_t,
+  SF_CHECK(false, "sf_pose_conv: no kernel for Cin=%d kt=%d stride (%d, %d) Cout=%d (the pose stacks do not use it)", a->Cin, a->kt, a->stride_t,
            a->stride_s, a->Cout);
-  SF_HIP_LAUNCH_CHECK("sf_pose_conv");
-  return 0;
 }
 
 extern "C" int sf_pose_conv_window(const sf_pose_conv_args* a, const sf_pose_window* win, void* stream) {
@@ -351,16 +344,12 @@ extern "C" int sf_pose_conv_window(const sf_pose_conv_args* a, const sf_pose_win
   pw.t_hi = win->x_t0 + a->T < win->t_end ? win->x_t0 + a->T : win->t_end;
   pw.t_out0 = win->t_out0;
   hipStream_t s = (hipStream_t)stream;
-  int rc;
   switch (key) {
-    case 311: rc = launch<8, 3, 1, 1, 1>(p, s, &pw); break;
-    case 1311: rc = launch<16, 3, 1, 1, 1>(p, s, &pw); break;
-    case 1312: rc = launch<16, 3, 1, 2, 1>(p, s, &pw); break;
-    default: rc = launch<16, 3, 2, 2, 1>(p, s, &pw); break;
+    case 311: return launch<8, 3, 1, 1, 1>(p, who, s, &pw);
+    case 1311: return launch<16, 3, 1, 1, 1>(p, who, s, &pw);
+    case 1312: return launch<16, 3, 1, 2, 1>(p, who, s, &pw);
+    default: return launch<16, 3, 2, 2, 1>(p, who, s, &pw);
   }
-  if (rc != 0) return rc;
-  SF_HIP_LAUNCH_CHECK(who);
-  return 0;
 }
 
 extern "C" int sf_pose_prepare(const void* src, int dtype, int hwc, int F, int H, int W, int lead, void* out, void* stream) {
@@ -377,11 +366,9 @@ extern "C" int sf_pose_prepare(const void* src, int dtype, int hwc, int F, int H
   hipStream_t s = (hipStream_t)stream;
   const long plane = (long)F * hw;
   if (dtype == SF_POSE_U8)
-    hipLaunchKernelGGL(pose_prepare_kernel<uint8_t>, grid, dim3(256), 0, s, (const uint8_t*)src, (bf16_t*)out, n_pos, (int)hw, plane, hwc, lead);
-  else if (dtype == SF_POSE_F32)
-    hipLaunchKernelGGL(pose_prepare_kernel<float>, grid, dim3(256), 0, s, (const float*)src, (bf16_t*)out, n_pos, (int)hw, plane, hwc, lead);
-  else
-    hipLaunchKernelGGL(pose_prepare_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)src, (bf16_t*)out, n_pos, (int)hw, plane, hwc, lead);
-  SF_HIP_LAUNCH_CHECK("sf_pose_prepare");
-  return 0;
+    return sf_launch<&pose_prepare_kernel<uint8_t>>("sf_pose_prepare", grid, dim3(256), 0, s, (const uint8_t*)src, (bf16_t*)out, n_pos, (int)hw, plane, hwc,
+                                                    lead);
+  if (dtype == SF_POSE_F32)
+    return sf_launch<&pose_prepare_kernel<float>>("sf_pose_prepare", grid, dim3(256), 0, s, (const float*)src, (bf16_t*)out, n_pos, (int)hw, plane, hwc, lead);
+  return sf_launch<&pose_prepare_kernel<bf16_t>>("sf_pose_prepare", grid, dim3(256), 0, s, (const bf16_t*)src, (bf16_t*)out, n_pos, (int)hw, plane, hwc, lead);
 }

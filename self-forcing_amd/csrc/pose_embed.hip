@@ -123,9 +123,8 @@ extern "C" int sf_pose_patch_embed(const void* x, int T, int H, int W, const voi
   const long tokens = (long)T * h * wd;
   SF_CHECK(tokens < (1L << 31) / 8, "%s: %ld tokens", who, tokens);
   const long n_pieces = tokens * 8;
-  hipLaunchKernelGGL(pose_patch_gather_kernel, dim3((unsigned)((n_pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)rows,
-                     n_pieces, H, W, h, wd);
-  SF_HIP_LAUNCH_CHECK(who);
+  SF_TRY(sf_launch<&pose_patch_gather_kernel>(who, dim3((unsigned)((n_pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)rows,
+                                              n_pieces, H, W, h, wd));
   return Gemm(rows, 64, w, 64, tokens_out, pose_dim, (int)tokens, pose_dim, 64).bias(bias).bf16(stream);
 }
 

@@ -236,9 +236,7 @@ extern "C" int sf_resize_frames(const void* frames, int layout, int n, int h, in
   SF_CHECK(lds <= 65536, "%s: %zu bytes of LDS for %dx%d -> %dx%d", who, lds, a.ch, a.cw, out_h, out_w);
   const dim3 grid((unsigned)((out_w + TW - 1) / TW), (unsigned)((out_h + TH - 1) / TH), (unsigned)n);
   hipStream_t s = (hipStream_t)stream;
-  if (out_dtype == SF_JPEG_U8) hipLaunchKernelGGL((resize_kernel<uint8_t>), grid, dim3(256), lds, s, a, (uint8_t*)out);
-  else if (out_dtype == SF_JPEG_F32) hipLaunchKernelGGL((resize_kernel<float>), grid, dim3(256), lds, s, a, (float*)out);
-  else hipLaunchKernelGGL((resize_kernel<bf16_t>), grid, dim3(256), lds, s, a, (bf16_t*)out);
-  SF_HIP_LAUNCH_CHECK(who);
-  return 0;
+  if (out_dtype == SF_JPEG_U8) return sf_launch<&resize_kernel<uint8_t>>(who, grid, dim3(256), lds, s, a, (uint8_t*)out);
+  if (out_dtype == SF_JPEG_F32) return sf_launch<&resize_kernel<float>>(who, grid, dim3(256), lds, s, a, (float*)out);
+  return sf_launch<&resize_kernel<bf16_t>>(who, grid, dim3(256), lds, s, a, (bf16_t*)out);
 }

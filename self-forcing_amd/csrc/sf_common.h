@@ -24,14 +24,13 @@ extern "C" void sf_set_error(const char* fmt, ...);
       return -1;                             \
     }                                        \
   } while (0)
-#define SF_HIP_LAUNCH_CHECK(name)                                              \
-  do {                                                                         \
-    hipError_t e__ = hipGetLastError();                                        \
-    if (e__ != hipSuccess) {                                                   \
-      sf_set_error("%s: launch failed: %s", name, hipGetErrorString(e__));     \
-      return -2;                                                               \
-    }                                                                          \
+// propagate a launcher's non-zero return
+#define SF_TRY(expr)            \
+  do {                          \
+    int rc__ = (expr);          \
+    if (rc__ != 0) return rc__; \
   } while (0)
+#include "sf_launch.h"
 
 #ifdef __HIPCC__
 __device__ __forceinline__ float bf2f(bf16_t v) { return (float)v; }
@@ -41,7 +40,10 @@ __device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)v; }
 // instead of six __shfl_xor steps: hipcc lowers those to ds_bpermute_b32 -- a round trip through the LDS crossbar each,
 // ~100 cycles of latency, six of them dependent per reduction -- which is most of what a one-pass norm kernel does
 // between its loads and its stores.  All 64 lanes must be active.  (The order of the fp32 additions differs from the
-// butterfly's; every caller rounds the result into bf16 outputs.)
+// butterfly's; every caller rounds the result into bf16 outputs.)  row_bcast15 / row_bcast31 exist on the gfx9 family only.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx90a__) && !defined(__gfx942__) && !defined(__gfx950__)
+#error "wave_sum / wave_max use DPP row_bcast15 / row_bcast31: build for gfx90a, gfx942 or gfx950"
+#endif
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float sf_dpp(float old, float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));

@@ -6,13 +6,6 @@
 #include "sf_common.h"
 #include "../../include/sf_hip.h"
 
-// propagate a launcher's non-zero return
-#define SF_TRY(expr)            \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
-
 // a failed hipMemsetAsync / hipMemcpyAsync as the library's error return: "<who>: <what> failed: <hip's words>"
 inline int sf_hip_ok(hipError_t e, const char* who, const char* what) {
   SF_CHECK(e == hipSuccess, "%s: %s failed: %s", who, what, hipGetErrorString(e));

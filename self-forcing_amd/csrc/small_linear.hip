@@ -182,16 +182,10 @@ __global__ __launch_bounds__(SLR_MAX_THREADS) void small_linear_reg_kernel(const
   }
 }
 
-// Dynamic LDS above 64 KB has to be registered with the runtime before the launch (8 rows at K = 5120, the 14B time
-// projection at batch x groups >= 5, stage 80 KB): one-time registration of the largest size asked for (idempotent).
-template <int R>
-void allow_large_lds(size_t bytes) {
-  static int attr_lds = 0;
-  if ((int)bytes > attr_lds && bytes > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_linear_kernel<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    attr_lds = (int)bytes;
-  }
-}
+// The most dynamic LDS small_linear_kernel is launched with (sf_small_linear checks it): registered with the runtime as
+// the kernel's cap, since a stage can be above 64 KB (8 rows at K = 5120, the 14B time projection at batch x groups >= 5,
+// 80 KB).
+constexpr int SL_LDS_CAP = 160 * 1024;
 
 }  // namespace
 
@@ -199,7 +193,7 @@ extern "C" int sf_small_linear(const void* x, const void* w, const void* bias, v
                                int act_in, int act_out, void* stream) {
   SF_CHECK(x && w && out, "sf_small_linear: null tensor");
   SF_CHECK(M > 0 && M <= 32 && N > 0 && K > 0 && K % 8 == 0, "sf_small_linear: unsupported shape M=%d N=%d K=%d (M<=32, K%%8==0)", M, N, K);
-  SF_CHECK((size_t)SL_MB_MAX * K * 2 <= 160 * 1024, "sf_small_linear: K=%d too large for the LDS activation stage", K);
+  SF_CHECK((size_t)SL_MB_MAX * K * 2 <= SL_LDS_CAP, "sf_small_linear: K=%d too large for the LDS activation stage", K);
   SF_CHECK(act_in >= 0 && act_in <= 2 && act_out >= 0 && act_out <= 2, "sf_small_linear: bad activation code");
   const int waves_needed = (N + SL_NPW - 1) / SL_NPW;
   const int ks = (K + 511) / 512;
@@ -209,33 +203,24 @@ extern "C" int sf_small_linear(const void* x, const void* w, const void* bias, v
     const dim3 grid((waves_needed + wpb - 1) / wpb), block(64 * wpb);
     const int xch = (M * ks * 64 + 255) / 256;                               // = XCH of the instantiation
     const size_t lds = act_in != 0 ? (size_t)xch * 64 * wpb * 16 : 0;        // chunks of 16 bytes, padded to whole passes
-#define SF_SLR(R, S)                                                                                                                  \
-  do {                                                                                                                                \
-    if (act_in == 0)                                                                                                                  \
-      hipLaunchKernelGGL((small_linear_reg_kernel<R, S, 0>), grid, block, lds, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)w, \
-                         (const bf16_t*)bias, (bf16_t*)out, N, K, act_out);                                                           \
-    else                                                                                                                              \
-      hipLaunchKernelGGL((small_linear_reg_kernel<R, S, 1>), grid, block, lds, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)w, \
-                         (const bf16_t*)bias, (bf16_t*)out, N, K, act_out);                                                           \
-  } while (0)
-#define SF_SLR_M(S)                                                                                                                   \
-  switch (M) { case 1: SF_SLR(1, S); break; case 2: SF_SLR(2, S); break; case 3: SF_SLR(3, S); break; case 4: SF_SLR(4, S); break; \
-               case 5: SF_SLR(5, S); break; case 6: SF_SLR(6, S); break; case 7: SF_SLR(7, S); break; default: SF_SLR(8, S); break; }
+#define SF_SLR(R, S)                                                                                                             \
+  return act_in == 0 ? sf_launch<&small_linear_reg_kernel<R, S, 0>>("sf_small_linear", grid, block, lds, (hipStream_t)stream,   \
+                           (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)out, N, K, act_out)                 \
+                     : sf_launch<&small_linear_reg_kernel<R, S, 1>>("sf_small_linear", grid, block, lds, (hipStream_t)stream,   \
+                           (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)out, N, K, act_out)
+#define SF_SLR_M(S)                                                                                                      \
+  switch (M) { case 1: SF_SLR(1, S); case 2: SF_SLR(2, S); case 3: SF_SLR(3, S); case 4: SF_SLR(4, S);                  \
+               case 5: SF_SLR(5, S); case 6: SF_SLR(6, S); case 7: SF_SLR(7, S); default: SF_SLR(8, S); }
     if (ks == 1) { SF_SLR_M(1) } else { SF_SLR_M(3) }
 #undef SF_SLR_M
 #undef SF_SLR
-    SF_HIP_LAUNCH_CHECK("sf_small_linear");
-    return 0;
   }
   const int blocks = min(1024, (waves_needed + 3) / 4);
   for (int m0 = 0; m0 < M; m0 += SL_MB_MAX) {
     const int mc = min(SL_MB_MAX, M - m0);
-#define SF_SL_LAUNCH(R)                                                                                                     \
-  do {                                                                                                                      \
-    allow_large_lds<R>((size_t)R * K * 2);                                                                                  \
-    hipLaunchKernelGGL(small_linear_kernel<R>, dim3(blocks), dim3(SL_THREADS), (size_t)R * K * 2, (hipStream_t)stream,      \
-                       (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)out, m0, mc, N, K, act_in, act_out); \
-  } while (0)
+#define SF_SL_LAUNCH(R)                                                                                                                 \
+  SF_TRY((sf_launch<&small_linear_kernel<R>, SL_LDS_CAP>("sf_small_linear", dim3(blocks), dim3(SL_THREADS), (size_t)R * K * 2,          \
+      (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)out, m0, mc, N, K, act_in, act_out)))
     if (mc == 1) SF_SL_LAUNCH(1);
     else if (mc == 2) SF_SL_LAUNCH(2);
     else if (mc == 3) SF_SL_LAUNCH(3);
@@ -243,6 +228,5 @@ extern "C" int sf_small_linear(const void* x, const void* w, const void* bias, v
     else SF_SL_LAUNCH(8);
 #undef SF_SL_LAUNCH
   }
-  SF_HIP_LAUNCH_CHECK("sf_small_linear");
   return 0;
 }

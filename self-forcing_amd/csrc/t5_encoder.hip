@@ -98,32 +98,27 @@ int check_model(const sf_t5_model* m, int B, int L) {
 
 extern "C" int sf_embedding_gather(const int64_t* ids, const void* table, void* out, int n_tokens, int dim, int vocab, void* stream) {
   SF_CHECK(ids && table && out && n_tokens > 0 && dim > 0 && dim % 8 == 0 && vocab > 0, "sf_embedding_gather: bad arguments");
-  hipLaunchKernelGGL(embedding_gather_kernel, dim3(n_tokens), dim3(256), 0, (hipStream_t)stream, ids, (const bf16_t*)table, (bf16_t*)out, dim, vocab);
-  SF_HIP_LAUNCH_CHECK("sf_embedding_gather");
-  return 0;
+  return sf_launch<&embedding_gather_kernel>("sf_embedding_gather", dim3(n_tokens), dim3(256), 0, (hipStream_t)stream, ids, (const bf16_t*)table, (bf16_t*)out,
+                                             dim, vocab);
 }
 
 extern "C" int sf_t5_softmax_bias(const float* s, void* p, const void* emb, const int32_t* rel_bucket, const int64_t* key_mask,
                                   int H, int L, int ld, void* stream) {
   SF_CHECK(s && p && emb && rel_bucket && key_mask && H > 0 && L > 0 && ld >= L, "sf_t5_softmax_bias: bad arguments");
-  hipLaunchKernelGGL(t5_softmax_bias_kernel, dim3(H * L), dim3(256), 0, (hipStream_t)stream, s, (bf16_t*)p, (const bf16_t*)emb, rel_bucket, key_mask, H, L, ld);
-  SF_HIP_LAUNCH_CHECK("sf_t5_softmax_bias");
-  return 0;
+  return sf_launch<&t5_softmax_bias_kernel>("sf_t5_softmax_bias", dim3(H * L), dim3(256), 0, (hipStream_t)stream, s, (bf16_t*)p, (const bf16_t*)emb, rel_bucket,
+                                            key_mask, H, L, ld);
 }
 
 extern "C" int sf_mul_bf16(const void* a, const void* b, void* out, int64_t n, void* stream) {
   SF_CHECK(a && b && out && n > 0 && n % 8 == 0, "sf_mul_bf16: n=%lld must be a positive multiple of 8", (long long)n);
   const long n8 = n / 8;
-  hipLaunchKernelGGL(mul_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)a, (const bf16x8*)b, (bf16x8*)out, n8);
-  SF_HIP_LAUNCH_CHECK("sf_mul_bf16");
-  return 0;
+  return sf_launch<&mul_bf16_kernel>("sf_mul_bf16", dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)a, (const bf16x8*)b,
+                                     (bf16x8*)out, n8);
 }
 
 extern "C" int sf_zero_masked_rows(void* x, const int64_t* mask, int rows, int dim, void* stream) {
   SF_CHECK(x && mask && rows > 0 && dim > 0 && dim % 8 == 0, "sf_zero_masked_rows: bad arguments");
-  hipLaunchKernelGGL(zero_masked_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, mask, dim);
-  SF_HIP_LAUNCH_CHECK("sf_zero_masked_rows");
-  return 0;
+  return sf_launch<&zero_masked_rows_kernel>("sf_zero_masked_rows", dim3(rows), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, mask, dim);
 }
 
 extern "C" size_t sf_t5_workspace_bytes(const sf_t5_model* m, int batch, int seq_len) {

@@ -118,8 +118,7 @@ int launch_epi(const TConvP& p, hipStream_t s) {
   constexpr int LDS = igemm::lds_bytes(NT);
   static_assert(LDS <= 64 * 1024, "the tiles of this kernel fit the default dynamic-LDS limit");
   static_assert(igemm::BM * igemm::out_row_bytes(NT) <= LDS, "the epilogue's output tile fits the stages");
-  hipLaunchKernelGGL((taehv_conv_kernel<NT, EPI>), dim3(p.tiles_m * p.tiles_n), dim3(igemm::THREADS), LDS, s, p);
-  return 0;
+  return sf_launch<&taehv_conv_kernel<NT, EPI>>("sf_taehv_conv", dim3(p.tiles_m * p.tiles_n), dim3(igemm::THREADS), LDS, s, p);
 }
 
 template <int NT>
@@ -131,7 +130,7 @@ int launch_nt(const TConvP& p, int epi, hipStream_t s) {
     case SF_TAEHV_RELU: return launch_epi<NT, SF_TAEHV_RELU>(p, s);
     case SF_TAEHV_HEAD_F32: return launch_epi<NT, SF_TAEHV_HEAD_F32>(p, s);
     case SF_TAEHV_LATENT_F32: return launch_epi<NT, SF_TAEHV_LATENT_F32>(p, s);
-    default: return -1;
+    default: SF_CHECK(false, "sf_taehv_conv: unknown epilogue %d", epi);
   }
 }
 
@@ -187,13 +186,9 @@ extern "C" int sf_taehv_conv(const sf_taehv_conv_args* a, void* stream) {
   p.tiles_m = (p.M + igemm::BM - 1) / igemm::BM;
   p.tiles_n = (a->Cout + 32 * nt - 1) / (32 * nt);
   hipStream_t s = (hipStream_t)stream;
-  int rc = 0;
   switch (nt) {
-    case 4: rc = launch_nt<4>(p, a->epilogue, s); break;
-    case 2: rc = launch_nt<2>(p, a->epilogue, s); break;
-    default: rc = launch_nt<1>(p, a->epilogue, s); break;
+    case 4: return launch_nt<4>(p, a->epilogue, s);
+    case 2: return launch_nt<2>(p, a->epilogue, s);
+    default: return launch_nt<1>(p, a->epilogue, s);
   }
-  SF_CHECK(rc == 0, "sf_taehv_conv: unknown epilogue %d", a->epilogue);
-  SF_HIP_LAUNCH_CHECK("sf_taehv_conv");
-  return 0;
 }

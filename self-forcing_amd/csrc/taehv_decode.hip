@@ -121,10 +121,8 @@ extern "C" int sf_taehv_prepare_latent(const void* latent, void* out, int n, int
   SF_CHECK(n > 0 && z > 0 && h > 0 && w > 0 && c_pad >= z && c_pad % 8 == 0, "sf_taehv_prepare_latent: n=%d z=%d %dx%d c_pad=%d", n, z, h, w, c_pad);
   SF_CHECK((uintptr_t)out % 16 == 0, "sf_taehv_prepare_latent: misaligned output");
   const long n_pos = (long)n * h * w;
-  hipLaunchKernelGGL(taehv_prepare_kernel, dim3((unsigned)((n_pos + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)latent, (bf16_t*)out,
-                     n_pos, h * w, z, c_pad);
-  SF_HIP_LAUNCH_CHECK("sf_taehv_prepare_latent");
-  return 0;
+  return sf_launch<&taehv_prepare_kernel>("sf_taehv_prepare_latent", dim3((unsigned)((n_pos + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                                          (const bf16_t*)latent, (bf16_t*)out, n_pos, h * w, z, c_pad);
 }
 
 extern "C" size_t sf_taehv_state_bytes(const sf_taehv_model* model, int lat_h, int lat_w) {

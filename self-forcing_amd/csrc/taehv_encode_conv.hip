@@ -140,7 +140,7 @@ __global__ __launch_bounds__(igemm::THREADS, 2) void taehv_down_conv_kernel(TDow
 }
 
 template <int KT>
-void launch_down(const sf_taehv_down_conv_args* a, int nk, unsigned x_bytes, hipStream_t s) {
+int launch_down(const sf_taehv_down_conv_args* a, int nk, unsigned x_bytes, hipStream_t s) {
   constexpr int NT = 2;
   constexpr int LDS = igemm::lds_bytes(NT);
   static_assert(LDS <= 64 * 1024, "the tiles of this kernel fit the default dynamic-LDS limit");
@@ -154,7 +154,7 @@ void launch_down(const sf_taehv_down_conv_args* a, int nk, unsigned x_bytes, hip
   p.tiles_m = (p.M + igemm::BM - 1) / igemm::BM;
   p.tiles_n = a->Cout / (32 * NT);
   p.x_bytes = x_bytes;
-  hipLaunchKernelGGL((taehv_down_conv_kernel<KT>), dim3(p.tiles_m * p.tiles_n), dim3(igemm::THREADS), LDS, s, p);
+  return sf_launch<&taehv_down_conv_kernel<KT>>("sf_taehv_down_conv", dim3(p.tiles_m * p.tiles_n), dim3(igemm::THREADS), LDS, s, p);
 }
 
 }  // namespace
@@ -173,14 +173,12 @@ extern "C" int sf_taehv_encode_stem(const void* pixels, int dtype, int64_t c_str
   const long blocks = (long)tiles_x * tiles_y * n_frames;
   SF_CHECK(blocks < (1L << 31), "sf_taehv_encode_stem: too many tiles");
   hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)blocks), block(256);
   if (dtype == SF_TAEHV_PIXEL_F32)
-    hipLaunchKernelGGL(taehv_stem_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)pixels, (long)c_stride, H, W, lead, tiles_x, tiles_y,
-                       (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)out);
-  else
-    hipLaunchKernelGGL(taehv_stem_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)pixels, (long)c_stride, H, W, lead, tiles_x, tiles_y,
-                       (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)out);
-  SF_HIP_LAUNCH_CHECK("sf_taehv_encode_stem");
-  return 0;
+    return sf_launch<&taehv_stem_kernel<float>>("sf_taehv_encode_stem", grid, block, 0, s, (const float*)pixels, (long)c_stride, H, W, lead, tiles_x, tiles_y,
+                                                (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)out);
+  return sf_launch<&taehv_stem_kernel<bf16_t>>("sf_taehv_encode_stem", grid, block, 0, s, (const bf16_t*)pixels, (long)c_stride, H, W, lead, tiles_x, tiles_y,
+                                               (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)out);
 }
 
 extern "C" int sf_taehv_down_conv(const sf_taehv_down_conv_args* a, void* stream) {
@@ -200,8 +198,5 @@ extern "C" int sf_taehv_down_conv(const sf_taehv_down_conv_args* a, void* stream
   const long xb = (long)a->kt * a->Tout * (2L * a->H) * (2L * a->W) * a->Cin * 2;
   SF_CHECK(xb < 0xFFFFFF00L, "sf_taehv_down_conv: input volume of %ld bytes exceeds the 4 GiB the gather's 32-bit offsets cover", xb);
   hipStream_t s = (hipStream_t)stream;
-  if (a->kt == 2) launch_down<2>(a, nk, (unsigned)xb, s);
-  else launch_down<1>(a, nk, (unsigned)xb, s);
-  SF_HIP_LAUNCH_CHECK("sf_taehv_down_conv");
-  return 0;
+  return a->kt == 2 ? launch_down<2>(a, nk, (unsigned)xb, s) : launch_down<1>(a, nk, (unsigned)xb, s);
 }

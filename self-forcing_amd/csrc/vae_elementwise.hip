@@ -123,25 +123,22 @@ extern "C" int sf_rmsnorm_silu_cl(const void* x, const void* gamma, void* out, i
   const dim3 grid((unsigned)((rows + rpb - 1) / rpb)), block(256);
   const bf16_t* xp = (const bf16_t*)x; const bf16_t* gp = (const bf16_t*)gamma; bf16_t* op = (bf16_t*)out;
   switch (lpr) {
-    case 1: hipLaunchKernelGGL(rmsnorm_silu_kernel<1>, grid, block, 0, s, xp, gp, op, (long)rows, C, silu); break;
-    case 2: hipLaunchKernelGGL(rmsnorm_silu_kernel<2>, grid, block, 0, s, xp, gp, op, (long)rows, C, silu); break;
-    case 4: hipLaunchKernelGGL(rmsnorm_silu_kernel<4>, grid, block, 0, s, xp, gp, op, (long)rows, C, silu); break;
-    case 8: hipLaunchKernelGGL(rmsnorm_silu_kernel<8>, grid, block, 0, s, xp, gp, op, (long)rows, C, silu); break;
-    case 16: hipLaunchKernelGGL(rmsnorm_silu_kernel<16>, grid, block, 0, s, xp, gp, op, (long)rows, C, silu); break;
-    case 32: hipLaunchKernelGGL(rmsnorm_silu_kernel<32>, grid, block, 0, s, xp, gp, op, (long)rows, C, silu); break;
-    default: hipLaunchKernelGGL(rmsnorm_silu_kernel<64>, grid, block, 0, s, xp, gp, op, (long)rows, C, silu); break;
+    case 1: return sf_launch<&rmsnorm_silu_kernel<1>>("sf_rmsnorm_silu_cl", grid, block, 0, s, xp, gp, op, (long)rows, C, silu);
+    case 2: return sf_launch<&rmsnorm_silu_kernel<2>>("sf_rmsnorm_silu_cl", grid, block, 0, s, xp, gp, op, (long)rows, C, silu);
+    case 4: return sf_launch<&rmsnorm_silu_kernel<4>>("sf_rmsnorm_silu_cl", grid, block, 0, s, xp, gp, op, (long)rows, C, silu);
+    case 8: return sf_launch<&rmsnorm_silu_kernel<8>>("sf_rmsnorm_silu_cl", grid, block, 0, s, xp, gp, op, (long)rows, C, silu);
+    case 16: return sf_launch<&rmsnorm_silu_kernel<16>>("sf_rmsnorm_silu_cl", grid, block, 0, s, xp, gp, op, (long)rows, C, silu);
+    case 32: return sf_launch<&rmsnorm_silu_kernel<32>>("sf_rmsnorm_silu_cl", grid, block, 0, s, xp, gp, op, (long)rows, C, silu);
+    default: return sf_launch<&rmsnorm_silu_kernel<64>>("sf_rmsnorm_silu_cl", grid, block, 0, s, xp, gp, op, (long)rows, C, silu);
   }
-  SF_HIP_LAUNCH_CHECK("sf_rmsnorm_silu_cl");
-  return 0;
 }
 
 extern "C" int sf_softmax_rows(const float* sm, int64_t lds, void* p, int64_t ldp, int rows, int cols, int cols_padded,
                                float scale, void* stream) {
   SF_CHECK(sm && p, "sf_softmax_rows: null tensor");
   SF_CHECK(rows > 0 && cols > 0 && cols_padded >= cols && lds >= cols && ldp >= cols_padded, "sf_softmax_rows: bad shape rows=%d cols=%d padded=%d", rows, cols, cols_padded);
-  hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, sm, (long)lds, (bf16_t*)p, (long)ldp, cols, cols_padded, scale);
-  SF_HIP_LAUNCH_CHECK("sf_softmax_rows");
-  return 0;
+  return sf_launch<&softmax_rows_kernel>("sf_softmax_rows", dim3(rows), dim3(256), 0, (hipStream_t)stream, sm, (long)lds, (bf16_t*)p, (long)ldp, cols,
+                                         cols_padded, scale);
 }
 
 extern "C" int sf_vae_prepare_latent(const void* latent, const float* mean, const float* stdv, const void* conv2_w, const void* conv2_b,
@@ -149,10 +146,8 @@ extern "C" int sf_vae_prepare_latent(const void* latent, const float* mean, cons
   SF_CHECK(latent && mean && stdv && conv2_w && conv2_b && out, "sf_vae_prepare_latent: null tensor");
   SF_CHECK(z > 0 && z <= 32 && c_pad >= z && h > 0 && w > 0, "sf_vae_prepare_latent: bad shape z=%d c_pad=%d", z, c_pad);
   const int hw = h * w;
-  hipLaunchKernelGGL(prepare_latent_kernel, dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)latent, mean, stdv,
-                     (const bf16_t*)conv2_w, (const bf16_t*)conv2_b, (bf16_t*)out, z, hw, c_pad);
-  SF_HIP_LAUNCH_CHECK("sf_vae_prepare_latent");
-  return 0;
+  return sf_launch<&prepare_latent_kernel>("sf_vae_prepare_latent", dim3((hw + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)latent, mean,
+                                           stdv, (const bf16_t*)conv2_w, (const bf16_t*)conv2_b, (bf16_t*)out, z, hw, c_pad);
 }
 
 extern "C" int sf_vae_prepare_pixels(const void* pixels, int is_f32, int64_t c_stride, void* out, int T, int H, int W, int c_pad, void* stream) {
@@ -163,11 +158,10 @@ extern "C" int sf_vae_prepare_pixels(const void* pixels, int is_f32, int64_t c_s
   SF_CHECK((uintptr_t)out % 16 == 0, "sf_vae_prepare_pixels: misaligned output");
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   if (is_f32)
-    hipLaunchKernelGGL(prepare_pixels_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)pixels, (long)c_stride, (bf16_t*)out, n, c_pad);
-  else
-    hipLaunchKernelGGL(prepare_pixels_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)pixels, (long)c_stride, (bf16_t*)out, n, c_pad);
-  SF_HIP_LAUNCH_CHECK("sf_vae_prepare_pixels");
-  return 0;
+    return sf_launch<&prepare_pixels_kernel<float>>("sf_vae_prepare_pixels", grid, block, 0, (hipStream_t)stream, (const float*)pixels, (long)c_stride,
+                                                    (bf16_t*)out, n, c_pad);
+  return sf_launch<&prepare_pixels_kernel<bf16_t>>("sf_vae_prepare_pixels", grid, block, 0, (hipStream_t)stream, (const bf16_t*)pixels, (long)c_stride,
+                                                   (bf16_t*)out, n, c_pad);
 }
 
 extern "C" int sf_vae_finish_latent(const void* head_out, int ld_in, int cin, const void* conv1_w, int ld_w, const void* conv1_b,
@@ -177,8 +171,6 @@ extern "C" int sf_vae_finish_latent(const void* head_out, int ld_in, int cin, co
            cin, ld_in, ld_w, z);
   SF_CHECK(T > 0 && h > 0 && w > 0, "sf_vae_finish_latent: bad shape T=%d h=%d w=%d", T, h, w);
   const long n = (long)T * h * w;
-  hipLaunchKernelGGL(finish_latent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)head_out, ld_in, cin,
-                     (const bf16_t*)conv1_w, ld_w, (const bf16_t*)conv1_b, mean, stdv, out, n, h * w, z);
-  SF_HIP_LAUNCH_CHECK("sf_vae_finish_latent");
-  return 0;
+  return sf_launch<&finish_latent_kernel>("sf_vae_finish_latent", dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)head_out,
+                                          ld_in, cin, (const bf16_t*)conv1_w, ld_w, (const bf16_t*)conv1_b, mean, stdv, out, n, h * w, z);
 }

@@ -38,6 +38,7 @@ Models (weights + C descriptors) are Python objects that own device memory; oper
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import threading
 import time
 import weakref
@@ -54,9 +55,12 @@ NAMESPACE = "sf_hip"
 _MODELS: "weakref.WeakValueDictionary[int, object]" = weakref.WeakValueDictionary()
 
 
+_HANDLES = itertools.count(1)   # never reused: a freed model's handle stays unregistered (id(obj) could come back as a new object's)
+
+
 def register_model(obj) -> int:
     """Handle of a model object (CausalWanModel / WanVAEDecoder / UMT5Encoder) for the operators that need its weights."""
-    h = id(obj)
+    h = next(_HANDLES)
     _MODELS[h] = obj
     return h
 

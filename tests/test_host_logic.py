@@ -536,6 +536,28 @@ def test_torch_custom_ops_have_fake_implementations():
         assert tuple(t.shape) == (2, 512, 4096) and t.dtype == torch.bfloat16
 
 
+def test_model_handles_are_never_reused():
+    """Two models get distinct handles; a freed model's handle raises and is not handed to a later model."""
+    import gc
+
+    class _Stub:
+        pass
+    first, second = _Stub(), _Stub()
+    h1, h2 = sfa.torch_ops.register_model(first), sfa.torch_ops.register_model(second)
+    assert h1 != h2
+    assert sfa.torch_ops._model(h1) is first and sfa.torch_ops._model(h2) is second
+    del first
+    gc.collect()
+    with pytest.raises(RuntimeError, match="not registered"):
+        sfa.torch_ops._model(h1)
+    later = [_Stub() for _ in range(64)]          # one of these may well take the freed object's address
+    handles = [sfa.torch_ops.register_model(m) for m in later]
+    assert h1 not in handles and h2 not in handles and len(set(handles)) == len(handles)
+    with pytest.raises(RuntimeError, match="not registered"):
+        sfa.torch_ops._model(h1)
+    assert sfa.torch_ops._model(h2) is second
+
+
 def test_torch_custom_ops_refuse_cpu_tensors():
     x = torch.zeros(4, 64, dtype=torch.bfloat16)
     with pytest.raises(ValueError, match="CUDA"):
