@@ -63,6 +63,28 @@ __device__ __forceinline__ void fold_of_sample(const AttP& p, int b, int& lk, fl
   }
 }
 
+// What a workgroup works on: the base pointers of its (batch, head), its sample b (for fold_of_sample) and query tile.
+struct AttWork {
+  const bf16_t *qbase, *kbase, *vbase;
+  bf16_t* obase;
+  int b, qt;
+};
+
+__device__ __forceinline__ AttWork att_work(const AttP& p, int bh, int qt) {
+  const int b = bh / p.H, head = bh - b * p.H;
+  return {p.q + (long)b * p.q_bstride + head * HD, p.k + (long)b * p.kv_bstride + head * HD,
+          p.v + (long)b * p.kv_bstride + head * HD, p.o + (long)b * p.o_bstride + head * HD, b, qt};
+}
+
+// The w4 / w8 kernels' workgroup -> (batch * head, query tile): XCD-aware bijective remap so that workgroups on one XCD
+// share (batch, head) -> K/V hit in L2.
+__device__ __forceinline__ AttWork att_work_of_wg(const AttP& p) {
+  const int nwg = gridDim.x, bid = blockIdx.x;
+  const int wg = sf_xcd_remap(bid, nwg);
+  const int bh = wg / p.q_tiles, qt = wg - bh * p.q_tiles;
+  return att_work(p, bh, qt);
+}
+
 __device__ __forceinline__ int lds_off(int row, int ch) {
   return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
 }
@@ -71,6 +93,36 @@ typedef __attribute__((address_space(3))) bf16x4* lds_bf16x4_ptr;
 
 __device__ __forceinline__ bf16x4 lds_tr_read(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(p));
+}
+
+// The buffer descriptor of one (batch, head) K or V slab of `bytes` bytes, for LDS-DMA from inline asm: rows past the
+// sample's key count fall outside its range and read as zero.
+__device__ __forceinline__ u32x4 make_srd(const bf16_t* base, unsigned bytes) {
+  const unsigned long long a64 = (unsigned long long)base;
+  u32x4 d;
+  d[0] = __builtin_amdgcn_readfirstlane((unsigned)a64);
+  d[1] = __builtin_amdgcn_readfirstlane((unsigned)(a64 >> 32) & 0xFFFFu);
+  d[2] = __builtin_amdgcn_readfirstlane(bytes);
+  d[3] = 0x00020000u;
+  return d;
+}
+
+// Narrow store epilogue: the lane's own 8-byte pieces O[q][32 db + 8 rg + 4 hh .. + 3] = O^T / l of query row qrow
+// (nothing for rows past Lq).  ACC: out = bf16(float(out) + O / l): read, add, write.
+template <bool ACC>
+__device__ __forceinline__ void store_narrow(const AttP& p, bf16_t* obase, int qrow, int hh, const f32x16 (&o_acc)[4], float inv) {
+  if (qrow >= p.Lq) return;
+  bf16_t* op = obase + (long)qrow * p.o_stride + 4 * hh;
+#pragma unroll
+  for (int db = 0; db < 4; ++db)
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) {
+      bf16x4 w;
+      if (ACC) w = *reinterpret_cast<const bf16x4*>(op + db * 32 + rg * 8);   // this lane's own 8 bytes: read, add, write
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w[j] = (bf16_t)(ACC ? (float)w[j] + o_acc[db][4 * rg + j] * inv : o_acc[db][4 * rg + j] * inv);
+      *reinterpret_cast<bf16x4*>(op + db * 32 + rg * 8) = w;
+    }
 }
 
 // KIND only gives self-attention (0: keys = the KV cache) and cross-attention (1: keys = the text
@@ -85,28 +137,19 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // XCD-aware bijective remap so that workgroups on one XCD share (batch, head) -> K/V hit in L2.
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int wg = sf_xcd_remap(bid, nwg);
-  const int bh = wg / p.q_tiles, qt = wg - bh * p.q_tiles;
-  const int b = bh / p.H, head = bh - b * p.H;
-
-  const bf16_t* qbase = p.q + (long)b * p.q_bstride + head * HD;
-  const bf16_t* kbase = p.k + (long)b * p.kv_bstride + head * HD;
-  const bf16_t* vbase = p.v + (long)b * p.kv_bstride + head * HD;
-  bf16_t* obase = p.o + (long)b * p.o_bstride + head * HD;
+  const AttWork w = att_work_of_wg(p);
   int lk;
   float wl;
-  fold_of_sample(p, b, lk, wl);
+  fold_of_sample(p, w.b, lk, wl);
 
   const int r32 = lane & 31, hh = lane >> 5;
-  const int qrow = qt * QT + wave * 32 + r32;
+  const int qrow = w.qt * QT + wave * 32 + r32;
   const int qrow_c = min(qrow, p.Lq - 1);
 
   // ---- Q fragments (B operand of S^T = K . Q^T): lane holds Q[q][16 s + 8 hh + j]
   bf16x8 qf[8];
   {
-    const bf16_t* qp = qbase + (long)qrow_c * p.q_stride + 8 * hh;
+    const bf16_t* qp = w.qbase + (long)qrow_c * p.q_stride + 8 * hh;
 #pragma unroll
     for (int s = 0; s < 8; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
   }
@@ -123,8 +166,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
   // read as zero (no clamping, no per-tile address arithmetic).  The range of one (batch, head)
   // slab is (Lk-1) * stride + 128 elements < 2^31 bytes (checked on the host).
   const unsigned kv_bytes = (unsigned)(((long)(lk - 1) * p.kv_stride + HD) * 2);
-  const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(kbase), 0, kv_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(vbase), 0, kv_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(w.kbase), 0, kv_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(w.vbase), 0, kv_bytes, 0x00020000);
   unsigned st_goff[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) st_goff[i] = (unsigned)(((long)(st_row + 16 * i) * p.kv_stride + st_ch * 8) * 2);
@@ -306,21 +349,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(AttP p) {
   // ---- epilogue: O[q][d] = O^T[d][q] / l
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = 1.0f / l_tot;
-  if (qrow < p.Lq) {
-    bf16_t* op = obase + (long)qrow * p.o_stride + 4 * hh;
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        bf16x4 w;
-        if (ACC) w = *reinterpret_cast<const bf16x4*>(op + db * 32 + rg * 8);   // this lane's own 8 bytes: read, add, write
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = (bf16_t)(ACC ? (float)w[j] + o_acc[db][4 * rg + j] * inv : o_acc[db][4 * rg + j] * inv);
-        *reinterpret_cast<bf16x4*>(op + db * 32 + rg * 8) = w;
-      }
-  }
+  store_narrow<ACC>(p, w.obase, qrow, hh, o_acc, inv);
 }
-
 
 // ------------------------------------------------------------------------------------------
 // 8-wave structure (used when it fills the chip): ONE workgroup per CU = 256 query rows of one
@@ -362,26 +392,18 @@ __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = wave >> 2;  // 0 = A, 1 = B
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int wg = sf_xcd_remap(bid, nwg);
-  const int bh = wg / p.q_tiles, qt = wg - bh * p.q_tiles;
-  const int b = bh / p.H, head = bh - b * p.H;
-
-  const bf16_t* qbase = p.q + (long)b * p.q_bstride + head * HD;
-  const bf16_t* kbase = p.k + (long)b * p.kv_bstride + head * HD;
-  const bf16_t* vbase = p.v + (long)b * p.kv_bstride + head * HD;
-  bf16_t* obase = p.o + (long)b * p.o_bstride + head * HD;
+  const AttWork w = att_work_of_wg(p);
   int lk;
   float wl;
-  fold_of_sample(p, b, lk, wl);
+  fold_of_sample(p, w.b, lk, wl);
 
   const int r32 = lane & 31, hh = lane >> 5;
-  const int qrow = qt * QT8 + wave * 32 + r32;
+  const int qrow = w.qt * QT8 + wave * 32 + r32;
   const int qrow_c = min(qrow, p.Lq - 1);
 
   bf16x8 qf[8];
   {
-    const bf16_t* qp = qbase + (long)qrow_c * p.q_stride + 8 * hh;
+    const bf16_t* qp = w.qbase + (long)qrow_c * p.q_stride + 8 * hh;
 #pragma unroll
     for (int s = 0; s < 8; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
   }
@@ -393,16 +415,7 @@ __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
   // hipcc puts `s_waitcnt vmcnt(0)` in front of every later ds_read (it cannot tell the buffers apart).
   // No staging registers, no ds_write; completion = one vmcnt(0) before the barrier of the next step.
   const unsigned kv_bytes = (unsigned)(((long)(lk - 1) * p.kv_stride + HD) * 2);
-  auto make_srd = [&](const bf16_t* base) {
-    const unsigned long long a64 = (unsigned long long)base;
-    u32x4 d;
-    d[0] = __builtin_amdgcn_readfirstlane((unsigned)a64);
-    d[1] = __builtin_amdgcn_readfirstlane((unsigned)(a64 >> 32) & 0xFFFFu);
-    d[2] = __builtin_amdgcn_readfirstlane(kv_bytes);
-    d[3] = 0x00020000u;
-    return d;
-  };
-  const u32x4 k_srd = make_srd(kbase), v_srd = make_srd(vbase);
+  const u32x4 k_srd = make_srd(w.kbase, kv_bytes), v_srd = make_srd(w.vbase, kv_bytes);
   unsigned dma_off[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -656,9 +669,9 @@ __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
   // lane l + 32 the odd one -- 8 x dwordx4 per lane instead of 16 x dwordx2 (the store tail of an attention epilogue is
   // issue-bound: cdna_hip_programming.md T21).  Validity is per query row, i.e. the same for both lanes of a pair.
   // (the accumulate epilogue adds in fp32 BEFORE the rounding, i.e. in the lanes' own 8-byte layout: it takes the narrow path)
-  const bool wide = !ACC && (((uintptr_t)obase | (uintptr_t)(p.o_stride * 2)) & 15) == 0;
+  const bool wide = !ACC && (((uintptr_t)w.obase | (uintptr_t)(p.o_stride * 2)) & 15) == 0;
   if (wide) {
-    bf16_t* op = obase + (long)min(qrow, p.Lq - 1) * p.o_stride + 8 * hh;
+    bf16_t* op = w.obase + (long)min(qrow, p.Lq - 1) * p.o_stride + 8 * hh;
 #pragma unroll
     for (int db = 0; db < 4; ++db)
 #pragma unroll
@@ -676,22 +689,10 @@ __global__ __launch_bounds__(ATT8_THREADS, 2) void attention_w8_kernel(AttP p) {
         const u32x4 v = {s0[0], s1[0], s0[1], s1[1]};
         if (qrow < p.Lq) *reinterpret_cast<u32x4*>(op + db * 32 + pr * 16) = v;
       }
-  } else if (qrow < p.Lq) {
-    bf16_t* op = obase + (long)qrow * p.o_stride + 4 * hh;
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        bf16x4 w;
-        if (ACC) w = *reinterpret_cast<const bf16x4*>(op + db * 32 + rg * 8);   // this lane's own 8 bytes: read, add, write
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = (bf16_t)(ACC ? (float)w[j] + o_acc[db][4 * rg + j] * inv : o_acc[db][4 * rg + j] * inv);
-        *reinterpret_cast<bf16x4*>(op + db * 32 + rg * 8) = w;
-      }
+  } else {
+    store_narrow<ACC>(p, w.obase, qrow, hh, o_acc, inv);
   }
 }
-
-
 
 // ------------------------------------------------------------------------------------------
 // 64 query rows per wave, one wave per SIMD, hand-scheduled: the C++ below only computes the per-lane
@@ -733,14 +734,10 @@ __global__ __launch_bounds__(256) void attention_r64_kernel(AttP p) {
     bh = 8 * f + g / Q;
     qt = g - (g / Q) * Q;
   }
-  const int b = bh / p.H, head = bh - b * p.H;
-  const bf16_t* qbase = p.q + (long)b * p.q_bstride + head * HD;
-  const bf16_t* kbase = p.k + (long)b * p.kv_bstride + head * HD;
-  const bf16_t* vbase = p.v + (long)b * p.kv_bstride + head * HD;
-  bf16_t* obase = p.o + (long)b * p.o_bstride + head * HD;
+  const AttWork w = att_work(p, bh, qt);
   int lk_b;
   float wl;
-  fold_of_sample(p, b, lk_b, wl);
+  fold_of_sample(p, w.b, lk_b, wl);
 
   const int r32 = lane & 31, hh = lane >> 5;
   const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem;
@@ -767,10 +764,10 @@ __global__ __launch_bounds__(256) void attention_r64_kernel(AttP p) {
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
       const int qrow = qt * QT64 + wave * 64 + qb * 32 + r32;
-      const unsigned long long qa = (unsigned long long)(qbase + (long)min(qrow, p.Lq - 1) * p.q_stride + 8 * hh);
+      const unsigned long long qa = (unsigned long long)(w.qbase + (long)min(qrow, p.Lq - 1) * p.q_stride + 8 * hh);
       // (the epilogue regroups a lane pair's two 8-byte halves into 16-byte stores: lane l writes the even 16-byte group,
       // lane l + 32 the odd one)
-      const unsigned long long oa = (unsigned long long)(obase + (long)min(qrow, p.Lq - 1) * p.o_stride + 8 * hh);
+      const unsigned long long oa = (unsigned long long)(w.obase + (long)min(qrow, p.Lq - 1) * p.o_stride + 8 * hh);
       prm[20 + 2 * qb] = (unsigned)qa; prm[21 + 2 * qb] = (unsigned)(qa >> 32);
       prm[24 + 2 * qb] = (unsigned)oa; prm[25 + 2 * qb] = (unsigned)(oa >> 32);
       prm[29 + qb] = qrow < p.Lq ? 1u : 0u;
@@ -782,16 +779,7 @@ __global__ __launch_bounds__(256) void attention_r64_kernel(AttP p) {
   for (int j = 0; j < SF_R64_N_PARAM; ++j) pl[j * 256 + tid] = prm[j];
 
   const unsigned kv_bytes = (unsigned)(((long)(lk_b - 1) * p.kv_stride + HD) * 2);
-  auto make_srd = [&](const bf16_t* base) {
-    const unsigned long long a64 = (unsigned long long)base;
-    u32x4 d;
-    d[0] = __builtin_amdgcn_readfirstlane((unsigned)a64);
-    d[1] = __builtin_amdgcn_readfirstlane((unsigned)(a64 >> 32) & 0xFFFFu);
-    d[2] = __builtin_amdgcn_readfirstlane(kv_bytes);
-    d[3] = 0x00020000u;
-    return d;
-  };
-  const u32x4 k_srd = make_srd(kbase), v_srd = make_srd(vbase);
+  const u32x4 k_srd = make_srd(w.kbase, kv_bytes), v_srd = make_srd(w.vbase, kv_bytes);
   const unsigned tile_bytes = __builtin_amdgcn_readfirstlane((unsigned)((long)KT * p.kv_stride * 2));
   const int ntiles = __builtin_amdgcn_readfirstlane((lk_b + KT - 1) / KT);
   const int lk = __builtin_amdgcn_readfirstlane(lk_b);
@@ -806,9 +794,16 @@ __global__ __launch_bounds__(256) void attention_r64_kernel(AttP p) {
                : SF_R64_CLOBBERS);
 }
 
-
-
 }  // namespace
+
+// Picks a structure's KIND (see attention_kernel) and launches it: launch(std::integral_constant<int, KIND>{}).
+template <bool HAS_ACCUM, class L>
+static int launch_kind(bool accum, int Lk, L&& launch) {
+  if constexpr (HAS_ACCUM)
+    if (accum) return launch(std::integral_constant<int, 2>{});
+  if (Lk > 1024) return launch(std::integral_constant<int, 0>{});
+  return launch(std::integral_constant<int, 1>{});
+}
 
 // accum: out += the attention (KIND 2 of the W4 / W8 kernels) instead of out = the attention
 static int attention_launch(const void* q, const void* k, const void* v, void* out, int B, int H, int Lq,
@@ -851,22 +846,23 @@ static int attention_launch(const void* q, const void* k, const void* v, void* o
     SF_CHECK(out16, "sf_attention: the r64 structure needs 16-byte aligned output rows (out %% 16, o_stride %% 8, o_bstride %% 8)");
     p.q_tiles = (Lq + QT64 - 1) / QT64;
     const dim3 grid((unsigned)nwg64), block(256);
-    if (Lk > 1024) return sf_launch<&attention_r64_kernel<0>, ATT64_LDS>("sf_attention", grid, block, ATT64_LDS, s, p);
-    return sf_launch<&attention_r64_kernel<1>, ATT64_LDS>("sf_attention", grid, block, ATT64_LDS, s, p);
+    return launch_kind<false>(accum, Lk, [&](auto kind) {
+      return sf_launch<&attention_r64_kernel<decltype(kind)::value>, ATT64_LDS>("sf_attention", grid, block, ATT64_LDS, s, p);
+    });
   }
   if (structure == SF_ATTN_W8) {
     p.q_tiles = (Lq + QT8 - 1) / QT8;
     const dim3 grid((unsigned)nwg8), block(ATT8_THREADS);
-    if (accum) return sf_launch<&attention_w8_kernel<2>>("sf_attention", grid, block, ATT8_LDS, s, p);
-    if (Lk > 1024) return sf_launch<&attention_w8_kernel<0>>("sf_attention", grid, block, ATT8_LDS, s, p);
-    return sf_launch<&attention_w8_kernel<1>>("sf_attention", grid, block, ATT8_LDS, s, p);
+    return launch_kind<true>(accum, Lk, [&](auto kind) {
+      return sf_launch<&attention_w8_kernel<decltype(kind)::value>>("sf_attention", grid, block, ATT8_LDS, s, p);
+    });
   }
   const long nwg = (long)p.q_tiles * H * B;
   SF_CHECK(nwg < (1L << 30), "sf_attention: grid too large");
   const dim3 grid((unsigned)nwg), block(ATT_THREADS);
-  if (accum) return sf_launch<&attention_kernel<2>>("sf_attention", grid, block, ATT_LDS, s, p);
-  if (Lk > 1024) return sf_launch<&attention_kernel<0>>("sf_attention", grid, block, ATT_LDS, s, p);
-  return sf_launch<&attention_kernel<1>>("sf_attention", grid, block, ATT_LDS, s, p);
+  return launch_kind<true>(accum, Lk, [&](auto kind) {
+    return sf_launch<&attention_kernel<decltype(kind)::value>>("sf_attention", grid, block, ATT_LDS, s, p);
+  });
 }
 
 extern "C" int sf_attention(const sf_attention_args* a, void* stream) {

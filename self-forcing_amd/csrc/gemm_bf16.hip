@@ -82,14 +82,37 @@ __device__ __forceinline__ void fp8_scale_acc(const GemmP& p, f32x4 (&acc)[MT][4
   }
 }
 
-// Epilogue arithmetic on the 4 consecutive output columns a lane owns of row m: bias, GELU, gate, residual.
-template <int EPI>
-__device__ __forceinline__ bf16x4 epi_apply(const GemmP& p, const f32x4& a4, int m, int n, const bf16_t* e0row) {
+// Workgroup -> output tile (tm, tn).  XCD-aware bijective remap: blocks b and b+8 share an XCD (round-robin dispatch),
+// so give each XCD a contiguous range of tiles -> neighbouring tiles (same A rows / same W panel) share one L2.
+// Grouped order on top of the XCD remap: consecutive workgroups (which run concurrently on one
+// XCD and advance through K in step) cover GROUP_M row tiles x a run of column tiles, so both the
+// A panel and the W tiles they stream are shared in that XCD's L2.  Row-major tile order made
+// every sweep of a row re-read the whole weight matrix: 1.05 GB fetched for the 1.3B ffn.0 GEMM
+// (FETCH_SIZE x 2) against 126 MB of operands + output.  Placement affects speed only.
+template <int GROUP_M>
+__device__ __forceinline__ void gemm_tile_of(const GemmP& p, int& tm, int& tn) {
+  const int nwg = gridDim.x, bid = blockIdx.x;
+  const int wg = sf_xcd_remap(bid, nwg);
+  const int width = GROUP_M * p.tiles_n;
+  const int group = wg / width, first_m = group * GROUP_M;
+  const int gsz = min(p.tiles_m - first_m, GROUP_M);
+  const int in_group = wg - group * width;
+  tm = first_m + in_group % gsz;
+  tn = in_group / gsz;
+}
+
+// Epilogue arithmetic on the 4 consecutive output columns a lane owns of one row: bias, GELU, gate, residual, one
+// rounding.  `ops` hands out the operands where the arithmetic asks for them, by one of two strategies:
+//   EpiLoads  direct loads per piece (gemm_epilogue); without a bias the add is skipped;
+//   EpiRegs   operands requested first and already in registers (gemm_epilogue_lds); without a bias a zero vector is
+//             added (the two differ for an accumulator of -0.0).
+template <int EPI, class Ops>
+__device__ __forceinline__ bf16x4 epi_math(const f32x4& a4, const Ops& ops) {
   float y[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) y[j] = a4[j];
-  if (p.bias) {
-    const bf16x4 b = *reinterpret_cast<const bf16x4*>(p.bias + n);
+  if (ops.has_bias()) {
+    const bf16x4 b = ops.bias();
 #pragma unroll
     for (int j = 0; j < 4; ++j) y[j] += (float)b[j];
   }
@@ -98,13 +121,13 @@ __device__ __forceinline__ bf16x4 epi_apply(const GemmP& p, const f32x4& a4, int
     for (int j = 0; j < 4; ++j) y[j] = gelu_tanh_f(y[j]);
   }
   if (EPI == SF_EPI_BIAS_GATE_RESID) {
-    const bf16x4 gm = *reinterpret_cast<const bf16x4*>(p.gate_mod + n);
-    const bf16x4 ge = *reinterpret_cast<const bf16x4*>(e0row + n);
+    const bf16x4 gm = ops.gate_mod();
+    const bf16x4 ge = ops.gate_e0();
 #pragma unroll
     for (int j = 0; j < 4; ++j) y[j] *= (float)(bf16_t)((float)gm[j] + (float)ge[j]);
   }
   if (EPI == SF_EPI_BIAS_RESID || EPI == SF_EPI_BIAS_GATE_RESID) {
-    const bf16x4 rv = *reinterpret_cast<const bf16x4*>(p.resid + (long)m * p.ldr + n);
+    const bf16x4 rv = ops.resid();
 #pragma unroll
     for (int j = 0; j < 4; ++j) y[j] += (float)rv[j];
   }
@@ -113,6 +136,26 @@ __device__ __forceinline__ bf16x4 epi_apply(const GemmP& p, const f32x4& a4, int
   for (int j = 0; j < 4; ++j) o[j] = (bf16_t)y[j];
   return o;
 }
+
+struct EpiLoads {
+  const GemmP& p;
+  int m, n;
+  const bf16_t* e0row;
+  __device__ __forceinline__ bool has_bias() const { return p.bias != nullptr; }
+  __device__ __forceinline__ bf16x4 bias() const { return *reinterpret_cast<const bf16x4*>(p.bias + n); }
+  __device__ __forceinline__ bf16x4 gate_mod() const { return *reinterpret_cast<const bf16x4*>(p.gate_mod + n); }
+  __device__ __forceinline__ bf16x4 gate_e0() const { return *reinterpret_cast<const bf16x4*>(e0row + n); }
+  __device__ __forceinline__ bf16x4 resid() const { return *reinterpret_cast<const bf16x4*>(p.resid + (long)m * p.ldr + n); }
+};
+
+struct EpiRegs {
+  bf16x4 b, gm, ge, rv;
+  __device__ __forceinline__ bool has_bias() const { return true; }
+  __device__ __forceinline__ bf16x4 bias() const { return b; }
+  __device__ __forceinline__ bf16x4 gate_mod() const { return gm; }
+  __device__ __forceinline__ bf16x4 gate_e0() const { return ge; }
+  __device__ __forceinline__ bf16x4 resid() const { return rv; }
+};
 
 // Direct epilogue: the lane holds out[m][n .. n+3] for each (mt, nt) of its wave's sub-tile
 // (m = mrow + 16 mt, n = ncol + 16 nt) and stores them as they are (8-byte pieces).
@@ -132,33 +175,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[MT][4
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + (long)m * p.ldo + n) = acc[mt][nt];
         continue;
       }
-      *reinterpret_cast<bf16x4*>(p.out + (long)m * p.ldo + n) = epi_apply<EPI>(p, acc[mt][nt], m, n, e0row);
+      *reinterpret_cast<bf16x4*>(p.out + (long)m * p.ldo + n) = epi_math<EPI>(acc[mt][nt], EpiLoads{p, m, n, e0row});
     }
   }
-}
-
-// Epilogue arithmetic on operands that are already in registers (see gemm_epilogue_lds).
-template <int EPI>
-__device__ __forceinline__ bf16x4 epi_math(const f32x4& a4, const bf16x4& b, const bf16x4& gm, const bf16x4& ge, const bf16x4& rv) {
-  float y[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) y[j] = a4[j] + (float)b[j];
-  if (EPI == SF_EPI_BIAS_GELU) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = gelu_tanh_f(y[j]);
-  }
-  if (EPI == SF_EPI_BIAS_GATE_RESID) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] *= (float)(bf16_t)((float)gm[j] + (float)ge[j]);
-  }
-  if (EPI == SF_EPI_BIAS_RESID || EPI == SF_EPI_BIAS_GATE_RESID) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] += (float)rv[j];
-  }
-  bf16x4 o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = (bf16_t)y[j];
-  return o;
 }
 
 // Epilogue through LDS: the wave's (16 MT) x 64 sub-tile is written to its own LDS region as bf16 rows of
@@ -214,7 +233,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmP& p, f32x4 (&acc)[M
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) {
         const int col = nt * 16 + cg * 4;                     // 0..63 within the wave's columns
-        const bf16x4 o = epi_math<EPI>(acc[m0 + i][nt], bias_v[nt], gm_v[nt], ge[i][nt], rv[i][nt]);
+        const bf16x4 o = epi_math<EPI>(acc[m0 + i][nt], EpiRegs{bias_v[nt], gm_v[nt], ge[i][nt], rv[i][nt]});
         const int chunk = (col >> 3) ^ (row & 7);
         *reinterpret_cast<bf16x4*>(wbuf + row * 128 + (chunk << 4) + (col & 4) * 2) = o;
       }
@@ -238,28 +257,14 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(GemmP p) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // XCD-aware bijective remap: blocks b and b+8 share an XCD (round-robin dispatch), so give
-  // each XCD a contiguous range of tiles -> neighbouring tiles (same A rows / same W panel)
-  // share one L2.  Placement affects speed only.
   if (blockIdx.y) {   // batched launch (per-head products of the text encoder): same tile grid per batch entry
     const long bz = blockIdx.y;
     p.a += bz * p.a_bs; p.w += bz * p.w_bs;
     if (EPI == SF_EPI_F32) p.out = reinterpret_cast<bf16_t*>(reinterpret_cast<float*>(p.out) + bz * p.o_bs); else p.out += bz * p.o_bs;
     if (p.resid) p.resid += bz * p.r_bs;
   }
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int wg = sf_xcd_remap(bid, nwg);
-  // Grouped order on top of the XCD remap: consecutive workgroups (which run concurrently on one
-  // XCD and advance through K in step) cover GROUP_M row tiles x a run of column tiles, so both the
-  // A panel and the W tiles they stream are shared in that XCD's L2.  Row-major tile order made
-  // every sweep of a row re-read the whole weight matrix: 1.05 GB fetched for the 1.3B ffn.0 GEMM
-  // (FETCH_SIZE x 2) against 126 MB of operands + output.
-  constexpr int GROUP_M = 8;
-  const int width = GROUP_M * p.tiles_n;
-  const int group = wg / width, first_m = group * GROUP_M;
-  const int gsz = min(p.tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * width;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
+  int tm, tn;
+  gemm_tile_of<8>(p, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
 
   // ---- staging addresses: wave w issues 4 A pieces + 4 W pieces of 1 KiB (8 rows x 128 B) each
@@ -427,6 +432,41 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(GemmP p) {
 // after the last request has landed everywhere and nothing is requested after it (the third bullet above).
 constexpr int PP_THREADS = 512;
 
+// ---- building blocks of both ping-pong schedules
+// The end of a load segment: the wave's fragment reads are retired before the barrier that ends the interval.
+__device__ __forceinline__ void pp_end_load_segment() {
+  __builtin_amdgcn_s_waitcnt(0xc07f);               // lgkmcnt(0): this wave's fragment reads are retired
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// One MFMA cluster, from registers: NQ row tiles (accumulator rows R0 .. R0 + NQ - 1, A fragments af[0 .. NQ - 1]) x the
+// column tiles c0, c0 + 1 x 2 sub-steps of 32 (bf16) or one scaled MFMA (F8), and the barrier that ends its interval.
+template <bool F8, int R0, int NQ, int MT, int NA>
+__device__ __forceinline__ void pp_cluster(f32x4 (&acc)[MT][4], const bf16x8 (&af)[NA][2], const bf16x8 (&bfr)[4][2], int c0) {
+  __builtin_amdgcn_s_setprio(1);
+  if constexpr (F8) {
+#pragma unroll
+    for (int mt = 0; mt < NQ; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+        acc[R0 + mt][c0 + nt] = mfma_f8(bfr[c0 + nt][0], bfr[c0 + nt][1], af[mt][0], af[mt][1], acc[R0 + mt][c0 + nt]);
+  } else {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int mt = 0; mt < NQ; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+          acc[R0 + mt][c0 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[c0 + nt][ks], af[mt][ks], acc[R0 + mt][c0 + nt], 0, 0, 0);
+  }
+  __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+
 template <int MT>   // M tiles of 16 rows per wave: 8 (256-row workgroup tile), 7 (224), 6 (192)
 struct PPCfg {
   static constexpr int BM = 32 * MT;
@@ -448,14 +488,8 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp_kernel(GemmP p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave >> 2, wc = wave & 3;          // grp: M half of the tile = which of the two staggered wave groups
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int wg = sf_xcd_remap(bid, nwg);
-  constexpr int GROUP_M = MT >= 6 ? 4 : 8;
-  const int width = GROUP_M * p.tiles_n;
-  const int group = wg / width, first_m = group * GROUP_M;
-  const int gsz = min(p.tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * width;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
+  int tm, tn;
+  gemm_tile_of<(MT >= 6 ? 4 : 8)>(p, tm, tn);
   const int m0 = tm * BMp, n0 = tn * 256;
 
   // ---- LDS-DMA source addresses: a piece = 8 rows x 128 B; half-tile h of A = rows [h BM/2, (h+1) BM/2), of B =
@@ -504,7 +538,7 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp_kernel(GemmP p) {
   bf16x8 af[HQA][2], bfr[4][2];
 
 #ifdef SF_STAMP   // diagnostic build (tools/probes/gemm_stamp.py): where a tile's time goes; stamps go to a buffer of their own
-  unsigned long long* stamp = (EPI == SF_EPI_BIAS && p.gate_e0) ? reinterpret_cast<unsigned long long*>(const_cast<bf16_t*>(p.gate_e0)) + ((long)bid * 2 + grp) * 8 : nullptr;
+  unsigned long long* stamp = (EPI == SF_EPI_BIAS && p.gate_e0) ? reinterpret_cast<unsigned long long*>(const_cast<bf16_t*>(p.gate_e0)) + ((long)blockIdx.x * 2 + grp) * 8 : nullptr;
   if (stamp && (tid & 255) == 0) { stamp[0] = __builtin_amdgcn_s_memtime(); stamp[4] = __builtin_amdgcn_s_memrealtime(); }
 #endif
   const int nk = p.K / BK;
@@ -518,34 +552,10 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp_kernel(GemmP p) {
 #endif
   if (grp == 1) __builtin_amdgcn_s_barrier();       // the second wave group runs one interval behind the first
 
-  auto end_load_segment = [&]() {
-    __builtin_amdgcn_s_waitcnt(0xc07f);             // lgkmcnt(0): this wave's fragment reads are retired
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto cluster = [&](auto qc, int c0) {             // one quarter: HQA / HQB row tiles x 2 column tiles x 2 sub-steps of 32
-    constexpr int q = decltype(qc)::value, NQ = q == 0 ? HQA : HQB;
-    __builtin_amdgcn_s_setprio(1);
-    if constexpr (F8) {
-#pragma unroll
-      for (int mt = 0; mt < NQ; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-          acc[q * HQA + mt][c0 + nt] = mfma_f8(bfr[c0 + nt][0], bfr[c0 + nt][1], af[mt][0], af[mt][1], acc[q * HQA + mt][c0 + nt]);
-    } else {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int mt = 0; mt < NQ; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < 2; ++nt)
-            acc[q * HQA + mt][c0 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[c0 + nt][ks], af[mt][ks], acc[q * HQA + mt][c0 + nt], 0, 0, 0);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+  // (the cluster is bound through a lambda: called directly from the phases, pp_cluster comes out with other registers)
+  auto cluster = [&](auto qc, int c0) {
+    constexpr int q = decltype(qc)::value;
+    pp_cluster<F8, q * HQA, q == 0 ? HQA : HQB>(acc, af, bfr, c0);
   };
   auto read_a = [&](const char* buf, auto qc) {
     constexpr int q = decltype(qc)::value, NQ = q == 0 ? HQA : HQB;
@@ -572,17 +582,17 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp_kernel(GemmP p) {
     read_a(buf, Q0);
     read_b(buf, 0);
     if (more1) dma_a(0, kt + 1);
-    end_load_segment();
+    pp_end_load_segment();
     cluster(Q0, 0);
     // phase 1
     read_b(buf, 2);
     if (more1) dma_a(1, kt + 1);
-    end_load_segment();
+    pp_end_load_segment();
     cluster(Q0, 2);
     // phase 2
     read_a(buf, Q1);
     if (more2) dma_b(0, kt + 2);
-    end_load_segment();
+    pp_end_load_segment();
     cluster(Q1, 2);
     // phase 3: everything but the two half-tiles of B(kt + 2) must have landed before the next tile's first reads
     if (more2) {
@@ -591,7 +601,7 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp_kernel(GemmP p) {
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    end_load_segment();
+    pp_end_load_segment();
     cluster(Q1, 0);
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();       // pairs with the extra barrier of the second group: all clusters done
@@ -633,14 +643,8 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp2_kernel(GemmP p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave >> 2, wc = wave & 3;
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int wg = sf_xcd_remap(bid, nwg);
-  constexpr int GROUP_M = 8;
-  const int width = GROUP_M * p.tiles_n;
-  const int group = wg / width, first_m = group * GROUP_M;
-  const int gsz = min(p.tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * width;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
+  int tm, tn;
+  gemm_tile_of<8>(p, tm, tn);
   const int m0 = tm * 128, n0 = tn * 256;
 
   const bf16_t* a_src[2];
@@ -686,34 +690,7 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp2_kernel(GemmP p) {
   __builtin_amdgcn_s_barrier();
   if (grp == 1) __builtin_amdgcn_s_barrier();
 
-  auto end_load_segment = [&]() {
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto cluster = [&](int c0) {
-    __builtin_amdgcn_s_setprio(1);
-    if constexpr (F8) {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-          acc[mt][c0 + nt] = mfma_f8(bfr[c0 + nt][0], bfr[c0 + nt][1], af[mt][0], af[mt][1], acc[mt][c0 + nt]);
-    } else {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < 2; ++nt)
-            acc[mt][c0 + nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[c0 + nt][ks], af[mt][ks], acc[mt][c0 + nt], 0, 0, 0);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
+  auto cluster = [&](int c0) { pp_cluster<F8, 0, 4>(acc, af, bfr, c0); };
 
   int slot = 0;                       // kt % 3
   for (int kt = 0; kt < nk; ++kt) {
@@ -731,7 +708,7 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp2_kernel(GemmP p) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) bfr[nt][ks] = *reinterpret_cast<const bf16x8*>(bbuf + w_row_off + nt * 2048 + coff[ks]);
     if (more2) dma_a(nslot, kt + 2);
-    end_load_segment();
+    pp_end_load_segment();
     cluster(0);
     // phase 1
 #pragma unroll
@@ -744,7 +721,7 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp2_kernel(GemmP p) {
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    end_load_segment();
+    pp_end_load_segment();
     cluster(2);
     slot = slot == 2 ? 0 : slot + 1;
   }
@@ -758,42 +735,49 @@ __global__ __launch_bounds__(PP_THREADS) void gemm_pp2_kernel(GemmP p) {
     gemm_epilogue<EPI, 4>(p, acc, m_base + (lane & 15), n_base + (lane >> 4) * 4);
 }
 
-template <int EPI, bool F8>
-int launch_pp2(GemmP& p, const char* name, hipStream_t s) {
-  p.tiles_m = (p.M + 127) / 128;
-  p.tiles_n = (p.N + 255) / 256;
-  return sf_launch<&gemm_pp2_kernel<EPI, F8>, PP2_LDS>(name, dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), PP2_LDS, s, p);
-}
-
-template <bool F8>
-int launch_pp2_epi(GemmP& p, int epilogue, const char* name, hipStream_t s) {
+// The one epilogue dispatcher: calls f(std::integral_constant<int, EPI>{}) for the bf16-output epilogue `epilogue`.
+template <class F>
+int with_epilogue(int epilogue, const char* name, F&& f) {
   switch (epilogue) {
-    case SF_EPI_BIAS: return launch_pp2<SF_EPI_BIAS, F8>(p, name, s);
-    case SF_EPI_BIAS_GELU: return launch_pp2<SF_EPI_BIAS_GELU, F8>(p, name, s);
-    case SF_EPI_BIAS_RESID: return launch_pp2<SF_EPI_BIAS_RESID, F8>(p, name, s);
-    case SF_EPI_BIAS_GATE_RESID: return launch_pp2<SF_EPI_BIAS_GATE_RESID, F8>(p, name, s);
+    case SF_EPI_BIAS: return f(std::integral_constant<int, SF_EPI_BIAS>{});
+    case SF_EPI_BIAS_GELU: return f(std::integral_constant<int, SF_EPI_BIAS_GELU>{});
+    case SF_EPI_BIAS_RESID: return f(std::integral_constant<int, SF_EPI_BIAS_RESID>{});
+    case SF_EPI_BIAS_GATE_RESID: return f(std::integral_constant<int, SF_EPI_BIAS_GATE_RESID>{});
     default: SF_CHECK(false, "%s: unknown epilogue %d", name, epilogue);
   }
-}
-
-template <int EPI, int MT, bool F8>
-int launch_pp(GemmP& p, const char* name, hipStream_t s) {
-  using Cfg = PPCfg<MT>;
-  p.tiles_m = (p.M + Cfg::BM - 1) / Cfg::BM;
-  p.tiles_n = (p.N + 255) / 256;
-  return sf_launch<&gemm_pp_kernel<EPI, MT, F8>, Cfg::LDS>(name, dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), Cfg::LDS, s, p);
 }
 
 template <int MT, bool F8>
-int launch_pp_epi(GemmP& p, int epilogue, const char* name, hipStream_t s) {
-  switch (epilogue) {
-    case SF_EPI_BIAS: return launch_pp<SF_EPI_BIAS, MT, F8>(p, name, s);
-    case SF_EPI_BIAS_GELU: return launch_pp<SF_EPI_BIAS_GELU, MT, F8>(p, name, s);
-    case SF_EPI_BIAS_RESID: return launch_pp<SF_EPI_BIAS_RESID, MT, F8>(p, name, s);
-    case SF_EPI_BIAS_GATE_RESID: return launch_pp<SF_EPI_BIAS_GATE_RESID, MT, F8>(p, name, s);
-    default: SF_CHECK(false, "%s: unknown epilogue %d", name, epilogue);
-  }
+int launch_pp(GemmP& p, int epilogue, const char* name, hipStream_t s) {
+  using Cfg = PPCfg<MT>;
+  p.tiles_m = (p.M + Cfg::BM - 1) / Cfg::BM;
+  p.tiles_n = (p.N + 255) / 256;
+  return with_epilogue(epilogue, name, [&](auto epi) {
+    return sf_launch<&gemm_pp_kernel<decltype(epi)::value, MT, F8>, Cfg::LDS>(name, dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), Cfg::LDS, s, p);
+  });
 }
+
+template <bool F8>
+int launch_pp2(GemmP& p, int epilogue, const char* name, hipStream_t s) {
+  p.tiles_m = (p.M + 127) / 128;
+  p.tiles_n = (p.N + 255) / 256;
+  return with_epilogue(epilogue, name, [&](auto epi) {
+    return sf_launch<&gemm_pp2_kernel<decltype(epi)::value, F8>, PP2_LDS>(name, dim3(p.tiles_m * p.tiles_n), dim3(PP_THREADS), PP2_LDS, s, p);
+  });
+}
+
+// The ping-pong structures, one row each: rows of the workgroup tile (x 256 columns, one workgroup per CU), the cost of
+// a k-loop relative to its rows (slightly worse for the smaller register tiles), the launcher.
+struct PPStructure {
+  int st, rows;
+  double rel;
+  int (*launch)(GemmP&, int, const char*, hipStream_t);
+};
+template <bool F8>
+constexpr PPStructure PP_STRUCTURES[] = {{SF_GEMM_PP256, 256, 1.00, launch_pp<8, F8>},
+                                         {SF_GEMM_PP224, 224, 1.02, launch_pp<7, F8>},
+                                         {SF_GEMM_PP192, 192, 1.05, launch_pp<6, F8>},
+                                         {SF_GEMM_PP128, 128, 1.14, launch_pp2<F8>}};
 
 // Argument checks shared by both entry points (`name` prefixes the messages); K is in elements of the operand type.
 int check_args(const sf_gemm_args* a, const char* name, int bk) {
@@ -829,41 +813,32 @@ int run_gemm(const sf_gemm_args* a, GemmP& p, const char* name, hipStream_t s) {
     // else: 128 x 128 tiles, two per CU.
     st = SF_GEMM_T128;
     if (pp_ok && a->M >= 1024 && a->N >= 1024 && a->K >= 512) {
-      static const struct { int st, rows; double rel; } cand[] = {
-          {SF_GEMM_PP256, 256, 1.00}, {SF_GEMM_PP224, 224, 1.02}, {SF_GEMM_PP192, 192, 1.05}, {SF_GEMM_PP128, 128, 1.14}};
       const long tn = (a->N + 255) / 256;
       double best = 1e30;
-      for (const auto& c : cand) {
+      for (const auto& c : PP_STRUCTURES<F8>) {
         const long tiles = (long)((a->M + c.rows - 1) / c.rows) * tn;
         const double cost = (double)((tiles + 255) / 256) * (c.rows / 256.0 * c.rel + 0.04);
         if (cost < best - 1e-9) { best = cost; st = c.st; }
       }
     }
   }
-  const bool is_pp = st == SF_GEMM_PP256 || st == SF_GEMM_PP224 || st == SF_GEMM_PP192 || st == SF_GEMM_PP128;
-  if (is_pp && !pp_ok) st = SF_GEMM_T128;
-  else if (is_pp)
-    return st == SF_GEMM_PP256 ? launch_pp_epi<8, F8>(p, a->epilogue, name, s)
-         : st == SF_GEMM_PP224 ? launch_pp_epi<7, F8>(p, a->epilogue, name, s)
-         : st == SF_GEMM_PP192 ? launch_pp_epi<6, F8>(p, a->epilogue, name, s) : launch_pp2_epi<F8>(p, a->epilogue, name, s);
+  if (pp_ok)   // (a ping-pong structure that cannot run this problem falls back to the 128 x 128 tiles)
+    for (const auto& c : PP_STRUCTURES<F8>)
+      if (c.st == st) return c.launch(p, a->epilogue, name, s);
   const int batch = a->batch > 1 ? a->batch : 1;
   p.a_bs = a->a_bstride; p.w_bs = a->w_bstride; p.o_bs = a->o_bstride; p.r_bs = a->r_bstride;
   SF_CHECK(batch == 1 || (a->a_bstride % 8 == 0 && a->w_bstride % 8 == 0 && a->o_bstride % 4 == 0 && a->r_bstride % 4 == 0),
            "%s: batch strides must keep 16-byte (operands) / 8-byte (output) alignment", name);
   const dim3 grid(p.tiles_m * p.tiles_n, batch), block(GEMM_THREADS);
-  switch (a->epilogue) {
-    case SF_EPI_BIAS: return sf_launch<&gemm_bf16_kernel<SF_EPI_BIAS, F8>>(name, grid, block, GEMM_LDS, s, p);
-    case SF_EPI_BIAS_GELU: return sf_launch<&gemm_bf16_kernel<SF_EPI_BIAS_GELU, F8>>(name, grid, block, GEMM_LDS, s, p);
-    case SF_EPI_BIAS_RESID: return sf_launch<&gemm_bf16_kernel<SF_EPI_BIAS_RESID, F8>>(name, grid, block, GEMM_LDS, s, p);
-    case SF_EPI_BIAS_GATE_RESID: return sf_launch<&gemm_bf16_kernel<SF_EPI_BIAS_GATE_RESID, F8>>(name, grid, block, GEMM_LDS, s, p);
-    case SF_EPI_F32:
-      if constexpr (F8) {
-        SF_CHECK(false, "%s: the raw fp32 epilogue is bf16-only", name);
-      } else {
-        SF_CHECK((uintptr_t)a->out % 16 == 0, "%s: fp32 output must be 16-byte aligned", name);
-        return sf_launch<&gemm_bf16_kernel<SF_EPI_F32, false>>(name, grid, block, GEMM_LDS, s, p);
-      }
-    default: SF_CHECK(false, "%s: unknown epilogue %d", name, a->epilogue);
+  if (a->epilogue != SF_EPI_F32)
+    return with_epilogue(a->epilogue, name, [&](auto epi) {
+      return sf_launch<&gemm_bf16_kernel<decltype(epi)::value, F8>>(name, grid, block, GEMM_LDS, s, p);
+    });
+  if constexpr (F8) {
+    SF_CHECK(false, "%s: the raw fp32 epilogue is bf16-only", name);
+  } else {
+    SF_CHECK((uintptr_t)a->out % 16 == 0, "%s: fp32 output must be 16-byte aligned", name);
+    return sf_launch<&gemm_bf16_kernel<SF_EPI_F32, false>>(name, grid, block, GEMM_LDS, s, p);
   }
 }
 

@@ -164,6 +164,47 @@ def test_gemm_every_structure(structure, M, N, K, epi):
     assert torch.equal(out, ops.gemm(ad, wd, bd, epilogue=epi, **kw))          # the automatic choice
 
 
+@pytest.fixture(scope="module")
+def direct_case():
+    """M, N, K = 300, 260, 128: two k-tiles (the ping-pong structures run it), two column tiles, ragged rows, and
+    N % 8 == 4, so every structure takes the direct (non-LDS) epilogue.  Inputs and the fp32 references, made once."""
+    M, N, K, groups = 300, 260, 128, 3
+    g = torch.Generator().manual_seed(M + N + K)
+    a, w, bias, resid = bf((M, K), g), bf((N, K), g, 1.0 / K ** 0.5), bf((N,), g, 0.5), bf((M, N), g)
+    gate_mod, e0 = bf((N,), g, 0.5), bf((groups, 6, N), g, 0.5)
+    y = a.float() @ w.float().t() + bias.float()
+    gate = (gate_mod.float()[None] + e0[:, 5].float()).to(torch.bfloat16).float()
+    ref = {"bias": y, "gelu": torch.nn.functional.gelu(y, approximate="tanh"), "resid": resid.float() + y,
+           "gate_resid": resid.float() + y * gate.repeat_interleave(M // groups, dim=0)}
+    rd = resid.to(DEV)
+    kw = {"bias": {}, "gelu": {}, "resid": {"resid": rd},
+          "gate_resid": dict(resid=rd, gate_mod=gate_mod.to(DEV), gate_e0=e0.to(DEV)[:, 5], rows_per_group=M // groups)}
+    return a.to(DEV), w.to(DEV), bias.to(DEV), ref, kw
+
+
+@pytest.mark.parametrize("structure", ["pp256", "pp224", "pp192", "pp128"])
+@pytest.mark.parametrize("epi", ["bias", "gelu", "resid", "gate_resid"])
+def test_gemm_pingpong_direct_epilogue(direct_case, structure, epi):
+    """The direct epilogue under the ping-pong structures (every other forced-pp* case has N % 8 == 0 and stores
+    through LDS): one bf16 rounding of the fp32 product, and the 128 x 128 structure's bits."""
+    a, w, bias, ref, kw = direct_case
+    out = ops.gemm(a, w, bias, epilogue=epi, structure=structure, **kw[epi])
+    assert rel(out, ref[epi]) < 4e-3
+    assert torch.equal(out, ops.gemm(a, w, bias, epilogue=epi, structure="t128", **kw[epi]))
+
+
+@pytest.mark.parametrize("structure", ["pp256", "pp224", "pp192", "pp128"])
+def test_gemm_pingpong_direct_epilogue_into_a_wider_buffer(direct_case, structure):
+    """N = 256 written through `out=` into the first 256 columns of a [300, 260] buffer: N % 8 == 0 but ldo % 8 == 4,
+    the other way into the direct epilogue.  Columns 256..259 keep their fill value."""
+    a, w, bias, ref, _ = direct_case
+    buf = torch.full((300, 260), 7.0, dtype=torch.bfloat16, device=DEV)
+    ops.gemm(a, w[:256], bias[:256], out=buf[:, :256], structure=structure)
+    assert rel(buf[:, :256], ref["bias"][:, :256]) < 4e-3
+    assert (buf[:, 256:] == 7.0).all()
+    assert torch.equal(buf[:, :256], ops.gemm(a, w[:256], bias[:256], structure="t128"))
+
+
 def test_gemm_pingpong_is_race_free_under_repetition():
     """The ping-pong structure keeps LDS-DMA requests in flight across barriers (counted vmcnt): an early fragment
     read or a late buffer reuse would show as rare wrong tiles that come and go with timing.  200 launches of two
