@@ -29,7 +29,10 @@ with the weights of `--pose_weights_path` (a file with `dwpose_embedding.*` / `r
 writes, or a skeleton renderer's output), with `--ref_pose_path ref.jpg` as `random_ref_dwpose`: the frames are read by
 `mjpeg.read_avi` and decoded on the GPU by `JpegDecoder`, with no host decode.  `--pose_resize stretch|cover` resizes both on
 the GPU to the output size (`FrameResizer`: Pillow's antialiased bilinear, bit for bit), so a clip of any size can drive the
-generation; the default `none` takes them as they are.  Rendering skeletons is outside this driver.
+generation; the default `none` takes them as they are.  `--pose_path clip.npz --ref_pose_path ref.npz` takes KEYPOINTS instead of
+frames: the array `keypoints` (a `.npy` file holds the array itself), float [F, P, 134, 3] or [F, 134, 3] = (x, y, score) in DWPose's
+whole-body order, in [0, 1] (`--pose_pixel_coords`: in pixels of the output); the ref file holds one frame, [P, 134, 3] or [134, 3].
+`PoseRenderer` draws them on the GPU at the output size, so `--pose_resize` does not apply to them.
 
 `--i2v` (inference.py:83-90, 136-149) reads `--data_path` as a TextImagePairDataset directory -- one
 `target_crop_info_<ratio>.json` listing `file_name` / `caption` entries, images under `<ratio>/` --, encodes each
@@ -115,6 +118,51 @@ def load_pose(path: str):
     return tuple(torch.as_tensor(d[k]) for k in ("dwpose_data", "random_ref_dwpose"))
 
 
+def pose_file_kind(path: str) -> str:
+    """"mjpeg" (.avi), "keypoints" (.npz, or a .npy that holds a plain array) or "dict" (.pt, or a .npy that holds a pickled dict)."""
+    low = path.lower()
+    if low.endswith(".avi"):
+        return "mjpeg"
+    if low.endswith(".npz"):
+        return "keypoints"
+    if low.endswith(".npy"):
+        import numpy as np
+        try:
+            np.load(path, mmap_mode="r", allow_pickle=False)
+        except (ValueError, EOFError):                             # an object array: the pickled dict (or no .npy file at all)
+            return "dict"
+        return "keypoints"
+    return "dict"
+
+
+def read_keypoints(path: str, one_frame: bool = False):
+    """float32 [F, P, 134, 3] from the array `keypoints` of a .npz or the array a .npy holds; `one_frame`: the file holds a single
+    frame, [P, 134, 3] or [134, 3] (or [1, P, 134, 3])."""
+    import numpy as np
+    d = np.load(path, allow_pickle=False)
+    if hasattr(d, "files"):
+        if "keypoints" not in d.files:
+            raise SystemExit(f"{path}: no array 'keypoints' in the file (it holds {', '.join(d.files) or 'nothing'})")
+        d = d["keypoints"]
+    k = np.asarray(d, dtype=np.float32)
+    if one_frame and k.ndim in (2, 3):
+        k = k.reshape((1,) * (4 - k.ndim) + k.shape)
+    try:
+        frames, people = sfa.pose_render_reference.check_keypoints_shape(k.shape)
+    except ValueError as e:
+        raise SystemExit(f"{path}: {e}")
+    if one_frame and frames != 1:
+        raise SystemExit(f"{path}: the reference pose is one frame of keypoints, the file holds {frames}")
+    return k.reshape(frames, people, 134, 3)
+
+
+def load_pose_keypoints(clip_path: str, ref_path: str, device, size, normalized: bool = True):
+    """(dwpose_data uint8 [3, F, H, W], random_ref_dwpose uint8 [H, W, 3]) on `device`, drawn there from two keypoint files."""
+    renderer = sfa.PoseRenderer(device=device)
+    clip, ref = read_keypoints(clip_path), read_keypoints(ref_path, one_frame=True)
+    return renderer.render(clip, size, "pose", normalized=normalized), renderer.render(ref, size, "hwc", normalized=normalized)[0]
+
+
 def load_pose_mjpeg(clip_path: str, ref_path: str, device, size=None, fit: str = "stretch"):
     """(dwpose_data uint8 [3, F, H, W], random_ref_dwpose uint8 [H, W, 3]) on `device` from an MJPEG AVI and a JPEG file;
     with `size` both are resized to it on the device (antialiased bilinear, Pillow's bits on the decoded samples)."""
@@ -160,11 +208,16 @@ def main():
     ap.add_argument("--fp8", action="store_true",
                     help="FP8 linear layers in the generator (the reference's enable_fp8 / torchao PerTensor quantisation)")
     ap.add_argument("--pose_path", default=None,
-                    help=".pt / .npy dict with dwpose_data [3, F, H, W] and random_ref_dwpose [H, W, 3], or an MJPEG .avi (with --ref_pose_path)")
-    ap.add_argument("--ref_pose_path", default=None, help="--pose_path clip.avi: the JPEG file that is random_ref_dwpose")
+                    help=".pt / .npy dict with dwpose_data [3, F, H, W] and random_ref_dwpose [H, W, 3], an MJPEG .avi, or keypoints: a .npz with the "
+                         "array 'keypoints' [F, P, 134, 3] / a .npy array (both with --ref_pose_path)")
+    ap.add_argument("--ref_pose_path", default=None,
+                    help="--pose_path clip.avi: the JPEG file that is random_ref_dwpose; --pose_path clip.npz / .npy: one frame of keypoints (.npz / .npy)")
+    ap.add_argument("--pose_pixel_coords", action="store_true",
+                    help="keypoint --pose_path: x and y are pixels of the output (8 x the latent size), not fractions of it in [0, 1]")
     ap.add_argument("--pose_resize", choices=("none", "stretch", "cover"), default="none",
                     help="--pose_path clip.avi: resize the clip and --ref_pose_path on the GPU to the output size (8 x the latent size): stretch, or "
-                         "cover = the largest centred crop with the output's aspect ratio; none: their size must be the output size")
+                         "cover = the largest centred crop with the output's aspect ratio; none: their size must be the output size.  Does not apply "
+                         "to keypoints (.npz / .npy array), which are drawn at the output size")
     ap.add_argument("--pose_weights_path", default=None, help="pose embedding weights (dwpose_embedding.* / randomref_embedding_pose.*)")
     ap.add_argument("--pose_random_init_seed", type=int, default=None, help="seeded random pose embedding weights instead")
     ap.add_argument("--video_format", choices=("pt", "mjpeg"), default="pt",
@@ -180,17 +233,28 @@ def main():
         if not os.path.exists(a.pose_path):
             ap.error(f"--pose_path {a.pose_path}: no such file (a .pt / .npy dict with dwpose_data and random_ref_dwpose; few-step and "
                      "multi-step configs both take it)")
-        pose_is_mjpeg = a.pose_path.lower().endswith(".avi")
-        if a.ref_pose_path and not pose_is_mjpeg:
-            ap.error("--ref_pose_path goes with an MJPEG --pose_path (.avi); a .pt / .npy dict holds its own random_ref_dwpose")
+        pose_kind = pose_file_kind(a.pose_path)
+        pose_is_mjpeg = pose_kind == "mjpeg"
+        if a.ref_pose_path and pose_kind == "dict":
+            ap.error("--ref_pose_path goes with an MJPEG --pose_path (.avi) or a keypoint one (.npz / .npy array); a .pt / .npy dict holds its own "
+                     "random_ref_dwpose")
         if pose_is_mjpeg and not a.ref_pose_path:
             ap.error("--pose_path clip.avi needs --ref_pose_path: the JPEG file that is random_ref_dwpose")
-        if pose_is_mjpeg and not os.path.exists(a.ref_pose_path):
+        if pose_kind == "keypoints" and not a.ref_pose_path:
+            ap.error("--pose_path with keypoints needs --ref_pose_path: a .npz / .npy with one frame of keypoints, drawn as random_ref_dwpose")
+        if pose_kind != "dict" and not os.path.exists(a.ref_pose_path):
             ap.error(f"--ref_pose_path {a.ref_pose_path}: no such file")
+        if pose_kind == "keypoints" and pose_file_kind(a.ref_pose_path) != "keypoints":
+            ap.error(f"--ref_pose_path {a.ref_pose_path}: keypoints (.npz / .npy array) expected beside a keypoint --pose_path")
+        if a.pose_pixel_coords and pose_kind != "keypoints":
+            ap.error("--pose_pixel_coords goes with a keypoint --pose_path (.npz / .npy array)")
     elif a.ref_pose_path:
-        ap.error("--ref_pose_path needs --pose_path clip.avi")
+        ap.error("--ref_pose_path needs --pose_path clip.avi or keypoints (.npz / .npy array)")
+    elif a.pose_pixel_coords:
+        ap.error("--pose_pixel_coords needs a keypoint --pose_path")
     if a.pose_resize != "none" and not (a.pose_path and a.pose_path.lower().endswith(".avi")):
-        ap.error("--pose_resize goes with an MJPEG --pose_path (.avi); a .pt / .npy dict is taken at the size it has")
+        ap.error("--pose_resize goes with an MJPEG --pose_path (.avi); a .pt / .npy dict is taken at the size it has, keypoints are drawn at the "
+                 "output size")
     if a.input_image:
         if (a.clip_path is None) == (a.clip_random_init_seed is None):
             ap.error("--input_image needs exactly one of --clip_path / --clip_random_init_seed")
@@ -270,6 +334,8 @@ def main():
         if pose_is_mjpeg:
             pose_size = None if a.pose_resize == "none" else (8 * a.latent_height, 8 * a.latent_width)
             pose_data = load_pose_mjpeg(a.pose_path, a.ref_pose_path, device, pose_size, "stretch" if pose_size is None else a.pose_resize)
+        elif pose_kind == "keypoints":
+            pose_data = load_pose_keypoints(a.pose_path, a.ref_pose_path, device, (8 * a.latent_height, 8 * a.latent_width), not a.pose_pixel_coords)
         else:
             pose_data = load_pose(a.pose_path)
     image_encoder = input_image = None

@@ -869,6 +869,38 @@ int sf_resize_frames(const void* frames, int layout, int n, int h, int w, const 
                      int out_layout, int out_dtype, int out_h, int out_w, void* stream);
 
 /* ==========================================================================================
+ * Pose renderer (DWPose whole-body keypoints -> skeleton frames).  The reference has no renderer: its dwpose_data
+ * arrives already drawn, in the DWPose style of UniAnimate-DiT.  The drawing is this project's definition in that style,
+ * self_forcing_amd/pose_render_reference.py (`quantize`, `primitives`, `inside`), in exact integer arithmetic; the kernel
+ * equals it bit for bit.  Per person 185 primitives in a fixed painter's order: 17 limbs (ellipses with semi-axes
+ * (length / 2, 4), in 3/5 of the palette colour), 18 body joints (discs, r = 4), per hand 20 edges (capsules of
+ * half-width 1) and 21 discs (r = 4), 68 face discs (r = 3).
+ *   keypoints float32 [F][P][134][3] = (x, y, score), DWPose's order: 0-17 body, 18-23 feet (ignored), 24-91 face,
+ *             92-112 left hand, 113-133 right hand
+ *   pixel     normalized: X = (int)(x * W), Y = (int)(y * H), one fp32 multiply; else X = (int)x, Y = (int)y
+ *   valid     x, y, score finite, score >= score_threshold, x >= 0, y >= 0, X and Y <= SF_POSE_RENDER_MAX_COORD
+ * One kernel, one launch for all frames: a workgroup per 16 x 64 tile lists the primitives whose box reaches the tile
+ * in LDS, then every lane decides four pixels from the back of the list.  The library keeps no state and needs no
+ * workspace.
+ * ========================================================================================== */
+
+#define SF_POSE_RENDER_MAX_PEOPLE 8
+#define SF_POSE_RENDER_MAX_SIZE 4096
+#define SF_POSE_RENDER_MAX_COORD 8191
+
+typedef struct sf_pose_render_args {
+  const float* keypoints;     /* DEVICE float32 [F][P][134][3], 4-byte aligned                                     */
+  void* out;                  /* F frames of H x W in `layout` / `dtype`, 16-byte aligned; every element is written */
+  int32_t F, P, H, W;         /* 1 <= F <= 65535, 1 <= P <= SF_POSE_RENDER_MAX_PEOPLE, 1 <= H, W <= SF_POSE_RENDER_MAX_SIZE */
+  int32_t layout;             /* enum sf_jpeg_layout                                                               */
+  int32_t dtype;              /* enum sf_jpeg_dtype: u8 = the samples, f32 / bf16 = u8 / 127.5 - 1 as the decoder converts */
+  int32_t normalized;         /* 1: x, y in [0, 1]; 0: in pixels                                                   */
+  float score_threshold;      /* finite; DWPose's drawing uses 0.3                                                 */
+} sf_pose_render_args;
+
+int sf_pose_render_frames(const sf_pose_render_args* args, void* stream);
+
+/* ==========================================================================================
  * Pose front end (DWPose frames -> pose tokens): `dwpose_embedding` and `randomref_embedding_pose` of the many-step
  * sampler (pipeline/causal_diffusion_inference.py:87-122) with their input transform (:337-343).  Runs once per clip.
  * Activations are channels-last bf16 volumes [T][H][W][C] with C = 8 (the three input channels, stored padded with

@@ -52,6 +52,8 @@ JPEG_DECODE_FILE_BYTES = 8960
 # enum sf_resize_filter; SF_RESIZE_MAX_RATIO (layouts and output types are the decoder's: JPEG_LAYOUTS, JPEG_DTYPES)
 RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1}
 RESIZE_MAX_RATIO = 8
+# SF_POSE_RENDER_MAX_PEOPLE / _MAX_SIZE / _MAX_COORD (layouts and output types are the decoder's too)
+POSE_RENDER_MAX_PEOPLE, POSE_RENDER_MAX_SIZE, POSE_RENDER_MAX_COORD = 8, 4096, 8191
 # enum sf_clip_dtype
 CLIP_DTYPES = {"float32": 0, "bfloat16": 1}
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
@@ -236,6 +238,12 @@ class TaehvEncoder(C.Structure):
                 ("head", TaehvLayer)]
 
 
+class PoseRenderArgs(C.Structure):
+    _fields_ = ([("keypoints", C.c_void_p), ("out", C.c_void_p)]
+                + [(n, C.c_int32) for n in ("F", "P", "H", "W", "layout", "dtype", "normalized")]
+                + [("score_threshold", C.c_float)])
+
+
 class PoseConvArgs(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("x", "w", "bias", "out")]
                 + [(n, C.c_int32) for n in ("T", "H", "W", "Cin", "Cout", "kt", "stride_t", "stride_s", "ldw", "ldo", "silu")])
@@ -359,6 +367,7 @@ SIGNATURES = {
     "sf_jpeg_decode_frames": (C.c_int, [_vp, _sz, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i, _i, _vp, _vp]),
     "sf_resize_kernel_size": (C.c_int, [_i, _i, _i]),
     "sf_resize_frames": (C.c_int, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "sf_pose_render_frames": (C.c_int, [C.POINTER(PoseRenderArgs), _vp]),
     "sf_embedding_gather": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_t5_softmax_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_mul_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),

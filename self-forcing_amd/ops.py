@@ -605,6 +605,17 @@ def resize_frames(frames: Tensor, tables_h, tables_v, filter: str, layout: str =
     return torch.ops.sf_hip.resize_frames(frames, tables_h[0], tables_h[1], tables_v[0], tables_v[1], filter, layout, out_layout, dtype, crop)
 
 
+# -------------------------------------------------------------------------------------- pose renderer (csrc/pose_render.hip)
+def pose_render_frames(keypoints: Tensor, height: int, width: int, layout: str = "pose", dtype=torch.uint8, normalized: bool = True,
+                       score_threshold: float = 0.3, out: Optional[Tensor] = None) -> Tensor:
+    """float32 keypoints [F, P, 134, 3] on the device -> skeleton frames in `layout` / `dtype`
+    (torch.ops.sf_hip.pose_render_frames over sf_pose_render_frames); `out`: the tensor to fill, already shaped."""
+    if out is not None:
+        torch.ops.sf_hip.pose_render_frames_out(out, keypoints, layout, normalized, score_threshold)
+        return out
+    return torch.ops.sf_hip.pose_render_frames(keypoints, height, width, layout, dtype, normalized, score_threshold)
+
+
 # -------------------------------------------------------------------------------------- CLIP image encoder (csrc/clip_encoder.hip)
 def clip_preprocess(frames: Tensor, image_size: int = 224, patch: int = 14, kp: Optional[int] = None) -> Tensor:
     """frames [n, 3, H, W] float32 / bfloat16 in [-1, 1] -> bf16 patch rows [n * (image_size/patch)^2, kp] (sf_clip_preprocess)."""

@@ -31,6 +31,8 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::clip_encode(model, frames, workspace!) -> out
     sf_hip::resize_frames(frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, dtype, crop?) -> out
     sf_hip::resize_frames_out(out!, frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, crop?) -> ()
+    sf_hip::pose_render_frames(keypoints, height, width, layout, dtype, normalized, score_threshold) -> out
+    sf_hip::pose_render_frames_out(out!, keypoints, layout, normalized, score_threshold) -> ()
 
 Models (weights + C descriptors) are Python objects that own device memory; operators take an integer HANDLE from
 `register_model` (a constant to a tracer).  There is no CPU implementation: CPU tensors raise.
@@ -899,6 +901,64 @@ def resize_frames_out(out: Tensor, frames: Tensor, bounds_h: Tensor, coefs_h: Te
 
 @resize_frames_out.register_fake
 def _(out, frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, crop=None):
+    return None
+
+
+# ------------------------------------------------------------------------------------------ pose renderer
+def _pose_render_geometry(keypoints: Tensor) -> Tuple[int, int]:
+    """(F, P) of float32 keypoints [F, P, 134, 3]."""
+    if keypoints.dim() != 4 or tuple(keypoints.shape[2:]) != (134, 3) or keypoints.shape[0] < 1 or not 1 <= keypoints.shape[1] <= _lib.POSE_RENDER_MAX_PEOPLE:
+        raise ValueError(f"pose_render_frames: keypoints must be [F, P, 134, 3] with F >= 1 and 1 <= P <= {_lib.POSE_RENDER_MAX_PEOPLE}, "
+                         f"got {tuple(keypoints.shape)}")
+    return int(keypoints.shape[0]), int(keypoints.shape[1])
+
+
+def _pose_render_launch(out: Tensor, keypoints: Tensor, layout: str, normalized: bool, score_threshold: float) -> None:
+    if keypoints.dtype != torch.float32:
+        raise ValueError(f"pose_render_frames: keypoints must be float32, got {keypoints.dtype}")
+    f, p = _pose_render_geometry(keypoints)
+    if out.dtype not in _RESIZE_DTYPES:
+        raise ValueError(f"dtype must be torch.uint8, float32 or bfloat16, got {out.dtype}")
+    if layout not in _lib.JPEG_LAYOUTS or out.dim() != 4:
+        raise ValueError(f"pose_render_frames: out must be a 4-d tensor in layout 'hwc', 'pose' or 'chw', got {layout!r} {tuple(out.shape)}")
+    on, h, w = _frame_geometry(out, layout)
+    if on != f:
+        raise ValueError(f"pose_render_frames: out holds {on} frames, keypoints {f}")
+    _need_gpu(keypoints, "keypoints", torch.float32), _need_gpu(out, "out", None)
+    if out.device != keypoints.device:
+        raise ValueError(f"pose_render_frames: keypoints on {keypoints.device}, out on {out.device}")
+    if not keypoints.is_contiguous() or not out.is_contiguous() or out.data_ptr() % 16:
+        raise ValueError("pose_render_frames: keypoints and out must be contiguous, out 16-byte aligned")
+    args = _lib.PoseRenderArgs(keypoints=keypoints.data_ptr(), out=out.data_ptr(), F=f, P=p, H=h, W=w, layout=_lib.JPEG_LAYOUTS[layout],
+                               dtype=_lib.JPEG_DTYPES[_RESIZE_DTYPES[out.dtype]], normalized=int(bool(normalized)), score_threshold=score_threshold)
+    _lib.check(_lib.lib().sf_pose_render_frames(C.byref(args), _stream(keypoints)), "sf_pose_render_frames")
+
+
+@custom_op(f"{NAMESPACE}::pose_render_frames", mutates_args=())
+def pose_render_frames(keypoints: Tensor, height: int, width: int, layout: str, dtype: torch.dtype, normalized: bool = True,
+                       score_threshold: float = 0.3) -> Tensor:
+    """float32 keypoints [F, P, 134, 3] on the device -> F skeleton frames of height x width in `layout` / `dtype`, every
+    pixel as `pose_render_reference.render` defines it (sf_pose_render_frames)."""
+    f, _ = _pose_render_geometry(keypoints)
+    out = torch.empty(_frame_shape(layout, f, height, width), dtype=dtype, device=keypoints.device)
+    _pose_render_launch(out, keypoints, layout, normalized, score_threshold)
+    return out
+
+
+@pose_render_frames.register_fake
+def _(keypoints, height, width, layout, dtype, normalized=True, score_threshold=0.3):
+    f, _ = _pose_render_geometry(keypoints)
+    return keypoints.new_empty(_frame_shape(layout, f, height, width), dtype=dtype)
+
+
+@custom_op(f"{NAMESPACE}::pose_render_frames_out", mutates_args=("out",))
+def pose_render_frames_out(out: Tensor, keypoints: Tensor, layout: str, normalized: bool = True, score_threshold: float = 0.3) -> None:
+    """`pose_render_frames` into a caller's tensor (its shape gives the frame size, its dtype the output type)."""
+    _pose_render_launch(out, keypoints, layout, normalized, score_threshold)
+
+
+@pose_render_frames_out.register_fake
+def _(out, keypoints, layout, normalized=True, score_threshold=0.3):
     return None
 
 
