@@ -33,6 +33,9 @@ generation; the default `none` takes them as they are.  `--pose_path clip.npz --
 frames: the array `keypoints` (a `.npy` file holds the array itself), float [F, P, 134, 3] or [F, 134, 3] = (x, y, score) in DWPose's
 whole-body order, in [0, 1] (`--pose_pixel_coords`: in pixels of the output); the ref file holds one frame, [P, 134, 3] or [134, 3].
 `PoseRenderer` draws them on the GPU at the output size, so `--pose_resize` does not apply to them.
+`--pose_align` first gives the driving skeleton the reference person's proportions and position, `--pose_fps N[/D]` resamples keypoints
+recorded at another frame rate to the pipeline's 16 frames/s, and `--pose_source_size HxW` names the size of the video they come from
+where its aspect differs from the output's: all three run on the GPU in `PoseRetargeter`, between the upload and the renderer.
 
 `--i2v` (inference.py:83-90, 136-149) reads `--data_path` as a TextImagePairDataset directory -- one
 `target_crop_info_<ratio>.json` listing `file_name` / `caption` entries, images under `<ratio>/` --, encodes each
@@ -52,11 +55,13 @@ import argparse
 import glob
 import json
 import os
+import re
 import sys
 
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
+POSE_TARGET_FPS = 16    # the generator's timeline: what --pose_fps is resampled to
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
@@ -156,11 +161,21 @@ def read_keypoints(path: str, one_frame: bool = False):
     return k.reshape(frames, people, 134, 3)
 
 
-def load_pose_keypoints(clip_path: str, ref_path: str, device, size, normalized: bool = True):
-    """(dwpose_data uint8 [3, F, H, W], random_ref_dwpose uint8 [H, W, 3]) on `device`, drawn there from two keypoint files."""
+def load_pose_keypoints(clip_path: str, ref_path: str, device, size, normalized: bool = True, align: bool = False, source_fps=None, source_size=None):
+    """(dwpose_data uint8 [3, F, H, W], random_ref_dwpose uint8 [H, W, 3]) on `device`, drawn there from two keypoint files.
+    With `align`, a `source_fps` or a `source_size` the clip first goes through `PoseRetargeter` (to the pipeline's
+    POSE_TARGET_FPS); the reference pose is drawn from the reference keypoints as they are."""
     renderer = sfa.PoseRenderer(device=device)
     clip, ref = read_keypoints(clip_path), read_keypoints(ref_path, one_frame=True)
-    return renderer.render(clip, size, "pose", normalized=normalized), renderer.render(ref, size, "hwc", normalized=normalized)[0]
+    ref_frame = renderer.render(ref, size, "hwc", normalized=normalized)[0]
+    if not align and source_fps is None and source_size is None:
+        return renderer.render(clip, size, "pose", normalized=normalized), ref_frame
+    try:
+        moved = sfa.PoseRetargeter(device=device).retarget(clip, ref[0], size, source_fps=POSE_TARGET_FPS if source_fps is None else source_fps,
+                                                           target_fps=POSE_TARGET_FPS, align=align, normalized=normalized, source_size=source_size)
+    except ValueError as e:
+        raise SystemExit(f"{clip_path}: {e}")
+    return renderer.render(moved, size, "pose", normalized=False), ref_frame
 
 
 def load_pose_mjpeg(clip_path: str, ref_path: str, device, size=None, fit: str = "stretch"):
@@ -214,6 +229,15 @@ def main():
                     help="--pose_path clip.avi: the JPEG file that is random_ref_dwpose; --pose_path clip.npz / .npy: one frame of keypoints (.npz / .npy)")
     ap.add_argument("--pose_pixel_coords", action="store_true",
                     help="keypoint --pose_path: x and y are pixels of the output (8 x the latent size), not fractions of it in [0, 1]")
+    ap.add_argument("--pose_align", action="store_true",
+                    help="keypoint --pose_path: give the driving skeleton the proportions and position of the --ref_pose_path person on the GPU "
+                         "(PoseRetargeter) before it is drawn")
+    ap.add_argument("--pose_fps", default=None, metavar="N[/D]",
+                    help=f"keypoint --pose_path: the frame rate of the keypoints, e.g. 30 or 30000/1001; they are resampled on the GPU to the "
+                         f"pipeline's {POSE_TARGET_FPS} frames/s")
+    ap.add_argument("--pose_source_size", default=None, metavar="HxW",
+                    help="keypoint --pose_path: the size of the video the keypoints come from, where its aspect differs from the output's: they are "
+                         "scaled by the heights, not stretched")
     ap.add_argument("--pose_resize", choices=("none", "stretch", "cover"), default="none",
                     help="--pose_path clip.avi: resize the clip and --ref_pose_path on the GPU to the output size (8 x the latent size): stretch, or "
                          "cover = the largest centred crop with the output's aspect ratio; none: their size must be the output size.  Does not apply "
@@ -227,6 +251,8 @@ def main():
     a = ap.parse_args()
     if not 1 <= a.jpeg_quality <= 100:
         ap.error("--jpeg_quality must be 1..100")
+    retarget_flags = (("--pose_align", a.pose_align), ("--pose_fps", a.pose_fps is not None), ("--pose_source_size", a.pose_source_size is not None))
+    pose_source_size = None
     if a.pose_path or a.pose_weights_path or a.pose_random_init_seed is not None:
         if not a.pose_path or (a.pose_weights_path is None) == (a.pose_random_init_seed is None):
             ap.error("pose conditioning needs --pose_path and exactly one of --pose_weights_path / --pose_random_init_seed")
@@ -248,10 +274,27 @@ def main():
             ap.error(f"--ref_pose_path {a.ref_pose_path}: keypoints (.npz / .npy array) expected beside a keypoint --pose_path")
         if a.pose_pixel_coords and pose_kind != "keypoints":
             ap.error("--pose_pixel_coords goes with a keypoint --pose_path (.npz / .npy array)")
+        for flag, given in retarget_flags:
+            if given and pose_kind != "keypoints":
+                ap.error(f"{flag} goes with a keypoint --pose_path (.npz / .npy array)")
+        if a.pose_fps is not None:
+            try:
+                sfa.pose_retarget_reference.rate(a.pose_fps, POSE_TARGET_FPS)
+            except ValueError as e:
+                ap.error(f"--pose_fps {a.pose_fps}: {e}")
+        if a.pose_source_size is not None:
+            m = re.fullmatch(r"(\d+)x(\d+)", a.pose_source_size)
+            if not m or not int(m.group(1)) or not int(m.group(2)):
+                ap.error(f"--pose_source_size {a.pose_source_size}: HxW expected, two positive integers, e.g. 720x1280")
+            pose_source_size = (int(m.group(1)), int(m.group(2)))
     elif a.ref_pose_path:
         ap.error("--ref_pose_path needs --pose_path clip.avi or keypoints (.npz / .npy array)")
     elif a.pose_pixel_coords:
         ap.error("--pose_pixel_coords needs a keypoint --pose_path")
+    else:
+        for flag, given in retarget_flags:
+            if given:
+                ap.error(f"{flag} needs a keypoint --pose_path")
     if a.pose_resize != "none" and not (a.pose_path and a.pose_path.lower().endswith(".avi")):
         ap.error("--pose_resize goes with an MJPEG --pose_path (.avi); a .pt / .npy dict is taken at the size it has, keypoints are drawn at the "
                  "output size")
@@ -335,7 +378,8 @@ def main():
             pose_size = None if a.pose_resize == "none" else (8 * a.latent_height, 8 * a.latent_width)
             pose_data = load_pose_mjpeg(a.pose_path, a.ref_pose_path, device, pose_size, "stretch" if pose_size is None else a.pose_resize)
         elif pose_kind == "keypoints":
-            pose_data = load_pose_keypoints(a.pose_path, a.ref_pose_path, device, (8 * a.latent_height, 8 * a.latent_width), not a.pose_pixel_coords)
+            pose_data = load_pose_keypoints(a.pose_path, a.ref_pose_path, device, (8 * a.latent_height, 8 * a.latent_width), not a.pose_pixel_coords,
+                                            a.pose_align, a.pose_fps, pose_source_size)
         else:
             pose_data = load_pose(a.pose_path)
     image_encoder = input_image = None

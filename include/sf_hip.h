@@ -901,6 +901,52 @@ typedef struct sf_pose_render_args {
 int sf_pose_render_frames(const sf_pose_render_args* args, void* stream);
 
 /* ==========================================================================================
+ * Pose retargeter (driving keypoints -> keypoints of the reference person's proportions, on the generator's timeline).
+ * The reference has no counterpart: its poses arrive drawn and aligned.  The numbers are this project's definition,
+ * self_forcing_amd/pose_retarget_reference.py (`lift`, `resample`, `fit`, `retarget_frame`): float32, every sub, mul,
+ * add, div and sqrt rounded on its own; the kernel equals it bit for bit.
+ *   valid     the renderer's rule on the raw values: x, y, score finite, score >= score_threshold, x >= 0, y >= 0;
+ *             an invalid output point is (-1, -1, 0)
+ *   lift      x * sx, y * sy, one fp32 multiply each; the factors come from the host (formed in double, rounded once)
+ *   resample  output frame j sits at source position j * num / den: i0 = j num / den, rem = j num % den, i1 = i0 + (rem != 0);
+ *             rem == 0 copies; both valid: a + (rem / den) * (b - a), score the smaller; one valid: taken when nearer
+ *             (a when 2 rem <= den)
+ *   fit       per person from clip frame 0 and the reference over the renderer's 17 limbs: a global ratio g of summed
+ *             lengths, nine ratios of symmetric limb groups; the anchor is the neck (point 1), without it in both the
+ *             person is lifted and resampled only
+ *   retarget  the neck goes to R[1] + g * (q - S0[1]); every other point is placed from its parent (limbs) or anchor
+ *             (feet, face, hands) at ratio * its offset in the resampled frame
+ * One kernel, one launch per piece, a workgroup per (output frame, person).  The library keeps no state and needs no
+ * workspace; a streaming caller keeps clip frame 0 and the last source frame it has seen.
+ * ========================================================================================== */
+
+#define SF_POSE_RETARGET_MAX_RATE 65535
+#define SF_POSE_RETARGET_MAX_FRAMES 1048576
+
+typedef struct sf_pose_retarget_args {
+  const float* src;           /* DEVICE float32 [n_src][people][134][3]: clip frames src0 .. src0 + n_src - 1          */
+  const float* first;         /* DEVICE float32 [people][134][3]: clip frame 0 (S0), as it came                        */
+  const float* ref;           /* DEVICE float32 [ref_people][134][3]                                                   */
+  float* out;                 /* DEVICE float32 [n_out][people][134][3]: output frames out0 ..; every element is written */
+  int64_t src0;               /* clip index of src's first frame                                                       */
+  int64_t out0;               /* index of the first output frame                                                       */
+  int32_t n_src, n_out;       /* n_src >= 1, 1 <= n_out <= SF_POSE_RETARGET_MAX_FRAMES; i0 and i1 of every output frame lie in src */
+  int32_t people, ref_people; /* 1 <= people <= SF_POSE_RENDER_MAX_PEOPLE; ref_people = 1 (serves everyone) or people  */
+  int32_t num, den;           /* source_fps / target_fps in lowest terms, both 1 .. SF_POSE_RETARGET_MAX_RATE          */
+  float src_sx, src_sy;       /* lift of the source, finite                                                            */
+  float ref_sx, ref_sy;       /* lift of the reference, finite                                                         */
+  float score_threshold;      /* finite                                                                                */
+  int32_t align;              /* 1: fit and retarget; 0: lift and resample only                                        */
+} sf_pose_retarget_args;
+
+int sf_pose_retarget_frames(const sf_pose_retarget_args* args, void* stream);
+
+/* Host only: the output frames that become final once n more source frames follow the `frames_before` already seen
+ * (frame j is final when source frame i1(j) is in): [*first_out, *first_out + *n_out).  A clip of F frames gives
+ * (F - 1) * den / num + 1 output frames. */
+int sf_pose_retarget_plan(int64_t frames_before, int64_t n, int num, int den, int64_t* first_out, int64_t* n_out);
+
+/* ==========================================================================================
  * Pose front end (DWPose frames -> pose tokens): `dwpose_embedding` and `randomref_embedding_pose` of the many-step
  * sampler (pipeline/causal_diffusion_inference.py:87-122) with their input transform (:337-343).  Runs once per clip.
  * Activations are channels-last bf16 volumes [T][H][W][C] with C = 8 (the three input channels, stored padded with

@@ -9,7 +9,7 @@ raise if the library is missing -- there is no fallback path.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -614,6 +614,22 @@ def pose_render_frames(keypoints: Tensor, height: int, width: int, layout: str =
         torch.ops.sf_hip.pose_render_frames_out(out, keypoints, layout, normalized, score_threshold)
         return out
     return torch.ops.sf_hip.pose_render_frames(keypoints, height, width, layout, dtype, normalized, score_threshold)
+
+
+# -------------------------------------------------------------------------------------- pose retargeter (csrc/pose_retarget.hip)
+def pose_retarget_frames(src: Tensor, first: Tensor, ref: Tensor, src0: int, out0: int, n_out: int, num: int, den: int, src_sx: float,
+                         src_sy: float, ref_sx: float, ref_sy: float, score_threshold: float = 0.3, align: bool = True) -> Tensor:
+    """Source frames src0 .. of a clip (float32 [n, P, 134, 3] on the device), its frame 0 [P, 134, 3] and the reference
+    [Pr, 134, 3] -> output frames out0 .. out0 + n_out - 1, float32 [n_out, P, 134, 3] in output pixels
+    (torch.ops.sf_hip.pose_retarget_frames over sf_pose_retarget_frames)."""
+    return torch.ops.sf_hip.pose_retarget_frames(src, first, ref, src0, out0, n_out, num, den, src_sx, src_sy, ref_sx, ref_sy, score_threshold, align)
+
+
+def pose_retarget_plan(frames_before: int, n: int, num: int, den: int) -> Tuple[int, int]:
+    """(first_out, n_out) of sf_pose_retarget_plan: the output frames final once n more source frames are in."""
+    first, count = C.c_int64(), C.c_int64()
+    check(lib().sf_pose_retarget_plan(frames_before, n, num, den, C.byref(first), C.byref(count)), "sf_pose_retarget_plan")
+    return first.value, count.value
 
 
 # -------------------------------------------------------------------------------------- CLIP image encoder (csrc/clip_encoder.hip)

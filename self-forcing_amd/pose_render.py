@@ -11,6 +11,7 @@ import torch
 
 from . import _lib, ops
 from . import pose_render_reference as pr
+from . import pose_retarget_reference as rr
 
 Tensor = torch.Tensor
 _DTYPES = (torch.uint8, torch.float32, torch.bfloat16)
@@ -25,6 +26,18 @@ def check_arguments(size, layout: str, dtype, score_threshold) -> Tuple[int, int
         raise ValueError(f"dtype must be torch.uint8, float32 or bfloat16, got {dtype}")
     pr.check_threshold(score_threshold)
     return h, w
+
+
+def as_tensor(keypoints, what: str) -> Tensor:
+    """A numpy array (or what `np.asarray` takes), a host tensor or a device tensor of numbers -> a tensor, where it is."""
+    if not isinstance(keypoints, Tensor):
+        keypoints = np.asarray(keypoints)
+        if keypoints.dtype.kind not in "fiu":
+            raise ValueError(f"{what} must be numbers, got an array of {keypoints.dtype}")
+        return torch.from_numpy(np.ascontiguousarray(keypoints, dtype=np.float32))
+    if keypoints.is_complex() or keypoints.dtype == torch.bool:
+        raise ValueError(f"{what} must be numbers, got {keypoints.dtype}")
+    return keypoints
 
 
 class PoseRenderer:
@@ -44,13 +57,7 @@ class PoseRenderer:
     def render(self, keypoints, size: Sequence[int], layout: str = "pose", dtype=torch.uint8, normalized: bool = True,
                score_threshold: float = 0.3, out: Optional[Tensor] = None) -> Tensor:
         h, w = check_arguments(size, layout, dtype, score_threshold)
-        if not isinstance(keypoints, Tensor):
-            keypoints = np.asarray(keypoints)
-            if keypoints.dtype.kind not in "fiu":
-                raise ValueError(f"PoseRenderer: keypoints must be numbers, got an array of {keypoints.dtype}")
-            keypoints = torch.from_numpy(np.ascontiguousarray(keypoints, dtype=np.float32))
-        elif keypoints.is_complex() or keypoints.dtype == torch.bool:
-            raise ValueError(f"PoseRenderer: keypoints must be numbers, got {keypoints.dtype}")
+        keypoints = as_tensor(keypoints, "PoseRenderer: keypoints")
         f, p = pr.check_keypoints_shape(keypoints.shape)
         device = keypoints.device if keypoints.is_cuda else self.device
         if device.type != "cuda":
@@ -67,18 +74,52 @@ class PoseRenderer:
             return ops.pose_render_frames(keypoints, h, w, layout, dtype, bool(normalized), float(score_threshold), out)
 
 
+def _stacked(frames: List):
+    return torch.stack(frames) if isinstance(frames[0], Tensor) else np.stack([np.asarray(k) for k in frames])
+
+
+def _retargeted_feed(keypoints: Iterable, renderer: PoseRenderer, stream, size: Tuple[int, int], frames_per_piece: int,
+                     score_threshold: float) -> Iterator[Tensor]:
+    """`pose_feed` through a `PoseRetargetStream`: source frames are gathered until the stream's plan says that a piece of
+    output frames is final, pushed in one call, and the output is drawn `frames_per_piece` frames at a time."""
+    if (stream.params.h, stream.params.w) != size:
+        raise ValueError(f"pose_feed: the retargeter was opened for {(stream.params.h, stream.params.w)}, the frames are {size}")
+    ready: Optional[Tensor] = None         # retargeted frames not yet drawn, fewer than a piece
+    gathered: List = []
+    for k in keypoints:
+        gathered.append(k)
+        held = 0 if ready is None else ready.shape[0]
+        if held + rr.plan(stream.frames_in, len(gathered), stream.params.num, stream.params.den)[1] < frames_per_piece:
+            continue
+        new, gathered = stream.push(_stacked(gathered)), []
+        ready = new if ready is None else torch.cat([ready, new])
+        while ready.shape[0] >= frames_per_piece:
+            piece, ready = ready[:frames_per_piece], ready[frames_per_piece:]
+            yield renderer.render(piece, size, "pose", torch.uint8, False, score_threshold)
+    if gathered:                           # source frames behind the last output frame: they make nothing final
+        new = stream.push(_stacked(gathered))
+        ready = new if ready is None else torch.cat([ready, new])
+    if ready is not None and ready.shape[0]:
+        yield renderer.render(ready, size, "pose", torch.uint8, False, score_threshold)
+
+
 def pose_feed(keypoints: Iterable, renderer: PoseRenderer, size: Sequence[int], frames_per_piece: int = 12, normalized: bool = True,
-              score_threshold: float = 0.3) -> Iterator[Tensor]:
+              score_threshold: float = 0.3, retargeter=None) -> Iterator[Tensor]:
     """Keypoints as the pieces `CausalInferencePipeline.stream(pose_feed=...)` pulls, the counterpart of `jpeg.pose_feed`:
     uint8 [3, n, H, W], n = `frames_per_piece` (the last piece may be shorter), each rendered when it is asked for.
-    `keypoints` yields one frame at a time, [P, 134, 3] or [134, 3] (an array [F, P, 134, 3] does); it may be a live source."""
+    `keypoints` yields one frame at a time, [P, 134, 3] or [134, 3] (an array [F, P, 134, 3] does); it may be a live source.
+    `retargeter`: a `PoseRetargetStream` (`PoseRetargeter.open_stream`, opened for the same `size`) the source frames go
+    through first; pieces are then counted in its OUTPUT frames, and `normalized` is the stream's own (its output is drawn
+    as pixels)."""
     if frames_per_piece < 1:
         raise ValueError(f"frames_per_piece must be >= 1, got {frames_per_piece}")
     check_arguments(size, "pose", torch.uint8, score_threshold)
+    if retargeter is not None:
+        yield from _retargeted_feed(keypoints, renderer, retargeter, pr.check_size(size), frames_per_piece, score_threshold)
+        return
 
     def piece_of(frames: List) -> Tensor:
-        stacked = torch.stack(frames) if isinstance(frames[0], Tensor) else np.stack([np.asarray(k) for k in frames])
-        return renderer.render(stacked, size, "pose", torch.uint8, normalized, score_threshold)
+        return renderer.render(_stacked(frames), size, "pose", torch.uint8, normalized, score_threshold)
 
     piece: List = []
     for k in keypoints:

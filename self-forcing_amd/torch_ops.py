@@ -33,6 +33,7 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::resize_frames_out(out!, frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, crop?) -> ()
     sf_hip::pose_render_frames(keypoints, height, width, layout, dtype, normalized, score_threshold) -> out
     sf_hip::pose_render_frames_out(out!, keypoints, layout, normalized, score_threshold) -> ()
+    sf_hip::pose_retarget_frames(src, first, ref, src0, out0, n_out, num, den, src_sx, src_sy, ref_sx, ref_sy, score_threshold, align) -> out
 
 Models (weights + C descriptors) are Python objects that own device memory; operators take an integer HANDLE from
 `register_model` (a constant to a tracer).  There is no CPU implementation: CPU tensors raise.
@@ -960,6 +961,45 @@ def pose_render_frames_out(out: Tensor, keypoints: Tensor, layout: str, normaliz
 @pose_render_frames_out.register_fake
 def _(out, keypoints, layout, normalized=True, score_threshold=0.3):
     return None
+
+
+# ------------------------------------------------------------------------------------------ pose retargeter
+def _pose_retarget_geometry(src: Tensor, first: Tensor, ref: Tensor, n_out: int) -> Tuple[int, int, int]:
+    """(n_src, P, Pr) of src [n, P, 134, 3], first [P, 134, 3] and ref [Pr, 134, 3]."""
+    _pose_render_geometry(src)
+    n, p = int(src.shape[0]), int(src.shape[1])
+    if tuple(first.shape) != (p, 134, 3):
+        raise ValueError(f"pose_retarget_frames: first must be [{p}, 134, 3] (the clip's frame 0), got {tuple(first.shape)}")
+    if ref.dim() != 3 or tuple(ref.shape[1:]) != (134, 3) or ref.shape[0] not in (1, p):
+        raise ValueError(f"pose_retarget_frames: ref must be [Pr, 134, 3] with Pr = 1 or {p}, got {tuple(ref.shape)}")
+    if not 1 <= n_out <= _lib.POSE_RETARGET_MAX_FRAMES:
+        raise ValueError(f"pose_retarget_frames: n_out={n_out} (1..{_lib.POSE_RETARGET_MAX_FRAMES})")
+    return n, p, int(ref.shape[0])
+
+
+@custom_op(f"{NAMESPACE}::pose_retarget_frames", mutates_args=())
+def pose_retarget_frames(src: Tensor, first: Tensor, ref: Tensor, src0: int, out0: int, n_out: int, num: int, den: int, src_sx: float,
+                         src_sy: float, ref_sx: float, ref_sy: float, score_threshold: float = 0.3, align: bool = True) -> Tensor:
+    """float32 source frames src0 .. of a clip [n, P, 134, 3], its frame 0 [P, 134, 3] and the reference [Pr, 134, 3], all on
+    one device -> output frames out0 .. out0 + n_out - 1 at source_fps / target_fps = num / den, float32 [n_out, P, 134, 3] in
+    output pixels, every number as `pose_retarget_reference.frames` defines it (sf_pose_retarget_frames)."""
+    n, p, pr = _pose_retarget_geometry(src, first, ref, n_out)
+    for name, t in (("src", src), ("first", first), ("ref", ref)):
+        _need_gpu(t, name, torch.float32)
+        if t.device != src.device or not t.is_contiguous():
+            raise ValueError(f"pose_retarget_frames: {name} must be contiguous and on src's device {src.device}")
+    out = torch.empty((n_out, p, 134, 3), dtype=torch.float32, device=src.device)
+    args = _lib.PoseRetargetArgs(src=src.data_ptr(), first=first.data_ptr(), ref=ref.data_ptr(), out=out.data_ptr(), src0=src0, out0=out0, n_src=n,
+                                 n_out=n_out, people=p, ref_people=pr, num=num, den=den, src_sx=src_sx, src_sy=src_sy, ref_sx=ref_sx, ref_sy=ref_sy,
+                                 score_threshold=score_threshold, align=int(bool(align)))
+    _lib.check(_lib.lib().sf_pose_retarget_frames(C.byref(args), _stream(src)), "sf_pose_retarget_frames")
+    return out
+
+
+@pose_retarget_frames.register_fake
+def _(src, first, ref, src0, out0, n_out, num, den, src_sx, src_sy, ref_sx, ref_sy, score_threshold=0.3, align=True):
+    _, p, _ = _pose_retarget_geometry(src, first, ref, n_out)
+    return src.new_empty((n_out, p, 134, 3), dtype=torch.float32)
 
 
 # every operator this module registered, by its name under torch.ops.sf_hip
