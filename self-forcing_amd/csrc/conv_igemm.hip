@@ -210,7 +210,8 @@ extern "C" int sf_conv_igemm(const sf_conv_args* a, void* stream) {
     const int rc = sf_conv_halo_launch(a, stream);
     if (rc <= 0) return rc;   // launched, or the launch failed
     SF_CHECK(a->structure == SF_CONV_AUTO && !a->norm_out, "sf_conv_igemm: the halo structure needs 3x3 spatial taps, "
-             "Cout %% 96 == 0 (a fused norm output: Cout 96 or 192), H, W >= 16, a bf16 bias / bias + residual epilogue and no interleave");
+             "Cout %% 96 == 0 (a fused norm output: Cout 96 or 192, norm_ld %% 8 == 0), H, W >= 16, ldo %% 8 == 0, a bf16 bias / bias + residual "
+             "epilogue and no interleave");
   }
   ConvP p;
   p.x = (const bf16_t*)a->x; p.w = (const bf16_t*)a->w; p.bias = (const bf16_t*)a->bias;
