@@ -36,6 +36,8 @@ whole-body order, in [0, 1] (`--pose_pixel_coords`: in pixels of the output); th
 `--pose_align` first gives the driving skeleton the reference person's proportions and position, `--pose_fps N[/D]` resamples keypoints
 recorded at another frame rate to the pipeline's 16 frames/s, and `--pose_source_size HxW` names the size of the video they come from
 where its aspect differs from the output's: all three run on the GPU in `PoseRetargeter`, between the upload and the renderer.
+`--pose_smooth MIN_CUTOFF[,BETA[,D_CUTOFF]]` steadies jittery keypoints with a One-Euro filter per point and `--pose_hold N` bridges up to N
+frames in which a point is missing, both on the GPU in `PoseSmoother`, in front of the retargeter; the reference file is never smoothed.
 
 `--i2v` (inference.py:83-90, 136-149) reads `--data_path` as a TextImagePairDataset directory -- one
 `target_crop_info_<ratio>.json` listing `file_name` / `caption` entries, images under `<ratio>/` --, encodes each
@@ -161,13 +163,21 @@ def read_keypoints(path: str, one_frame: bool = False):
     return k.reshape(frames, people, 134, 3)
 
 
-def load_pose_keypoints(clip_path: str, ref_path: str, device, size, normalized: bool = True, align: bool = False, source_fps=None, source_size=None):
+def load_pose_keypoints(clip_path: str, ref_path: str, device, size, normalized: bool = True, align: bool = False, source_fps=None, source_size=None,
+                        smooth=None, hold: int = 0):
     """(dwpose_data uint8 [3, F, H, W], random_ref_dwpose uint8 [H, W, 3]) on `device`, drawn there from two keypoint files.
-    With `align`, a `source_fps` or a `source_size` the clip first goes through `PoseRetargeter` (to the pipeline's
-    POSE_TARGET_FPS); the reference pose is drawn from the reference keypoints as they are."""
+    With `smooth` = (min_cutoff[, beta[, d_cutoff]]) or `hold` > 0 the clip first goes through `PoseSmoother` at `source_fps`
+    (POSE_TARGET_FPS when none is given); with `align`, a `source_fps` or a `source_size` it then goes through
+    `PoseRetargeter` (to the pipeline's POSE_TARGET_FPS).  The reference pose is drawn from the reference keypoints as they
+    are: it is neither smoothed nor moved."""
     renderer = sfa.PoseRenderer(device=device)
     clip, ref = read_keypoints(clip_path), read_keypoints(ref_path, one_frame=True)
     ref_frame = renderer.render(ref, size, "hwc", normalized=normalized)[0]
+    if smooth is not None or hold:
+        try:
+            clip = sfa.PoseSmoother(device=device).smooth(clip, POSE_TARGET_FPS if source_fps is None else source_fps, *(smooth or ()), max_gap=hold)
+        except ValueError as e:
+            raise SystemExit(f"{clip_path}: {e}")
     if not align and source_fps is None and source_size is None:
         return renderer.render(clip, size, "pose", normalized=normalized), ref_frame
     try:
@@ -238,6 +248,13 @@ def main():
     ap.add_argument("--pose_source_size", default=None, metavar="HxW",
                     help="keypoint --pose_path: the size of the video the keypoints come from, where its aspect differs from the output's: they are "
                          "scaled by the heights, not stretched")
+    ap.add_argument("--pose_smooth", default=None, metavar="MIN_CUTOFF[,BETA[,D_CUTOFF]]",
+                    help=f"keypoint --pose_path: steady jittery keypoints on the GPU (PoseSmoother, a One-Euro filter per point) before anything "
+                         f"else: the cutoff of a point at rest in Hz (lower is steadier and lags more), how fast the cutoff grows with the point's "
+                         f"speed (default 0) and the cutoff of the speed estimate in Hz (default 1); the rate is --pose_fps, else {POSE_TARGET_FPS}")
+    ap.add_argument("--pose_hold", type=int, default=None, metavar="N",
+                    help="keypoint --pose_path: bridge up to N frames in a row in which a point is missing with its last smoothed position "
+                         "(PoseSmoother; with no --pose_smooth the filter runs at its defaults)")
     ap.add_argument("--pose_resize", choices=("none", "stretch", "cover"), default="none",
                     help="--pose_path clip.avi: resize the clip and --ref_pose_path on the GPU to the output size (8 x the latent size): stretch, or "
                          "cover = the largest centred crop with the output's aspect ratio; none: their size must be the output size.  Does not apply "
@@ -252,7 +269,8 @@ def main():
     if not 1 <= a.jpeg_quality <= 100:
         ap.error("--jpeg_quality must be 1..100")
     retarget_flags = (("--pose_align", a.pose_align), ("--pose_fps", a.pose_fps is not None), ("--pose_source_size", a.pose_source_size is not None))
-    pose_source_size = None
+    smooth_flags = (("--pose_smooth", a.pose_smooth is not None), ("--pose_hold", a.pose_hold is not None))       # they do not retarget
+    pose_source_size = pose_smooth = None
     if a.pose_path or a.pose_weights_path or a.pose_random_init_seed is not None:
         if not a.pose_path or (a.pose_weights_path is None) == (a.pose_random_init_seed is None):
             ap.error("pose conditioning needs --pose_path and exactly one of --pose_weights_path / --pose_random_init_seed")
@@ -274,7 +292,7 @@ def main():
             ap.error(f"--ref_pose_path {a.ref_pose_path}: keypoints (.npz / .npy array) expected beside a keypoint --pose_path")
         if a.pose_pixel_coords and pose_kind != "keypoints":
             ap.error("--pose_pixel_coords goes with a keypoint --pose_path (.npz / .npy array)")
-        for flag, given in retarget_flags:
+        for flag, given in retarget_flags + smooth_flags:
             if given and pose_kind != "keypoints":
                 ap.error(f"{flag} goes with a keypoint --pose_path (.npz / .npy array)")
         if a.pose_fps is not None:
@@ -287,12 +305,23 @@ def main():
             if not m or not int(m.group(1)) or not int(m.group(2)):
                 ap.error(f"--pose_source_size {a.pose_source_size}: HxW expected, two positive integers, e.g. 720x1280")
             pose_source_size = (int(m.group(1)), int(m.group(2)))
+        if a.pose_smooth is not None or a.pose_hold is not None:
+            try:
+                pose_smooth = () if a.pose_smooth is None else tuple(float(v) for v in a.pose_smooth.split(","))
+                if a.pose_smooth is not None and not 1 <= len(pose_smooth) <= 3:
+                    raise ValueError("one to three numbers expected")
+            except ValueError as e:
+                ap.error(f"--pose_smooth {a.pose_smooth}: MIN_CUTOFF[,BETA[,D_CUTOFF]] expected, e.g. 1.0,0.05 ({e})")
+            try:
+                sfa.pose_smooth_reference.prepare(POSE_TARGET_FPS if a.pose_fps is None else a.pose_fps, *pose_smooth, max_gap=a.pose_hold or 0)
+            except ValueError as e:
+                ap.error(f"--pose_smooth {a.pose_smooth} --pose_hold {a.pose_hold}: {e}")
     elif a.ref_pose_path:
         ap.error("--ref_pose_path needs --pose_path clip.avi or keypoints (.npz / .npy array)")
     elif a.pose_pixel_coords:
         ap.error("--pose_pixel_coords needs a keypoint --pose_path")
     else:
-        for flag, given in retarget_flags:
+        for flag, given in retarget_flags + smooth_flags:
             if given:
                 ap.error(f"{flag} needs a keypoint --pose_path")
     if a.pose_resize != "none" and not (a.pose_path and a.pose_path.lower().endswith(".avi")):
@@ -379,7 +408,7 @@ def main():
             pose_data = load_pose_mjpeg(a.pose_path, a.ref_pose_path, device, pose_size, "stretch" if pose_size is None else a.pose_resize)
         elif pose_kind == "keypoints":
             pose_data = load_pose_keypoints(a.pose_path, a.ref_pose_path, device, (8 * a.latent_height, 8 * a.latent_width), not a.pose_pixel_coords,
-                                            a.pose_align, a.pose_fps, pose_source_size)
+                                            a.pose_align, a.pose_fps, pose_source_size, pose_smooth, a.pose_hold or 0)
         else:
             pose_data = load_pose(a.pose_path)
     image_encoder = input_image = None

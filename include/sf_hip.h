@@ -947,6 +947,46 @@ int sf_pose_retarget_frames(const sf_pose_retarget_args* args, void* stream);
 int sf_pose_retarget_plan(int64_t frames_before, int64_t n, int num, int den, int64_t* first_out, int64_t* n_out);
 
 /* ==========================================================================================
+ * Pose smoother (jittery keypoints with dropped points -> smoothed keypoints, in front of the retargeter).  The reference
+ * has no counterpart: its poses arrive drawn.  The numbers are this project's definition,
+ * self_forcing_amd/pose_smooth_reference.py (`frames`): a One-Euro filter per point on x and y with a bounded hold across
+ * missing samples, float32, every sub, mul, add and div rounded on its own; the kernel equals it bit for bit.
+ *   valid     the renderer's rule on the raw values: x, y, score finite, score >= score_threshold, x >= 0, y >= 0
+ *   state     per (person, point) 8 words of 32 bits: hx, hy (filtered position), dx, dy (filtered speed), s (the last
+ *             valid score) as float; gap (frames since the last valid sample), seen as int32; 0.  Zero-filled is fresh.
+ *   a frame   te = (float)(gap + 1) * period.
+ *             valid and seen: per coordinate with sample v:  e = v - h;  dx = e / te;  rd = kd * te;  ad = rd / (rd + 1);
+ *               t = dx - d;  t = ad * t;  d' = d + t;  fc = beta * |d'|;  fc = min_cutoff + fc;  r = fp32(2 pi) * fc;
+ *               r = r * te;  a = r / (r + 1);  t = a * e;  h' = h + t.  All four of h', d' finite: they become the state;
+ *               else the point is seeded afresh.
+ *             valid and not seen, or seeded afresh: h = (x, y), d = 0.
+ *             either valid case: s = score, gap = 0, seen = 1; the output is (hx, hy, s).
+ *             invalid, seen and gap < max_gap: gap += 1; the output is (hx, hy, s).
+ *             invalid otherwise: seen = 0, gap = 0; the output is (-1, -1, 0); h, d and s keep their bits.
+ * One kernel, one launch per piece, one lane per (person, point) that walks the piece's frames with its state in
+ * registers.  The library keeps no state and needs no workspace: the caller owns `state` and hands it to every piece of
+ * one clip, so any partition of a clip gives the whole clip's bits.
+ * ========================================================================================== */
+
+typedef struct sf_pose_smooth_args {
+  const float* src;           /* DEVICE float32 [n][people][134][3], in the caller's units                             */
+  float* out;                 /* DEVICE float32 [n][people][134][3]; every element is written                          */
+  void* state;                /* DEVICE [people][134][8] 32-bit words, 16-byte aligned; read and advanced              */
+  int32_t n, people;          /* 1 <= n <= SF_POSE_RETARGET_MAX_FRAMES, 1 <= people <= SF_POSE_RENDER_MAX_PEOPLE; src, out and state do not overlap */
+  float period;               /* seconds per frame, fp32(den / num) of the source rate; finite, > 0                    */
+  float min_cutoff;           /* Hz; finite, > 0                                                                       */
+  float beta;                 /* 1 / unit; finite, >= 0                                                                */
+  float kd;                   /* fp32(2 pi d_cutoff); finite, > 0                                                      */
+  float score_threshold;      /* finite                                                                                */
+  int32_t max_gap;            /* 0 .. 65535: the longest run of invalid samples that is bridged                        */
+} sf_pose_smooth_args;
+
+int sf_pose_smooth_frames(const sf_pose_smooth_args* args, void* stream);
+
+/* Host only: the bytes of `state` for `people` people (people * 134 * 32); 0 for people out of range. */
+size_t sf_pose_smooth_state_bytes(int people);
+
+/* ==========================================================================================
  * Pose front end (DWPose frames -> pose tokens): `dwpose_embedding` and `randomref_embedding_pose` of the many-step
  * sampler (pipeline/causal_diffusion_inference.py:87-122) with their input transform (:337-343).  Runs once per clip.
  * Activations are channels-last bf16 volumes [T][H][W][C] with C = 8 (the three input channels, stored padded with

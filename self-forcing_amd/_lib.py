@@ -55,6 +55,7 @@ RESIZE_MAX_RATIO = 8
 # SF_POSE_RENDER_MAX_PEOPLE / _MAX_SIZE / _MAX_COORD (layouts and output types are the decoder's too)
 POSE_RENDER_MAX_PEOPLE, POSE_RENDER_MAX_SIZE, POSE_RENDER_MAX_COORD = 8, 4096, 8191
 POSE_RETARGET_MAX_RATE, POSE_RETARGET_MAX_FRAMES = 65535, 1 << 20   # SF_POSE_RETARGET_MAX_RATE / _MAX_FRAMES
+POSE_SMOOTH_MAX_GAP = 65535                                         # sf_pose_smooth_args.max_gap
 # enum sf_clip_dtype
 CLIP_DTYPES = {"float32": 0, "bfloat16": 1}
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
@@ -253,6 +254,13 @@ class PoseRetargetArgs(C.Structure):
                 + [("align", C.c_int32)])
 
 
+class PoseSmoothArgs(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("src", "out", "state")]
+                + [("n", C.c_int32), ("people", C.c_int32)]
+                + [(n, C.c_float) for n in ("period", "min_cutoff", "beta", "kd", "score_threshold")]
+                + [("max_gap", C.c_int32)])
+
+
 class PoseConvArgs(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("x", "w", "bias", "out")]
                 + [(n, C.c_int32) for n in ("T", "H", "W", "Cin", "Cout", "kt", "stride_t", "stride_s", "ldw", "ldo", "silu")])
@@ -379,6 +387,8 @@ SIGNATURES = {
     "sf_pose_render_frames": (C.c_int, [C.POINTER(PoseRenderArgs), _vp]),
     "sf_pose_retarget_frames": (C.c_int, [C.POINTER(PoseRetargetArgs), _vp]),
     "sf_pose_retarget_plan": (C.c_int, [_i64, _i64, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sf_pose_smooth_frames": (C.c_int, [C.POINTER(PoseSmoothArgs), _vp]),
+    "sf_pose_smooth_state_bytes": (C.c_size_t, [_i]),
     "sf_embedding_gather": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_t5_softmax_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_mul_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),

@@ -632,6 +632,20 @@ def pose_retarget_plan(frames_before: int, n: int, num: int, den: int) -> Tuple[
     return first.value, count.value
 
 
+# -------------------------------------------------------------------------------------- pose smoother (csrc/pose_smooth.hip)
+def pose_smooth_frames(src: Tensor, state: Tensor, period: float, min_cutoff: float, beta: float, kd: float, threshold: float = 0.3,
+                       max_gap: int = 0) -> Tensor:
+    """The frames of one piece of a clip (float32 [n, P, 134, 3] on the device) and the packed filter state int32
+    [P, 134, 8] the clip has reached -> the frames smoothed, float32 [n, P, 134, 3]; `state` is advanced in place
+    (torch.ops.sf_hip.pose_smooth_frames over sf_pose_smooth_frames)."""
+    return torch.ops.sf_hip.pose_smooth_frames(src, state, period, min_cutoff, beta, kd, threshold, max_gap)
+
+
+def pose_smooth_state_bytes(people: int) -> int:
+    """sf_pose_smooth_state_bytes: the bytes of the state of `people` people, 0 out of range."""
+    return int(lib().sf_pose_smooth_state_bytes(people))
+
+
 # -------------------------------------------------------------------------------------- CLIP image encoder (csrc/clip_encoder.hip)
 def clip_preprocess(frames: Tensor, image_size: int = 224, patch: int = 14, kp: Optional[int] = None) -> Tensor:
     """frames [n, 3, H, W] float32 / bfloat16 in [-1, 1] -> bf16 patch rows [n * (image_size/patch)^2, kp] (sf_clip_preprocess)."""

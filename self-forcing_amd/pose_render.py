@@ -79,9 +79,14 @@ def _stacked(frames: List):
 
 
 def _retargeted_feed(keypoints: Iterable, renderer: PoseRenderer, stream, size: Tuple[int, int], frames_per_piece: int,
-                     score_threshold: float) -> Iterator[Tensor]:
+                     score_threshold: float, smoother=None) -> Iterator[Tensor]:
     """`pose_feed` through a `PoseRetargetStream`: source frames are gathered until the stream's plan says that a piece of
-    output frames is final, pushed in one call, and the output is drawn `frames_per_piece` frames at a time."""
+    output frames is final, pushed in one call (through the `PoseSmoothStream` `smoother` first, where there is one), and
+    the output is drawn `frames_per_piece` frames at a time."""
+    def push(frames: List) -> Tensor:
+        batch = _stacked(frames)
+        return stream.push(batch if smoother is None else smoother.push(batch))
+
     if (stream.params.h, stream.params.w) != size:
         raise ValueError(f"pose_feed: the retargeter was opened for {(stream.params.h, stream.params.w)}, the frames are {size}")
     ready: Optional[Tensor] = None         # retargeted frames not yet drawn, fewer than a piece
@@ -91,35 +96,38 @@ def _retargeted_feed(keypoints: Iterable, renderer: PoseRenderer, stream, size: 
         held = 0 if ready is None else ready.shape[0]
         if held + rr.plan(stream.frames_in, len(gathered), stream.params.num, stream.params.den)[1] < frames_per_piece:
             continue
-        new, gathered = stream.push(_stacked(gathered)), []
+        new, gathered = push(gathered), []
         ready = new if ready is None else torch.cat([ready, new])
         while ready.shape[0] >= frames_per_piece:
             piece, ready = ready[:frames_per_piece], ready[frames_per_piece:]
             yield renderer.render(piece, size, "pose", torch.uint8, False, score_threshold)
     if gathered:                           # source frames behind the last output frame: they make nothing final
-        new = stream.push(_stacked(gathered))
+        new = push(gathered)
         ready = new if ready is None else torch.cat([ready, new])
     if ready is not None and ready.shape[0]:
         yield renderer.render(ready, size, "pose", torch.uint8, False, score_threshold)
 
 
 def pose_feed(keypoints: Iterable, renderer: PoseRenderer, size: Sequence[int], frames_per_piece: int = 12, normalized: bool = True,
-              score_threshold: float = 0.3, retargeter=None) -> Iterator[Tensor]:
+              score_threshold: float = 0.3, retargeter=None, smoother=None) -> Iterator[Tensor]:
     """Keypoints as the pieces `CausalInferencePipeline.stream(pose_feed=...)` pulls, the counterpart of `jpeg.pose_feed`:
     uint8 [3, n, H, W], n = `frames_per_piece` (the last piece may be shorter), each rendered when it is asked for.
     `keypoints` yields one frame at a time, [P, 134, 3] or [134, 3] (an array [F, P, 134, 3] does); it may be a live source.
     `retargeter`: a `PoseRetargetStream` (`PoseRetargeter.open_stream`, opened for the same `size`) the source frames go
     through first; pieces are then counted in its OUTPUT frames, and `normalized` is the stream's own (its output is drawn
-    as pixels)."""
+    as pixels).  `smoother`: a `PoseSmoothStream` (`PoseSmoother.open_stream`) the source frames go through before anything
+    else: with a retargeter each gathered batch is smoothed and then pushed to it, without one each piece is smoothed and
+    then drawn with `normalized`."""
     if frames_per_piece < 1:
         raise ValueError(f"frames_per_piece must be >= 1, got {frames_per_piece}")
     check_arguments(size, "pose", torch.uint8, score_threshold)
     if retargeter is not None:
-        yield from _retargeted_feed(keypoints, renderer, retargeter, pr.check_size(size), frames_per_piece, score_threshold)
+        yield from _retargeted_feed(keypoints, renderer, retargeter, pr.check_size(size), frames_per_piece, score_threshold, smoother)
         return
 
     def piece_of(frames: List) -> Tensor:
-        return renderer.render(_stacked(frames), size, "pose", torch.uint8, normalized, score_threshold)
+        stacked = _stacked(frames)
+        return renderer.render(stacked if smoother is None else smoother.push(stacked), size, "pose", torch.uint8, normalized, score_threshold)
 
     piece: List = []
     for k in keypoints:

@@ -34,6 +34,7 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::pose_render_frames(keypoints, height, width, layout, dtype, normalized, score_threshold) -> out
     sf_hip::pose_render_frames_out(out!, keypoints, layout, normalized, score_threshold) -> ()
     sf_hip::pose_retarget_frames(src, first, ref, src0, out0, n_out, num, den, src_sx, src_sy, ref_sx, ref_sy, score_threshold, align) -> out
+    sf_hip::pose_smooth_frames(src, state!, period, min_cutoff, beta, kd, score_threshold, max_gap) -> out
 
 Models (weights + C descriptors) are Python objects that own device memory; operators take an integer HANDLE from
 `register_model` (a constant to a tracer).  There is no CPU implementation: CPU tensors raise.
@@ -1000,6 +1001,44 @@ def pose_retarget_frames(src: Tensor, first: Tensor, ref: Tensor, src0: int, out
 def _(src, first, ref, src0, out0, n_out, num, den, src_sx, src_sy, ref_sx, ref_sy, score_threshold=0.3, align=True):
     _, p, _ = _pose_retarget_geometry(src, first, ref, n_out)
     return src.new_empty((n_out, p, 134, 3), dtype=torch.float32)
+
+
+# ------------------------------------------------------------------------------------------ pose smoother
+def _pose_smooth_geometry(src: Tensor, state: Tensor) -> Tuple[int, int]:
+    """(n, P) of src [n, P, 134, 3] and its state, int32 [P, 134, 8]."""
+    if src.dim() != 4 or tuple(src.shape[2:]) != (134, 3) or not 1 <= src.shape[0] <= _lib.POSE_RETARGET_MAX_FRAMES \
+            or not 1 <= src.shape[1] <= _lib.POSE_RENDER_MAX_PEOPLE:
+        raise ValueError(f"pose_smooth_frames: src must be [n, P, 134, 3] with 1 <= n <= {_lib.POSE_RETARGET_MAX_FRAMES} and 1 <= P <= "
+                         f"{_lib.POSE_RENDER_MAX_PEOPLE}, got {tuple(src.shape)}")
+    n, p = int(src.shape[0]), int(src.shape[1])
+    if state.dtype != torch.int32 or tuple(state.shape) != (p, 134, 8):
+        raise ValueError(f"pose_smooth_frames: state must be int32 [{p}, 134, 8], got {state.dtype} {tuple(state.shape)}")
+    return n, p
+
+
+@custom_op(f"{NAMESPACE}::pose_smooth_frames", mutates_args=("state",))
+def pose_smooth_frames(src: Tensor, state: Tensor, period: float, min_cutoff: float, beta: float, kd: float, score_threshold: float = 0.3,
+                       max_gap: int = 0) -> Tensor:
+    """float32 frames [n, P, 134, 3] of a clip and the packed filter state int32 [P, 134, 8] it has reached (zeros before the
+    first frame), on one device -> the frames smoothed, float32 [n, P, 134, 3], every number as
+    `pose_smooth_reference.frames` defines it; `state` is advanced in place (sf_pose_smooth_frames)."""
+    n, p = _pose_smooth_geometry(src, state)
+    _need_gpu(src, "src", torch.float32)
+    _need_gpu(state, "state", torch.int32)
+    if state.device != src.device or not src.is_contiguous() or not state.is_contiguous() or state.data_ptr() % 16:
+        raise ValueError(f"pose_smooth_frames: src and state must be contiguous and on one device, state 16-byte aligned (src on {src.device}, "
+                         f"state on {state.device})")
+    out = torch.empty((n, p, 134, 3), dtype=torch.float32, device=src.device)
+    args = _lib.PoseSmoothArgs(src=src.data_ptr(), out=out.data_ptr(), state=state.data_ptr(), n=n, people=p, period=period, min_cutoff=min_cutoff,
+                               beta=beta, kd=kd, score_threshold=score_threshold, max_gap=max_gap)
+    _lib.check(_lib.lib().sf_pose_smooth_frames(C.byref(args), _stream(src)), "sf_pose_smooth_frames")
+    return out
+
+
+@pose_smooth_frames.register_fake
+def _(src, state, period, min_cutoff, beta, kd, score_threshold=0.3, max_gap=0):
+    n, p = _pose_smooth_geometry(src, state)
+    return src.new_empty((n, p, 134, 3), dtype=torch.float32)
 
 
 # every operator this module registered, by its name under torch.ops.sf_hip
