@@ -38,6 +38,10 @@ recorded at another frame rate to the pipeline's 16 frames/s, and `--pose_source
 where its aspect differs from the output's: all three run on the GPU in `PoseRetargeter`, between the upload and the renderer.
 `--pose_smooth MIN_CUTOFF[,BETA[,D_CUTOFF]]` steadies jittery keypoints with a One-Euro filter per point and `--pose_hold N` bridges up to N
 frames in which a point is missing, both on the GPU in `PoseSmoother`, in front of the retargeter; the reference file is never smoothed.
+`--pose_track [SLOTS]` first puts each person of a multi-person keypoint file into one stable slot across frames (`PoseTracker`, on the GPU,
+in front of the smoother), for detectors that list the people of a frame in detection order; `--pose_track_gate G` is how far a person may
+move between matches, in diagonals of its own body box, and `--pose_track_age N` how many frames a slot waits for its person.  The
+reference file is never tracked.
 
 `--i2v` (inference.py:83-90, 136-149) reads `--data_path` as a TextImagePairDataset directory -- one
 `target_crop_info_<ratio>.json` listing `file_name` / `caption` entries, images under `<ratio>/` --, encodes each
@@ -164,15 +168,21 @@ def read_keypoints(path: str, one_frame: bool = False):
 
 
 def load_pose_keypoints(clip_path: str, ref_path: str, device, size, normalized: bool = True, align: bool = False, source_fps=None, source_size=None,
-                        smooth=None, hold: int = 0):
+                        smooth=None, hold: int = 0, track=None):
     """(dwpose_data uint8 [3, F, H, W], random_ref_dwpose uint8 [H, W, 3]) on `device`, drawn there from two keypoint files.
-    With `smooth` = (min_cutoff[, beta[, d_cutoff]]) or `hold` > 0 the clip first goes through `PoseSmoother` at `source_fps`
+    With `track` = a dict of `PoseTracker.track` arguments (slots, gate, max_age; an empty one for the defaults) the clip first
+    goes through `PoseTracker`.  With `smooth` = (min_cutoff[, beta[, d_cutoff]]) or `hold` > 0 it then goes through `PoseSmoother` at `source_fps`
     (POSE_TARGET_FPS when none is given); with `align`, a `source_fps` or a `source_size` it then goes through
     `PoseRetargeter` (to the pipeline's POSE_TARGET_FPS).  The reference pose is drawn from the reference keypoints as they
-    are: it is neither smoothed nor moved."""
+    are: it is neither tracked, smoothed nor moved."""
     renderer = sfa.PoseRenderer(device=device)
     clip, ref = read_keypoints(clip_path), read_keypoints(ref_path, one_frame=True)
     ref_frame = renderer.render(ref, size, "hwc", normalized=normalized)[0]
+    if track is not None:
+        try:
+            clip = sfa.PoseTracker(device=device).track(clip, **track).keypoints
+        except ValueError as e:
+            raise SystemExit(f"{clip_path}: {e}")
     if smooth is not None or hold:
         try:
             clip = sfa.PoseSmoother(device=device).smooth(clip, POSE_TARGET_FPS if source_fps is None else source_fps, *(smooth or ()), max_gap=hold)
@@ -255,6 +265,14 @@ def main():
     ap.add_argument("--pose_hold", type=int, default=None, metavar="N",
                     help="keypoint --pose_path: bridge up to N frames in a row in which a point is missing with its last smoothed position "
                          "(PoseSmoother; with no --pose_smooth the filter runs at its defaults)")
+    ap.add_argument("--pose_track", nargs="?", const="", default=None, metavar="SLOTS",
+                    help="keypoint --pose_path: put each person into one stable slot across frames on the GPU (PoseTracker) before anything else, "
+                         "for keypoints whose people are listed in detection order; SLOTS (1..8) is the number of people kept at once, by default "
+                         "the number of people per frame in the file")
+    ap.add_argument("--pose_track_gate", type=float, default=None, metavar="G",
+                    help="--pose_track: how far a person may move between two matches, in diagonals of its own body box (default 0.5)")
+    ap.add_argument("--pose_track_age", type=int, default=None, metavar="N",
+                    help="--pose_track: the frames a slot waits for its person before it is freed (default 2); keep --pose_hold at or below it")
     ap.add_argument("--pose_resize", choices=("none", "stretch", "cover"), default="none",
                     help="--pose_path clip.avi: resize the clip and --ref_pose_path on the GPU to the output size (8 x the latent size): stretch, or "
                          "cover = the largest centred crop with the output's aspect ratio; none: their size must be the output size.  Does not apply "
@@ -270,7 +288,9 @@ def main():
         ap.error("--jpeg_quality must be 1..100")
     retarget_flags = (("--pose_align", a.pose_align), ("--pose_fps", a.pose_fps is not None), ("--pose_source_size", a.pose_source_size is not None))
     smooth_flags = (("--pose_smooth", a.pose_smooth is not None), ("--pose_hold", a.pose_hold is not None))       # they do not retarget
-    pose_source_size = pose_smooth = None
+    track_flags = (("--pose_track", a.pose_track is not None), ("--pose_track_gate", a.pose_track_gate is not None),
+                   ("--pose_track_age", a.pose_track_age is not None))                                               # nor do these
+    pose_source_size = pose_smooth = pose_track = None
     if a.pose_path or a.pose_weights_path or a.pose_random_init_seed is not None:
         if not a.pose_path or (a.pose_weights_path is None) == (a.pose_random_init_seed is None):
             ap.error("pose conditioning needs --pose_path and exactly one of --pose_weights_path / --pose_random_init_seed")
@@ -292,7 +312,7 @@ def main():
             ap.error(f"--ref_pose_path {a.ref_pose_path}: keypoints (.npz / .npy array) expected beside a keypoint --pose_path")
         if a.pose_pixel_coords and pose_kind != "keypoints":
             ap.error("--pose_pixel_coords goes with a keypoint --pose_path (.npz / .npy array)")
-        for flag, given in retarget_flags + smooth_flags:
+        for flag, given in retarget_flags + smooth_flags + track_flags:
             if given and pose_kind != "keypoints":
                 ap.error(f"{flag} goes with a keypoint --pose_path (.npz / .npy array)")
         if a.pose_fps is not None:
@@ -316,12 +336,28 @@ def main():
                 sfa.pose_smooth_reference.prepare(POSE_TARGET_FPS if a.pose_fps is None else a.pose_fps, *pose_smooth, max_gap=a.pose_hold or 0)
             except ValueError as e:
                 ap.error(f"--pose_smooth {a.pose_smooth} --pose_hold {a.pose_hold}: {e}")
+        if any(given for _, given in track_flags):
+            if a.pose_track is None:
+                ap.error("--pose_track_gate and --pose_track_age go with --pose_track")
+            try:
+                slots = int(a.pose_track) if a.pose_track else None                                                   # "": the people per frame
+            except ValueError:
+                ap.error(f"--pose_track {a.pose_track}: SLOTS expected, an integer in 1..8")
+            pose_track = {name: value for name, value in (("slots", slots), ("gate", a.pose_track_gate), ("max_age", a.pose_track_age))
+                          if value is not None}
+            try:
+                tracked = sfa.pose_track_reference.prepare(**pose_track)
+            except ValueError as e:
+                ap.error(f"--pose_track {a.pose_track} --pose_track_gate {a.pose_track_gate} --pose_track_age {a.pose_track_age}: {e}")
+            if (a.pose_hold or 0) > tracked.max_age:
+                ap.error(f"--pose_hold {a.pose_hold} exceeds --pose_track_age {tracked.max_age}: a tracker's slot is empty for max_age + 1 frames "
+                         f"between two different people, so a longer hold could smooth one person towards another")
     elif a.ref_pose_path:
         ap.error("--ref_pose_path needs --pose_path clip.avi or keypoints (.npz / .npy array)")
     elif a.pose_pixel_coords:
         ap.error("--pose_pixel_coords needs a keypoint --pose_path")
     else:
-        for flag, given in retarget_flags + smooth_flags:
+        for flag, given in retarget_flags + smooth_flags + track_flags:
             if given:
                 ap.error(f"{flag} needs a keypoint --pose_path")
     if a.pose_resize != "none" and not (a.pose_path and a.pose_path.lower().endswith(".avi")):
@@ -408,7 +444,7 @@ def main():
             pose_data = load_pose_mjpeg(a.pose_path, a.ref_pose_path, device, pose_size, "stretch" if pose_size is None else a.pose_resize)
         elif pose_kind == "keypoints":
             pose_data = load_pose_keypoints(a.pose_path, a.ref_pose_path, device, (8 * a.latent_height, 8 * a.latent_width), not a.pose_pixel_coords,
-                                            a.pose_align, a.pose_fps, pose_source_size, pose_smooth, a.pose_hold or 0)
+                                            a.pose_align, a.pose_fps, pose_source_size, pose_smooth, a.pose_hold or 0, pose_track)
         else:
             pose_data = load_pose(a.pose_path)
     image_encoder = input_image = None

@@ -987,6 +987,52 @@ int sf_pose_smooth_frames(const sf_pose_smooth_args* args, void* stream);
 size_t sf_pose_smooth_state_bytes(int people);
 
 /* ==========================================================================================
+ * Pose tracker (the people of each frame in the detector's order -> each person in one stable slot, in front of the
+ * smoother).  The reference has no counterpart: its poses arrive drawn.  The numbers are this project's definition,
+ * self_forcing_amd/pose_track_reference.py (`frames`): float32, every sub, mul, add and div rounded on its own; the
+ * kernels equal it bit for bit.  A slot's output row is the matched detection's 134 x 3 floats copied bit for bit, or
+ * the marker (-1, -1, 0) at all 134 points; ids[f][s] is the track id, -1 beside a marker row.
+ *   valid     a point, by the renderer's rule on the raw values: x, y, score finite, score >= score_threshold, x >= 0,
+ *             y >= 0.  Only the body points 0..17 are matched; a detection is a person iff >= min_points of them are valid.
+ *   state     [slots + 1][40] 32-bit words.  Row s < slots: words 0..35 the float bits of x, y of the 18 points of the
+ *             last detection matched to the slot, 36 their validity mask (bit j for point j), 37 age (frames since that
+ *             match), 38 id, 39 alive.  Row `slots`: next_id in word 0, the rest is not touched.  Zero-filled is fresh.
+ *   cost      of (live slot t, person d) over the points j = 0..17, ascending, valid in both (n of them):
+ *               dx = xd - xt;  dy = yd - yt;  q = dx * dx + dy * dy;  acc = acc + q;
+ *             w, h = max - min of the slot's valid x and y;  s2 = w * w + h * h;  cost = (acc / (float)n) / s2.
+ *             Admissible iff n >= min_common, s2 > 0 and finite, cost finite, cost <= gate2.
+ *   a frame   match: repeatedly the admissible pair of an unassigned slot and an unassigned person with the smallest
+ *             (cost bits, t, d); age: a matched slot gets age = 0, an unmatched live one age += 1 and dies if
+ *             age > max_age; birth: the unassigned persons in ascending order take the lowest slots that were free at the
+ *             START of the frame, id = next_id++ & 0x7fffffff, and those without a slot are dropped; the memory of every
+ *             slot that has a detection is replaced.
+ * Two kernels on one stream: a one-wave assignment kernel that walks the piece's frames (lane = 8 * slot + detection,
+ * the state in LDS) and writes assign[f][s] = the detection index or -1, and a gather kernel over every element of out.
+ * The library keeps no state: the caller owns `state` and hands it to every piece of one clip, so any partition of a
+ * clip gives the whole clip's bits.  `assign` is scratch of n * slots * 4 bytes; its contents after the call are the
+ * detection indices.
+ * ========================================================================================== */
+
+typedef struct sf_pose_track_args {
+  const float* src;           /* DEVICE float32 [n][people][134][3], in the caller's units                             */
+  float* out;                 /* DEVICE float32 [n][slots][134][3]; every element is written                           */
+  int32_t* ids;               /* DEVICE int32 [n][slots]; every element is written                                     */
+  void* state;                /* DEVICE [slots + 1][40] 32-bit words, 16-byte aligned; read and advanced               */
+  int32_t* assign;            /* DEVICE scratch int32 [n][slots], 4-byte aligned; every element is written             */
+  int32_t n, people, slots;   /* 1 <= n <= SF_POSE_RETARGET_MAX_FRAMES, 1 <= people, slots <= SF_POSE_RENDER_MAX_PEOPLE; no two of the five ranges overlap */
+  int32_t min_points;         /* 1 .. 18: the valid body points that make a detection a person                         */
+  int32_t min_common;         /* 1 .. 18: the points a slot and a person must share to be compared                     */
+  int32_t max_age;            /* 0 .. 65535: the frames a slot waits for its person before it is freed                 */
+  float gate2;                /* fp32(gate * gate): the largest admissible cost; finite, > 0                           */
+  float score_threshold;      /* finite                                                                                */
+} sf_pose_track_args;
+
+int sf_pose_track_frames(const sf_pose_track_args* args, void* stream);
+
+/* Host only: the bytes of `state` for `slots` slots ((slots + 1) * 160); 0 for slots out of range. */
+size_t sf_pose_track_state_bytes(int slots);
+
+/* ==========================================================================================
  * Pose front end (DWPose frames -> pose tokens): `dwpose_embedding` and `randomref_embedding_pose` of the many-step
  * sampler (pipeline/causal_diffusion_inference.py:87-122) with their input transform (:337-343).  Runs once per clip.
  * Activations are channels-last bf16 volumes [T][H][W][C] with C = 8 (the three input channels, stored padded with

@@ -56,6 +56,7 @@ RESIZE_MAX_RATIO = 8
 POSE_RENDER_MAX_PEOPLE, POSE_RENDER_MAX_SIZE, POSE_RENDER_MAX_COORD = 8, 4096, 8191
 POSE_RETARGET_MAX_RATE, POSE_RETARGET_MAX_FRAMES = 65535, 1 << 20   # SF_POSE_RETARGET_MAX_RATE / _MAX_FRAMES
 POSE_SMOOTH_MAX_GAP = 65535                                         # sf_pose_smooth_args.max_gap
+POSE_TRACK_MAX_AGE, POSE_TRACK_STATE_WORDS = 65535, 40              # sf_pose_track_args.max_age; the words of a row of its state
 # enum sf_clip_dtype
 CLIP_DTYPES = {"float32": 0, "bfloat16": 1}
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
@@ -261,6 +262,12 @@ class PoseSmoothArgs(C.Structure):
                 + [("max_gap", C.c_int32)])
 
 
+class PoseTrackArgs(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("src", "out", "ids", "state", "assign")]
+                + [(n, C.c_int32) for n in ("n", "people", "slots", "min_points", "min_common", "max_age")]
+                + [(n, C.c_float) for n in ("gate2", "score_threshold")])
+
+
 class PoseConvArgs(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("x", "w", "bias", "out")]
                 + [(n, C.c_int32) for n in ("T", "H", "W", "Cin", "Cout", "kt", "stride_t", "stride_s", "ldw", "ldo", "silu")])
@@ -389,6 +396,8 @@ SIGNATURES = {
     "sf_pose_retarget_plan": (C.c_int, [_i64, _i64, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sf_pose_smooth_frames": (C.c_int, [C.POINTER(PoseSmoothArgs), _vp]),
     "sf_pose_smooth_state_bytes": (C.c_size_t, [_i]),
+    "sf_pose_track_frames": (C.c_int, [C.POINTER(PoseTrackArgs), _vp]),
+    "sf_pose_track_state_bytes": (C.c_size_t, [_i]),
     "sf_embedding_gather": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_t5_softmax_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_mul_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),

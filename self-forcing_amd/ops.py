@@ -646,6 +646,20 @@ def pose_smooth_state_bytes(people: int) -> int:
     return int(lib().sf_pose_smooth_state_bytes(people))
 
 
+# -------------------------------------------------------------------------------------- pose tracker (csrc/pose_track.hip)
+def pose_track_frames(src: Tensor, state: Tensor, slots: int, gate2: float, threshold: float = 0.3, min_points: int = 4, min_common: int = 3,
+                      max_age: int = 2) -> Tuple[Tensor, Tensor]:
+    """The detections of one piece of a clip (float32 [n, P, 134, 3] on the device, in any order per frame) and the packed
+    tracker state int32 [slots + 1, 40] the clip has reached -> (float32 [n, slots, 134, 3] with each person in one slot,
+    int32 [n, slots] track ids); `state` is advanced in place (torch.ops.sf_hip.pose_track_frames over sf_pose_track_frames)."""
+    return torch.ops.sf_hip.pose_track_frames(src, state, slots, gate2, threshold, min_points, min_common, max_age)
+
+
+def pose_track_state_bytes(slots: int) -> int:
+    """sf_pose_track_state_bytes: the bytes of the state of `slots` slots, 0 out of range."""
+    return int(lib().sf_pose_track_state_bytes(slots))
+
+
 # -------------------------------------------------------------------------------------- CLIP image encoder (csrc/clip_encoder.hip)
 def clip_preprocess(frames: Tensor, image_size: int = 224, patch: int = 14, kp: Optional[int] = None) -> Tensor:
     """frames [n, 3, H, W] float32 / bfloat16 in [-1, 1] -> bf16 patch rows [n * (image_size/patch)^2, kp] (sf_clip_preprocess)."""

@@ -78,14 +78,20 @@ def _stacked(frames: List):
     return torch.stack(frames) if isinstance(frames[0], Tensor) else np.stack([np.asarray(k) for k in frames])
 
 
+def _front(batch, tracker, smoother):
+    """A batch of source frames through the tracker, then the smoother, where there are any."""
+    if tracker is not None:
+        batch = tracker.push(batch)
+    return batch if smoother is None else smoother.push(batch)
+
+
 def _retargeted_feed(keypoints: Iterable, renderer: PoseRenderer, stream, size: Tuple[int, int], frames_per_piece: int,
-                     score_threshold: float, smoother=None) -> Iterator[Tensor]:
+                     score_threshold: float, smoother=None, tracker=None) -> Iterator[Tensor]:
     """`pose_feed` through a `PoseRetargetStream`: source frames are gathered until the stream's plan says that a piece of
-    output frames is final, pushed in one call (through the `PoseSmoothStream` `smoother` first, where there is one), and
-    the output is drawn `frames_per_piece` frames at a time."""
+    output frames is final, pushed in one call (through the `PoseTrackStream` `tracker` and then the `PoseSmoothStream`
+    `smoother` first, where there are any), and the output is drawn `frames_per_piece` frames at a time."""
     def push(frames: List) -> Tensor:
-        batch = _stacked(frames)
-        return stream.push(batch if smoother is None else smoother.push(batch))
+        return stream.push(_front(_stacked(frames), tracker, smoother))
 
     if (stream.params.h, stream.params.w) != size:
         raise ValueError(f"pose_feed: the retargeter was opened for {(stream.params.h, stream.params.w)}, the frames are {size}")
@@ -109,7 +115,7 @@ def _retargeted_feed(keypoints: Iterable, renderer: PoseRenderer, stream, size: 
 
 
 def pose_feed(keypoints: Iterable, renderer: PoseRenderer, size: Sequence[int], frames_per_piece: int = 12, normalized: bool = True,
-              score_threshold: float = 0.3, retargeter=None, smoother=None) -> Iterator[Tensor]:
+              score_threshold: float = 0.3, retargeter=None, smoother=None, tracker=None) -> Iterator[Tensor]:
     """Keypoints as the pieces `CausalInferencePipeline.stream(pose_feed=...)` pulls, the counterpart of `jpeg.pose_feed`:
     uint8 [3, n, H, W], n = `frames_per_piece` (the last piece may be shorter), each rendered when it is asked for.
     `keypoints` yields one frame at a time, [P, 134, 3] or [134, 3] (an array [F, P, 134, 3] does); it may be a live source.
@@ -117,17 +123,24 @@ def pose_feed(keypoints: Iterable, renderer: PoseRenderer, size: Sequence[int], 
     through first; pieces are then counted in its OUTPUT frames, and `normalized` is the stream's own (its output is drawn
     as pixels).  `smoother`: a `PoseSmoothStream` (`PoseSmoother.open_stream`) the source frames go through before anything
     else: with a retargeter each gathered batch is smoothed and then pushed to it, without one each piece is smoothed and
-    then drawn with `normalized`."""
+    then drawn with `normalized`.  `tracker`: a `PoseTrackStream` (`PoseTracker.open_stream`) in front of the smoother, for a
+    source that lists the people of a frame in no stable order: source frames go through the tracker, then the smoother,
+    then the retargeter.  A tracker keeps a slot empty for at least max_age + 1 frames between two different people, so a
+    smoother that bridges at most max_age frames never filters one person towards another; a smoother whose max_gap
+    exceeds the tracker's max_age is refused."""
+    if tracker is not None and smoother is not None and smoother.params.max_gap > tracker.params.max_age:
+        raise ValueError(f"pose_feed: the smoother bridges gaps of up to max_gap = {smoother.params.max_gap} frames, the tracker keeps a slot empty "
+                         f"for only max_age + 1 = {tracker.params.max_age + 1} frames between two different people: with max_gap > max_age the "
+                         f"smoother could filter one person towards another")
     if frames_per_piece < 1:
         raise ValueError(f"frames_per_piece must be >= 1, got {frames_per_piece}")
     check_arguments(size, "pose", torch.uint8, score_threshold)
     if retargeter is not None:
-        yield from _retargeted_feed(keypoints, renderer, retargeter, pr.check_size(size), frames_per_piece, score_threshold, smoother)
+        yield from _retargeted_feed(keypoints, renderer, retargeter, pr.check_size(size), frames_per_piece, score_threshold, smoother, tracker)
         return
 
     def piece_of(frames: List) -> Tensor:
-        stacked = _stacked(frames)
-        return renderer.render(stacked if smoother is None else smoother.push(stacked), size, "pose", torch.uint8, normalized, score_threshold)
+        return renderer.render(_front(_stacked(frames), tracker, smoother), size, "pose", torch.uint8, normalized, score_threshold)
 
     piece: List = []
     for k in keypoints:

@@ -35,6 +35,7 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::pose_render_frames_out(out!, keypoints, layout, normalized, score_threshold) -> ()
     sf_hip::pose_retarget_frames(src, first, ref, src0, out0, n_out, num, den, src_sx, src_sy, ref_sx, ref_sy, score_threshold, align) -> out
     sf_hip::pose_smooth_frames(src, state!, period, min_cutoff, beta, kd, score_threshold, max_gap) -> out
+    sf_hip::pose_track_frames(src, state!, slots, gate2, score_threshold, min_points, min_common, max_age) -> (out, ids)
 
 Models (weights + C descriptors) are Python objects that own device memory; operators take an integer HANDLE from
 `register_model` (a constant to a tracer).  There is no CPU implementation: CPU tensors raise.
@@ -1039,6 +1040,49 @@ def pose_smooth_frames(src: Tensor, state: Tensor, period: float, min_cutoff: fl
 def _(src, state, period, min_cutoff, beta, kd, score_threshold=0.3, max_gap=0):
     n, p = _pose_smooth_geometry(src, state)
     return src.new_empty((n, p, 134, 3), dtype=torch.float32)
+
+
+# ------------------------------------------------------------------------------------------ pose tracker
+def _pose_track_geometry(src: Tensor, state: Tensor, slots: int) -> Tuple[int, int]:
+    """(n, P) of src [n, P, 134, 3]; its state is int32 [slots + 1, 40]."""
+    if src.dim() != 4 or tuple(src.shape[2:]) != (134, 3) or not 1 <= src.shape[0] <= _lib.POSE_RETARGET_MAX_FRAMES \
+            or not 1 <= src.shape[1] <= _lib.POSE_RENDER_MAX_PEOPLE:
+        raise ValueError(f"pose_track_frames: src must be [n, P, 134, 3] with 1 <= n <= {_lib.POSE_RETARGET_MAX_FRAMES} and 1 <= P <= "
+                         f"{_lib.POSE_RENDER_MAX_PEOPLE}, got {tuple(src.shape)}")
+    if not 1 <= slots <= _lib.POSE_RENDER_MAX_PEOPLE:
+        raise ValueError(f"pose_track_frames: slots must be 1..{_lib.POSE_RENDER_MAX_PEOPLE}, got {slots}")
+    if state.dtype != torch.int32 or tuple(state.shape) != (slots + 1, _lib.POSE_TRACK_STATE_WORDS):
+        raise ValueError(f"pose_track_frames: state must be int32 [{slots + 1}, {_lib.POSE_TRACK_STATE_WORDS}], got {state.dtype} {tuple(state.shape)}")
+    return int(src.shape[0]), int(src.shape[1])
+
+
+@custom_op(f"{NAMESPACE}::pose_track_frames", mutates_args=("state",))
+def pose_track_frames(src: Tensor, state: Tensor, slots: int, gate2: float, score_threshold: float = 0.3, min_points: int = 4,
+                      min_common: int = 3, max_age: int = 2) -> Tuple[Tensor, Tensor]:
+    """float32 detections [n, P, 134, 3] of a clip, in any order per frame, and the packed tracker state int32 [slots + 1, 40]
+    it has reached (zeros before the first frame), on one device -> (the frames with each person in one slot, float32
+    [n, slots, 134, 3], and the track ids int32 [n, slots]), as `pose_track_reference.frames` defines them; `state` is
+    advanced in place (sf_pose_track_frames; its scratch of n * slots int32 is allocated here)."""
+    n, p = _pose_track_geometry(src, state, slots)
+    _need_gpu(src, "src", torch.float32)
+    _need_gpu(state, "state", torch.int32)
+    if state.device != src.device or not src.is_contiguous() or not state.is_contiguous() or state.data_ptr() % 16:
+        raise ValueError(f"pose_track_frames: src and state must be contiguous and on one device, state 16-byte aligned (src on {src.device}, "
+                         f"state on {state.device})")
+    out = torch.empty((n, slots, 134, 3), dtype=torch.float32, device=src.device)
+    ids = torch.empty((n, slots), dtype=torch.int32, device=src.device)
+    assign = torch.empty((n, slots), dtype=torch.int32, device=src.device)
+    args = _lib.PoseTrackArgs(src=src.data_ptr(), out=out.data_ptr(), ids=ids.data_ptr(), state=state.data_ptr(), assign=assign.data_ptr(), n=n,
+                              people=p, slots=slots, min_points=min_points, min_common=min_common, max_age=max_age, gate2=gate2,
+                              score_threshold=score_threshold)
+    _lib.check(_lib.lib().sf_pose_track_frames(C.byref(args), _stream(src)), "sf_pose_track_frames")
+    return out, ids
+
+
+@pose_track_frames.register_fake
+def _(src, state, slots, gate2, score_threshold=0.3, min_points=4, min_common=3, max_age=2):
+    n, _p = _pose_track_geometry(src, state, slots)
+    return src.new_empty((n, slots, 134, 3), dtype=torch.float32), src.new_empty((n, slots), dtype=torch.int32)
 
 
 # every operator this module registered, by its name under torch.ops.sf_hip
