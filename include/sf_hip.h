@@ -1033,6 +1033,102 @@ int sf_pose_track_frames(const sf_pose_track_args* args, void* stream);
 size_t sf_pose_track_state_bytes(int slots);
 
 /* ==========================================================================================
+ * DWPose glue (a frame on the device -> keypoints [F][P][134][3] on the device, around the caller's two networks): what
+ * DWPose does in numpy and OpenCV on the host, one frame and one person at a time.  The reference has no counterpart: its
+ * poses arrive drawn.  The numbers are this project's definition, self_forcing_amd/pose_estimate_reference.py
+ * (`decode_boxes`, `person_window`, `crop_people`, `decode_simcc`): DWPose's formulas in float32, every add, sub, mul and
+ * div rounded on its own, not OpenCV's fixed-point bits; the kernels equal it bit for bit.  DWPose's constants (640 x 640,
+ * strides 8 / 16 / 32, 0.3, 0.45, 1.25, 384 x 288, split ratio 2, mean / std, the reorder) are the caller's arguments.
+ *   boxes     head float32 [F][A][5 + C], anchors stride-major, then row-major (gy, gx).  cx = (o0 + gx) * s, cy likewise,
+ *             w = exp32(o2) * s, h likewise (decoded: o0..o3 as they are); corners cx -+ w * 0.5 and cy -+ h * 0.5, each
+ *             divided by ratio; score = o4 * o[5 + class_index].  exp32: x clamped to [-20, 20], n = rint(x * log2e), a
+ *             two-constant Cody-Waite reduction, a degree-6 Taylor polynomial by Horner, ldexp; within 2^-20 of e^x.  A
+ *             candidate has a finite score > score_threshold and finite corners.  Greedy NMS, at most P rounds: the largest
+ *             live score (ties: the lowest anchor) is emitted and removed with every live candidate whose iou with it is
+ *             > iou_threshold; area = (x2 - x1 + 1) * (y2 - y1 + 1), iw = max(0, min(x2a, x2b) - max(x1a, x1b) + 1).
+ *   window    cx = (x1 + x2) * 0.5; bw = (x2 - x1) * padding; aspect = (float)out_w / (float)out_h; bw > bh * aspect ?
+ *             bh = bw / aspect : bw = bh * aspect; ax = bw / out_w; ay = bh / out_h.  Valid iff all six are finite and
+ *             bw, bh > 0.  A person is PRESENT iff p < count[f] and the window of boxes[f][p] is valid.
+ *   crops     element (c, j, i) of a present person: sx = cx + (i - out_w * 0.5) * ax, x0 = floor(sx), fx = sx - x0 (y
+ *             likewise), four taps (0 outside the frame) blended a = p00 + (p01 - p00) * fx, b likewise, v = a + (b - a) * fy,
+ *             out = (v - mean[c]) / std[c]; v = 0 without a read unless -1 <= sx <= W and -1 <= sy <= H.  Other rows are 0.
+ *   keypoints per (person, point) the first index of the maximum of the non-NaN entries of its simcc_x and simcc_y row;
+ *             s = the smaller maximum; valid iff the person is present, s finite and > 0; x = cx + (ix / split_ratio -
+ *             out_w * 0.5) * ax, y likewise, divided by W and H when normalized; else (-1, -1, 0).  The neck is the mean of
+ *             COCO points 5 and 6 with score 1 when both are valid with s > neck_threshold.  tmp = 17 body points, the
+ *             neck, the other 116; out[i] = tmp[order[i]].
+ * Four kernels: a lane per (frame, anchor) writes the live score and the corners to `scratch`, one workgroup per frame
+ * runs the NMS rounds with its live scores in registers; a lane per crop pixel; a workgroup per person for the keypoints.
+ * The library keeps no state, makes no host read and no synchronisation.
+ * ========================================================================================== */
+
+#define SF_POSE_BOXES_MAX_ANCHORS 16384
+#define SF_POSE_BOXES_MAX_STRIDES 4
+#define SF_POSE_BOXES_MAX_CLASSES 255
+#define SF_POSE_BOXES_MAX_FRAMES 65535
+#define SF_POSE_CROP_MAX_SIZE 1024
+#define SF_POSE_CROP_MAX_FRAME 16384
+#define SF_POSE_SIMCC_POINTS 133
+#define SF_POSE_SIMCC_MAX_BINS 65536
+enum sf_pose_simcc_dtype { SF_POSE_SIMCC_F32 = 0, SF_POSE_SIMCC_F16 = 1 };
+
+typedef struct sf_pose_boxes_args {
+  const float* head;          /* DEVICE float32 [F][A][5 + C], 4-byte aligned                                          */
+  float* boxes;               /* DEVICE float32 [F][P][5] = (x1, y1, x2, y2, score) in descending score, then (-1, -1, -1, -1, 0); every element is written */
+  int32_t* count;             /* DEVICE int32 [F]: the boxes of each frame; every element is written                   */
+  float* scratch;             /* DEVICE sf_pose_boxes_scratch_bytes(F, A) bytes, 4-byte aligned                        */
+  int32_t F, A, C, P;         /* 1 <= F <= 65535, A = sum (in_h / s)(in_w / s) <= 16384, 1 <= C <= 255, 1 <= P <= SF_POSE_RENDER_MAX_PEOPLE; no two ranges overlap */
+  int32_t in_h, in_w;         /* the detector's input size, a multiple of every stride                                 */
+  int32_t n_strides;          /* 1 .. SF_POSE_BOXES_MAX_STRIDES                                                        */
+  int32_t strides[SF_POSE_BOXES_MAX_STRIDES];
+  int32_t class_index;        /* 0 .. C - 1                                                                            */
+  int32_t decoded;            /* 1: o0..o3 are cx, cy, w, h already                                                    */
+  float ratio;                /* the letterbox scale, fp32 min(in_h / H, in_w / W); finite, > 0                        */
+  float score_threshold;      /* finite, >= 0                                                                          */
+  float iou_threshold;        /* finite                                                                                */
+} sf_pose_boxes_args;
+
+int sf_pose_boxes_decode(const sf_pose_boxes_args* args, void* stream);
+
+/* Host only: the bytes of `scratch` (F * A * 20); 0 for F or A out of range. */
+size_t sf_pose_boxes_scratch_bytes(int F, int A);
+
+typedef struct sf_pose_crop_args {
+  const void* frames;         /* DEVICE uint8, F frames of H x W in `layout`                                           */
+  const float* boxes;         /* DEVICE float32 [F][P][5]                                                              */
+  const int32_t* count;       /* DEVICE int32 [F]                                                                      */
+  void* out;                  /* DEVICE [F * P][3][out_h][out_w] in `dtype`; every element is written                  */
+  int32_t F, P, H, W;         /* 1 <= F <= 65535, 1 <= P <= SF_POSE_RENDER_MAX_PEOPLE, 1 <= H, W <= SF_POSE_CROP_MAX_FRAME; no two ranges overlap */
+  int32_t layout;             /* enum sf_jpeg_layout                                                                   */
+  int32_t out_h, out_w;       /* 1 .. SF_POSE_CROP_MAX_SIZE                                                            */
+  int32_t dtype;              /* SF_JPEG_F32 or SF_JPEG_BF16 (round-to-nearest-even of the float32 value)              */
+  int32_t bgr;                /* 1: output channel c is the frame's channel 2 - c                                      */
+  float padding;              /* finite, > 0                                                                           */
+  float mean[3], std[3];      /* by OUTPUT channel; finite, std > 0                                                    */
+} sf_pose_crop_args;
+
+int sf_pose_crop_people(const sf_pose_crop_args* args, void* stream);
+
+typedef struct sf_pose_simcc_args {
+  const void* simcc_x;        /* DEVICE [F * P][133][Wx] in `dtype`                                                    */
+  const void* simcc_y;        /* DEVICE [F * P][133][Wy] in `dtype`                                                    */
+  const float* boxes;         /* DEVICE float32 [F][P][5]                                                              */
+  const int32_t* count;       /* DEVICE int32 [F]                                                                      */
+  float* out;                 /* DEVICE float32 [F][P][134][3]; every element is written                               */
+  const uint8_t* order;       /* HOST uint8 [134], each < 134: out[i] = tmp[order[i]]                                  */
+  int32_t F, P, H, W;         /* as sf_pose_crop_args: the frame the boxes are in                                      */
+  int32_t Wx, Wy;             /* 1 .. SF_POSE_SIMCC_MAX_BINS                                                           */
+  int32_t dtype;              /* enum sf_pose_simcc_dtype; float16 widens exactly                                      */
+  int32_t out_h, out_w;       /* the crop's size, 1 .. SF_POSE_CROP_MAX_SIZE                                           */
+  int32_t normalized;         /* 1: x / W, y / H; 0: source-frame pixels                                               */
+  float padding;              /* as the crop's                                                                         */
+  float split_ratio;          /* bins per crop pixel; finite, > 0                                                      */
+  float neck_threshold;       /* finite                                                                                */
+} sf_pose_simcc_args;
+
+int sf_pose_simcc_decode(const sf_pose_simcc_args* args, void* stream);
+
+/* ==========================================================================================
  * Pose front end (DWPose frames -> pose tokens): `dwpose_embedding` and `randomref_embedding_pose` of the many-step
  * sampler (pipeline/causal_diffusion_inference.py:87-122) with their input transform (:337-343).  Runs once per clip.
  * Activations are channels-last bf16 volumes [T][H][W][C] with C = 8 (the three input channels, stored padded with

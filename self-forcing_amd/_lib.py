@@ -57,6 +57,10 @@ POSE_RENDER_MAX_PEOPLE, POSE_RENDER_MAX_SIZE, POSE_RENDER_MAX_COORD = 8, 4096, 8
 POSE_RETARGET_MAX_RATE, POSE_RETARGET_MAX_FRAMES = 65535, 1 << 20   # SF_POSE_RETARGET_MAX_RATE / _MAX_FRAMES
 POSE_SMOOTH_MAX_GAP = 65535                                         # sf_pose_smooth_args.max_gap
 POSE_TRACK_MAX_AGE, POSE_TRACK_STATE_WORDS = 65535, 40              # sf_pose_track_args.max_age; the words of a row of its state
+# SF_POSE_BOXES_MAX_* / SF_POSE_CROP_MAX_* / SF_POSE_SIMCC_*; enum sf_pose_simcc_dtype (the crop's output types are JPEG_DTYPES' two float ones)
+POSE_BOXES_MAX_ANCHORS, POSE_BOXES_MAX_STRIDES, POSE_BOXES_MAX_CLASSES, POSE_BOXES_MAX_FRAMES = 16384, 4, 255, 65535
+POSE_CROP_MAX_SIZE, POSE_CROP_MAX_FRAME, POSE_SIMCC_POINTS, POSE_SIMCC_MAX_BINS = 1024, 16384, 133, 65536
+POSE_SIMCC_DTYPES = {"float32": 0, "float16": 1}
 # enum sf_clip_dtype
 CLIP_DTYPES = {"float32": 0, "bfloat16": 1}
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
@@ -268,6 +272,26 @@ class PoseTrackArgs(C.Structure):
                 + [(n, C.c_float) for n in ("gate2", "score_threshold")])
 
 
+class PoseBoxesArgs(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("head", "boxes", "count", "scratch")]
+                + [(n, C.c_int32) for n in ("F", "A", "C", "P", "in_h", "in_w", "n_strides")]
+                + [("strides", C.c_int32 * POSE_BOXES_MAX_STRIDES)]
+                + [("class_index", C.c_int32), ("decoded", C.c_int32)]
+                + [(n, C.c_float) for n in ("ratio", "score_threshold", "iou_threshold")])
+
+
+class PoseCropArgs(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("frames", "boxes", "count", "out")]
+                + [(n, C.c_int32) for n in ("F", "P", "H", "W", "layout", "out_h", "out_w", "dtype", "bgr")]
+                + [("padding", C.c_float), ("mean", C.c_float * 3), ("std", C.c_float * 3)])
+
+
+class PoseSimccArgs(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("simcc_x", "simcc_y", "boxes", "count", "out", "order")]
+                + [(n, C.c_int32) for n in ("F", "P", "H", "W", "Wx", "Wy", "dtype", "out_h", "out_w", "normalized")]
+                + [(n, C.c_float) for n in ("padding", "split_ratio", "neck_threshold")])
+
+
 class PoseConvArgs(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("x", "w", "bias", "out")]
                 + [(n, C.c_int32) for n in ("T", "H", "W", "Cin", "Cout", "kt", "stride_t", "stride_s", "ldw", "ldo", "silu")])
@@ -398,6 +422,10 @@ SIGNATURES = {
     "sf_pose_smooth_state_bytes": (C.c_size_t, [_i]),
     "sf_pose_track_frames": (C.c_int, [C.POINTER(PoseTrackArgs), _vp]),
     "sf_pose_track_state_bytes": (C.c_size_t, [_i]),
+    "sf_pose_boxes_decode": (C.c_int, [C.POINTER(PoseBoxesArgs), _vp]),
+    "sf_pose_boxes_scratch_bytes": (C.c_size_t, [_i, _i]),
+    "sf_pose_crop_people": (C.c_int, [C.POINTER(PoseCropArgs), _vp]),
+    "sf_pose_simcc_decode": (C.c_int, [C.POINTER(PoseSimccArgs), _vp]),
     "sf_embedding_gather": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_t5_softmax_bias": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sf_mul_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),

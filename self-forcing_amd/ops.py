@@ -660,6 +660,49 @@ def pose_track_state_bytes(slots: int) -> int:
     return int(lib().sf_pose_track_state_bytes(slots))
 
 
+# -------------------------------------------------------------------------------------- DWPose glue (csrc/pose_estimate.hip)
+def decode_boxes(head: Tensor, ratio: float, max_people: int, input_size=(640, 640), strides=(8, 16, 32), class_index: int = 0,
+                 score_threshold: float = 0.3, iou_threshold: float = 0.45, decoded: bool = False) -> Tuple[Tensor, Tensor]:
+    """A YOLOX head float32 [F, A, 5 + C] on the device -> (boxes float32 [F, P, 5] in source-frame pixels, count int32 [F])
+    (torch.ops.sf_hip.pose_boxes_decode over sf_pose_boxes_decode); ratio = the letterbox scale min(in_h / H, in_w / W)."""
+    return torch.ops.sf_hip.pose_boxes_decode(head, int(input_size[0]), int(input_size[1]), [int(s) for s in strides], float(ratio), max_people,
+                                              class_index, float(score_threshold), float(iou_threshold), decoded)
+
+
+def pose_boxes_scratch_bytes(frames: int, anchors: int) -> int:
+    """sf_pose_boxes_scratch_bytes: the bytes of scratch behind `decode_boxes`, 0 out of range."""
+    return int(lib().sf_pose_boxes_scratch_bytes(frames, anchors))
+
+
+def crop_people(frames: Tensor, boxes: Tensor, count: Tensor, layout: str = "hwc", out_size=(384, 288), padding: float = 1.25,
+                mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), channels: str = "rgb", dtype=torch.float32) -> Tensor:
+    """uint8 frames in `layout` and their people -> the pose network's input [F * P, 3, out_h, out_w] in `dtype`
+    (torch.ops.sf_hip.pose_crop_people over sf_pose_crop_people)."""
+    if channels not in ("rgb", "bgr"):
+        raise ValueError(f"channels must be 'rgb' or 'bgr', got {channels!r}")
+    return torch.ops.sf_hip.pose_crop_people(frames, boxes, count, layout, int(out_size[0]), int(out_size[1]), float(padding), [float(v) for v in mean],
+                                             [float(v) for v in std], channels == "bgr", dtype)
+
+
+def decode_simcc(simcc_x: Tensor, simcc_y: Tensor, boxes: Tensor, count: Tensor, frame_size, out_size=(384, 288), padding: float = 1.25,
+                 split_ratio: float = 2.0, normalized: bool = True, neck_threshold: float = 0.3, order=None) -> Tensor:
+    """SimCC logits and the people they were cropped for -> keypoints float32 [F, P, 134, 3] in the renderer's layout
+    (torch.ops.sf_hip.pose_simcc_decode over sf_pose_simcc_decode); order: `pose_estimate_reference.reorder_table` (a host uint8 tensor or array), DWPose's by default."""
+    global _POSE_ORDER
+    if order is None:
+        if _POSE_ORDER is None:
+            from .pose_estimate_reference import reorder_table
+            _POSE_ORDER = torch.from_numpy(reorder_table())
+        order = _POSE_ORDER
+    elif not isinstance(order, Tensor):
+        order = torch.as_tensor(order, dtype=torch.uint8)
+    return torch.ops.sf_hip.pose_simcc_decode(simcc_x, simcc_y, boxes, count, int(frame_size[0]), int(frame_size[1]), int(out_size[0]), int(out_size[1]),
+                                              float(padding), float(split_ratio), normalized, float(neck_threshold), order)
+
+
+_POSE_ORDER: Optional[Tensor] = None          # the default reorder table, uint8 [134] on the host
+
+
 # -------------------------------------------------------------------------------------- CLIP image encoder (csrc/clip_encoder.hip)
 def clip_preprocess(frames: Tensor, image_size: int = 224, patch: int = 14, kp: Optional[int] = None) -> Tensor:
     """frames [n, 3, H, W] float32 / bfloat16 in [-1, 1] -> bf16 patch rows [n * (image_size/patch)^2, kp] (sf_clip_preprocess)."""

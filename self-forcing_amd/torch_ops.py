@@ -36,6 +36,9 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::pose_retarget_frames(src, first, ref, src0, out0, n_out, num, den, src_sx, src_sy, ref_sx, ref_sy, score_threshold, align) -> out
     sf_hip::pose_smooth_frames(src, state!, period, min_cutoff, beta, kd, score_threshold, max_gap) -> out
     sf_hip::pose_track_frames(src, state!, slots, gate2, score_threshold, min_points, min_common, max_age) -> (out, ids)
+    sf_hip::pose_boxes_decode(head, in_h, in_w, strides, ratio, max_people, class_index, score_threshold, iou_threshold, decoded) -> (boxes, count)
+    sf_hip::pose_crop_people(frames, boxes, count, layout, out_h, out_w, padding, mean, std, bgr, dtype) -> out
+    sf_hip::pose_simcc_decode(simcc_x, simcc_y, boxes, count, height, width, out_h, out_w, padding, split_ratio, normalized, neck_threshold, order) -> out
 
 Models (weights + C descriptors) are Python objects that own device memory; operators take an integer HANDLE from
 `register_model` (a constant to a tracer).  There is no CPU implementation: CPU tensors raise.
@@ -1083,6 +1086,151 @@ def pose_track_frames(src: Tensor, state: Tensor, slots: int, gate2: float, scor
 def _(src, state, slots, gate2, score_threshold=0.3, min_points=4, min_common=3, max_age=2):
     n, _p = _pose_track_geometry(src, state, slots)
     return src.new_empty((n, slots, 134, 3), dtype=torch.float32), src.new_empty((n, slots), dtype=torch.int32)
+
+
+# ------------------------------------------------------------------------------------------ DWPose glue
+def _pose_boxes_geometry(head: Tensor, in_h: int, in_w: int, strides: Sequence[int], max_people: int) -> Tuple[int, int, int]:
+    """(F, A, C) of a head [F, A, 5 + C] for the detector's input size and strides."""
+    if not 1 <= len(strides) <= _lib.POSE_BOXES_MAX_STRIDES or any(s < 1 or in_h % s or in_w % s for s in strides) or in_h < 1 or in_w < 1:
+        raise ValueError(f"pose_boxes_decode: strides must be 1..{_lib.POSE_BOXES_MAX_STRIDES} divisors of the input size {in_h} x {in_w}, got {list(strides)}")
+    anchors = sum((in_h // s) * (in_w // s) for s in strides)
+    if anchors > _lib.POSE_BOXES_MAX_ANCHORS:
+        raise ValueError(f"pose_boxes_decode: {anchors} anchors, at most {_lib.POSE_BOXES_MAX_ANCHORS}")
+    if head.dim() != 3 or not 1 <= head.shape[0] <= _lib.POSE_BOXES_MAX_FRAMES or head.shape[1] != anchors \
+            or not 6 <= head.shape[2] <= 5 + _lib.POSE_BOXES_MAX_CLASSES:
+        raise ValueError(f"pose_boxes_decode: head must be [F, {anchors}, 5 + C] with 1 <= F <= {_lib.POSE_BOXES_MAX_FRAMES} and 1 <= C <= "
+                         f"{_lib.POSE_BOXES_MAX_CLASSES}, got {tuple(head.shape)}")
+    if not 1 <= max_people <= _lib.POSE_RENDER_MAX_PEOPLE:
+        raise ValueError(f"pose_boxes_decode: max_people must be 1..{_lib.POSE_RENDER_MAX_PEOPLE}, got {max_people}")
+    return int(head.shape[0]), anchors, int(head.shape[2]) - 5
+
+
+@custom_op(f"{NAMESPACE}::pose_boxes_decode", mutates_args=())
+def pose_boxes_decode(head: Tensor, in_h: int, in_w: int, strides: List[int], ratio: float, max_people: int, class_index: int = 0,
+                      score_threshold: float = 0.3, iou_threshold: float = 0.45, decoded: bool = False) -> Tuple[Tensor, Tensor]:
+    """A YOLOX head float32 [F, A, 5 + C] on the device -> (boxes float32 [F, P, 5] = (x1, y1, x2, y2, score) in source-frame
+    pixels, count int32 [F]) after greedy NMS, as `pose_estimate_reference.decode_boxes` defines them (sf_pose_boxes_decode;
+    its scratch of F * A * 5 floats is allocated here)."""
+    f, a, c = _pose_boxes_geometry(head, in_h, in_w, strides, max_people)
+    _need_gpu(head, "head", torch.float32)
+    if not head.is_contiguous():
+        raise ValueError("pose_boxes_decode: head must be contiguous")
+    boxes = torch.empty((f, max_people, 5), dtype=torch.float32, device=head.device)
+    count = torch.empty((f,), dtype=torch.int32, device=head.device)
+    scratch = torch.empty((f, 5, a), dtype=torch.float32, device=head.device)
+    args = _lib.PoseBoxesArgs(head=head.data_ptr(), boxes=boxes.data_ptr(), count=count.data_ptr(), scratch=scratch.data_ptr(), F=f, A=a, C=c,
+                              P=max_people, in_h=in_h, in_w=in_w, n_strides=len(strides),
+                              strides=(C.c_int32 * _lib.POSE_BOXES_MAX_STRIDES)(*strides), class_index=class_index, decoded=int(bool(decoded)),
+                              ratio=ratio, score_threshold=score_threshold, iou_threshold=iou_threshold)
+    _lib.check(_lib.lib().sf_pose_boxes_decode(C.byref(args), _stream(head)), "sf_pose_boxes_decode")
+    return boxes, count
+
+
+@pose_boxes_decode.register_fake
+def _(head, in_h, in_w, strides, ratio, max_people, class_index=0, score_threshold=0.3, iou_threshold=0.45, decoded=False):
+    f, _a, _c = _pose_boxes_geometry(head, in_h, in_w, strides, max_people)
+    return head.new_empty((f, max_people, 5), dtype=torch.float32), head.new_empty((f,), dtype=torch.int32)
+
+
+def _pose_people_geometry(op: str, boxes: Tensor, count: Tensor) -> Tuple[int, int]:
+    """(F, P) of boxes float32 [F, P, 5] and count int32 [F]."""
+    if boxes.dim() != 3 or boxes.shape[2] != 5 or not 1 <= boxes.shape[0] <= _lib.POSE_BOXES_MAX_FRAMES \
+            or not 1 <= boxes.shape[1] <= _lib.POSE_RENDER_MAX_PEOPLE or boxes.dtype != torch.float32:
+        raise ValueError(f"{op}: boxes must be float32 [F, P, 5] with 1 <= F <= {_lib.POSE_BOXES_MAX_FRAMES} and 1 <= P <= "
+                         f"{_lib.POSE_RENDER_MAX_PEOPLE}, got {boxes.dtype} {tuple(boxes.shape)}")
+    if count.dtype != torch.int32 or tuple(count.shape) != (boxes.shape[0],):
+        raise ValueError(f"{op}: count must be int32 [{boxes.shape[0]}], got {count.dtype} {tuple(count.shape)}")
+    return int(boxes.shape[0]), int(boxes.shape[1])
+
+
+def _pose_crop_size(op: str, out_h: int, out_w: int) -> None:
+    if not 1 <= out_h <= _lib.POSE_CROP_MAX_SIZE or not 1 <= out_w <= _lib.POSE_CROP_MAX_SIZE:
+        raise ValueError(f"{op}: out_size must be 1..{_lib.POSE_CROP_MAX_SIZE} each way, got {out_h} x {out_w}")
+
+
+def _pose_crop_geometry(frames: Tensor, boxes: Tensor, count: Tensor, layout: str, out_h: int, out_w: int, dtype: torch.dtype) -> Tuple[int, int, int, int]:
+    f, p = _pose_people_geometry("pose_crop_people", boxes, count)
+    n, h, w = _frame_geometry(frames, layout)
+    if frames.dtype != torch.uint8 or n != f or not 1 <= h <= _lib.POSE_CROP_MAX_FRAME or not 1 <= w <= _lib.POSE_CROP_MAX_FRAME:
+        raise ValueError(f"pose_crop_people: frames must be {f} uint8 frames of at most {_lib.POSE_CROP_MAX_FRAME} pixels each way, got {frames.dtype} "
+                         f"{tuple(frames.shape)} in layout {layout!r}")
+    _pose_crop_size("pose_crop_people", out_h, out_w)
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"pose_crop_people: dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+    return f, p, h, w
+
+
+def _same_device(op: str, first: Tensor, **others: Tensor) -> None:
+    for name, t in others.items():
+        if not t.is_cuda or t.device != first.device or not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be contiguous and on {first.device} (the HIP path has no CPU fallback), got {t.device}")
+
+
+@custom_op(f"{NAMESPACE}::pose_crop_people", mutates_args=())
+def pose_crop_people(frames: Tensor, boxes: Tensor, count: Tensor, layout: str, out_h: int, out_w: int, padding: float, mean: List[float],
+                     std: List[float], bgr: bool, dtype: torch.dtype) -> Tensor:
+    """uint8 frames in `layout` and the people of `pose_boxes_decode` -> the pose network's input [F * P, 3, out_h, out_w] in
+    `dtype`, zeros for the rows without a person, as `pose_estimate_reference.crop_people` defines it (sf_pose_crop_people)."""
+    f, p, h, w = _pose_crop_geometry(frames, boxes, count, layout, out_h, out_w, dtype)
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("pose_crop_people: mean and std must be three numbers each")
+    _need_gpu(frames, "frames", torch.uint8)
+    _same_device("pose_crop_people", frames, frames=frames, boxes=boxes, count=count)
+    out = torch.empty((f * p, 3, out_h, out_w), dtype=dtype, device=frames.device)
+    args = _lib.PoseCropArgs(frames=frames.data_ptr(), boxes=boxes.data_ptr(), count=count.data_ptr(), out=out.data_ptr(), F=f, P=p, H=h, W=w,
+                             layout=_lib.JPEG_LAYOUTS[layout], out_h=out_h, out_w=out_w, dtype=_lib.JPEG_DTYPES[_RESIZE_DTYPES[dtype]],
+                             bgr=int(bool(bgr)), padding=padding, mean=(C.c_float * 3)(*mean), std=(C.c_float * 3)(*std))
+    _lib.check(_lib.lib().sf_pose_crop_people(C.byref(args), _stream(frames)), "sf_pose_crop_people")
+    return out
+
+
+@pose_crop_people.register_fake
+def _(frames, boxes, count, layout, out_h, out_w, padding, mean, std, bgr, dtype):
+    f, p, _h, _w = _pose_crop_geometry(frames, boxes, count, layout, out_h, out_w, dtype)
+    return frames.new_empty((f * p, 3, out_h, out_w), dtype=dtype)
+
+
+def _pose_simcc_geometry(simcc_x: Tensor, simcc_y: Tensor, boxes: Tensor, count: Tensor, height: int, width: int, out_h: int, out_w: int,
+                         order: Tensor) -> Tuple[int, int]:
+    f, p = _pose_people_geometry("pose_simcc_decode", boxes, count)
+    for name, t in (("simcc_x", simcc_x), ("simcc_y", simcc_y)):
+        if t.dim() != 3 or t.shape[0] != f * p or t.shape[1] != _lib.POSE_SIMCC_POINTS or not 1 <= t.shape[2] <= _lib.POSE_SIMCC_MAX_BINS:
+            raise ValueError(f"pose_simcc_decode: {name} must be [{f * p}, {_lib.POSE_SIMCC_POINTS}, bins] with 1 <= bins <= {_lib.POSE_SIMCC_MAX_BINS}, "
+                             f"got {tuple(t.shape)}")
+    if simcc_x.dtype != simcc_y.dtype or _dtype_name(simcc_x) not in _lib.POSE_SIMCC_DTYPES:
+        raise ValueError(f"pose_simcc_decode: simcc_x and simcc_y must both be float32 or both float16, got {simcc_x.dtype} and {simcc_y.dtype}")
+    if not 1 <= height <= _lib.POSE_CROP_MAX_FRAME or not 1 <= width <= _lib.POSE_CROP_MAX_FRAME:
+        raise ValueError(f"pose_simcc_decode: the frame size must be 1..{_lib.POSE_CROP_MAX_FRAME} each way, got {height} x {width}")
+    _pose_crop_size("pose_simcc_decode", out_h, out_w)
+    if order.dtype != torch.uint8 or tuple(order.shape) != (134,):
+        raise ValueError(f"pose_simcc_decode: order must be a host uint8 tensor [134] of indices below 134, got {order.dtype} {tuple(order.shape)}")
+    return f, p
+
+
+@custom_op(f"{NAMESPACE}::pose_simcc_decode", mutates_args=())
+def pose_simcc_decode(simcc_x: Tensor, simcc_y: Tensor, boxes: Tensor, count: Tensor, height: int, width: int, out_h: int, out_w: int,
+                      padding: float, split_ratio: float, normalized: bool, neck_threshold: float, order: Tensor) -> Tensor:
+    """SimCC logits [F * P, 133, Wx] and [F * P, 133, Wy] (float32 or float16) and the people they were cropped for -> keypoints
+    float32 [F, P, 134, 3] in the renderer's layout, as `pose_estimate_reference.decode_simcc` defines them (sf_pose_simcc_decode).  order: uint8 [134] in HOST memory,
+    `pose_estimate_reference.reorder_table` (the library reads it before it launches)."""
+    f, p = _pose_simcc_geometry(simcc_x, simcc_y, boxes, count, height, width, out_h, out_w, order)
+    _need_gpu(simcc_x, "simcc_x", None)
+    _same_device("pose_simcc_decode", simcc_x, simcc_x=simcc_x, simcc_y=simcc_y, boxes=boxes, count=count)
+    out = torch.empty((f, p, 134, 3), dtype=torch.float32, device=simcc_x.device)
+    if order.is_cuda or not order.is_contiguous():
+        raise ValueError("pose_simcc_decode: order must be a contiguous host tensor")
+    args = _lib.PoseSimccArgs(simcc_x=simcc_x.data_ptr(), simcc_y=simcc_y.data_ptr(), boxes=boxes.data_ptr(), count=count.data_ptr(),
+                              out=out.data_ptr(), order=order.data_ptr(), F=f, P=p, H=height, W=width, Wx=simcc_x.shape[2], Wy=simcc_y.shape[2],
+                              dtype=_lib.POSE_SIMCC_DTYPES[_dtype_name(simcc_x)], out_h=out_h, out_w=out_w, normalized=int(bool(normalized)),
+                              padding=padding, split_ratio=split_ratio, neck_threshold=neck_threshold)
+    _lib.check(_lib.lib().sf_pose_simcc_decode(C.byref(args), _stream(simcc_x)), "sf_pose_simcc_decode")
+    return out
+
+
+@pose_simcc_decode.register_fake
+def _(simcc_x, simcc_y, boxes, count, height, width, out_h, out_w, padding, split_ratio, normalized, neck_threshold, order):
+    f, p = _pose_simcc_geometry(simcc_x, simcc_y, boxes, count, height, width, out_h, out_w, order)
+    return simcc_x.new_empty((f, p, 134, 3), dtype=torch.float32)
 
 
 # every operator this module registered, by its name under torch.ops.sf_hip
