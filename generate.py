@@ -178,24 +178,21 @@ def load_pose_keypoints(clip_path: str, ref_path: str, device, size, normalized:
     renderer = sfa.PoseRenderer(device=device)
     clip, ref = read_keypoints(clip_path), read_keypoints(ref_path, one_frame=True)
     ref_frame = renderer.render(ref, size, "hwc", normalized=normalized)[0]
-    if track is not None:
-        try:
-            clip = sfa.PoseTracker(device=device).track(clip, **track).keypoints
-        except ValueError as e:
-            raise SystemExit(f"{clip_path}: {e}")
-    if smooth is not None or hold:
-        try:
-            clip = sfa.PoseSmoother(device=device).smooth(clip, POSE_TARGET_FPS if source_fps is None else source_fps, *(smooth or ()), max_gap=hold)
-        except ValueError as e:
-            raise SystemExit(f"{clip_path}: {e}")
-    if not align and source_fps is None and source_size is None:
-        return renderer.render(clip, size, "pose", normalized=normalized), ref_frame
+    fps = POSE_TARGET_FPS if source_fps is None else source_fps
+    stages = {}
     try:
-        moved = sfa.PoseRetargeter(device=device).retarget(clip, ref[0], size, source_fps=POSE_TARGET_FPS if source_fps is None else source_fps,
-                                                           target_fps=POSE_TARGET_FPS, align=align, normalized=normalized, source_size=source_size)
+        if track is not None:
+            stages["tracker"] = sfa.PoseTracker(device=device).open_stream(**track)
+        if smooth is not None or hold:
+            stages["smoother"] = sfa.PoseSmoother(device=device).open_stream(fps, *(smooth or ()), max_gap=hold)
+        if align or source_fps is not None or source_size is not None:
+            stages["retargeter"] = sfa.PoseRetargeter(device=device).open_stream(ref[0], size, source_fps=fps, target_fps=POSE_TARGET_FPS, align=align,
+                                                                                 normalized=normalized, source_size=source_size)
+        chain = sfa.KeypointChain(**stages)
+        clip = chain.push(clip)
     except ValueError as e:
         raise SystemExit(f"{clip_path}: {e}")
-    return renderer.render(moved, size, "pose", normalized=False), ref_frame
+    return renderer.render(clip, size, "pose", normalized=normalized and not chain.in_pixels), ref_frame
 
 
 def load_pose_mjpeg(clip_path: str, ref_path: str, device, size=None, fit: str = "stretch"):
@@ -211,6 +208,86 @@ def load_pose_mjpeg(clip_path: str, ref_path: str, device, size=None, fit: str =
         return decoder.decode(frames, layout="pose", size=size, fit=fit), decoder.decode([ref], layout="hwc", size=size, fit=fit)[0]
     except ValueError as e:
         raise SystemExit(f"{clip_path} / {ref_path}: {e}")
+
+
+def check_pose_flags(ap, a):
+    """The parser's checks of the pose flags, each ending in `ap.error`: (the kind of --pose_path as `pose_file_kind` names it, None without
+    one; --pose_source_size as (hs, ws); --pose_smooth / --pose_hold as the smoother's tuple; the --pose_track flags as the tracker's dict), each
+    None where the flags do not ask for it."""
+    retarget_flags = (("--pose_align", a.pose_align), ("--pose_fps", a.pose_fps is not None), ("--pose_source_size", a.pose_source_size is not None))
+    smooth_flags = (("--pose_smooth", a.pose_smooth is not None), ("--pose_hold", a.pose_hold is not None))       # they do not retarget
+    track_flags = (("--pose_track", a.pose_track is not None), ("--pose_track_gate", a.pose_track_gate is not None),
+                   ("--pose_track_age", a.pose_track_age is not None))                                               # nor do these
+    pose_kind = pose_source_size = pose_smooth = pose_track = None
+    if a.pose_path or a.pose_weights_path or a.pose_random_init_seed is not None:
+        if not a.pose_path or (a.pose_weights_path is None) == (a.pose_random_init_seed is None):
+            ap.error("pose conditioning needs --pose_path and exactly one of --pose_weights_path / --pose_random_init_seed")
+        if not os.path.exists(a.pose_path):
+            ap.error(f"--pose_path {a.pose_path}: no such file (a .pt / .npy dict with dwpose_data and random_ref_dwpose; few-step and "
+                     "multi-step configs both take it)")
+        pose_kind = pose_file_kind(a.pose_path)
+        if a.ref_pose_path and pose_kind == "dict":
+            ap.error("--ref_pose_path goes with an MJPEG --pose_path (.avi) or a keypoint one (.npz / .npy array); a .pt / .npy dict holds its own "
+                     "random_ref_dwpose")
+        if pose_kind == "mjpeg" and not a.ref_pose_path:
+            ap.error("--pose_path clip.avi needs --ref_pose_path: the JPEG file that is random_ref_dwpose")
+        if pose_kind == "keypoints" and not a.ref_pose_path:
+            ap.error("--pose_path with keypoints needs --ref_pose_path: a .npz / .npy with one frame of keypoints, drawn as random_ref_dwpose")
+        if pose_kind != "dict" and not os.path.exists(a.ref_pose_path):
+            ap.error(f"--ref_pose_path {a.ref_pose_path}: no such file")
+        if pose_kind == "keypoints" and pose_file_kind(a.ref_pose_path) != "keypoints":
+            ap.error(f"--ref_pose_path {a.ref_pose_path}: keypoints (.npz / .npy array) expected beside a keypoint --pose_path")
+        if a.pose_pixel_coords and pose_kind != "keypoints":
+            ap.error("--pose_pixel_coords goes with a keypoint --pose_path (.npz / .npy array)")
+        for flag, given in retarget_flags + smooth_flags + track_flags:
+            if given and pose_kind != "keypoints":
+                ap.error(f"{flag} goes with a keypoint --pose_path (.npz / .npy array)")
+        if a.pose_fps is not None:
+            try:
+                sfa.pose_retarget_reference.rate(a.pose_fps, POSE_TARGET_FPS)
+            except ValueError as e:
+                ap.error(f"--pose_fps {a.pose_fps}: {e}")
+        if a.pose_source_size is not None:
+            m = re.fullmatch(r"(\d+)x(\d+)", a.pose_source_size)
+            if not m or not int(m.group(1)) or not int(m.group(2)):
+                ap.error(f"--pose_source_size {a.pose_source_size}: HxW expected, two positive integers, e.g. 720x1280")
+            pose_source_size = (int(m.group(1)), int(m.group(2)))
+        if a.pose_smooth is not None or a.pose_hold is not None:
+            try:
+                pose_smooth = () if a.pose_smooth is None else tuple(float(v) for v in a.pose_smooth.split(","))
+                if a.pose_smooth is not None and not 1 <= len(pose_smooth) <= 3:
+                    raise ValueError("one to three numbers expected")
+            except ValueError as e:
+                ap.error(f"--pose_smooth {a.pose_smooth}: MIN_CUTOFF[,BETA[,D_CUTOFF]] expected, e.g. 1.0,0.05 ({e})")
+            try:
+                sfa.pose_smooth_reference.prepare(POSE_TARGET_FPS if a.pose_fps is None else a.pose_fps, *pose_smooth, max_gap=a.pose_hold or 0)
+            except ValueError as e:
+                ap.error(f"--pose_smooth {a.pose_smooth} --pose_hold {a.pose_hold}: {e}")
+        if any(given for _, given in track_flags):
+            if a.pose_track is None:
+                ap.error("--pose_track_gate and --pose_track_age go with --pose_track")
+            try:
+                slots = int(a.pose_track) if a.pose_track else None                                                   # "": the people per frame
+            except ValueError:
+                ap.error(f"--pose_track {a.pose_track}: SLOTS expected, an integer in 1..8")
+            pose_track = {name: value for name, value in (("slots", slots), ("gate", a.pose_track_gate), ("max_age", a.pose_track_age))
+                          if value is not None}
+            try:
+                tracked = sfa.pose_track_reference.prepare(**pose_track)
+            except ValueError as e:
+                ap.error(f"--pose_track {a.pose_track} --pose_track_gate {a.pose_track_gate} --pose_track_age {a.pose_track_age}: {e}")
+            if sfa.KeypointChain.bridges_two_people(a.pose_hold or 0, tracked.max_age):
+                ap.error(f"--pose_hold {a.pose_hold} exceeds --pose_track_age {tracked.max_age}: a tracker's slot is empty for max_age + 1 frames "
+                         f"between two different people, so a longer hold could smooth one person towards another")
+    elif a.ref_pose_path:
+        ap.error("--ref_pose_path needs --pose_path clip.avi or keypoints (.npz / .npy array)")
+    elif a.pose_pixel_coords:
+        ap.error("--pose_pixel_coords needs a keypoint --pose_path")
+    else:
+        for flag, given in retarget_flags + smooth_flags + track_flags:
+            if given:
+                ap.error(f"{flag} needs a keypoint --pose_path")
+    return pose_kind, pose_source_size, pose_smooth, pose_track
 
 
 def main():
@@ -286,80 +363,7 @@ def main():
     a = ap.parse_args()
     if not 1 <= a.jpeg_quality <= 100:
         ap.error("--jpeg_quality must be 1..100")
-    retarget_flags = (("--pose_align", a.pose_align), ("--pose_fps", a.pose_fps is not None), ("--pose_source_size", a.pose_source_size is not None))
-    smooth_flags = (("--pose_smooth", a.pose_smooth is not None), ("--pose_hold", a.pose_hold is not None))       # they do not retarget
-    track_flags = (("--pose_track", a.pose_track is not None), ("--pose_track_gate", a.pose_track_gate is not None),
-                   ("--pose_track_age", a.pose_track_age is not None))                                               # nor do these
-    pose_source_size = pose_smooth = pose_track = None
-    if a.pose_path or a.pose_weights_path or a.pose_random_init_seed is not None:
-        if not a.pose_path or (a.pose_weights_path is None) == (a.pose_random_init_seed is None):
-            ap.error("pose conditioning needs --pose_path and exactly one of --pose_weights_path / --pose_random_init_seed")
-        if not os.path.exists(a.pose_path):
-            ap.error(f"--pose_path {a.pose_path}: no such file (a .pt / .npy dict with dwpose_data and random_ref_dwpose; few-step and "
-                     "multi-step configs both take it)")
-        pose_kind = pose_file_kind(a.pose_path)
-        pose_is_mjpeg = pose_kind == "mjpeg"
-        if a.ref_pose_path and pose_kind == "dict":
-            ap.error("--ref_pose_path goes with an MJPEG --pose_path (.avi) or a keypoint one (.npz / .npy array); a .pt / .npy dict holds its own "
-                     "random_ref_dwpose")
-        if pose_is_mjpeg and not a.ref_pose_path:
-            ap.error("--pose_path clip.avi needs --ref_pose_path: the JPEG file that is random_ref_dwpose")
-        if pose_kind == "keypoints" and not a.ref_pose_path:
-            ap.error("--pose_path with keypoints needs --ref_pose_path: a .npz / .npy with one frame of keypoints, drawn as random_ref_dwpose")
-        if pose_kind != "dict" and not os.path.exists(a.ref_pose_path):
-            ap.error(f"--ref_pose_path {a.ref_pose_path}: no such file")
-        if pose_kind == "keypoints" and pose_file_kind(a.ref_pose_path) != "keypoints":
-            ap.error(f"--ref_pose_path {a.ref_pose_path}: keypoints (.npz / .npy array) expected beside a keypoint --pose_path")
-        if a.pose_pixel_coords and pose_kind != "keypoints":
-            ap.error("--pose_pixel_coords goes with a keypoint --pose_path (.npz / .npy array)")
-        for flag, given in retarget_flags + smooth_flags + track_flags:
-            if given and pose_kind != "keypoints":
-                ap.error(f"{flag} goes with a keypoint --pose_path (.npz / .npy array)")
-        if a.pose_fps is not None:
-            try:
-                sfa.pose_retarget_reference.rate(a.pose_fps, POSE_TARGET_FPS)
-            except ValueError as e:
-                ap.error(f"--pose_fps {a.pose_fps}: {e}")
-        if a.pose_source_size is not None:
-            m = re.fullmatch(r"(\d+)x(\d+)", a.pose_source_size)
-            if not m or not int(m.group(1)) or not int(m.group(2)):
-                ap.error(f"--pose_source_size {a.pose_source_size}: HxW expected, two positive integers, e.g. 720x1280")
-            pose_source_size = (int(m.group(1)), int(m.group(2)))
-        if a.pose_smooth is not None or a.pose_hold is not None:
-            try:
-                pose_smooth = () if a.pose_smooth is None else tuple(float(v) for v in a.pose_smooth.split(","))
-                if a.pose_smooth is not None and not 1 <= len(pose_smooth) <= 3:
-                    raise ValueError("one to three numbers expected")
-            except ValueError as e:
-                ap.error(f"--pose_smooth {a.pose_smooth}: MIN_CUTOFF[,BETA[,D_CUTOFF]] expected, e.g. 1.0,0.05 ({e})")
-            try:
-                sfa.pose_smooth_reference.prepare(POSE_TARGET_FPS if a.pose_fps is None else a.pose_fps, *pose_smooth, max_gap=a.pose_hold or 0)
-            except ValueError as e:
-                ap.error(f"--pose_smooth {a.pose_smooth} --pose_hold {a.pose_hold}: {e}")
-        if any(given for _, given in track_flags):
-            if a.pose_track is None:
-                ap.error("--pose_track_gate and --pose_track_age go with --pose_track")
-            try:
-                slots = int(a.pose_track) if a.pose_track else None                                                   # "": the people per frame
-            except ValueError:
-                ap.error(f"--pose_track {a.pose_track}: SLOTS expected, an integer in 1..8")
-            pose_track = {name: value for name, value in (("slots", slots), ("gate", a.pose_track_gate), ("max_age", a.pose_track_age))
-                          if value is not None}
-            try:
-                tracked = sfa.pose_track_reference.prepare(**pose_track)
-            except ValueError as e:
-                ap.error(f"--pose_track {a.pose_track} --pose_track_gate {a.pose_track_gate} --pose_track_age {a.pose_track_age}: {e}")
-            if (a.pose_hold or 0) > tracked.max_age:
-                ap.error(f"--pose_hold {a.pose_hold} exceeds --pose_track_age {tracked.max_age}: a tracker's slot is empty for max_age + 1 frames "
-                         f"between two different people, so a longer hold could smooth one person towards another")
-    elif a.ref_pose_path:
-        ap.error("--ref_pose_path needs --pose_path clip.avi or keypoints (.npz / .npy array)")
-    elif a.pose_pixel_coords:
-        ap.error("--pose_pixel_coords needs a keypoint --pose_path")
-    else:
-        for flag, given in retarget_flags + smooth_flags + track_flags:
-            if given:
-                ap.error(f"{flag} needs a keypoint --pose_path")
+    pose_kind, pose_source_size, pose_smooth, pose_track = check_pose_flags(ap, a)
     if a.pose_resize != "none" and not (a.pose_path and a.pose_path.lower().endswith(".avi")):
         ap.error("--pose_resize goes with an MJPEG --pose_path (.avi); a .pt / .npy dict is taken at the size it has, keypoints are drawn at the "
                  "output size")
@@ -439,7 +443,7 @@ def main():
     if a.pose_path:
         weights = a.pose_weights_path if a.pose_weights_path else sfa.synth_pose_state_dict(seed=a.pose_random_init_seed)
         pose_embedder = sfa.PoseEmbedder(weights, device=device, strict=cfg.get("pose_weights_strict", True))
-        if pose_is_mjpeg:
+        if pose_kind == "mjpeg":
             pose_size = None if a.pose_resize == "none" else (8 * a.latent_height, 8 * a.latent_width)
             pose_data = load_pose_mjpeg(a.pose_path, a.ref_pose_path, device, pose_size, "stretch" if pose_size is None else a.pose_resize)
         elif pose_kind == "keypoints":

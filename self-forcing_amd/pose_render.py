@@ -11,7 +11,7 @@ import torch
 
 from . import _lib, ops
 from . import pose_render_reference as pr
-from . import pose_retarget_reference as rr
+from .pose_keypoints import KeypointChain, KeypointStage, as_tensor
 
 Tensor = torch.Tensor
 _DTYPES = (torch.uint8, torch.float32, torch.bfloat16)
@@ -28,19 +28,7 @@ def check_arguments(size, layout: str, dtype, score_threshold) -> Tuple[int, int
     return h, w
 
 
-def as_tensor(keypoints, what: str) -> Tensor:
-    """A numpy array (or what `np.asarray` takes), a host tensor or a device tensor of numbers -> a tensor, where it is."""
-    if not isinstance(keypoints, Tensor):
-        keypoints = np.asarray(keypoints)
-        if keypoints.dtype.kind not in "fiu":
-            raise ValueError(f"{what} must be numbers, got an array of {keypoints.dtype}")
-        return torch.from_numpy(np.ascontiguousarray(keypoints, dtype=np.float32))
-    if keypoints.is_complex() or keypoints.dtype == torch.bool:
-        raise ValueError(f"{what} must be numbers, got {keypoints.dtype}")
-    return keypoints
-
-
-class PoseRenderer:
+class PoseRenderer(KeypointStage):
     """`render(keypoints, size)` -> skeleton frames on the device, every pixel as `pose_render_reference.render` defines it.
 
     keypoints: float [F, P, 134, 3] or [F, 134, 3] = (x, y, score) in DWPose's whole-body order, P <= 8; a numpy array, a
@@ -51,13 +39,10 @@ class PoseRenderer:
     decoder's conversion); H, W <= 4096.  `out`: a contiguous, 16-byte-aligned tensor of that shape to fill, a slice of a
     larger buffer included.  Work runs on the current stream."""
 
-    def __init__(self, device="cuda"):
-        self.device = torch.device(device)
-
     def render(self, keypoints, size: Sequence[int], layout: str = "pose", dtype=torch.uint8, normalized: bool = True,
                score_threshold: float = 0.3, out: Optional[Tensor] = None) -> Tensor:
         h, w = check_arguments(size, layout, dtype, score_threshold)
-        keypoints = as_tensor(keypoints, "PoseRenderer: keypoints")
+        keypoints = as_tensor(keypoints, "PoseRenderer")
         f, p = pr.check_keypoints_shape(keypoints.shape)
         device = keypoints.device if keypoints.is_cuda else self.device
         if device.type != "cuda":
@@ -74,46 +59,6 @@ class PoseRenderer:
             return ops.pose_render_frames(keypoints, h, w, layout, dtype, bool(normalized), float(score_threshold), out)
 
 
-def _stacked(frames: List):
-    return torch.stack(frames) if isinstance(frames[0], Tensor) else np.stack([np.asarray(k) for k in frames])
-
-
-def _front(batch, tracker, smoother):
-    """A batch of source frames through the tracker, then the smoother, where there are any."""
-    if tracker is not None:
-        batch = tracker.push(batch)
-    return batch if smoother is None else smoother.push(batch)
-
-
-def _retargeted_feed(keypoints: Iterable, renderer: PoseRenderer, stream, size: Tuple[int, int], frames_per_piece: int,
-                     score_threshold: float, smoother=None, tracker=None) -> Iterator[Tensor]:
-    """`pose_feed` through a `PoseRetargetStream`: source frames are gathered until the stream's plan says that a piece of
-    output frames is final, pushed in one call (through the `PoseTrackStream` `tracker` and then the `PoseSmoothStream`
-    `smoother` first, where there are any), and the output is drawn `frames_per_piece` frames at a time."""
-    def push(frames: List) -> Tensor:
-        return stream.push(_front(_stacked(frames), tracker, smoother))
-
-    if (stream.params.h, stream.params.w) != size:
-        raise ValueError(f"pose_feed: the retargeter was opened for {(stream.params.h, stream.params.w)}, the frames are {size}")
-    ready: Optional[Tensor] = None         # retargeted frames not yet drawn, fewer than a piece
-    gathered: List = []
-    for k in keypoints:
-        gathered.append(k)
-        held = 0 if ready is None else ready.shape[0]
-        if held + rr.plan(stream.frames_in, len(gathered), stream.params.num, stream.params.den)[1] < frames_per_piece:
-            continue
-        new, gathered = push(gathered), []
-        ready = new if ready is None else torch.cat([ready, new])
-        while ready.shape[0] >= frames_per_piece:
-            piece, ready = ready[:frames_per_piece], ready[frames_per_piece:]
-            yield renderer.render(piece, size, "pose", torch.uint8, False, score_threshold)
-    if gathered:                           # source frames behind the last output frame: they make nothing final
-        new = push(gathered)
-        ready = new if ready is None else torch.cat([ready, new])
-    if ready is not None and ready.shape[0]:
-        yield renderer.render(ready, size, "pose", torch.uint8, False, score_threshold)
-
-
 def pose_feed(keypoints: Iterable, renderer: PoseRenderer, size: Sequence[int], frames_per_piece: int = 12, normalized: bool = True,
               score_threshold: float = 0.3, retargeter=None, smoother=None, tracker=None) -> Iterator[Tensor]:
     """Keypoints as the pieces `CausalInferencePipeline.stream(pose_feed=...)` pulls, the counterpart of `jpeg.pose_feed`:
@@ -127,26 +72,33 @@ def pose_feed(keypoints: Iterable, renderer: PoseRenderer, size: Sequence[int], 
     source that lists the people of a frame in no stable order: source frames go through the tracker, then the smoother,
     then the retargeter.  A tracker keeps a slot empty for at least max_age + 1 frames between two different people, so a
     smoother that bridges at most max_age frames never filters one person towards another; a smoother whose max_gap
-    exceeds the tracker's max_age is refused."""
-    if tracker is not None and smoother is not None and smoother.params.max_gap > tracker.params.max_age:
-        raise ValueError(f"pose_feed: the smoother bridges gaps of up to max_gap = {smoother.params.max_gap} frames, the tracker keeps a slot empty "
-                         f"for only max_age + 1 = {tracker.params.max_age + 1} frames between two different people: with max_gap > max_age the "
-                         f"smoother could filter one person towards another")
+    exceeds the tracker's max_age is refused.  Source frames are gathered until the chain's plan says that a piece of
+    output frames is final, pushed through it in one call, and the output is drawn `frames_per_piece` frames at a time."""
+    chain = KeypointChain(tracker, smoother, retargeter)
     if frames_per_piece < 1:
         raise ValueError(f"frames_per_piece must be >= 1, got {frames_per_piece}")
-    check_arguments(size, "pose", torch.uint8, score_threshold)
-    if retargeter is not None:
-        yield from _retargeted_feed(keypoints, renderer, retargeter, pr.check_size(size), frames_per_piece, score_threshold, smoother, tracker)
-        return
+    size = check_arguments(size, "pose", torch.uint8, score_threshold)
+    if retargeter is not None and (retargeter.params.h, retargeter.params.w) != size:
+        raise ValueError(f"pose_feed: the retargeter was opened for {(retargeter.params.h, retargeter.params.w)}, the frames are {size}")
+    normalized = normalized and not chain.in_pixels
 
-    def piece_of(frames: List) -> Tensor:
-        return renderer.render(_front(_stacked(frames), tracker, smoother), size, "pose", torch.uint8, normalized, score_threshold)
+    def pushed(ready, frames: List):
+        """`frames` through the chain as one batch, behind the output frames that wait in `ready`."""
+        new = chain.push(torch.stack(frames) if isinstance(frames[0], Tensor) else np.stack([np.asarray(k) for k in frames]))
+        return new if ready is None or not ready.shape[0] else torch.cat([ready, new])
 
-    piece: List = []
+    ready = None                           # output frames not yet drawn, fewer than a piece
+    gathered: List = []
     for k in keypoints:
-        piece.append(k)
-        if len(piece) == frames_per_piece:
-            yield piece_of(piece)
-            piece = []
-    if piece:
-        yield piece_of(piece)
+        gathered.append(k)
+        held = 0 if ready is None else ready.shape[0]
+        if held + chain.planned(len(gathered)) < frames_per_piece:
+            continue
+        ready, gathered = pushed(ready, gathered), []
+        while ready.shape[0] >= frames_per_piece:
+            piece, ready = ready[:frames_per_piece], ready[frames_per_piece:]
+            yield renderer.render(piece, size, "pose", torch.uint8, normalized, score_threshold)
+    if gathered:                           # the clip's end, or source frames behind the last output frame, which make nothing final
+        ready = pushed(ready, gathered)
+    if ready is not None and ready.shape[0]:
+        yield renderer.render(ready, size, "pose", torch.uint8, normalized, score_threshold)

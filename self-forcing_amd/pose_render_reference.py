@@ -82,6 +82,13 @@ def check_keypoints_shape(shape: Sequence[int]) -> Tuple[int, int]:
     return shape[0], shape[1]
 
 
+def as_source(keypoints) -> np.ndarray:
+    """Keypoints [F, P, 134, 3] or [F, 134, 3] -> float32 [F, P, 134, 3]."""
+    k = np.asarray(keypoints, dtype=np.float32)
+    f, people = check_keypoints_shape(k.shape)
+    return k.reshape(f, people, KEYPOINTS, 3)
+
+
 def quantize(keypoints: np.ndarray, size: Tuple[int, int], normalized: bool = True, score_threshold: float = 0.3):
     """float32 [..., 3] -> (X int64 [...], Y int64 [...], valid bool [...]); X and Y are 0 where the point is invalid."""
     k = np.asarray(keypoints, dtype=np.float32)

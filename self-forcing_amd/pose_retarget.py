@@ -13,16 +13,9 @@ import torch
 from . import ops
 from . import pose_render_reference as pr
 from . import pose_retarget_reference as rr
-from .pose_render import as_tensor
+from .pose_keypoints import KeypointStage, KeypointStream, as_tensor, place
 
 Tensor = torch.Tensor
-
-
-def _place(keypoints: Tensor, device: torch.device, shape) -> Tensor:
-    """float32 [shape] on `device`: a host tensor is uploaded (the only host-to-device copy), a device tensor stays."""
-    if device.type != "cuda":
-        raise ValueError("PoseRetargeter: expected a CUDA/ROCm device (the HIP path has no CPU fallback)")
-    return keypoints.to(device=device, dtype=torch.float32).reshape(shape).contiguous()
 
 
 def _launch(p: rr.Params, src: Tensor, src0: int, first: Tensor, ref: Tensor, out0: int, n_out: int) -> Tensor:
@@ -33,7 +26,7 @@ def _launch(p: rr.Params, src: Tensor, src0: int, first: Tensor, ref: Tensor, ou
                                         float(p.ref_sy), float(p.threshold), p.align)
 
 
-class PoseRetargetStream:
+class PoseRetargetStream(KeypointStream):
     """`PoseRetargeter.retarget` piece by piece, for a live source.  `push(piece)` takes source frames [n, P, 134, 3] or
     [n, 134, 3] (numpy, host tensor or device tensor; a device tensor causes no host copy and no synchronisation) and
     returns the output frames that became final, float32 [m, P, 134, 3] on the device; m may be 0.  Output frame j is final
@@ -41,45 +34,33 @@ class PoseRetargetStream:
     `retarget` on the whole clip.  The stream keeps the clip's frame 0 and the last source frame on the device; its two
     counters are plain integers (a piece's length is known to the host)."""
 
+    who = "PoseRetargeter"
+
     def __init__(self, device: torch.device, ref_keypoints, params: rr.Params):
-        self.params = params
-        self.device = device
-        self._ref_in = as_tensor(ref_keypoints, "PoseRetargeter: ref_keypoints")
+        super().__init__(device, params)
+        self._ref_in = as_tensor(ref_keypoints, self.who, "ref_keypoints")
         rr.check_reference_shape(self._ref_in.shape)
-        self.frames_in = self.frames_out = 0
-        self.closed = False
+        self.frames_out = 0
         self._first = self._last = self._ref = None
 
-    def push(self, piece) -> Tensor:
-        if self.closed:
-            raise ValueError("PoseRetargetStream: the stream is closed")
-        piece = as_tensor(piece, "PoseRetargeter: keypoints")
-        n, people = pr.check_keypoints_shape(piece.shape)
-        if self._first is None:
-            pr_people = rr.check_reference_shape(self._ref_in.shape, people)
-            if piece.is_cuda:
-                self.device = piece.device
-            k = _place(piece, self.device, (n, people, pr.KEYPOINTS, 3))
-            self._ref = _place(self._ref_in, self.device, (pr_people, pr.KEYPOINTS, 3))
-            self._first = k[0].clone()
-        else:
-            if people != self._first.shape[0]:
-                raise ValueError(f"PoseRetargetStream: the stream holds {self._first.shape[0]} people, the piece {people}")
-            k = _place(piece, self.device, (n, people, pr.KEYPOINTS, 3))
+    def _admit(self, people: int) -> None:
+        rr.check_reference_shape(self._ref_in.shape, people)
+
+    def _open(self, people: int, k: Tensor) -> None:
+        self._ref = place(self._ref_in, k.device, (-1, pr.KEYPOINTS, 3), self.who)     # [Pr, 134, 3], Pr = P or 1: `_admit` has checked it
+        self._first = k[0].clone()
+        self.people = people
+
+    def _launch(self, k: Tensor) -> Tensor:
         window, src0 = (k, 0) if self._last is None else (torch.cat([self._last, k]), self.frames_in - 1)
-        out0, n_out = rr.plan(self.frames_in, n, self.params.num, self.params.den)
+        out0, n_out = rr.plan(self.frames_in, k.shape[0], self.params.num, self.params.den)
         out = _launch(self.params, window, src0, self._first, self._ref, out0, n_out)
         self._last = k[-1:].clone()
-        self.frames_in += n
         self.frames_out += n_out
         return out
 
-    def close(self) -> None:
-        """Ends the stream.  Nothing further comes out: every frame that can be computed has been returned."""
-        self.closed = True
 
-
-class PoseRetargeter:
+class PoseRetargeter(KeypointStage):
     """`retarget(keypoints, ref_keypoints, size)` -> float32 [F_out, P, 134, 3] on the device, in pixels of the (H, W) output,
     every number as `pose_retarget_reference.retarget` defines it.
 
@@ -91,18 +72,15 @@ class PoseRetargeter:
     and F_out = (F - 1) * den // num + 1.  align=False lifts and resamples only.  Work runs on the current stream, with no
     synchronisation."""
 
-    def __init__(self, device="cuda"):
-        self.device = torch.device(device)
-
     def retarget(self, keypoints, ref_keypoints, size: Sequence[int], source_fps=16, target_fps=16, align: bool = True, normalized: bool = True,
                  score_threshold: float = 0.3, source_size: Optional[Sequence[float]] = None) -> Tensor:
         p = rr.prepare(size, source_fps, target_fps, align, normalized, score_threshold, source_size)
-        keypoints, ref = as_tensor(keypoints, "PoseRetargeter: keypoints"), as_tensor(ref_keypoints, "PoseRetargeter: ref_keypoints")
+        keypoints, ref = as_tensor(keypoints, "PoseRetargeter"), as_tensor(ref_keypoints, "PoseRetargeter", "ref_keypoints")
         f, people = pr.check_keypoints_shape(keypoints.shape)
         ref_people = rr.check_reference_shape(ref.shape, people)
         device = keypoints.device if keypoints.is_cuda else (ref.device if ref.is_cuda else self.device)
-        k = _place(keypoints, device, (f, people, pr.KEYPOINTS, 3))
-        r = _place(ref, device, (ref_people, pr.KEYPOINTS, 3))
+        k = place(keypoints, device, (f, people, pr.KEYPOINTS, 3), "PoseRetargeter")
+        r = place(ref, device, (ref_people, pr.KEYPOINTS, 3), "PoseRetargeter")
         return _launch(p, k, 0, k[0], r, 0, rr.frames_out(f, p.num, p.den))
 
     def open_stream(self, ref_keypoints, size: Sequence[int], source_fps=16, target_fps=16, align: bool = True, normalized: bool = True,

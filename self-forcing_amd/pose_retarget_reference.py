@@ -36,7 +36,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .pose_render_reference import KEYPOINTS, LIMBS, MAX_PEOPLE, check_keypoints_shape, check_size, check_threshold
+from .pose_render_reference import KEYPOINTS, LIMBS, MAX_PEOPLE, as_source, check_keypoints_shape, check_size, check_threshold
 
 F32 = np.float32
 MAX_RATE = 65535               # SF_POSE_RETARGET_MAX_RATE: num and den of source_fps / target_fps
@@ -256,12 +256,6 @@ def frames(src: np.ndarray, src0: int, first: np.ndarray, ref: np.ndarray, out0:
         o[..., :2] = np.where(ok[..., None], xy, F32(-1))
         o[..., 2] = np.where(ok, sc, F32(0))
     return out
-
-
-def as_source(keypoints) -> np.ndarray:
-    k = np.asarray(keypoints, dtype=F32)
-    f, people = check_keypoints_shape(k.shape)
-    return k.reshape(f, people, KEYPOINTS, 3)
 
 
 def as_reference(ref_keypoints, people: int) -> np.ndarray:

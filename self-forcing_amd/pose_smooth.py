@@ -5,33 +5,19 @@ The definition of every number is `pose_smooth_reference.py` (float32, every ope
 kernel equals bit for bit.  The values stay in the caller's units; a missing point comes out as (-1, -1, 0)."""
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 
 from . import ops
 from . import pose_render_reference as pr
 from . import pose_smooth_reference as sr
-from .pose_render import as_tensor
+from .pose_keypoints import KeypointStage, KeypointStream
 
 Tensor = torch.Tensor
 
 
-def _place(keypoints: Tensor, device: torch.device, shape) -> Tensor:
-    """float32 [shape] on `device`: a host tensor is uploaded (the only host-to-device copy), a device tensor stays."""
-    if device.type != "cuda":
-        raise ValueError("PoseSmoother: expected a CUDA/ROCm device (the HIP path has no CPU fallback)")
-    return keypoints.to(device=device, dtype=torch.float32).reshape(shape).contiguous()
-
-
-def _launch(p: sr.Params, src: Tensor, state: Tensor) -> Tensor:
-    with torch.cuda.device(src.device):
-        return ops.pose_smooth_frames(src, state, float(p.period), float(p.min_cutoff), float(p.beta), float(p.kd), float(p.threshold), p.max_gap)
-
-
-def _fresh_state(people: int, device: torch.device) -> Tensor:
-    return torch.zeros((people, pr.KEYPOINTS, sr.STATE_WORDS), dtype=torch.int32, device=device)
-
-
-class PoseSmoothStream:
+class PoseSmoothStream(KeypointStream):
     """`PoseSmoother.smooth` piece by piece, for a live source.  `push(piece)` takes frames [n, P, 134, 3] or [n, 134, 3]
     (numpy, host tensor or device tensor; a device tensor causes no host copy and no synchronisation) and returns them
     smoothed, float32 [n, P, 134, 3] on the device: the filter is causal, so every push returns as many frames as it
@@ -39,35 +25,24 @@ class PoseSmoothStream:
     int32 [P, 134, 8] on the device (`pose_smooth_reference`), allocated zeroed at the first push, once P is known; the
     stream keeps nothing else of the caller's."""
 
-    def __init__(self, device: torch.device, params: sr.Params):
-        self.params = params
-        self.device = device
-        self.frames_in = 0
-        self.closed = False
-        self.state = None
+    who = "PoseSmoother"
+    state: Optional[Tensor] = None
 
-    def push(self, piece) -> Tensor:
-        if self.closed:
-            raise ValueError("PoseSmoothStream: the stream is closed")
-        piece = as_tensor(piece, "PoseSmoother: keypoints")
-        n, people = pr.check_keypoints_shape(piece.shape)
-        if self.state is not None and people != self.state.shape[0]:
-            raise ValueError(f"PoseSmoothStream: the stream holds {self.state.shape[0]} people, the piece {people}")
-        if self.state is None and piece.is_cuda:
-            self.device = piece.device
-        k = _place(piece, self.device, (n, people, pr.KEYPOINTS, 3))
-        if self.state is None:
-            self.state = _fresh_state(people, self.device)
-        out = _launch(self.params, k, self.state)
-        self.frames_in += n
-        return out
+    @property
+    def people(self) -> Optional[int]:
+        """The state says how many people the stream holds: a caller may hand a stream the state of another."""
+        return None if self.state is None else self.state.shape[0]
 
-    def close(self) -> None:
-        """Ends the stream.  Nothing further comes out: every frame has been returned by its push."""
-        self.closed = True
+    def _open(self, people: int, k: Tensor) -> None:
+        self.state = torch.zeros((people, pr.KEYPOINTS, sr.STATE_WORDS), dtype=torch.int32, device=k.device)
+
+    def _launch(self, k: Tensor) -> Tensor:
+        p = self.params
+        with torch.cuda.device(k.device):
+            return ops.pose_smooth_frames(k, self.state, float(p.period), float(p.min_cutoff), float(p.beta), float(p.kd), float(p.threshold), p.max_gap)
 
 
-class PoseSmoother:
+class PoseSmoother(KeypointStage):
     """`smooth(keypoints, fps)` -> float32 [F, P, 134, 3] on the device, in the keypoints' own units, every number as
     `pose_smooth_reference.smooth` defines it.
 
@@ -78,17 +53,9 @@ class PoseSmoother:
     of the speed estimate.  max_gap is the longest run of missing samples that is bridged with the last filtered position
     and the last valid score; 0 bridges none.  One launch on the current stream, with no synchronisation."""
 
-    def __init__(self, device="cuda"):
-        self.device = torch.device(device)
-
     def smooth(self, keypoints, fps, min_cutoff: float = 1.0, beta: float = 0.0, d_cutoff: float = 1.0, max_gap: int = 0,
                score_threshold: float = 0.3) -> Tensor:
-        p = sr.prepare(fps, min_cutoff, beta, d_cutoff, max_gap, score_threshold)
-        keypoints = as_tensor(keypoints, "PoseSmoother: keypoints")
-        f, people = pr.check_keypoints_shape(keypoints.shape)
-        device = keypoints.device if keypoints.is_cuda else self.device
-        k = _place(keypoints, device, (f, people, pr.KEYPOINTS, 3))
-        return _launch(p, k, _fresh_state(people, device))
+        return self.open_stream(fps, min_cutoff, beta, d_cutoff, max_gap, score_threshold).push(keypoints)
 
     def open_stream(self, fps, min_cutoff: float = 1.0, beta: float = 0.0, d_cutoff: float = 1.0, max_gap: int = 0,
                     score_threshold: float = 0.3) -> PoseSmoothStream:

@@ -34,7 +34,7 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
-from .pose_render_reference import KEYPOINTS, MAX_PEOPLE, check_keypoints_shape, check_threshold
+from .pose_render_reference import KEYPOINTS, MAX_PEOPLE, as_source, check_keypoints_shape, check_threshold
 from .pose_retarget_reference import MAX_RATE, parse_fps
 
 F32 = np.float32
@@ -154,12 +154,6 @@ def frames(src: np.ndarray, state: np.ndarray, p: Params, counts: Optional[dict]
         for name in RULES:
             counts[name] = counts.get(name, 0) + tally[name]
     return out
-
-
-def as_source(keypoints) -> np.ndarray:
-    k = np.asarray(keypoints, dtype=F32)
-    f, people = check_keypoints_shape(k.shape)
-    return k.reshape(f, people, KEYPOINTS, 3)
 
 
 def smooth(keypoints, fps, min_cutoff=1.0, beta=0.0, d_cutoff=1.0, max_gap=0, score_threshold=0.3) -> np.ndarray:

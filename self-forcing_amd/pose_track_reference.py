@@ -41,7 +41,7 @@ from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 
-from .pose_render_reference import KEYPOINTS, MAX_PEOPLE, check_keypoints_shape, check_threshold
+from .pose_render_reference import KEYPOINTS, MAX_PEOPLE, as_source, check_keypoints_shape, check_threshold
 
 F32 = np.float32
 BODY = 18                      # the body points 0..17 are what is matched
@@ -205,12 +205,6 @@ def frames(src: np.ndarray, state: np.ndarray, p: Params, counts: Optional[dict]
         for name in RULES:
             counts[name] = counts.get(name, 0) + tally[name]
     return out, ids
-
-
-def as_source(keypoints) -> np.ndarray:
-    k = np.asarray(keypoints, dtype=F32)
-    f, people = check_keypoints_shape(k.shape)
-    return k.reshape(f, people, KEYPOINTS, 3)
 
 
 def track(keypoints, slots=None, gate=0.5, max_age=2, min_points=4, min_common=3, score_threshold=0.3,

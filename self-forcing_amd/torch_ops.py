@@ -1008,13 +1008,18 @@ def _(src, first, ref, src0, out0, n_out, num, den, src_sx, src_sy, ref_sx, ref_
 
 
 # ------------------------------------------------------------------------------------------ pose smoother
-def _pose_smooth_geometry(src: Tensor, state: Tensor) -> Tuple[int, int]:
-    """(n, P) of src [n, P, 134, 3] and its state, int32 [P, 134, 8]."""
+def _pose_clip_geometry(op: str, src: Tensor) -> Tuple[int, int]:
+    """(n, P) of a clip src [n, P, 134, 3], for the operator `op`."""
     if src.dim() != 4 or tuple(src.shape[2:]) != (134, 3) or not 1 <= src.shape[0] <= _lib.POSE_RETARGET_MAX_FRAMES \
             or not 1 <= src.shape[1] <= _lib.POSE_RENDER_MAX_PEOPLE:
-        raise ValueError(f"pose_smooth_frames: src must be [n, P, 134, 3] with 1 <= n <= {_lib.POSE_RETARGET_MAX_FRAMES} and 1 <= P <= "
+        raise ValueError(f"{op}: src must be [n, P, 134, 3] with 1 <= n <= {_lib.POSE_RETARGET_MAX_FRAMES} and 1 <= P <= "
                          f"{_lib.POSE_RENDER_MAX_PEOPLE}, got {tuple(src.shape)}")
-    n, p = int(src.shape[0]), int(src.shape[1])
+    return int(src.shape[0]), int(src.shape[1])
+
+
+def _pose_smooth_geometry(src: Tensor, state: Tensor) -> Tuple[int, int]:
+    """(n, P) of src [n, P, 134, 3] and its state, int32 [P, 134, 8]."""
+    n, p = _pose_clip_geometry("pose_smooth_frames", src)
     if state.dtype != torch.int32 or tuple(state.shape) != (p, 134, 8):
         raise ValueError(f"pose_smooth_frames: state must be int32 [{p}, 134, 8], got {state.dtype} {tuple(state.shape)}")
     return n, p
@@ -1048,15 +1053,12 @@ def _(src, state, period, min_cutoff, beta, kd, score_threshold=0.3, max_gap=0):
 # ------------------------------------------------------------------------------------------ pose tracker
 def _pose_track_geometry(src: Tensor, state: Tensor, slots: int) -> Tuple[int, int]:
     """(n, P) of src [n, P, 134, 3]; its state is int32 [slots + 1, 40]."""
-    if src.dim() != 4 or tuple(src.shape[2:]) != (134, 3) or not 1 <= src.shape[0] <= _lib.POSE_RETARGET_MAX_FRAMES \
-            or not 1 <= src.shape[1] <= _lib.POSE_RENDER_MAX_PEOPLE:
-        raise ValueError(f"pose_track_frames: src must be [n, P, 134, 3] with 1 <= n <= {_lib.POSE_RETARGET_MAX_FRAMES} and 1 <= P <= "
-                         f"{_lib.POSE_RENDER_MAX_PEOPLE}, got {tuple(src.shape)}")
+    n, p = _pose_clip_geometry("pose_track_frames", src)
     if not 1 <= slots <= _lib.POSE_RENDER_MAX_PEOPLE:
         raise ValueError(f"pose_track_frames: slots must be 1..{_lib.POSE_RENDER_MAX_PEOPLE}, got {slots}")
     if state.dtype != torch.int32 or tuple(state.shape) != (slots + 1, _lib.POSE_TRACK_STATE_WORDS):
         raise ValueError(f"pose_track_frames: state must be int32 [{slots + 1}, {_lib.POSE_TRACK_STATE_WORDS}], got {state.dtype} {tuple(state.shape)}")
-    return int(src.shape[0]), int(src.shape[1])
+    return n, p
 
 
 @custom_op(f"{NAMESPACE}::pose_track_frames", mutates_args=("state",))
