@@ -10,8 +10,7 @@
 //
 // The format and the definition of every number are those of self_forcing_amd/jpeg_reference.py (the float64 host oracle).
 // Tables and the header travel as kernel arguments: the library uploads nothing and keeps no state.
-#include "sf_host.h"
-
+#include "sf_frame_host.h"
 
 namespace {
 
@@ -21,9 +20,6 @@ const uint8_t kBaseQuant[2][64] = {
      18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
     {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
      99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
-// kZigzag[k] = natural index of the k-th coefficient of the scan
-const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 const uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
 const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
 const uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
@@ -59,8 +55,6 @@ constexpr int BLOCK_MAX_BITS = 22 + 63 * 26;                       // 1660
 constexpr int BLOCK_MAX_BYTES = (BLOCK_MAX_BITS + 7) / 8;          // 208
 constexpr int SLOT_DW = 53;                                        // 52 dwords hold it; odd stride: lanes hit distinct banks
 constexpr int MERGE_DW = (64 * BLOCK_MAX_BITS + 7 + 31) / 32 + 2;  // one chunk of 64 blocks plus the carried bits
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int quant_value(int base, int quality) {
   const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
@@ -534,17 +528,13 @@ extern "C" int sf_jpeg_transform(const void* frames, int dtype, int value_range,
   const dim3 grid((unsigned)((w + TILE_W - 1) / TILE_W), (unsigned)g.mcus_y, (unsigned)n), block(256);
   hipStream_t s = (hipStream_t)stream;
   const int r01 = value_range == SF_JPEG_RANGE_01;
-#define SF_JPEG_LAUNCH(T, SUB) \
-  return sf_launch<&jpeg_transform_kernel<T, SUB>>(who, grid, block, 0, s, (const T*)frames, (int16_t*)coef, qt, h, w, r01, g.mcus_x, g.blocks)
-  if (subsampling == SF_JPEG_420) {
-    if (dtype == SF_JPEG_U8) SF_JPEG_LAUNCH(uint8_t, true);
-    if (dtype == SF_JPEG_F32) SF_JPEG_LAUNCH(float, true);
-    SF_JPEG_LAUNCH(bf16_t, true);
-  }
-  if (dtype == SF_JPEG_U8) SF_JPEG_LAUNCH(uint8_t, false);
-  if (dtype == SF_JPEG_F32) SF_JPEG_LAUNCH(float, false);
-  SF_JPEG_LAUNCH(bf16_t, false);
-#undef SF_JPEG_LAUNCH
+  const auto launch = [&](auto sub420) {
+    return pixel_dispatch(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      return sf_launch<&jpeg_transform_kernel<T, decltype(sub420)::value>>(who, grid, block, 0, s, (const T*)frames, (int16_t*)coef, qt, h, w, r01, g.mcus_x, g.blocks);
+    });
+  };
+  return subsampling == SF_JPEG_420 ? launch(std::true_type{}) : launch(std::false_type{});
 }
 
 extern "C" int sf_jpeg_entropy(const void* coef, int n, int h, int w, int subsampling, int quality, int restart_interval, void* workspace,

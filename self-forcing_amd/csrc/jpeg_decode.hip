@@ -16,14 +16,10 @@
 // table block (one JpegDecFile per file) followed by the files' bytes.  Every loop below is bounded by the interval's
 // block count and byte range, every read is clamped to the upload, every write to the call's geometry: a damaged file
 // sets bits of its status word and leaves zeros, it cannot reach another file's memory.
-#include "sf_host.h"
+#include "sf_frame_host.h"
 #include "pixel_format.h"
 
 namespace {
-
-// kZigzag[k] = natural index of the k-th coefficient of the scan
-const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 constexpr int LOOK_BITS = 9;
 // jpeg_reference.decode_tables: look[next 9 bits] = (length << 8) | symbol, 0 for a longer code; a code of length L > 9 is
@@ -54,8 +50,6 @@ struct DecGeometry {
   int tcw, tch;                    // the chroma components' true size: ceil(w / lbx), ceil(h / lby)
   size_t marks_off, counts_off, coef_off, plane_off[3], total;
 };
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int geometry(const char* who, int n, int h, int w, int sampling, int max_intervals, DecGeometry* g) {
   SF_CHECK(sampling >= SF_JPEG_DEC_420 && sampling <= SF_JPEG_DEC_GRAY, "%s: unknown sampling %d", who, sampling);
@@ -467,19 +461,13 @@ extern "C" int sf_jpeg_decode_pixels(const void* coef, const void* upload, size_
   hipStream_t s = (hipStream_t)stream;
   SF_TRY(sf_launch<&jpeg_decode_idct_kernel>(who, dim3((unsigned)((g.blocks + 31) / 32), (unsigned)n), dim3(256), 0, s, (const int16_t*)coef,
                                              (const uint8_t*)upload, py, pcb, pcr, tab, g.bpm, g.lbx, g.mcus_x, g.blocks, g.yw, g.yh, g.cw, g.ch));
-  const long hw = (long)h * w;
-  long sn, sc, sy, sx;
-  if (layout == SF_JPEG_HWC) sn = 3 * hw, sc = 1, sy = 3L * w, sx = 3;
-  else if (layout == SF_JPEG_POSE) sn = hw, sc = (long)n * hw, sy = w, sx = 1;
-  else sn = 3 * hw, sc = hw, sy = w, sx = 1;
+  const FrameStrides to = frame_strides(layout, n, h, w);
   const dim3 grid((unsigned)(((w + 3) / 4 + 63) / 64), (unsigned)((h + 3) / 4), (unsigned)n), block(64, 4);
-#define SF_JPEG_DEC_LAUNCH(T)                                                                                                                          \
-  return sf_launch<&jpeg_decode_colour_kernel<T>>(who, grid, block, 0, s, py, pcb, pcr, (T*)out, h, w, g.comps, g.lbx, g.lby, g.yw, g.yh, g.cw, g.ch, \
-                                                  g.tcw, g.tch, sn, sc, sy, sx)
-  if (dtype == SF_JPEG_U8) SF_JPEG_DEC_LAUNCH(uint8_t);
-  if (dtype == SF_JPEG_F32) SF_JPEG_DEC_LAUNCH(float);
-  SF_JPEG_DEC_LAUNCH(bf16_t);
-#undef SF_JPEG_DEC_LAUNCH
+  return pixel_dispatch(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return sf_launch<&jpeg_decode_colour_kernel<T>>(who, grid, block, 0, s, py, pcb, pcr, (T*)out, h, w, g.comps, g.lbx, g.lby, g.yw, g.yh, g.cw, g.ch,
+                                                    g.tcw, g.tch, to.sn, to.sc, to.sy, to.sx);
+  });
 }
 
 extern "C" int sf_jpeg_decode_frames(const void* upload, size_t upload_bytes, const int32_t* idct_table, int n, int h, int w, int sampling, int max_intervals,

@@ -22,8 +22,7 @@
 // The 3x3x3 layers also run over a temporal WINDOW of a clip (sf_pose_conv_window): x holds a range of the clip's frames,
 // the brick walk starts at any output frame, and every output element is formed from the same taps in the same k order
 // as in the whole-volume call, so a clip embedded piece by piece has the whole clip's bits.
-#include "sf_common.h"
-#include "../../include/sf_hip.h"
+#include "sf_frame_host.h"
 
 namespace {
 
@@ -365,10 +364,9 @@ extern "C" int sf_pose_prepare(const void* src, int dtype, int hwc, int F, int H
   const dim3 grid((unsigned)((n_pos + 255) / 256));
   hipStream_t s = (hipStream_t)stream;
   const long plane = (long)F * hw;
-  if (dtype == SF_POSE_U8)
-    return sf_launch<&pose_prepare_kernel<uint8_t>>("sf_pose_prepare", grid, dim3(256), 0, s, (const uint8_t*)src, (bf16_t*)out, n_pos, (int)hw, plane, hwc,
-                                                    lead);
-  if (dtype == SF_POSE_F32)
-    return sf_launch<&pose_prepare_kernel<float>>("sf_pose_prepare", grid, dim3(256), 0, s, (const float*)src, (bf16_t*)out, n_pos, (int)hw, plane, hwc, lead);
-  return sf_launch<&pose_prepare_kernel<bf16_t>>("sf_pose_prepare", grid, dim3(256), 0, s, (const bf16_t*)src, (bf16_t*)out, n_pos, (int)hw, plane, hwc, lead);
+  static_assert(SF_POSE_U8 == (int)SF_JPEG_U8 && SF_POSE_F32 == (int)SF_JPEG_F32 && SF_POSE_BF16 == (int)SF_JPEG_BF16, "pixel_dispatch reads sf_pose_dtype");
+  return pixel_dispatch(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return sf_launch<&pose_prepare_kernel<T>>("sf_pose_prepare", grid, dim3(256), 0, s, (const T*)src, (bf16_t*)out, n_pos, (int)hw, plane, hwc, lead);
+  });
 }

@@ -22,11 +22,11 @@
 // bound), every element of every output is written, and the entry points refuse ranges that overlap.
 #pragma clang fp contract(off)
 #include <cmath>
-#include "sf_host.h"
+#include "sf_frame_host.h"
 
 namespace {
 
-constexpr int WAVE = 64, POINTS = 134, SIMCC = SF_POSE_SIMCC_POINTS;
+constexpr int WAVE = 64, SIMCC = SF_POSE_SIMCC_POINTS;
 constexpr int CAND_THREADS = 256, CROP_THREADS = 256;
 constexpr int NMS_THREADS = 1024, NMS_WAVES = NMS_THREADS / WAVE, NMS_PER = SF_POSE_BOXES_MAX_ANCHORS / NMS_THREADS;
 constexpr int SIMCC_THREADS = 1024, SIMCC_WAVES = SIMCC_THREADS / WAVE, SIMCC_BATCH = 4;
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(SIMCC_THREADS) void pose_simcc_kernel(SimccArgs a) 
   float* __restrict__ out = a.out + (size_t)n * POINTS * 3;
   const Window win = window_of(a.boxes, a.count, n, a.people, a.out_h, a.out_w, a.padding);
   if (!win.valid) {                                       // the same in every lane: nothing of the logits is read
-    if (t < POINTS) out[t * 3] = -1.f, out[t * 3 + 1] = -1.f, out[t * 3 + 2] = 0.f;
+    if (t < POINTS) out[t * 3] = ABSENT_XY, out[t * 3 + 1] = ABSENT_XY, out[t * 3 + 2] = ABSENT_SCORE;
     return;
   }
   constexpr int VEC = 16 / sizeof(T), BATCH = WAVE * SIMCC_BATCH;
@@ -373,28 +373,10 @@ __global__ __launch_bounds__(SIMCC_THREADS) void pose_simcc_kernel(SimccArgs a) 
   } else {
     p = point(src < 17 ? src : src - 1);
   }
-  out[t * 3] = p.ok ? p.x : -1.f, out[t * 3 + 1] = p.ok ? p.y : -1.f, out[t * 3 + 2] = p.ok ? p.s : 0.f;
+  out[t * 3] = p.ok ? p.x : ABSENT_XY, out[t * 3 + 1] = p.ok ? p.y : ABSENT_XY, out[t * 3 + 2] = p.ok ? p.s : ABSENT_SCORE;
 }
 
 // ------------------------------------------------------------------------------------------ host
-struct Range {
-  const char* name;
-  const void* p;
-  size_t bytes;
-};
-
-inline bool overlap(const Range& a, const Range& b) {
-  const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
-  return x < y + b.bytes && y < x + a.bytes;
-}
-
-template <int N>
-inline int disjoint(const char* who, const Range (&r)[N]) {
-  for (int i = 0; i < N; ++i)
-    for (int j = i + 1; j < N; ++j) SF_CHECK(!overlap(r[i], r[j]), "%s: %s and %s overlap", who, r[i].name, r[j].name);
-  return 0;
-}
-
 inline int check_people_frames(const char* who, int F, int P) {
   SF_CHECK(F > 0 && F <= SF_POSE_BOXES_MAX_FRAMES, "%s: F=%d (1..%d)", who, F, SF_POSE_BOXES_MAX_FRAMES);
   SF_CHECK(P > 0 && P <= SF_POSE_RENDER_MAX_PEOPLE, "%s: P=%d (1..%d)", who, P, SF_POSE_RENDER_MAX_PEOPLE);
@@ -481,9 +463,8 @@ extern "C" int sf_pose_crop_people(const sf_pose_crop_args* args, void* stream) 
   SF_TRY(disjoint(who, range));
   CropArgs a;
   a.frames = (const uint8_t*)args->frames, a.boxes = args->boxes, a.count = args->count, a.out = args->out;
-  a.frame_stride = args->layout == SF_JPEG_POSE ? (long)pixels : 3 * (long)pixels;
-  a.chan_stride = args->layout == SF_JPEG_HWC ? 1 : args->layout == SF_JPEG_POSE ? (long)args->F * (long)pixels : (long)pixels;
-  a.pix_stride = args->layout == SF_JPEG_HWC ? 3 : 1;
+  const FrameStrides from = frame_strides(args->layout, args->F, args->H, args->W);
+  a.frame_stride = from.sn, a.chan_stride = from.sc, a.pix_stride = from.sx;
   a.people = args->P, a.H = args->H, a.W = args->W, a.out_h = args->out_h, a.out_w = args->out_w, a.bgr = args->bgr != 0;
   a.padding = args->padding;
   for (int c = 0; c < 3; ++c) a.mean[c] = args->mean[c], a.std[c] = args->std[c];
@@ -491,9 +472,10 @@ extern "C" int sf_pose_crop_people(const sf_pose_crop_args* args, void* stream) 
   const size_t lanes = quads ? plane / 4 : plane;
   const dim3 grid((unsigned)(args->F * args->P), (unsigned)((lanes + CROP_THREADS - 1) / CROP_THREADS));
   const hipStream_t s = (hipStream_t)stream;
-  if (args->dtype == SF_JPEG_F32)
-    return quads ? sf_launch<&pose_crop_kernel<float, 4>>(who, grid, dim3(CROP_THREADS), 0, s, a) : sf_launch<&pose_crop_kernel<float, 1>>(who, grid, dim3(CROP_THREADS), 0, s, a);
-  return quads ? sf_launch<&pose_crop_kernel<bf16_t, 4>>(who, grid, dim3(CROP_THREADS), 0, s, a) : sf_launch<&pose_crop_kernel<bf16_t, 1>>(who, grid, dim3(CROP_THREADS), 0, s, a);
+  return pixel_dispatch<false>(args->dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return quads ? sf_launch<&pose_crop_kernel<T, 4>>(who, grid, dim3(CROP_THREADS), 0, s, a) : sf_launch<&pose_crop_kernel<T, 1>>(who, grid, dim3(CROP_THREADS), 0, s, a);
+  });
 }
 
 extern "C" int sf_pose_simcc_decode(const sf_pose_simcc_args* args, void* stream) {

@@ -18,13 +18,13 @@
 // Every read of the keypoints lies inside [F][P][134][3]; every write inside the tile and the frame (store_rgb4 drops the
 // columns >= W).
 #include <cmath>
-#include "sf_host.h"
+#include "sf_frame_host.h"
 #include "pixel_format.h"
 
 namespace {
 
 constexpr int TW = 64, TH = 16;                      // tile; 256 threads = TH rows x TW / 4 quads
-constexpr int POINTS = 134, PER_PERSON = 185;
+constexpr int PER_PERSON = 185;
 constexpr int LIST = PER_PERSON * SF_POSE_RENDER_MAX_PEOPLE;
 constexpr int PASSES = (LIST + 255) / 256;
 constexpr int LIMB = 0, DISC = 1, EDGE = 2;
@@ -207,13 +207,12 @@ extern "C" int sf_pose_render_frames(const sf_pose_render_args* args, void* stre
   RenderArgs a;
   a.kp = args->keypoints, a.P = args->P, a.H = args->H, a.W = args->W;
   a.normalized = args->normalized, a.threshold = args->score_threshold;
-  const long hw = (long)a.H * a.W;
-  if (args->layout == SF_JPEG_HWC) a.sn = 3 * hw, a.sc = 1, a.sy = 3L * a.W, a.sx = 3;
-  else if (args->layout == SF_JPEG_POSE) a.sn = hw, a.sc = (long)args->F * hw, a.sy = a.W, a.sx = 1;
-  else a.sn = 3 * hw, a.sc = hw, a.sy = a.W, a.sx = 1;
+  const FrameStrides to = frame_strides(args->layout, args->F, a.H, a.W);
+  a.sn = to.sn, a.sc = to.sc, a.sy = to.sy, a.sx = to.sx;
   const dim3 grid((unsigned)(((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH)), (unsigned)args->F);
   hipStream_t s = (hipStream_t)stream;
-  if (args->dtype == SF_JPEG_U8) return sf_launch<&pose_render_kernel<uint8_t>>(who, grid, dim3(256), 0, s, a, (uint8_t*)args->out);
-  if (args->dtype == SF_JPEG_F32) return sf_launch<&pose_render_kernel<float>>(who, grid, dim3(256), 0, s, a, (float*)args->out);
-  return sf_launch<&pose_render_kernel<bf16_t>>(who, grid, dim3(256), 0, s, a, (bf16_t*)args->out);
+  return pixel_dispatch(args->dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return sf_launch<&pose_render_kernel<T>>(who, grid, dim3(256), 0, s, a, (T*)args->out);
+  });
 }

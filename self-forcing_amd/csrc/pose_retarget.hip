@@ -17,11 +17,11 @@
 // that i0 and i1 of every requested frame fall in the piece); every write inside out [n_out][P][134][3].
 #pragma clang fp contract(off)
 #include <cmath>
-#include "sf_host.h"
+#include "sf_frame_host.h"
 
 namespace {
 
-constexpr int POINTS = 134, BODY = 18, EDGES = 17, GROUPS = 9, NECK = 1, THREADS = 192;
+constexpr int EDGES = 17, GROUPS = 9, NECK = 1, THREADS = 192;
 constexpr int HAND_GROUP = 2, FACE_GROUP = 7;         // the forearms {3, 5}, nose-eye {13, 15}
 constexpr long MAX_INDEX = 1L << 40;                  // frame indices: index * 65535 stays far inside int64
 
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(THREADS) void pose_retarget_kernel(RetargetArgs a) 
   }
   if (t < POINTS) {
     float* o = a.out + (((long)blockIdx.x * a.P + person) * POINTS + t) * 3;
-    o[0] = q.ok ? ox : -1.f, o[1] = q.ok ? oy : -1.f, o[2] = q.ok ? q.s : 0.f;
+    o[0] = q.ok ? ox : ABSENT_XY, o[1] = q.ok ? oy : ABSENT_XY, o[2] = q.ok ? q.s : ABSENT_SCORE;
   }
 }
 

@@ -11,11 +11,11 @@
 // state [P][134][8]; every element of out [n][P][134][3] is written; the entry point refuses ranges that overlap.
 #pragma clang fp contract(off)
 #include <cmath>
-#include "sf_host.h"
+#include "sf_frame_host.h"
 
 namespace {
 
-constexpr int POINTS = 134, THREADS = 64, STATE_BYTES = 32;
+constexpr int THREADS = 64, STATE_BYTES = 32;
 constexpr int MAX_GAP = 65535;
 constexpr float TWO_PI = 0x1.921fb6p+2f;              // fp32(2 pi)
 
@@ -77,7 +77,7 @@ __device__ __forceinline__ Sample step(Filter& k, Sample in, const SmoothArgs& a
   }
   k.gap = hold ? k.gap + 1 : 0;
   k.seen = ok || hold;
-  return {k.seen ? k.hx : -1.f, k.seen ? k.hy : -1.f, k.seen ? k.s : 0.f};
+  return {k.seen ? k.hx : ABSENT_XY, k.seen ? k.hy : ABSENT_XY, k.seen ? k.s : ABSENT_SCORE};
 }
 
 // Frame f + 1 is loaded before frame f's chain starts and frame f is stored behind it.  The first frame is peeled off the
@@ -108,11 +108,6 @@ __global__ __launch_bounds__(THREADS) void pose_smooth_kernel(SmoothArgs a) {
   st[1] = make_uint4(__float_as_uint(k.s), (unsigned)k.gap, k.seen ? 1u : 0u, 0u);
 }
 
-inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
-
 }  // namespace
 
 extern "C" size_t sf_pose_smooth_state_bytes(int people) {
@@ -135,9 +130,8 @@ extern "C" int sf_pose_smooth_frames(const sf_pose_smooth_args* args, void* stre
   SF_CHECK(std::isfinite(args->score_threshold), "%s: score_threshold must be finite", who);
   const int lanes = args->people * POINTS;
   const size_t frames_bytes = (size_t)args->n * lanes * 3 * sizeof(float), state_bytes = (size_t)lanes * STATE_BYTES;
-  SF_CHECK(!overlap(args->src, frames_bytes, args->out, frames_bytes), "%s: src and out overlap", who);
-  SF_CHECK(!overlap(args->src, frames_bytes, args->state, state_bytes), "%s: src and state overlap", who);
-  SF_CHECK(!overlap(args->out, frames_bytes, args->state, state_bytes), "%s: out and state overlap", who);
+  const Range range[3] = {{"src", args->src, frames_bytes}, {"out", args->out, frames_bytes}, {"state", args->state, state_bytes}};
+  SF_TRY(disjoint(who, range));
   SmoothArgs a;
   a.src = args->src, a.out = args->out, a.state = (uint4*)args->state;
   a.n = args->n, a.lanes = lanes;

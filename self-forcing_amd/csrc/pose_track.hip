@@ -17,11 +17,11 @@
 // assign is written; the entry point refuses ranges that overlap.
 #pragma clang fp contract(off)
 #include <cmath>
-#include "sf_host.h"
+#include "sf_frame_host.h"
 
 namespace {
 
-constexpr int POINTS = 134, BODY = 18, ROW = POINTS * 3, WAVE = 64, GRID = 8;
+constexpr int ROW = POINTS * 3, WAVE = 64, GRID = 8;
 constexpr int STATE_WORDS = 40, W_MASK = 36, W_AGE = 37, W_ID = 38, W_ALIVE = 39;
 constexpr int MAX_AGE = 65535, GATHER_THREADS = 256;
 
@@ -221,13 +221,8 @@ __global__ __launch_bounds__(GATHER_THREADS) void pose_track_gather_kernel(Gathe
   const int e = (int)(i - row * ROW);
   const int d = a.assign[row];
   const size_t f = row / (size_t)a.slots;
-  const float marker = e % 3 == 2 ? 0.f : -1.f;
+  const float marker = e % 3 == 2 ? ABSENT_SCORE : ABSENT_XY;
   a.out[i] = d >= 0 && d < a.people ? a.src[(f * a.people + d) * ROW + e] : marker;
-}
-
-inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
 }
 
 }  // namespace
@@ -252,15 +247,12 @@ extern "C" int sf_pose_track_frames(const sf_pose_track_args* args, void* stream
   SF_CHECK(std::isfinite(args->gate2) && args->gate2 > 0.f, "%s: gate2 must be finite and > 0", who);
   SF_CHECK(std::isfinite(args->score_threshold), "%s: score_threshold must be finite", who);
   const size_t rows = (size_t)args->n * args->slots;
-  const struct { const char* name; const void* p; size_t bytes; } range[5] = {
-      {"src", args->src, (size_t)args->n * args->people * ROW * sizeof(float)},
-      {"out", args->out, rows * ROW * sizeof(float)},
-      {"ids", args->ids, rows * sizeof(int32_t)},
-      {"state", args->state, sf_pose_track_state_bytes(args->slots)},
-      {"assign", args->assign, rows * sizeof(int32_t)}};
-  for (int i = 0; i < 5; ++i)
-    for (int j = i + 1; j < 5; ++j)
-      SF_CHECK(!overlap(range[i].p, range[i].bytes, range[j].p, range[j].bytes), "%s: %s and %s overlap", who, range[i].name, range[j].name);
+  const Range range[5] = {{"src", args->src, (size_t)args->n * args->people * ROW * sizeof(float)},
+                          {"out", args->out, rows * ROW * sizeof(float)},
+                          {"ids", args->ids, rows * sizeof(int32_t)},
+                          {"state", args->state, sf_pose_track_state_bytes(args->slots)},
+                          {"assign", args->assign, rows * sizeof(int32_t)}};
+  SF_TRY(disjoint(who, range));
   TrackArgs a;
   a.src = args->src, a.assign = args->assign, a.ids = args->ids, a.state = (uint4*)args->state;
   a.n = args->n, a.people = args->people, a.slots = args->slots;

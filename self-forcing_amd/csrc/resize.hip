@@ -16,7 +16,7 @@
 // LDS grows with the reduction ratio; at SF_RESIZE_MAX_RATIO per axis it is 58 KiB, which is where the limit comes from.
 // Nothing in the tables is trusted: every LDS index derived from them is checked against the tile's extent, every
 // global read lies inside the frames, every write inside the output tile.
-#include "sf_host.h"
+#include "sf_frame_host.h"
 #include "pixel_format.h"
 
 namespace {
@@ -176,13 +176,6 @@ int tile_extent(int in_size, int out_size, int filter, int tile) {
   return e + 3 < in_size ? (int)e + 3 : in_size;
 }
 
-void strides(int layout, int n, int h, int w, long* sn, long* sc, long* sy, long* sx) {
-  const long hw = (long)h * w;
-  if (layout == SF_JPEG_HWC) *sn = 3 * hw, *sc = 1, *sy = 3L * w, *sx = 3;
-  else if (layout == SF_JPEG_POSE) *sn = hw, *sc = (long)n * hw, *sy = w, *sx = 1;
-  else *sn = 3 * hw, *sc = hw, *sy = w, *sx = 1;
-}
-
 }  // namespace
 
 extern "C" int sf_resize_kernel_size(int in_size, int out_size, int filter) {
@@ -221,8 +214,8 @@ extern "C" int sf_resize_frames(const void* frames, int layout, int n, int h, in
   SF_CHECK(((uintptr_t)bounds_h | (uintptr_t)coefs_h | (uintptr_t)bounds_v | (uintptr_t)coefs_v) % 4 == 0, "%s: the tables must be 4-byte aligned", who);
   a.in = (const uint8_t*)frames;
   a.in_bytes = 3L * n * h * w;
-  strides(layout, n, h, w, &a.in_sn, &a.in_sc, &a.in_sy, &a.in_sx);
-  strides(out_layout, n, out_h, out_w, &a.sn, &a.sc, &a.sy, &a.sx);
+  const FrameStrides in = frame_strides(layout, n, h, w), to = frame_strides(out_layout, n, out_h, out_w);
+  a.in_sn = in.sn, a.in_sc = in.sc, a.in_sy = in.sy, a.in_sx = in.sx, a.sn = to.sn, a.sc = to.sc, a.sy = to.sy, a.sx = to.sx;
   a.bh = bounds_h, a.kh = coefs_h, a.bv = bounds_v, a.kv = coefs_v;
   a.ksh = sf_resize_kernel_size(a.cw, out_w, filter), a.ksv = sf_resize_kernel_size(a.ch, out_h, filter);
   a.oh = out_h, a.ow = out_w;
@@ -236,7 +229,8 @@ extern "C" int sf_resize_frames(const void* frames, int layout, int n, int h, in
   SF_CHECK(lds <= 65536, "%s: %zu bytes of LDS for %dx%d -> %dx%d", who, lds, a.ch, a.cw, out_h, out_w);
   const dim3 grid((unsigned)((out_w + TW - 1) / TW), (unsigned)((out_h + TH - 1) / TH), (unsigned)n);
   hipStream_t s = (hipStream_t)stream;
-  if (out_dtype == SF_JPEG_U8) return sf_launch<&resize_kernel<uint8_t>>(who, grid, dim3(256), lds, s, a, (uint8_t*)out);
-  if (out_dtype == SF_JPEG_F32) return sf_launch<&resize_kernel<float>>(who, grid, dim3(256), lds, s, a, (float*)out);
-  return sf_launch<&resize_kernel<bf16_t>>(who, grid, dim3(256), lds, s, a, (bf16_t*)out);
+  return pixel_dispatch(out_dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return sf_launch<&resize_kernel<T>>(who, grid, dim3(256), lds, s, a, (T*)out);
+  });
 }

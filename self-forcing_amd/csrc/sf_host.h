@@ -1,6 +1,8 @@
 // Internal scaffold shared by the host sequencers (dit_forward, t5_encoder, vae_decode / vae_encode through vae_common.h,
-// taehv_decode, pose_embed, jpeg): workspace carving, error propagation, and the one way to issue a GEMM.
-// Host-side only; not part of include/sf_hip.h.
+// taehv_decode, pose_embed): workspace carving, error propagation, and the one way to issue a GEMM.  The frame and
+// keypoint entry points (jpeg, jpeg_decode, resize, pose_render / retarget / smooth / track / estimate, sf_pose_prepare)
+// include sf_frame_host.h, which brings this file and adds their own shared pieces (strides, ranges, the pixel-type
+// dispatch, keypoint constants).  Host-side only; not part of include/sf_hip.h.
 #pragma once
 #include <cstring>
 #include "sf_common.h"
