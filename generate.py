@@ -42,6 +42,9 @@ frames in which a point is missing, both on the GPU in `PoseSmoother`, in front 
 in front of the smoother), for detectors that list the people of a frame in detection order; `--pose_track_gate G` is how far a person may
 move between matches, in diagonals of its own body box, and `--pose_track_age N` how many frames a slot waits for its person.  The
 reference file is never tracked.
+`--open_length` (few-step configs with a rolling KV cache, `local_attn_size` in `model_kwargs`) lets the pose clip decide the length
+instead of `--num_output_frames`: the clip goes piece by piece into `CausalInferencePipeline.open_session`, which generates until it
+ends -- past the 1024 frames of the RoPE tables too -- and the files are written as usual (`pt` and `mjpeg`).
 
 `--i2v` (inference.py:83-90, 136-149) reads `--data_path` as a TextImagePairDataset directory -- one
 `target_crop_info_<ratio>.json` listing `file_name` / `caption` entries, images under `<ratio>/` --, encodes each
@@ -356,6 +359,10 @@ def main():
                          "to keypoints (.npz / .npy array), which are drawn at the output size")
     ap.add_argument("--pose_weights_path", default=None, help="pose embedding weights (dwpose_embedding.* / randomref_embedding_pose.*)")
     ap.add_argument("--pose_random_init_seed", type=int, default=None, help="seeded random pose embedding weights instead")
+    ap.add_argument("--open_length", action="store_true",
+                    help="few-step configs with a rolling KV cache (local_attn_size in model_kwargs): let the pose clip of --pose_path decide the "
+                         "length, not --num_output_frames -- the clip is fed piece by piece to CausalInferencePipeline.open_session, which goes on "
+                         "until it ends")
     ap.add_argument("--video_format", choices=("pt", "mjpeg"), default="pt",
                     help="pt: <idx>-<sample>.video.pt (uint8 tensor); mjpeg: <idx>-<sample>.avi, JPEG frames encoded on the GPU, 16 frames/s")
     ap.add_argument("--jpeg_quality", type=int, default=90, help="--video_format mjpeg: 1..100")
@@ -364,6 +371,10 @@ def main():
     if not 1 <= a.jpeg_quality <= 100:
         ap.error("--jpeg_quality must be 1..100")
     pose_kind, pose_source_size, pose_smooth, pose_track = check_pose_flags(ap, a)
+    if a.open_length and not a.pose_path:
+        ap.error("--open_length needs --pose_path: the pose clip decides the length of the video")
+    if a.open_length and a.i2v:
+        ap.error("--open_length starts from noise: not together with --i2v (an initial latent)")
     if a.pose_resize != "none" and not (a.pose_path and a.pose_path.lower().endswith(".avi")):
         ap.error("--pose_resize goes with an MJPEG --pose_path (.avi); a .pt / .npy dict is taken at the size it has, keypoints are drawn at the "
                  "output size")
@@ -395,6 +406,9 @@ def main():
 
     cfg = load_config(a.config_path, a.default_config_path)
     kwargs = dict(cfg.get("model_kwargs") or {})
+    if a.open_length and (not is_few_step(cfg) or kwargs.get("local_attn_size", -1) == -1):
+        raise SystemExit("--open_length needs a few-step config with a rolling KV cache (model_kwargs.local_attn_size > 0): with global attention "
+                         "the cache holds every frame and the length is bounded by it")
     if a.checkpoint_path:
         if a.checkpoint_path.endswith(".safetensors"):
             from safetensors.torch import load_file
@@ -488,7 +502,12 @@ def main():
         n_noise = a.num_output_frames - (1 if a.i2v else 0)
         noise = torch.randn([a.num_samples, n_noise, 16, a.latent_height, a.latent_width], device=device, dtype=torch.bfloat16)
         dwpose, ref_pose = pose_data if a.pose_path else (None, None)
-        if few_step:
+        if a.open_length:      # the clip as a feed of 16-frame pieces; the session ends with it
+            session = pipe.open_session([prompts[idx]] * a.num_samples, (a.latent_height, a.latent_width), batch_size=a.num_samples,
+                                        pose_feed=iter(dwpose.split(16, dim=1)), random_ref_dwpose=ref_pose, input_image=input_image)
+            chunks = [(lat, pixels) for _, lat, pixels in session]
+            latents, video = torch.cat([c[0] for c in chunks], dim=1), torch.cat([c[1] for c in chunks], dim=1)
+        elif few_step:
             video, latents = pipe.inference(noise=noise, text_prompts=[prompts[idx]] * a.num_samples, initial_latent=initial,
                                             return_latents=True, input_image=input_image, dwpose_data=dwpose, random_ref_dwpose=ref_pose)
         else:

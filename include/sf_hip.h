@@ -147,6 +147,18 @@ int sf_qkv_norm_rope_cache(const void* qkv, const void* norm_q_w, const void* no
 int sf_kv_evict(void* cache, int B, int64_t cache_tokens, int row_elems, int sink, int evict, int keep,
                 void* scratch, size_t scratch_bytes, void* stream);
 
+/* Re-base the temporal RoPE of cached keys, in place: rows [row0, row0 + rows) of every sample of the bf16
+ * [B, cache_tokens, num_heads, 128] cache are rotated back by delta_frames frames, so that a session can subtract
+ * delta_frames from every temporal position it still holds (scores depend on pos_q - pos_k only).  Of each head only
+ * the temporal pairs change -- complex pairs j < 22, columns 2j and 2j + 1, angles from table columns 0..21, the split
+ * of sf_qkv_norm_rope_cache: with c = rope_cos[delta_frames][j], s = rope_sin[delta_frames][j] and (a, b) the pair,
+ *   a' = bf16(fl(fl(a c) + fl(b s))),  b' = bf16(fl(fl(b c) - fl(a s)))
+ * every fp32 operation rounded on its own, bf16 by round-to-nearest-even (rope_shift_reference.py; bit exact).
+ * Columns 44..127, rows outside the range and V are never written.  1 <= delta_frames <= 1023; rows == 0 is a no-op.
+ * No scratch. */
+int sf_kv_rope_shift(void* k_cache, int B, int64_t cache_tokens, int num_heads, int64_t row0, int64_t rows,
+                     const float* rope_cos, const float* rope_sin, int delta_frames, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Non-causal attention softmax(q k^T / sqrt(D)) v, D = 128.  Replaces flash_attn_varlen_func /
  * SDPA of wan/modules/attention.py:136-150, :198 for self-attention over the KV cache

@@ -353,6 +353,7 @@ SIGNATURES = {
     "sf_qkv_norm_rope_cache": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64,
                                          _i, _i, _f, _vp]),
     "sf_kv_evict": (C.c_int, [_vp, _i, _i64, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "sf_kv_rope_shift": (C.c_int, [_vp, _i, _i64, _i, _i64, _i64, _vp, _vp, _i, _vp]),
     "sf_attention": (C.c_int, [C.POINTER(AttentionArgs), _vp]),
     "sf_cross_fold_scan": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _i, _i, _i, _vp, _vp, _vp]),
     "sf_patchify": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),

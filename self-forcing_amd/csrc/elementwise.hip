@@ -8,6 +8,7 @@
 //   qkv_norm_rope_cache q/k RMSNorm + 3-axis RoPE + KV-cache append   causal_model.py:112-114,
 //                                                       :28-56, :195-200, :221-229
 //   copy_rows           rolling-window eviction         causal_model.py:212-217
+//   kv_rope_shift       cached keys' temporal RoPE re-based by a frame count (open-length sessions; element-wise, no wave per row)
 //   patchify / unpatchify_x0 / add_noise / sinusoid     causal_model.py:775-781, :1081-1104,
 //                                                       wan_wrapper.py:204-228, scheduler.py:159-176,
 //                                                       model.py:15-25
@@ -215,6 +216,50 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const char* __restrict__
   char* d = dst + (long)blockIdx.y * dst_bstride;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x)
     reinterpret_cast<u32x4*>(d)[i] = reinterpret_cast<const u32x4*>(s)[i];
+}
+
+// Re-base the temporal RoPE of cached keys: rotate the temporal pairs of rows [row0, row0 + rows) of every sample back by
+// `delta` frames.  A head's temporal pairs are its first c0 = 22 complex pairs, columns 0..43 (the split of
+// qkv_norm_rope_cache_kernel above): five 16-byte chunks and one 8-byte chunk per head, one lane each, so no lane
+// touches column 44 or beyond.  cs / sn point at row `delta` of the tables.
+constexpr int ROPE_T_PAIRS = 22;                          // c0 of sf_qkv_norm_rope_cache: 64 - 2 * (64 / 3)
+constexpr int ROPE_T_CHUNKS = (ROPE_T_PAIRS + 3) / 4;     // 6: chunks 0..4 hold four pairs, chunk 5 the last two
+
+// float32 -> bf16 bits, round to nearest even, in integer arithmetic (what torch's conversion does, subnormals included,
+// whatever the wave's denormal mode makes of a convert instruction)
+__device__ __forceinline__ unsigned int bf16_bits_rne(float x) {
+  const unsigned int u = __builtin_bit_cast(unsigned int, x);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;      // NaN
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+template <int NP>
+__device__ __forceinline__ void rope_unrotate(bf16_t* p, const float* __restrict__ cs, const float* __restrict__ sn) {
+#pragma clang fp contract(off)  // fl(fl(a c) + fl(b s)), fl(fl(b c) - fl(a s)): the definition of rope_shift_reference.py
+  typedef unsigned int vec_t __attribute__((ext_vector_type(NP)));      // one 32-bit word per pair: a low, b high
+  const vec_t v = *reinterpret_cast<const vec_t*>(p);
+  vec_t o;
+#pragma unroll
+  for (int pp = 0; pp < NP; ++pp) {
+    const float a = __builtin_bit_cast(float, v[pp] << 16), b = __builtin_bit_cast(float, v[pp] & 0xffff0000u), c = cs[pp], s = sn[pp];
+    const float ac = a * c, bs = b * s, bc = b * c, as = a * s;
+    o[pp] = bf16_bits_rne(ac + bs) | (bf16_bits_rne(bc - as) << 16);
+  }
+  *reinterpret_cast<vec_t*>(p) = o;
+}
+
+// grid (blocks over a sample's items, B); items = rows * num_heads * ROPE_T_CHUNKS < 2^31, head fastest behind the chunk
+__global__ __launch_bounds__(256) void kv_rope_shift_kernel(bf16_t* __restrict__ k_cache, long cache_tokens, int num_heads, long row0,
+                                                            const float* __restrict__ cs, const float* __restrict__ sn, unsigned items) {
+  bf16_t* base = k_cache + ((long)blockIdx.y * cache_tokens + row0) * num_heads * 128;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < items; i += gridDim.x * blockDim.x) {
+    const unsigned chunk = i % ROPE_T_CHUNKS, hr = i / ROPE_T_CHUNKS;      // hr = row * num_heads + head: the (row, head) slices are contiguous
+    bf16_t* p = base + (long)hr * 128 + chunk * 8;
+    if (chunk < ROPE_T_CHUNKS - 1)
+      rope_unrotate<4>(p, cs + chunk * 4, sn + chunk * 4);
+    else
+      rope_unrotate<ROPE_T_PAIRS - 4 * (ROPE_T_CHUNKS - 1)>(p, cs + chunk * 4, sn + chunk * 4);
+  }
 }
 
 // x [B, F, Cin, H, W] -> cols [B*F*h*w, Cin*4], column c*4 + p*2 + q
@@ -470,6 +515,23 @@ extern "C" int sf_kv_evict(void* cache, int B, int64_t cache_tokens, int row_ele
   // go through a scratch buffer (cache -> scratch -> cache)
   SF_TRY(sf_launch<&copy_rows_kernel>("sf_kv_evict", grid, block, 0, s, base + (long)(sink + evict) * row_b, bstride, (char*)scratch, bytes, bytes));
   return sf_launch<&copy_rows_kernel>("sf_kv_evict", grid, block, 0, s, (const char*)scratch, bytes, base + (long)sink * row_b, bstride, bytes);
+}
+
+extern "C" int sf_kv_rope_shift(void* k_cache, int B, int64_t cache_tokens, int num_heads, int64_t row0, int64_t rows,
+                                const float* rope_cos, const float* rope_sin, int delta_frames, void* stream) {
+  SF_CHECK(k_cache && rope_cos && rope_sin, "sf_kv_rope_shift: null tensor");
+  SF_CHECK(B > 0 && cache_tokens > 0 && num_heads > 0, "sf_kv_rope_shift: bad shape (B=%d cache_tokens=%lld heads=%d; head_dim is 128)", B,
+           (long long)cache_tokens, num_heads);
+  SF_CHECK(delta_frames >= 1 && delta_frames <= 1023, "sf_kv_rope_shift: delta_frames=%d outside 1..1023 (the 1024-entry table)", delta_frames);
+  SF_CHECK(row0 >= 0 && rows >= 0 && row0 <= cache_tokens && rows <= cache_tokens - row0,
+           "sf_kv_rope_shift: rows [%lld, %lld + %lld) outside the cache of %lld", (long long)row0, (long long)row0, (long long)rows,
+           (long long)cache_tokens);
+  if (rows == 0) return 0;
+  const long items = (long)rows * num_heads * ROPE_T_CHUNKS;      // per sample
+  SF_CHECK(items < (1L << 31) && B <= 65535, "sf_kv_rope_shift: %lld rows of %d heads in %d samples exceed one launch", (long long)rows, num_heads, B);
+  const dim3 grid((unsigned)min((long)4096, (items + 255) / 256), B), block(256);
+  return sf_launch<&kv_rope_shift_kernel>("sf_kv_rope_shift", grid, block, 0, (hipStream_t)stream, (bf16_t*)k_cache, (long)cache_tokens, num_heads,
+                                         (long)row0, rope_cos + (long)delta_frames * 64, rope_sin + (long)delta_frames * 64, (unsigned)items);
 }
 
 extern "C" int sf_patchify(const void* x, void* cols, int B, int F, int Cin, int H, int W, void* stream) {

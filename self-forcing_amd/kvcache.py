@@ -92,6 +92,24 @@ def reset_kv_indices(kv: List[dict]) -> None:
             d["local_end_index"] = torch.tensor([0], dtype=torch.long, device=dev)
 
 
+def shift_positions(kv_cache: List[dict], delta_tokens: int) -> None:
+    """Subtract `delta_tokens` from every layer's `global_end_index` (and the host mirror): the cache's rows now stand
+    `delta_tokens` earlier in the timeline.  `local_end_index` -- where they lie in the cache -- does not change.  The
+    caller has re-based the cached keys' RoPE by as many frames (`WanDiffusionWrapper.rebase_positions`)."""
+    global_end, local_end = read_indices(kv_cache)
+    if delta_tokens < 0 or delta_tokens > global_end:
+        raise ValueError(f"shift_positions: cannot move global_end={global_end} back by {delta_tokens} tokens")
+    if delta_tokens == 0:
+        return
+    buf = shared_index_buffer(kv_cache)
+    if buf is not None:
+        buf[:, 0] -= delta_tokens
+    else:
+        for kv in kv_cache:
+            kv["global_end_index"].sub_(delta_tokens)
+    _set_mirror(kv_cache[0], global_end - delta_tokens, local_end)
+
+
 def new_crossattn_cache(shape, n_layers: int, batch_size: int, dtype, device) -> List[dict]:
     """causal_inference.py:300-312.  For an i2v shape every dict also holds the image keys / values "k_img" / "v_img"
     [B, clip_len, H, D], filled with "k" / "v" by the pass that finds is_init False."""

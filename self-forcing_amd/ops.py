@@ -174,6 +174,14 @@ def kv_evict(cache: Tensor, sink: int, evict: int, keep: int, scratch: Tensor) -
                             scratch.numel() * scratch.element_size(), _stream(cache)), "sf_kv_evict")
 
 
+def kv_rope_shift(k_cache: Tensor, rope_cos: Tensor, rope_sin: Tensor, delta_frames: int, row0: int = 0,
+                  rows: Optional[int] = None) -> Tensor:
+    """Re-base the temporal RoPE of cached keys [B, S, H, 128] in place: rows [row0, row0 + rows) (default: to the end) of
+    every sample are rotated back by `delta_frames` (1..1023).  Returns `k_cache`."""
+    torch.ops.sf_hip.kv_rope_shift(k_cache, rope_cos, rope_sin, delta_frames, row0, k_cache.shape[1] - row0 if rows is None else rows)
+    return k_cache
+
+
 def attention(q: Tensor, k: Tensor, v: Tensor, structure: str = "auto", keys: Optional[Tensor] = None,
               log2w: Optional[Tensor] = None) -> Tensor:
     """q [B,Lq,H,128], k/v [B,Lk,H,128] (token/batch strides free, [H,D] contiguous) -> [B,Lq,H,128].

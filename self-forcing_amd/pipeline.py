@@ -23,6 +23,10 @@ output timeline.  `dwpose_data` [3, F, H, W] with `random_ref_dwpose` [H, W, 3] 
 (`pose.PoseEmbedder`; a chunk's `add_condition` is a row range of the tokens), or already-embedded `dwpose_data_emb`
 [B, C_pose, F, h, w] is sliced per chunk; with an image too, the reference-pose map goes into `y`.  The semantics, checks
 and messages are those of `CausalDiffusionInferencePipeline`.  With none of these arguments nothing changes.
+
+Open length: `open_session(...)` returns a `live.LiveSession`, `stream` without a fixed frame count -- the
+same chunk loop (`_denoise_chunks` takes its chunks from a source) over noise drawn chunk by chunk, a rolling KV cache, re-based
+RoPE positions and a bounded pose-token buffer, until the pose feed or the noise feed ends or the caller closes it.
 """
 from __future__ import annotations
 
@@ -135,13 +139,15 @@ class CausalInferencePipeline(torch.nn.Module):
         return self.conditioner
 
     def _conditioning(self, batch_size, num_output_frames, height, width, input_image, dwpose_data, random_ref_dwpose, dwpose_data_emb,
-                      pose_feed=None):
+                      pose_feed=None, live_chunk_frames=None):
         """The clip's conditioning beyond the prompt: (entries of the condition dict that hold for the whole clip,
         chunk_condition(first_frame, n, warm_up=False) -> the entries of the pass(es) over those latent frames), or
         (None, None) when there is none.  All checks come first, before any work; the image is encoded by CLIP and the
         pose clip embedded here, once; `y` is produced by `chunk_condition`, in timeline order, one request per chunk.
         `pose_feed` (an iterable of [3, n, H, W] pieces, `stream` only) replaces the pose clip: its first piece is taken
-        here for the size check, every further piece when `chunk_condition` needs rows that are not final yet."""
+        here for the size check, every further piece when `chunk_condition` needs rows that are not final yet.
+        An open-length session (`open_session`) passes `num_output_frames` None and its chunk length as `live_chunk_frames`:
+        the feed's rows then live in a bounded buffer, and `chunk_condition` returns None once the feed has ended."""
         is_i2v = getattr(getattr(getattr(self, "generator", None), "model", None), "model_type", "t2v") == "i2v"
         if input_image is not None and not is_i2v:
             raise NotImplementedError("input_image: this generator has no i2v branch (img_emb, k_img / v_img, the 36-channel patch "
@@ -199,7 +205,13 @@ class CausalInferencePipeline(torch.nn.Module):
         pose_tokens = self._pose_embedder().embed(dwpose_data)[0] if use_pose else None      # [1, F'*h*w, 5120], once per clip
         next_frame = [0]
         feed_rows = None
-        if feed is not None:
+        live_rows = None
+        if feed is not None and num_output_frames is None:
+            # open length: a bounded buffer that holds only the rows of the chunks in flight (live.PoseRows)
+            from .live import PoseRows
+            live_rows = PoseRows(self._pose_embedder().open_stream(*feed_first.shape[2:]), fs, live_chunk_frames, feed, feed_first)
+            pose_tokens = live_rows.buffer
+        elif feed is not None:
             # the clip's rows in one buffer, filled as the feed delivers; a chunk's add_condition stays a row range of it
             pose_stream = self._pose_embedder().open_stream(*feed_first.shape[2:])
             pose_tokens = torch.empty(1, num_output_frames * fs, POSE_DIM, dtype=torch.bfloat16, device=pose_stream.embedder.device)
@@ -221,6 +233,13 @@ class CausalInferencePipeline(torch.nn.Module):
 
         def chunk_condition(first_frame: int, n: int, warm_up: bool = False) -> dict:
             entries = {}
+            if live_rows is not None and not warm_up:
+                # an open-length session: the chunk's rows first, since a feed that has ended ends the session (None)
+                # before anything of the chunk is encoded
+                condition = live_rows.take(first_frame, n)
+                if condition is None:
+                    return None
+                entries["add_condition"] = condition.expand(batch_size, -1, -1).contiguous() if batch_size > 1 else condition
             if cond is not None:
                 assert first_frame == next_frame[0], f"y is produced in timeline order: frame {next_frame[0]} is next, not {first_frame}"
                 next_frame[0] += n
@@ -229,13 +248,14 @@ class CausalInferencePipeline(torch.nn.Module):
                 return entries
             if dwpose_data_emb is not None:
                 entries["add_condition"] = dwpose_data_emb[:, :, first_frame:first_frame + n].permute(0, 2, 3, 4, 1).flatten(1, 3).contiguous()
-            elif pose_tokens is not None:
+            elif pose_tokens is not None and live_rows is None:
                 if feed_rows is not None:
                     feed_rows(first_frame, first_frame + n)
                 # token-major: the chunk's tokens are a row range, no copy (batch > 1: the one clip, expanded)
                 condition = pose_tokens[:, first_frame * fs:(first_frame + n) * fs]
                 entries["add_condition"] = condition.expand(batch_size, -1, -1).contiguous() if batch_size > 1 else condition
             return entries
+        chunk_condition.live_rows = live_rows
         return clip_entries, chunk_condition
 
     def inference(self, noise: torch.Tensor, text_prompts: List[str], initial_latent: Optional[torch.Tensor] = None,
@@ -315,7 +335,7 @@ class CausalInferencePipeline(torch.nn.Module):
         if self.independent_first_frame and initial_latent is None:
             all_num_frames = [1] + all_num_frames
         for chunk_idx, start_frame, denoised_pred in self._denoise_chunks(
-                noise, conditional_dict, all_num_frames, current_start_frame, num_input_frames, skip_last_context=False,
+                self._noise_chunks(noise, all_num_frames), conditional_dict, set(all_num_frames), current_start_frame, skip_last_context=False,
                 chunk_condition=chunk_condition, on_chunk_start=(lambda: block_events.append([ev(), ev()]) or block_events[-1][0].record()) if profile else None,
                 on_chunk_end=(lambda: block_events[-1][1].record()) if profile else None):
             output[:, start_frame:start_frame + denoised_pred.shape[1]] = denoised_pred
@@ -350,16 +370,37 @@ class CausalInferencePipeline(torch.nn.Module):
         return video
 
     # ------------------------------------------------------------------------------------------
-    def _denoise_chunks(self, noise, conditional_dict, all_num_frames, current_start_frame, num_input_frames,
-                        skip_last_context, on_chunk_start=None, on_chunk_end=None, chunk_condition=None):
+    @staticmethod
+    def _noise_chunks(noise, all_num_frames):
+        """A whole clip's noise [B, F, C, H, W] as `_denoise_chunks` takes it: one slice per chunk."""
+        at = 0
+        for n in all_num_frames:
+            yield noise[:, at:at + n]
+            at += n
+
+    def _denoise_chunks(self, chunks, conditional_dict, lengths, current_start_frame, skip_last_context,
+                        on_chunk_start=None, on_chunk_end=None, chunk_condition=None, rebase=None):
         """The chunk loop of causal_inference.py:176-244 as a generator: yields
         (chunk_index, start_frame, x0 [B, f, C, H, W]) as soon as a chunk's last denoising step is
         enqueued; the context pass that rewrites the chunk's K/V "clean" follows (and is skipped for
         the final chunk when `skip_last_context`, as demo.py:396 does: nothing reads that update).
+        `chunks`: the source of the noise, one [B, f, C, H, W] tensor per chunk -- slices of a clip's noise
+        (`_noise_chunks`) or a live session's feed; the loop runs until it ends and looks one chunk ahead (a chunk is the last
+        one when nothing follows it).  `lengths`: the chunk lengths the caller expects, whose timestep tables are built
+        before the first chunk (any other length gets its own on first use).
         `chunk_condition` (`_conditioning`): asked once per chunk, right before the chunk's first pass, for the chunk's
-        `y` / `add_condition`, which then stay in `conditional_dict` for all of the chunk's passes."""
+        `y` / `add_condition`, which then stay in `conditional_dict` for all of the chunk's passes.  An open-length session's
+        returns None when its pose source has ended: the loop ends there.
+        `rebase` (`live.LiveSession`): asked before every generator call with the highest frame position the call needs
+        (for a pair the second pass's start_frame + f); it may move the cache back in the timeline and returns by how
+        many frames, which the loop subtracts from the positions it passes on.  `start_frame` as yielded and as
+        `chunk_condition` sees it stays the frame of the output timeline."""
         gen = self.generator
-        batch_size = noise.shape[0]
+        chunks = iter(chunks)
+        noisy_input = next(chunks, None)
+        if noisy_input is None:
+            return
+        batch_size, device = noisy_input.shape[0], noisy_input.device
         # Every timestep tensor of the rollout is built HERE, once: the reference builds `ones([B, f], int64) * t` for each
         # forward and `t_next * ones([B * f], long)` for each re-noise (causal_inference.py:190-216, :228) -- three small
         # launches per step of kernels this library does not own.  One host->device copy of the step list, one broadcast
@@ -367,14 +408,19 @@ class CausalInferencePipeline(torch.nn.Module):
         # global-RNG re-noise, :208, which must stay) and the caller's copy of the chunk into `output`.  (A chunk's `y` adds
         # VAE encode calls and sf_i2v_assemble_y, all this library's; one clip's pose tokens are a view.  Only pose tokens for a
         # batch, or already-embedded ones, are copied by torch once per chunk, as in the multi-step pipeline.)
-        steps = self.denoising_step_list.to(noise.device)
+        steps = self.denoising_step_list.to(device)
         ctx_noise = getattr(self.args, "context_noise", 0)
         tables = {}
-        for f in set(all_num_frames):
-            ones = torch.ones([batch_size, f], device=noise.device, dtype=torch.int64)
-            per_step = (ones.unsqueeze(0) * steps.reshape(-1, 1, 1)).contiguous()      # [S, B, f], dtype as `ones * t`
-            tables[f] = (list(per_step.unbind(0)), [t.flatten() for t in per_step.unbind(0)],
-                         torch.ones_like(per_step[0]) * ctx_noise)
+
+        def table(f):
+            if f not in tables:
+                ones = torch.ones([batch_size, f], device=device, dtype=torch.int64)
+                per_step = (ones.unsqueeze(0) * steps.reshape(-1, 1, 1)).contiguous()      # [S, B, f], dtype as `ones * t`
+                tables[f] = (list(per_step.unbind(0)), [t.flatten() for t in per_step.unbind(0)],
+                             torch.ones_like(per_step[0]) * ctx_noise)
+            return tables[f]
+        for f in lengths:
+            table(f)
         n_steps = steps.shape[0]
         # A chunk's context pass and the next chunk's first denoising pass run back to back in the reference (:226-235, then
         # :190-205) and layer l of the second needs only layer l's K / V of the first: a generator that offers `forward_pair`
@@ -385,24 +431,33 @@ class CausalInferencePipeline(torch.nn.Module):
         pair_ok = bool(self.pair_context_with_next and self._cache_only_kw and hasattr(gen, "forward_pair")
                        and gen.can_pair(conditional_dict)
                        and (chunk_condition is not None or conditional_dict.get("add_condition") is None)
-                       and batch_size * max(all_num_frames) * self.frame_seq_length <= self.pair_max_rows)
+                       and batch_size * max(lengths) * self.frame_seq_length <= self.pair_max_rows)
+        position = current_start_frame      # the chunk's first frame as RoPE and the cache indices see it: behind the timeline by the re-bases
+
+        def place(need):
+            nonlocal position
+            if rebase is not None:
+                position -= rebase(need)
+            return position * self.frame_seq_length
         first_pred = None          # x0 of this chunk's first step when the previous chunk's pair has already computed it
         next_entries = None        # ... and the chunk's condition entries, which that pair has already asked for
-        for chunk_idx, current_num_frames in enumerate(all_num_frames):
+        chunk_idx = 0
+        while noisy_input is not None:
+            current_num_frames = noisy_input.shape[1]
             if on_chunk_start is not None:
                 on_chunk_start()
             if chunk_condition is not None:
                 entries = next_entries if next_entries is not None else chunk_condition(current_start_frame, current_num_frames)
                 next_entries = None
+                if entries is None:
+                    return
                 conditional_dict.update(entries)
-            noisy_input = noise[:, current_start_frame - num_input_frames:
-                                current_start_frame + current_num_frames - num_input_frames]
-            start_tok = current_start_frame * self.frame_seq_length
-            step_ts, step_ts_flat, context_timestep = tables[current_num_frames]
+            step_ts, step_ts_flat, context_timestep = table(current_num_frames)
             for index in range(n_steps):
                 if index == 0 and first_pred is not None:
                     denoised_pred, first_pred = first_pred, None
                 else:
+                    start_tok = place(position + current_num_frames)
                     _, denoised_pred = gen(noisy_image_or_video=noisy_input, conditional_dict=conditional_dict,
                                            timestep=step_ts[index], kv_cache=self.kv_cache1,
                                            crossattn_cache=self.crossattn_cache, current_start=start_tok)
@@ -412,26 +467,34 @@ class CausalInferencePipeline(torch.nn.Module):
                                                            ).unflatten(0, denoised_pred.shape[:2])
             yield chunk_idx, current_start_frame, denoised_pred
             # rerun at the context timestep so the cache holds clean K/V (causal_inference.py:226-235)
-            is_last = chunk_idx == len(all_num_frames) - 1
-            if not (skip_last_context and is_last):
-                if pair_ok and not is_last and all_num_frames[chunk_idx + 1] == current_num_frames:
-                    nxt = current_start_frame + current_num_frames
+            next_noise = next(chunks, None)
+            if not (skip_last_context and next_noise is None):
+                paired = False
+                if pair_ok and next_noise is not None and next_noise.shape[1] == current_num_frames:
                     pair_kw = {}
                     if chunk_condition is not None:      # pose tokens: the context pass takes this chunk's, the paired pass the next chunk's
-                        next_entries = chunk_condition(nxt, current_num_frames)
-                        if "add_condition" in next_entries:
+                        next_entries = chunk_condition(current_start_frame + current_num_frames, current_num_frames)
+                        if next_entries is None:
+                            next_noise = None            # the pose source has ended: this chunk is the last one
+                        elif "add_condition" in next_entries:
                             pair_kw["add_conditions"] = (conditional_dict["add_condition"], next_entries["add_condition"])
-                    first_pred = gen.forward_pair(denoised_pred, context_timestep,
-                                                  noise[:, nxt - num_input_frames:nxt + current_num_frames - num_input_frames], step_ts[0],
-                                                  conditional_dict, self.kv_cache1, self.crossattn_cache, start_tok,
-                                                  nxt * self.frame_seq_length, **pair_kw)[1]
-                else:
+                    if next_noise is not None:
+                        start_tok = place(position + 2 * current_num_frames)
+                        first_pred = gen.forward_pair(denoised_pred, context_timestep, next_noise, step_ts[0],
+                                                      conditional_dict, self.kv_cache1, self.crossattn_cache, start_tok,
+                                                      start_tok + current_num_frames * self.frame_seq_length, **pair_kw)[1]
+                        paired = True
+                if not paired:
+                    start_tok = place(position + current_num_frames)
                     gen(noisy_image_or_video=denoised_pred, conditional_dict=conditional_dict, timestep=context_timestep,
                         kv_cache=self.kv_cache1, crossattn_cache=self.crossattn_cache, current_start=start_tok,
                         **self._cache_only_kw)
             if on_chunk_end is not None:
                 on_chunk_end()
             current_start_frame += current_num_frames
+            position += current_num_frames
+            noisy_input = next_noise
+            chunk_idx += 1
 
     def stream(self, noise: torch.Tensor, text_prompts: List[str], skip_last_context: bool = True,
                overlap_decode: bool = False, frame_encoder=None, input_image=None, dwpose_data: Optional[torch.Tensor] = None,
@@ -482,6 +545,13 @@ class CausalInferencePipeline(torch.nn.Module):
             for block_index in range(self.num_transformer_blocks):
                 self.crossattn_cache[block_index]["is_init"] = False
             self._reset_kv_indices()
+        chunks = self._denoise_chunks(self._noise_chunks(noise, all_num_frames), conditional_dict, set(all_num_frames), 0, skip_last_context,
+                                      chunk_condition=chunk_condition)
+        yield from self._decoded_chunks(chunks, noise.device, overlap_decode, frame_encoder)
+
+    def _decoded_chunks(self, chunks, device, overlap_decode, frame_encoder):
+        """What `stream` and a live session yield per chunk of `_denoise_chunks`: `(chunk_index, latents, pixels[, frames])`,
+        decoded at once or, with `overlap_decode`, on a second HIP stream while the next chunk is denoised."""
         decode_chunk = getattr(self.vae, "decode_chunk", None)
 
         def decode(x0, chunk_idx):
@@ -497,14 +567,13 @@ class CausalInferencePipeline(torch.nn.Module):
                 return chunk_idx, x0, decoded[0]
             return chunk_idx, x0, decoded[0], frame_encoder._to_host(*decoded[1])
 
-        chunks = self._denoise_chunks(noise, conditional_dict, all_num_frames, 0, 0, skip_last_context, chunk_condition=chunk_condition)
         if not overlap_decode:
             for chunk_idx, start_frame, x0 in chunks:
                 yield finish(chunk_idx, x0, decode(x0, chunk_idx))
             return
         if getattr(self, "_decode_stream", None) is None:
-            self._decode_stream = torch.cuda.Stream(device=noise.device)
-        side, main = self._decode_stream, torch.cuda.current_stream(noise.device)
+            self._decode_stream = torch.cuda.Stream(device=device)
+        side, main = self._decode_stream, torch.cuda.current_stream(device)
         pending = None            # (chunk_idx, x0, pixels, done event) of the chunk being decoded on the side stream
         for chunk_idx, start_frame, x0 in chunks:
             ready = torch.cuda.Event()
@@ -523,6 +592,16 @@ class CausalInferencePipeline(torch.nn.Module):
             pending[3].synchronize()
             main.wait_event(pending[3])
             yield finish(*pending[:3])
+
+    def open_session(self, text_prompts: List[str], latent_size, batch_size: int = 1, noise_feed=None, generator=None, input_image=None,
+                     random_ref_dwpose: Optional[torch.Tensor] = None, pose_feed=None, frame_encoder=None, overlap_decode: bool = False,
+                     rope_limit: Optional[int] = None):
+        """An open-length `stream`: a `live.LiveSession`, an iterator that yields what `stream` yields per chunk and goes on
+        until `pose_feed` or `noise_feed` ends or the caller closes it.  See live.py."""
+        from .live import LiveSession
+        return LiveSession(self, text_prompts, latent_size, batch_size=batch_size, noise_feed=noise_feed, generator=generator,
+                           input_image=input_image, random_ref_dwpose=random_ref_dwpose, pose_feed=pose_feed, frame_encoder=frame_encoder,
+                           overlap_decode=overlap_decode, rope_limit=rope_limit)
 
     # ------------------------------------------------------------------------------------------
     def _cache_tokens(self, total_frames: Optional[int] = None) -> int:

@@ -188,6 +188,28 @@ def _(ck_cache, cv_cache, keys, log2w):
     return None
 
 
+@custom_op(f"{NAMESPACE}::kv_rope_shift", mutates_args=("k_cache",))
+def kv_rope_shift(k_cache: Tensor, rope_cos: Tensor, rope_sin: Tensor, delta_frames: int, row0: int, rows: int) -> None:
+    """Rotate the temporal RoPE pairs of rows [row0, row0 + rows) of every sample of the cached keys (contiguous bf16
+    [B, S, H, 128]) back by `delta_frames`, in place (sf_kv_rope_shift; rope_shift_reference.shift_keys, bit for bit).
+    rope_cos / rope_sin: the model's float32 [1024, 64] tables."""
+    _need_gpu(k_cache, "k_cache")
+    if k_cache.dim() != 4 or k_cache.shape[3] != 128 or not k_cache.is_contiguous():
+        raise ValueError(f"kv_rope_shift: k_cache must be contiguous [B, S, H, 128], got {tuple(k_cache.shape)} {k_cache.stride()}")
+    for n, t in (("rope_cos", rope_cos), ("rope_sin", rope_sin)):
+        _need_gpu(t, n, torch.float32)
+        if tuple(t.shape) != (1024, 64) or not t.is_contiguous() or t.device != k_cache.device:
+            raise ValueError(f"kv_rope_shift: {n} must be a contiguous float32 [1024, 64] table on {k_cache.device}, got {tuple(t.shape)}")
+    B, S, H, _ = k_cache.shape
+    _lib.check(_lib.lib().sf_kv_rope_shift(k_cache.data_ptr(), B, S, H, row0, rows, rope_cos.data_ptr(), rope_sin.data_ptr(), delta_frames,
+                                           _stream(k_cache)), "sf_kv_rope_shift")
+
+
+@kv_rope_shift.register_fake
+def _(k_cache, rope_cos, rope_sin, delta_frames, row0, rows):
+    return None   # writes only its mutated argument
+
+
 def _fold_pair(keys: Optional[Tensor], log2w: Optional[Tensor], shape: tuple, device, who: str) -> None:
     """The kernels index these two by sample (and layer) without a bound of their own: check them here."""
     if (keys is None) != (log2w is None):

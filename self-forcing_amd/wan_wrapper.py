@@ -40,7 +40,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from .kvcache import add_image_cache, plan_cache_update, read_indices, shared_index_buffer, write_indices
+from .kvcache import add_image_cache, plan_cache_update, read_indices, shared_index_buffer, shift_positions, write_indices
 from .model import CausalWanModel
 from .scheduler import FlowMatchScheduler
 from .weights import (LORA_DEFAULT_TARGETS, NAMED_SHAPES, WanShape, apply_lora_file, load_lora_file, merge_lora, strip_prefix,
@@ -180,6 +180,18 @@ class WanDiffusionWrapper(torch.nn.Module):
         if self._evict_scratch is None or self._evict_scratch.numel() < batch * keep * dim * 2:
             self._evict_scratch = torch.empty(batch * cap * dim * 2, dtype=torch.uint8, device=self.model.device)
         return self._evict_scratch
+
+    @torch.no_grad()
+    def rebase_positions(self, kv_cache: List[dict], delta_frames: int, frame_seqlen: int) -> None:
+        """Move the cache `delta_frames` back in the timeline, between two calls: every layer's cached keys (rows
+        [0, local_end), sink rows included: their distance to the rest is kept, their new position is negative and never
+        looked up) are rotated back by `delta_frames` (sf_kv_rope_shift), then `global_end_index` drops by
+        delta_frames * frame_seqlen.  The caller passes `current_start` values `delta_frames` frames lower from here on."""
+        mdl = self.model
+        _, local_end = read_indices(kv_cache)
+        for kv in kv_cache:
+            torch.ops.sf_hip.kv_rope_shift(kv["k"], mdl.rope_cos, mdl.rope_sin, delta_frames, 0, local_end)
+        shift_positions(kv_cache, delta_frames * frame_seqlen)
 
     # --- cross-attention: a prompt's padding keys folded into one ---------------------------------
     # The rows of `prompt_embeds` behind the prompt's tokens are zero (utils/wan_wrapper.py:50-51) and everything from
