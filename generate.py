@@ -133,10 +133,12 @@ def load_pose(path: str):
 
 
 def pose_file_kind(path: str) -> str:
-    """"mjpeg" (.avi), "keypoints" (.npz, or a .npy that holds a plain array) or "dict" (.pt, or a .npy that holds a pickled dict)."""
+    """"mjpeg" (.avi), "y4m" (.y4m; a FIFO or /dev/stdin is one with --pose_format y4m), "keypoints" (.npz, or a .npy that holds a plain array) or "dict" (.pt, or a .npy that holds a pickled dict)."""
     low = path.lower()
     if low.endswith(".avi"):
         return "mjpeg"
+    if low.endswith(".y4m"):
+        return "y4m"
     if low.endswith(".npz"):
         return "keypoints"
     if low.endswith(".npy"):
@@ -213,6 +215,30 @@ def load_pose_mjpeg(clip_path: str, ref_path: str, device, size=None, fit: str =
         raise SystemExit(f"{clip_path} / {ref_path}: {e}")
 
 
+def open_pose_y4m(path: str):
+    """A `y4m.Y4mReader` over --pose_path (a file, a FIFO or /dev/stdin), its header read."""
+    try:
+        return sfa.y4m.Y4mReader(path)
+    except ValueError as e:
+        raise SystemExit(f"{path}: {e}")
+
+
+def pose_y4m_feed(reader, decoder, a, size, fit, frames_per_piece=16):
+    """The reader's frames as pose pieces uint8 [3, n, H, W] on the device, each read and decoded when it is asked for."""
+    return sfa.yuv.frame_feed(reader, decoder, reader.fmt, (reader.height, reader.width), frames_per_piece, "pose", size, a.pose_yuv_matrix or "bt601",
+                              reader.range, a.pose_yuv_chroma or "triangle", fit=fit)
+
+
+def load_pose_ref(ref_path: str, device, size=None, fit: str = "stretch"):
+    """random_ref_dwpose uint8 [H, W, 3] on `device` from a JPEG file, resized to `size` if one is given."""
+    with open(ref_path, "rb") as fh:
+        ref = fh.read()
+    try:
+        return sfa.JpegDecoder(device=device).decode([ref], layout="hwc", size=size, fit=fit)[0]
+    except ValueError as e:
+        raise SystemExit(f"{ref_path}: {e}")
+
+
 def check_pose_flags(ap, a):
     """The parser's checks of the pose flags, each ending in `ap.error`: (the kind of --pose_path as `pose_file_kind` names it, None without
     one; --pose_source_size as (hs, ws); --pose_smooth / --pose_hold as the smoother's tuple; the --pose_track flags as the tracker's dict), each
@@ -228,12 +254,16 @@ def check_pose_flags(ap, a):
         if not os.path.exists(a.pose_path):
             ap.error(f"--pose_path {a.pose_path}: no such file (a .pt / .npy dict with dwpose_data and random_ref_dwpose; few-step and "
                      "multi-step configs both take it)")
-        pose_kind = pose_file_kind(a.pose_path)
+        pose_kind = "y4m" if a.pose_format == "y4m" else pose_file_kind(a.pose_path)
         if a.ref_pose_path and pose_kind == "dict":
             ap.error("--ref_pose_path goes with an MJPEG --pose_path (.avi) or a keypoint one (.npz / .npy array); a .pt / .npy dict holds its own "
                      "random_ref_dwpose")
         if pose_kind == "mjpeg" and not a.ref_pose_path:
             ap.error("--pose_path clip.avi needs --ref_pose_path: the JPEG file that is random_ref_dwpose")
+        if pose_kind == "y4m" and not a.ref_pose_path:
+            ap.error("--pose_path clip.y4m needs --ref_pose_path: the JPEG file that is random_ref_dwpose")
+        if pose_kind != "y4m" and (a.pose_yuv_matrix or a.pose_yuv_chroma):
+            ap.error("--pose_yuv_matrix and --pose_yuv_chroma go with a YUV4MPEG2 --pose_path (.y4m, or --pose_format y4m)")
         if pose_kind == "keypoints" and not a.ref_pose_path:
             ap.error("--pose_path with keypoints needs --ref_pose_path: a .npz / .npy with one frame of keypoints, drawn as random_ref_dwpose")
         if pose_kind != "dict" and not os.path.exists(a.ref_pose_path):
@@ -282,6 +312,8 @@ def check_pose_flags(ap, a):
             if sfa.KeypointChain.bridges_two_people(a.pose_hold or 0, tracked.max_age):
                 ap.error(f"--pose_hold {a.pose_hold} exceeds --pose_track_age {tracked.max_age}: a tracker's slot is empty for max_age + 1 frames "
                          f"between two different people, so a longer hold could smooth one person towards another")
+    elif a.pose_format != "auto" or a.pose_yuv_matrix or a.pose_yuv_chroma:
+        ap.error("--pose_format, --pose_yuv_matrix and --pose_yuv_chroma need --pose_path")
     elif a.ref_pose_path:
         ap.error("--ref_pose_path needs --pose_path clip.avi or keypoints (.npz / .npy array)")
     elif a.pose_pixel_coords:
@@ -357,14 +389,23 @@ def main():
                     help="--pose_path clip.avi: resize the clip and --ref_pose_path on the GPU to the output size (8 x the latent size): stretch, or "
                          "cover = the largest centred crop with the output's aspect ratio; none: their size must be the output size.  Does not apply "
                          "to keypoints (.npz / .npy array), which are drawn at the output size")
+    ap.add_argument("--pose_format", choices=("auto", "y4m"), default="auto",
+                    help="auto: the kind of --pose_path is read from its name; y4m: it is a YUV4MPEG2 stream whatever it is called -- a FIFO or "
+                         "/dev/stdin, e.g. ffmpeg -i dance.mp4 -f yuv4mpegpipe - | generate.py --pose_path /dev/stdin --pose_format y4m ...")
+    ap.add_argument("--pose_yuv_matrix", choices=("bt601", "bt709"), default=None, help="--pose_path clip.y4m: the clip's colour matrix (default bt601)")
+    ap.add_argument("--pose_yuv_chroma", choices=("triangle", "nearest"), default=None,
+                    help="--pose_path clip.y4m: how subsampled chroma is up-sampled (default triangle, libjpeg's filter)")
     ap.add_argument("--pose_weights_path", default=None, help="pose embedding weights (dwpose_embedding.* / randomref_embedding_pose.*)")
     ap.add_argument("--pose_random_init_seed", type=int, default=None, help="seeded random pose embedding weights instead")
     ap.add_argument("--open_length", action="store_true",
                     help="few-step configs with a rolling KV cache (local_attn_size in model_kwargs): let the pose clip of --pose_path decide the "
                          "length, not --num_output_frames -- the clip is fed piece by piece to CausalInferencePipeline.open_session, which goes on "
                          "until it ends")
-    ap.add_argument("--video_format", choices=("pt", "mjpeg"), default="pt",
-                    help="pt: <idx>-<sample>.video.pt (uint8 tensor); mjpeg: <idx>-<sample>.avi, JPEG frames encoded on the GPU, 16 frames/s")
+    ap.add_argument("--video_format", choices=("pt", "mjpeg", "y4m"), default="pt",
+                    help="pt: <idx>-<sample>.video.pt (uint8 tensor); mjpeg: <idx>-<sample>.avi, JPEG frames encoded on the GPU, 16 frames/s; "
+                         "y4m: <idx>-<sample>.y4m, raw i420 frames converted on the GPU, 16 frames/s (with --open_length written chunk by chunk)")
+    ap.add_argument("--yuv_matrix", choices=("bt601", "bt709"), default="bt601", help="--video_format y4m: the colour matrix")
+    ap.add_argument("--yuv_range", choices=("limited", "full"), default="limited", help="--video_format y4m: the sample range")
     ap.add_argument("--jpeg_quality", type=int, default=90, help="--video_format mjpeg: 1..100")
     ap.add_argument("--jpeg_subsampling", choices=("420", "444"), default="420", help="--video_format mjpeg: chroma subsampling")
     a = ap.parse_args()
@@ -375,7 +416,7 @@ def main():
         ap.error("--open_length needs --pose_path: the pose clip decides the length of the video")
     if a.open_length and a.i2v:
         ap.error("--open_length starts from noise: not together with --i2v (an initial latent)")
-    if a.pose_resize != "none" and not (a.pose_path and a.pose_path.lower().endswith(".avi")):
+    if a.pose_resize != "none" and not (a.pose_path and (a.pose_path.lower().endswith(".avi") or pose_kind == "y4m")):
         ap.error("--pose_resize goes with an MJPEG --pose_path (.avi); a .pt / .npy dict is taken at the size it has, keypoints are drawn at the "
                  "output size")
     if a.input_image:
@@ -452,6 +493,7 @@ def main():
         raise SystemExit(f"--i2v needs the TAEHV encoder, but {a.taehv_path} holds no encoder.* tensors (taew2_1.pth does)")
     decode = not isinstance(vae, sfa.IdentityVAE)
     jpeg = sfa.JpegEncoder(a.jpeg_quality, a.jpeg_subsampling, device=device) if decode and a.video_format == "mjpeg" else None
+    yuv = sfa.YuvEncoder("i420", a.yuv_matrix, a.yuv_range, value_range=(0, 1), device=device) if decode and a.video_format == "y4m" else None
     few_step = is_few_step(cfg)        # inference.py:62-67: few-step rollout iff the config has denoising_step_list
     pose_embedder = None
     if a.pose_path:
@@ -460,6 +502,20 @@ def main():
         if pose_kind == "mjpeg":
             pose_size = None if a.pose_resize == "none" else (8 * a.latent_height, 8 * a.latent_width)
             pose_data = load_pose_mjpeg(a.pose_path, a.ref_pose_path, device, pose_size, "stretch" if pose_size is None else a.pose_resize)
+        elif pose_kind == "y4m":
+            pose_size = None if a.pose_resize == "none" else (8 * a.latent_height, 8 * a.latent_width)
+            pose_fit = "stretch" if pose_size is None else a.pose_resize
+            yuv_decoder = sfa.YuvDecoder(device)
+            ref_pose_y4m = load_pose_ref(a.ref_pose_path, device, pose_size, pose_fit)
+            pose_data = None
+            if not a.open_length:        # the whole clip, read and decoded piece by piece
+                try:
+                    pieces = list(pose_y4m_feed(open_pose_y4m(a.pose_path), yuv_decoder, a, pose_size, pose_fit))
+                except ValueError as e:
+                    raise SystemExit(f"{a.pose_path}: {e}")
+                if not pieces:
+                    raise SystemExit(f"{a.pose_path}: no frames in the stream")
+                pose_data = (torch.cat(pieces, dim=1), ref_pose_y4m)
         elif pose_kind == "keypoints":
             pose_data = load_pose_keypoints(a.pose_path, a.ref_pose_path, device, (8 * a.latent_height, 8 * a.latent_width), not a.pose_pixel_coords,
                                             a.pose_align, a.pose_fps, pose_source_size, pose_smooth, a.pose_hold or 0, pose_track)
@@ -491,6 +547,7 @@ def main():
         os.makedirs(a.output_folder, exist_ok=True)
     grp.barrier()
 
+    live_y4m_used = False
     for idx in shard_indices(len(prompts), rank, world):
         initial = None
         if a.i2v:   # inference.py:136-149: the encoded image is the first latent frame of every sample
@@ -501,12 +558,34 @@ def main():
             torch.save(initial[0].cpu(), os.path.join(a.output_folder, f"{idx}.initial_latent.pt"))
         n_noise = a.num_output_frames - (1 if a.i2v else 0)
         noise = torch.randn([a.num_samples, n_noise, 16, a.latent_height, a.latent_width], device=device, dtype=torch.bfloat16)
-        dwpose, ref_pose = pose_data if a.pose_path else (None, None)
+        dwpose, ref_pose = pose_data if a.pose_path and pose_data is not None else (None, None)
         if a.open_length:      # the clip as a feed of 16-frame pieces; the session ends with it
+            if pose_kind == "y4m":         # the reader is the live source: frames are read as the session asks for them
+                if live_y4m_used and not os.path.isfile(a.pose_path):
+                    raise SystemExit(f"{a.pose_path} is a live source and has been consumed by the first prompt; --open_length takes one prompt per rank from it")
+                live_y4m_used = True
+                pose_feed, ref_pose = pose_y4m_feed(open_pose_y4m(a.pose_path), yuv_decoder, a, pose_size, pose_fit), ref_pose_y4m
+            else:
+                pose_feed = iter(dwpose.split(16, dim=1))
             session = pipe.open_session([prompts[idx]] * a.num_samples, (a.latent_height, a.latent_width), batch_size=a.num_samples,
-                                        pose_feed=iter(dwpose.split(16, dim=1)), random_ref_dwpose=ref_pose, input_image=input_image)
-            chunks = [(lat, pixels) for _, lat, pixels in session]
-            latents, video = torch.cat([c[0] for c in chunks], dim=1), torch.cat([c[1] for c in chunks], dim=1)
+                                        pose_feed=pose_feed, random_ref_dwpose=ref_pose, input_image=input_image, frame_encoder=yuv)
+            if yuv is None:
+                chunks = [(lat, pixels) for _, lat, pixels in session]
+                latents, video = torch.cat([c[0] for c in chunks], dim=1), torch.cat([c[1] for c in chunks], dim=1)
+            else:                          # every chunk's frames go to the files as they arrive: the pixels are not kept
+                writers, kept, video = None, [], None
+                for _, lat, pixels, frames in session:
+                    if writers is None:
+                        writers = [sfa.y4m.Y4mWriter(os.path.join(a.output_folder, f"{idx}-{s}.y4m"), pixels.shape[-1], pixels.shape[-2], 16, "i420", a.yuv_range)
+                                   for s in range(a.num_samples)]
+                    t = pixels.shape[1]
+                    for s, wr in enumerate(writers):
+                        wr.write(frames[s * t:(s + 1) * t])
+                    kept.append(lat)
+                    video = pixels
+                for wr in writers or []:
+                    wr.close()
+                latents = torch.cat(kept, dim=1)
         elif few_step:
             video, latents = pipe.inference(noise=noise, text_prompts=[prompts[idx]] * a.num_samples, initial_latent=initial,
                                             return_latents=True, input_image=input_image, dwpose_data=dwpose, random_ref_dwpose=ref_pose)
@@ -515,7 +594,11 @@ def main():
                                             return_latents=True)
         for s in range(a.num_samples):
             torch.save(latents[s].cpu(), os.path.join(a.output_folder, f"{idx}-{s}.pt"))
-            if jpeg is not None:
+            if yuv is not None:
+                if not a.open_length:
+                    with sfa.y4m.Y4mWriter(os.path.join(a.output_folder, f"{idx}-{s}.y4m"), video.shape[-1], video.shape[-2], 16, "i420", a.yuv_range) as wr:
+                        wr.write(yuv.encode(video[s].float()))
+            elif jpeg is not None:
                 frames = jpeg.encode(video[s].float() * 2 - 1)
                 sfa.mjpeg.write_avi(os.path.join(a.output_folder, f"{idx}-{s}.avi"), frames, 16, video.shape[-1], video.shape[-2])
             elif decode:   # [T, 3, H, W] in [0, 1] -> [T, H, W, 3] uint8 (inference.py:186-187)

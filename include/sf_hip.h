@@ -881,6 +881,48 @@ int sf_resize_frames(const void* frames, int layout, int n, int h, int w, const 
                      int out_layout, int out_dtype, int out_h, int out_w, void* stream);
 
 /* ==========================================================================================
+ * Raw YUV frames <-> RGB frames: the pixel formats of video outside JPEG (a V4L2 webcam's YUYV, a hardware codec's NV12,
+ * the I420 / I422 / I444 planes and YUV4MPEG2 streams of software tools).  The reference takes its frames through PIL / cv2
+ * on the host (inference.py:84-88 and the pose loaders) and uploads RGB; here 1.5 or 2 bytes per pixel cross the bus and
+ * the conversion runs on the device.  8 bit, tightly packed, ch = ceil(h / 2), cw = ceil(w / 2):
+ *   I420  Y [h][w], U [ch][cw], V [ch][cw]        NV12  Y [h][w], UV [ch][cw][2]
+ *   I422  Y [h][w], U [h][cw], V [h][cw]          I444  Y, U, V [h][w] each
+ *   GRAY  Y [h][w] (U = V = 128)                  YUYV  [h][w / 2][4] = Y0 U Y1 V      UYVY  = U Y0 V Y1   (w even)
+ * The encoder writes the first four.  A frame's size may be odd, so frame k of a batch may start at any byte.
+ *
+ * constants: HOST int32 [16] = (yoff, CY, CRV, CGU, CGV, CBU, YR, YG, YB, UR, UG, UB, VR, VG, VB, 0), computed by the
+ * caller with self_forcing_amd/yuv_reference.py `constants(matrix, range)` (BT.601 / BT.709, full / limited range, 16-bit
+ * fixed point): the library holds no colour matrix of its own.  All arithmetic int32, shifts arithmetic, clamp to 0..255:
+ *   y = (Y - yoff) CY     cb = U - 128     cr = V - 128
+ *   R = clamp((y + CRV cr + 32768) >> 16)     G = clamp((y - CGU cb - CGV cr + 32768) >> 16)     B = clamp((y + CBU cb + 32768) >> 16)
+ *   Y = clamp(( YR R + YG G + YB B + (yoff << 16) + 32768) >> 16)
+ *   U = clamp((-UR R - UG G + UB B + (128 << 16) + 32767) >> 16)     V = clamp((VR R - VG G - VB B + (128 << 16) + 32767) >> 16)
+ * Subsampled chroma is up-sampled by replication (NEAREST) or by libjpeg's triangle filter for centre-sited chroma
+ * (TRIANGLE: the JPEG decoder's, edges replicated); the encoder converts every pixel and averages 2 x 2 as
+ * (a + b + c + d + 2) >> 2 and 2 x 1 as (a + b + 1) >> 1, an odd size's missing column or row being the edge's again.
+ * For BT.601 full range the decode is the JPEG decoder's colour step bit for bit.  One launch per call for all frames;
+ * the library keeps no state and needs no workspace.
+ * ========================================================================================== */
+
+#define SF_YUV_MAX_SIZE 16384
+enum sf_yuv_format {
+  SF_YUV_I420 = 0, SF_YUV_NV12 = 1, SF_YUV_I422 = 2, SF_YUV_I444 = 3,   /* decode and encode */
+  SF_YUV_GRAY = 4, SF_YUV_YUYV = 5, SF_YUV_UYVY = 6                     /* decode only       */
+};
+enum sf_yuv_chroma { SF_YUV_NEAREST = 0, SF_YUV_TRIANGLE = 1 };
+
+/* Bytes of one h x w frame; 0 = malformed arguments (sf_last_error says which). */
+size_t sf_yuv_frame_bytes(int format, int h, int w);
+/* raw: n frames back to back (any alignment) -> out in `layout` / `dtype` (enum sf_jpeg_layout / sf_jpeg_dtype: u8 = the
+ * samples, f32 / bf16 = u8 / 127.5 - 1 as the JPEG decoder converts), 16-byte aligned. */
+int sf_yuv_decode_frames(const void* raw, int format, int n, int h, int w, const int32_t* constants, int chroma,
+                         void* out, int layout, int dtype, void* stream);
+/* frames: u8 [n][h][w][3], or f32 / bf16 [n][3][h][w] in `value_range` (enum sf_jpeg_range, truncated to 8 bit as the JPEG
+ * encoder does) -> out: n frames of `format` back to back. */
+int sf_yuv_encode_frames(const void* frames, int dtype, int value_range, int n, int h, int w, const int32_t* constants,
+                         void* out, int format, void* stream);
+
+/* ==========================================================================================
  * Pose renderer (DWPose whole-body keypoints -> skeleton frames).  The reference has no renderer: its dwpose_data
  * arrives already drawn, in the DWPose style of UniAnimate-DiT.  The drawing is this project's definition in that style,
  * self_forcing_amd/pose_render_reference.py (`quantize`, `primitives`, `inside`), in exact integer arithmetic; the kernel

@@ -29,6 +29,8 @@ from .jpeg import JpegDecoder, JpegEncoder  # noqa: F401
 from . import jpeg_reference, mjpeg  # noqa: F401
 from .resize import FrameResizer  # noqa: F401
 from . import resize, resize_reference  # noqa: F401
+from .yuv import YuvDecoder, YuvEncoder  # noqa: F401
+from . import yuv, yuv_reference, y4m  # noqa: F401
 from .pose_keypoints import KeypointChain  # noqa: F401
 from .pose_render import PoseRenderer  # noqa: F401
 from . import pose_keypoints, pose_render, pose_render_reference  # noqa: F401
@@ -59,7 +61,7 @@ __all__ = ["WanShape", "WAN_1_3B", "WAN_14B", "WAN_REDUCED", "NAMED_SHAPES", "sy
            "VaeShape", "WAN_VAE", "VAE_REDUCED", "synth_vae_state_dict", "vae_param_shapes", "WanVAEWrapper",
            "TAEHVWrapper", "TAEHVDecoder", "taehv_param_shapes", "synth_taehv_state_dict", "taehv_decode_flops",
            "TAEHVEncoder", "taehv_encoder_param_shapes", "synth_taehv_encoder_state_dict", "taehv_encode_flops",
-           "JpegEncoder", "JpegDecoder", "jpeg_reference", "mjpeg", "FrameResizer", "resize_reference", "KeypointChain", "pose_keypoints", "PoseRenderer", "pose_render", "pose_render_reference", "PoseRetargeter", "PoseRetargetStream", "pose_retarget", "pose_retarget_reference", "PoseSmoother", "PoseSmoothStream", "pose_smooth", "pose_smooth_reference", "PoseTracker", "PoseTrackStream", "pose_track", "pose_track_reference", "PoseEstimator", "keypoint_feed", "pose_estimate", "pose_estimate_reference", "PoseEmbedder", "PoseStream", "pose_param_shapes", "synth_pose_state_dict", "pose_plan", "pose_embed_flops", "pose_embed_bytes",
+           "JpegEncoder", "JpegDecoder", "jpeg_reference", "mjpeg", "FrameResizer", "resize_reference", "YuvDecoder", "YuvEncoder", "yuv", "yuv_reference", "y4m", "KeypointChain", "pose_keypoints", "PoseRenderer", "pose_render", "pose_render_reference", "PoseRetargeter", "PoseRetargetStream", "pose_retarget", "pose_retarget_reference", "PoseSmoother", "PoseSmoothStream", "pose_smooth", "pose_smooth_reference", "PoseTracker", "PoseTrackStream", "pose_track", "pose_track_reference", "PoseEstimator", "keypoint_feed", "pose_estimate", "pose_estimate_reference", "PoseEmbedder", "PoseStream", "pose_param_shapes", "synth_pose_state_dict", "pose_plan", "pose_embed_flops", "pose_embed_bytes",
            "WanVAEDecoder", "repack_conv", "T5Shape", "UMT5_XXL", "T5_REDUCED", "synth_t5_state_dict", "t5_param_shapes",
            "WanTextEncoder", "UMT5Encoder", "relative_position_buckets", "FlowUniPCMultistepScheduler", "CausalDiffusionInferencePipeline",
            "ClipVisionShape", "CLIP_VIT_H_14", "CLIP_REDUCED", "clip_param_shapes", "synth_clip_state_dict", "CLIPModel", "CLIPVisionEncoder",

@@ -52,6 +52,10 @@ JPEG_DECODE_FILE_BYTES = 8960
 # enum sf_resize_filter; SF_RESIZE_MAX_RATIO (layouts and output types are the decoder's: JPEG_LAYOUTS, JPEG_DTYPES)
 RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1}
 RESIZE_MAX_RATIO = 8
+# enum sf_yuv_format / sf_yuv_chroma; SF_YUV_MAX_SIZE (yuv_reference.FORMATS / CHROMAS / MAX_SIZE hold the same values)
+YUV_FORMATS = {"i420": 0, "nv12": 1, "i422": 2, "i444": 3, "gray": 4, "yuyv": 5, "uyvy": 6}
+YUV_CHROMAS = {"nearest": 0, "triangle": 1}
+YUV_MAX_SIZE = 16384
 # SF_POSE_RENDER_MAX_PEOPLE / _MAX_SIZE / _MAX_COORD (layouts and output types are the decoder's too)
 POSE_RENDER_MAX_PEOPLE, POSE_RENDER_MAX_SIZE, POSE_RENDER_MAX_COORD = 8, 4096, 8191
 POSE_RETARGET_MAX_RATE, POSE_RETARGET_MAX_FRAMES = 65535, 1 << 20   # SF_POSE_RETARGET_MAX_RATE / _MAX_FRAMES
@@ -416,6 +420,9 @@ SIGNATURES = {
     "sf_jpeg_decode_frames": (C.c_int, [_vp, _sz, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i, _i, _vp, _vp]),
     "sf_resize_kernel_size": (C.c_int, [_i, _i, _i]),
     "sf_resize_frames": (C.c_int, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "sf_yuv_frame_bytes": (C.c_size_t, [_i, _i, _i]),
+    "sf_yuv_decode_frames": (C.c_int, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _vp, _i, _i, _vp]),
+    "sf_yuv_encode_frames": (C.c_int, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _vp, _i, _vp]),
     "sf_pose_render_frames": (C.c_int, [C.POINTER(PoseRenderArgs), _vp]),
     "sf_pose_retarget_frames": (C.c_int, [C.POINTER(PoseRetargetArgs), _vp]),
     "sf_pose_retarget_plan": (C.c_int, [_i64, _i64, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

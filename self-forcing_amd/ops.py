@@ -613,6 +613,31 @@ def resize_frames(frames: Tensor, tables_h, tables_v, filter: str, layout: str =
     return torch.ops.sf_hip.resize_frames(frames, tables_h[0], tables_h[1], tables_v[0], tables_v[1], filter, layout, out_layout, dtype, crop)
 
 
+# -------------------------------------------------------------------------------------- raw YUV frames (csrc/yuv.hip)
+def yuv_frame_bytes(fmt: str, h: int, w: int) -> int:
+    """Bytes of one h x w frame (sf_yuv_frame_bytes); equals yuv_reference.frame_bytes."""
+    if fmt not in _lib.YUV_FORMATS:
+        raise ValueError(f"format must be one of {', '.join(_lib.YUV_FORMATS)}, got {fmt!r}")
+    need = lib().sf_yuv_frame_bytes(_lib.YUV_FORMATS[fmt], h, w)
+    if need == 0:
+        check(-1, "sf_yuv_frame_bytes")
+    return need
+
+
+def yuv_decode_frames(raw: Tensor, fmt: str, h: int, w: int, constants, chroma: str = "triangle", layout: str = "hwc", dtype=torch.uint8) -> Tensor:
+    """uint8 raw [n, frame_bytes] -> n frames in `layout` / `dtype` (torch.ops.sf_hip.yuv_decode_frames over sf_yuv_decode_frames).
+    constants: `yuv_reference.constants(matrix, range)`."""
+    return torch.ops.sf_hip.yuv_decode_frames(raw, fmt, h, w, [int(v) for v in constants], chroma, layout, dtype)
+
+
+def yuv_encode_frames(frames: Tensor, fmt: str, constants, value_range=(-1, 1)) -> Tensor:
+    """uint8 [n, h, w, 3] or float32 / bfloat16 [n, 3, h, w] in `value_range` -> uint8 [n, frame_bytes]
+    (torch.ops.sf_hip.yuv_encode_frames over sf_yuv_encode_frames)."""
+    if tuple(value_range) not in _lib.JPEG_RANGES:
+        raise ValueError(f"value_range must be (-1, 1) or (0, 1), got {value_range}")
+    return torch.ops.sf_hip.yuv_encode_frames(frames, fmt, [int(v) for v in constants], tuple(value_range) == (0, 1))
+
+
 # -------------------------------------------------------------------------------------- pose renderer (csrc/pose_render.hip)
 def pose_render_frames(keypoints: Tensor, height: int, width: int, layout: str = "pose", dtype=torch.uint8, normalized: bool = True,
                        score_threshold: float = 0.3, out: Optional[Tensor] = None) -> Tensor:

@@ -31,6 +31,8 @@ tracing, and is opaque-but-legal to `torch.compile` -- which the reference's sec
     sf_hip::clip_encode(model, frames, workspace!) -> out
     sf_hip::resize_frames(frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, dtype, crop?) -> out
     sf_hip::resize_frames_out(out!, frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, crop?) -> ()
+    sf_hip::yuv_decode_frames(raw, fmt, height, width, constants, chroma, layout, dtype) -> out
+    sf_hip::yuv_encode_frames(frames, fmt, constants, range01) -> out
     sf_hip::pose_render_frames(keypoints, height, width, layout, dtype, normalized, score_threshold) -> out
     sf_hip::pose_render_frames_out(out!, keypoints, layout, normalized, score_threshold) -> ()
     sf_hip::pose_retarget_frames(src, first, ref, src0, out0, n_out, num, den, src_sx, src_sy, ref_sx, ref_sy, score_threshold, align) -> out
@@ -930,6 +932,89 @@ def resize_frames_out(out: Tensor, frames: Tensor, bounds_h: Tensor, coefs_h: Te
 @resize_frames_out.register_fake
 def _(out, frames, bounds_h, coefs_h, bounds_v, coefs_v, filter, layout, out_layout, crop=None):
     return None
+
+
+# ------------------------------------------------------------------------------------------ raw YUV frames
+def _yuv_frame_bytes(fmt: str, h: int, w: int) -> int:
+    if fmt not in _lib.YUV_FORMATS:
+        raise ValueError(f"format must be one of {', '.join(_lib.YUV_FORMATS)}, got {fmt!r}")
+    need = _lib.lib().sf_yuv_frame_bytes(_lib.YUV_FORMATS[fmt], h, w)
+    if need == 0:
+        _lib.check(-1, "sf_yuv_frame_bytes")
+    return need
+
+
+def _yuv_constants(constants: Sequence[int]):
+    if len(constants) != 16:
+        raise ValueError(f"constants must be the sixteen integers of yuv_reference.constants, got {len(constants)}")
+    return (C.c_int32 * 16)(*[int(v) for v in constants])
+
+
+def _yuv_raw_frames(raw: Tensor, fmt: str, h: int, w: int) -> int:
+    """n of uint8 raw [n, frame_bytes]."""
+    if raw.dtype != torch.uint8 or raw.dim() != 2 or raw.shape[0] < 1:
+        raise ValueError(f"yuv_decode_frames: raw must be uint8 [n, frame_bytes], got {raw.dtype} {tuple(raw.shape)}")
+    return int(raw.shape[0])
+
+
+@custom_op(f"{NAMESPACE}::yuv_decode_frames", mutates_args=())
+def yuv_decode_frames(raw: Tensor, fmt: str, height: int, width: int, constants: List[int], chroma: str, layout: str, dtype: torch.dtype) -> Tensor:
+    """uint8 raw [n, frame_bytes] of `fmt` frames -> n frames of height x width in `layout` / `dtype` as `yuv_reference.decode`
+    defines them (sf_yuv_decode_frames).  constants: `yuv_reference.constants(matrix, range)`."""
+    n = _yuv_raw_frames(raw, fmt, height, width)
+    need = _yuv_frame_bytes(fmt, height, width)
+    if raw.shape[1] != need:
+        raise ValueError(f"yuv_decode_frames: a {height}x{width} {fmt} frame has {need} bytes, raw holds {raw.shape[1]} per frame")
+    if chroma not in _lib.YUV_CHROMAS:
+        raise ValueError(f"chroma must be 'nearest' or 'triangle', got {chroma!r}")
+    if dtype not in _RESIZE_DTYPES:
+        raise ValueError(f"dtype must be torch.uint8, float32 or bfloat16, got {dtype}")
+    _need_gpu(raw, "raw", torch.uint8)
+    if not raw.is_contiguous():
+        raise ValueError("yuv_decode_frames: raw must be contiguous")
+    out = torch.empty(_frame_shape(layout, n, height, width), dtype=dtype, device=raw.device)
+    _lib.check(_lib.lib().sf_yuv_decode_frames(raw.data_ptr(), _lib.YUV_FORMATS[fmt], n, height, width, _yuv_constants(constants), _lib.YUV_CHROMAS[chroma],
+                                               out.data_ptr(), _lib.JPEG_LAYOUTS[layout], _lib.JPEG_DTYPES[_RESIZE_DTYPES[dtype]], _stream(raw)),
+               "sf_yuv_decode_frames")
+    return out
+
+
+@yuv_decode_frames.register_fake
+def _(raw, fmt, height, width, constants, chroma, layout, dtype):
+    return raw.new_empty(_frame_shape(layout, raw.shape[0], height, width), dtype=dtype)
+
+
+def _yuv_encode_geometry(frames: Tensor) -> Tuple[int, int, int]:
+    """(n, h, w) of uint8 [n, h, w, 3] or float32 / bfloat16 [n, 3, h, w]."""
+    if frames.dtype not in _RESIZE_DTYPES:
+        raise ValueError(f"yuv_encode_frames: frames must be uint8, float32 or bfloat16, got {frames.dtype}")
+    u8 = frames.dtype == torch.uint8
+    if frames.dim() != 4 or frames.shape[3 if u8 else 1] != 3 or frames.shape[0] < 1:
+        raise ValueError(f"yuv_encode_frames: expected {'uint8 [n, h, w, 3]' if u8 else 'float [n, 3, h, w]'}, got {tuple(frames.shape)}")
+    return (int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])) if u8 else (int(frames.shape[0]), int(frames.shape[2]), int(frames.shape[3]))
+
+
+@custom_op(f"{NAMESPACE}::yuv_encode_frames", mutates_args=())
+def yuv_encode_frames(frames: Tensor, fmt: str, constants: List[int], range01: bool) -> Tensor:
+    """uint8 [n, h, w, 3] or float32 / bfloat16 [n, 3, h, w] frames (range01: in (0, 1), else in (-1, 1)) -> uint8
+    [n, frame_bytes] of `fmt` as `yuv_reference.encode` defines them (sf_yuv_encode_frames)."""
+    n, h, w = _yuv_encode_geometry(frames)
+    need = _yuv_frame_bytes(fmt, h, w)
+    _need_gpu(frames, "frames", None)
+    if not frames.is_contiguous():
+        raise ValueError("yuv_encode_frames: frames must be contiguous")
+    out = torch.empty((n, need), dtype=torch.uint8, device=frames.device)
+    _lib.check(_lib.lib().sf_yuv_encode_frames(frames.data_ptr(), _lib.JPEG_DTYPES[_RESIZE_DTYPES[frames.dtype]],
+                                               _lib.JPEG_RANGES[(0, 1) if range01 else (-1, 1)], n, h, w, _yuv_constants(constants), out.data_ptr(),
+                                               _lib.YUV_FORMATS[fmt], _stream(frames)), "sf_yuv_encode_frames")
+    return out
+
+
+@yuv_encode_frames.register_fake
+def _(frames, fmt, constants, range01):
+    n, h, w = _yuv_encode_geometry(frames)
+    from . import yuv_reference
+    return frames.new_empty((n, yuv_reference.frame_bytes(fmt, h, w)), dtype=torch.uint8)
 
 
 # ------------------------------------------------------------------------------------------ pose renderer
