@@ -20,54 +20,16 @@ batch entries, and a guard band in front of and behind the buffer."""
 import pytest
 import torch
 
+from oracle.gemm_cases import INT, Canary, owned_mask          # the NaN-patterned output buffer, shared with test_gpu_gemm_exact.py
 from self_forcing_amd import _lib, ops
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-GUARD = 512                                    # elements in front of and behind every output buffer (keeps 16-byte alignment)
-FILL = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FC5A5A5}     # quiet NaNs with a payload
-INT = {torch.bfloat16: torch.int16, torch.float32: torch.int32}
 STRUCTURES = ["t128", "pp256", "pp224", "pp192", "pp128"]
 
 
 def bf(shape, g, scale=1.0):
     return (torch.randn(shape, generator=g) * scale).to(torch.bfloat16)
-
-
-def fill_value(dtype):
-    v = FILL[dtype]
-    return v - (1 << 16) if dtype == torch.bfloat16 and v >= 1 << 15 else v
-
-
-class Canary:
-    """`n` output elements of `dtype` between two guard bands, all pre-filled with the NaN pattern."""
-
-    def __init__(self, n, dtype):
-        self.n, self.dtype = n, dtype
-        self.raw = torch.full((n + 2 * GUARD,), fill_value(dtype), dtype=INT[dtype], device=DEV)
-        self.region = self.raw[GUARD:GUARD + n].view(dtype)
-
-    def ptr(self):
-        return self.region.data_ptr()
-
-    def host(self):
-        return self.region.cpu()
-
-    def assert_untouched_outside(self, owned):
-        """`owned`: bool [n], the elements the launch may write.  Everything else, guard bands included, is the fill."""
-        raw = self.raw.cpu()
-        fv = fill_value(self.dtype)
-        assert bool((raw[:GUARD] == fv).all()), "guard band in front of the output was written"
-        assert bool((raw[GUARD + self.n:] == fv).all()), "guard band behind the output was written"
-        stray = (raw[GUARD:GUARD + self.n] != fv) & ~owned
-        assert not bool(stray.any()), f"{int(stray.sum())} elements outside the product were written, first at {int(stray.nonzero()[0])}"
-
-
-def owned_mask(n, M, N, ldo, batch=1, o_bs=0):
-    m = torch.zeros(n, dtype=torch.bool)
-    for b in range(batch):
-        torch.as_strided(m, (M, N), (ldo, 1), b * o_bs).fill_(True)
-    return m
 
 
 def gemm_args(a_ptr, w_ptr, out_ptr, M, N, K, lda, ldw, ldo, epi=_lib.EPI_BIAS, bias=None, resid_ptr=None, ldr=0, batch=0,
