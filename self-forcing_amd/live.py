@@ -117,23 +117,11 @@ class LiveSession:
         self.rebases: List[int] = []
         self.closed = False
         device = pipe.device_
-        pipe.frame_seq_length = fs = (height // 2) * (width // 2)
-        clip_entries, chunk_condition = pipe._conditioning(self.batch_size, None, height, width, input_image, None, random_ref_dwpose, None,
-                                                           pose_feed, live_chunk_frames=chunk)
-        conditional_dict = pipe.text_encoder(text_prompts=text_prompts)
-        if chunk_condition is not None:
-            conditional_dict = dict(conditional_dict, **clip_entries)
-        self.pose_rows = getattr(chunk_condition, "live_rows", None)
+        conditional_dict, chunk_condition = pipe._begin_clip(text_prompts, self.batch_size, None, height, width, input_image=input_image,
+                                                             random_ref_dwpose=random_ref_dwpose, pose_feed=pose_feed, live_chunk_frames=chunk)
+        self.pose_rows = chunk_condition.live_rows if chunk_condition is not None else None
         dtype = torch.bfloat16
-        key = (self.batch_size, pipe._cache_tokens(), device)
-        if pipe.kv_cache1 is None or pipe._cache_key != key:
-            pipe._initialize_kv_cache(self.batch_size, dtype, device, cache_tokens=key[1])
-            pipe._initialize_crossattn_cache(self.batch_size, dtype, device)
-            pipe._cache_key = key
-        else:
-            for block_index in range(pipe.num_transformer_blocks):
-                pipe.crossattn_cache[block_index]["is_init"] = False
-            pipe._reset_kv_indices()
+        pipe._prepare_caches(self.batch_size, None, dtype, device)
         channels = getattr(getattr(model, "shape", None), "out_dim", 16)
         lengths = {chunk, 1} if pipe.independent_first_frame else {chunk}
 

@@ -445,6 +445,211 @@ def test_pipeline_calls_foreign_generator_like_the_reference():
     assert gen.calls == [0, 0, 0, 24, 24, 24]
 
 
+# ------------------------------------------------------------------ the many-step pipeline's loop, and both pipelines' cache reuse
+class _RecordingGenerator(_StubGenerator):
+    """Takes the keywords of both pipelines and records, per call, what it was given and the state it found the caches in; then
+    leaves them as a real pass does: `is_init` set, the indices behind the call's tokens."""
+
+    def __init__(self, model_type=None):
+        super().__init__()
+        if model_type is not None:
+            self.model.model_type = model_type
+
+    def forward(self, noisy_image_or_video, conditional_dict, timestep, kv_cache, crossattn_cache, current_start, cache_start=None,
+                cache_only=False):
+        from self_forcing_amd import kvcache
+        x = noisy_image_or_video
+        self.calls.append(SimpleNamespace(
+            kv=kv_cache, cross=crossattn_cache, shape=tuple(x.shape), t=timestep.flatten().tolist(), start=current_start,
+            cache_only=bool(cache_only), keys=sorted(conditional_dict), prompt=conditional_dict.get("prompt_embeds"),
+            add=conditional_dict.get("add_condition"), y=conditional_dict.get("y"), clip=conditional_dict.get("clip_feature"),
+            fresh=not any(c["is_init"] for c in crossattn_cache), indices=kvcache.read_indices(kv_cache),
+            layer_indices=[(int(d["global_end_index"]), int(d["local_end_index"])) for d in kv_cache]))
+        for c in crossattn_cache:
+            c["is_init"] = True
+        end = current_start + x.shape[1] * (x.shape[3] // 2) * (x.shape[4] // 2)
+        kvcache.write_indices(kv_cache, end, end)
+        return x * 0.5, x * 0.5
+
+    __call__ = forward
+
+
+def _cfg_pipeline(gen, iff, nfpb, monkeypatch, **kw):
+    monkeypatch.setattr(sfa.ops, "lincomb", lambda tensors, coeffs: sum(c * t for t, c in zip(tensors, coeffs)))
+    args = SimpleNamespace(num_train_timestep=1000, timestep_shift=5.0, independent_first_frame=iff, num_frame_per_block=nfpb,
+                           negative_prompt="no", guidance_scale=3.0)
+    kw.setdefault("vae", sfa.IdentityVAE())
+    pipe = sfa.CausalDiffusionInferencePipeline(args, "cpu", generator=gen, text_encoder=lambda text_prompts: {"prompt_embeds": text_prompts[0]},
+                                                **kw)
+    pipe.sampling_steps = 3
+    return pipe
+
+
+def _cfg_expected_passes(pipe, iff, nfpb, frames, initial, start_index):
+    """[(frames of the pass, first frame in `output`, timestep or None for a warm-up / context pass, cache_only)] in call order."""
+    warm = (([1] if iff else []) + [nfpb] * ((initial - (1 if iff else 0)) // nfpb)) if initial else []
+    first = iff and not initial
+    chunks = ([1] if first else []) + [nfpb] * ((frames - (1 if first else 0)) // nfpb)
+    steps = pipe._initialize_sample_scheduler(None).timesteps_host.tolist()
+    assert len(steps) == 3 and steps == sorted(steps, reverse=True) and steps[-1] > 0
+    passes, at = [], 0
+    for f in warm:
+        passes.append((f, at, None, True, True))
+        at += f
+    for f in chunks:
+        passes += [(f, at, float(t), False, False) for t in steps] + [(f, at, None, True, False)]
+        at += f
+    assert at == frames + initial
+    return passes
+
+
+@pytest.mark.parametrize("iff,nfpb,frames,initial,start_index", [(False, 3, 6, 0, 0), (True, 3, 4, 0, 0), (True, 3, 3, 4, 2), (False, 1, 2, 1, 0)])
+def test_cfg_pipeline_call_sequence_on_cpu(iff, nfpb, frames, initial, start_index, monkeypatch):
+    """The many-step sampler's bookkeeping without a GPU (causal_diffusion_inference.py:203-457): warm-up blocks at t = 0 into both
+    cache sets, cache only and without pose tokens; then per chunk steps x (prompt, negative prompt) and the t = 0 pair; positions
+    count from `start_frame_index`, `output` from 0; a chunk's `add_condition` is its slice of `dwpose_data_emb`."""
+    gen = _RecordingGenerator()
+    pipe = _cfg_pipeline(gen, iff, nfpb, monkeypatch)
+    g = torch.Generator().manual_seed(5)
+    noise = torch.randn(1, frames, 16, 8, 12, generator=g)
+    init = torch.randn(1, initial, 16, 8, 12, generator=g) if initial else None
+    emb = torch.randn(1, 8, start_index + frames + initial, 4, 6, generator=g)
+    emb_before = emb.clone()
+    video, lat = pipe.inference(noise, ["yes"], initial_latent=init, return_latents=True, start_frame_index=start_index, dwpose_data_emb=emb)
+    fs = 24
+    assert pipe.frame_seq_length == fs and tuple(lat.shape) == (1, frames + initial, 16, 8, 12) and torch.equal(emb, emb_before)
+    if initial:
+        assert torch.equal(lat[:, :initial], init)
+    passes = _cfg_expected_passes(pipe, iff, nfpb, frames, initial, start_index)
+    assert len(gen.calls) == 2 * len(passes)
+    for k, (f, at, t, cache_only, warm) in enumerate(passes):
+        for call, kv, cross, prompt in ((gen.calls[2 * k], pipe.kv_cache_pos, pipe.crossattn_cache_pos, "yes"),
+                                        (gen.calls[2 * k + 1], pipe.kv_cache_neg, pipe.crossattn_cache_neg, "no")):
+            assert call.kv is kv and call.cross is cross and call.prompt == prompt, k
+            assert call.shape == (1, f, 16, 8, 12) and call.start == (start_index + at) * fs and call.cache_only == cache_only, k
+            assert call.t == ([0] if warm else [0.0] * f if t is None else [t] * f), k
+            if warm:
+                assert call.keys == ["prompt_embeds"] and call.add is None
+            else:
+                assert call.keys == ["add_condition", "prompt_embeds"]
+                want = emb[:, :, start_index + at:start_index + at + f].permute(0, 2, 3, 4, 1).flatten(1, 3)
+                assert tuple(call.add.shape) == (1, f * fs, 8) and torch.equal(call.add, want), k
+
+
+def test_cfg_pipeline_hands_every_pass_its_frames_of_one_y(monkeypatch):
+    """An i2v generator: the image is encoded once, over the whole output timeline; every pass, warm-up passes included, gets the
+    frames of that `y` at its place in `output` (not at its RoPE position) and `clip_feature`, under both prompts."""
+    class EncodingVAE(sfa.IdentityVAE):
+        clips = []
+
+        def encode_to_latent(self, clip):                      # [1, 3, T, H, W] -> [1, (T - 1) / 4 + 1, 16, H / 8, W / 8]
+            self.clips.append(tuple(clip.shape))
+            lat_t = (clip.shape[2] - 1) // 4 + 1
+            return (torch.arange(lat_t * 16 * 8 * 12, dtype=torch.float32).reshape(1, lat_t, 16, 8, 12) % 251) / 8 + clip[0, 0, 0, 0, 0].float()
+
+    feature = torch.arange(6.0).reshape(1, 2, 3)
+    encoder = SimpleNamespace(visual=lambda videos: feature + float(videos[0].shape[1]))
+    gen, vae = _RecordingGenerator("i2v"), EncodingVAE()
+    pipe = _cfg_pipeline(gen, True, 3, monkeypatch, vae=vae, image_encoder=encoder)
+    noise, init, image = torch.randn(1, 3, 16, 8, 12), torch.randn(1, 4, 16, 8, 12), torch.full((3, 64, 96), 0.5)
+    y = pipe.encode_image(image, 4 * 6 + 1, 64, 96)["y"]
+    assert tuple(y.shape) == (1, 20, 7, 8, 12) and y.dtype == torch.bfloat16 and len({float(v) for v in y[0, 5, :, 0, 0]}) == 7
+    vae.clips.clear()
+    pipe.inference(noise, ["yes"], input_image=image, initial_latent=init, start_frame_index=2)
+    assert vae.clips == [(1, 3, 25, 64, 96)]
+    passes = _cfg_expected_passes(pipe, True, 3, 3, 4, 2)
+    assert [p[:2] for p in passes] == [(1, 0), (3, 1)] + [(3, 4)] * 4 and len(gen.calls) == 2 * len(passes)
+    for k, (f, at, t, cache_only, warm) in enumerate(passes):
+        for call in gen.calls[2 * k:2 * k + 2]:
+            assert call.keys == ["clip_feature", "prompt_embeds", "y"] and call.start == (2 + at) * 24
+            assert torch.equal(call.y, y[:, :, at:at + f]) and torch.equal(call.clip, (feature + 1.0).to(torch.bfloat16)), k
+
+
+def _few_step_pipeline(gen, nfpb=1):
+    args = SimpleNamespace(denoising_step_list=[1000, 500], warp_denoising_step=False, independent_first_frame=False,
+                           num_frame_per_block=nfpb, context_noise=0)
+    return sfa.CausalInferencePipeline(args, "cpu", generator=gen, text_encoder=lambda text_prompts: {"prompt_embeds": None}, vae=sfa.IdentityVAE())
+
+
+def _cache_tensors(pipe, names):
+    """Every cache's layer dicts and their K / V tensors, as ids; `keep` holds the objects so that no id is given out twice."""
+    objects = [[(d, d["k"], d["v"]) for d in getattr(pipe, name)] for name in names]
+    _cache_tensors.keep.append(objects)
+    return [[tuple(id(o) for o in entry) for entry in cache] for cache in objects]
+
+
+_cache_tensors.keep = []
+
+
+def _shared(a, b):
+    ids = lambda caches: {i for cache in caches for entry in cache for i in entry}      # noqa: E731
+    return ids(a) & ids(b)
+
+
+def _assert_reset(first_calls, n_sets):
+    """The first pass into each cache set found every `is_init` False and every layer's indices at zero."""
+    assert len(first_calls) == n_sets
+    for call in first_calls:
+        assert call.fresh and call.indices == (0, 0) and call.layer_indices == [(0, 0)] * len(call.kv)
+
+
+def test_few_step_pipeline_reuses_its_caches():
+    """A second `inference` and a second `stream` of the same batch size and cache capacity keep the cache tensors and take the
+    reset branch: `is_init` cleared, the indices back at zero; another batch size allocates anew."""
+    gen = _RecordingGenerator()
+    pipe = _few_step_pipeline(gen)
+    names = ("kv_cache1", "crossattn_cache")
+    noise = torch.randn(1, 2, 16, 8, 12)
+    pipe.inference(noise, ["p"])
+    tensors, lists = _cache_tensors(pipe, names), (pipe.kv_cache1, pipe.crossattn_cache)
+    assert len(gen.calls) == 6 and gen.calls[0].fresh and not gen.calls[1].fresh and gen.calls[-1].indices == (48, 48)
+    runs = [lambda: pipe.inference(noise, ["p"]), lambda: list(pipe.stream(noise, ["p"], skip_last_context=False)),
+            lambda: list(pipe.stream(noise, ["p"], skip_last_context=False)), lambda: pipe.inference(noise, ["p"])]
+    for run in runs:
+        assert all(c["is_init"] for c in pipe.crossattn_cache) and sfa.kvcache.read_indices(pipe.kv_cache1) == (48, 48)
+        gen.calls.clear()
+        run()
+        assert len(gen.calls) == 6 and (pipe.kv_cache1, pipe.crossattn_cache) == lists and lists[0] is pipe.kv_cache1
+        assert lists[1] is pipe.crossattn_cache and _cache_tensors(pipe, names) == tensors
+        _assert_reset(gen.calls[:1], 1)
+        assert not gen.calls[1].fresh and gen.calls[1].indices == (24, 24)
+    for run in (lambda n: pipe.inference(n, ["p", "q"]), lambda n: list(pipe.stream(n, ["p"]))):      # batch 2, then batch 1 again
+        gen.calls.clear()
+        before = _cache_tensors(pipe, names)
+        batch = 2 if pipe.kv_cache1[0]["k"].shape[0] == 1 else 1
+        run(torch.randn(batch, 2, 16, 8, 12))
+        after = _cache_tensors(pipe, names)
+        assert pipe.kv_cache1[0]["k"].shape[0] == batch and pipe.crossattn_cache[0]["k"].shape[0] == batch
+        assert not _shared(after, before)
+        _assert_reset(gen.calls[:1], 1)
+
+
+def test_cfg_pipeline_reuses_its_caches(monkeypatch):
+    """As above for the many-step pipeline's two cache sets."""
+    gen = _RecordingGenerator()
+    pipe = _cfg_pipeline(gen, False, 1, monkeypatch)
+    names = ("kv_cache_pos", "crossattn_cache_pos", "kv_cache_neg", "crossattn_cache_neg")
+    noise = torch.randn(1, 2, 16, 8, 12)
+    pipe.inference(noise, ["p"])
+    tensors, lists = _cache_tensors(pipe, names), [getattr(pipe, n) for n in names]
+    assert len(gen.calls) == 16 and gen.calls[0].fresh and gen.calls[1].fresh and not gen.calls[2].fresh
+    assert len({i for t in tensors for entry in t for i in entry}) == 4 * 2 * 3          # two sets, nothing shared between them
+    for _ in range(2):
+        for n in names:
+            cache = getattr(pipe, n)
+            assert all(c["is_init"] for c in cache) if n.startswith("cross") else sfa.kvcache.read_indices(cache) == (48, 48)
+        gen.calls.clear()
+        pipe.inference(noise, ["p"])
+        assert len(gen.calls) == 16 and all(getattr(pipe, n) is l for n, l in zip(names, lists)) and _cache_tensors(pipe, names) == tensors
+        assert gen.calls[0].kv is pipe.kv_cache_pos and gen.calls[1].kv is pipe.kv_cache_neg
+        _assert_reset(gen.calls[:2], 2)
+    gen.calls.clear()
+    pipe.inference(torch.randn(2, 2, 16, 8, 12), ["p", "q"])
+    after = _cache_tensors(pipe, names)
+    assert all(getattr(pipe, n)[0]["k"].shape[0] == 2 for n in names) and not _shared(after, tensors)
+    _assert_reset(gen.calls[:2], 2)
+
+
 # ------------------------------------------------------------------------------------------ VAE host logic
 def test_vae_repack_conv_matches_convolution_definition():
     """`repack_conv` lays weights out as [Cout][tap*Cin_pad + ci] with tap = (dt*kh + dh)*kw + dw: an explicit

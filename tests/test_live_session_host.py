@@ -190,6 +190,29 @@ def test_close_runs_nothing_more():
     assert len(gen.calls) == calls and list(session) == [] and session.closed
 
 
+def test_a_session_reuses_the_caches_of_a_clip_of_the_same_key():
+    """`open_session` after an `inference` with the same batch size and cache capacity (a rolling cache's does not depend on the
+    clip's length) keeps the cache tensors, clears `is_init` and resets the indices; another batch size allocates anew."""
+    gen = StubGenerator()
+    pipe = make_pipeline(gen)
+    pipe.inference(torch.zeros(1, 5, 16, 8, 12), ["p"])
+    kv, cross = pipe.kv_cache1, pipe.crossattn_cache
+    tensors = [(d, d["k"], d["v"]) for d in kv + cross]
+    assert kvcache.read_indices(kv) == (5 * FS, 3 * FS) and tuple(kv[0]["k"].shape[:2]) == (1, 3 * FS)
+    for d in cross:
+        d["is_init"] = True                                           # as the generator's first pass leaves it
+    session = pipe.open_session(["p"], (8, 12), noise_feed=[torch.zeros(1, 1, 16, 8, 12)] * 2)
+    assert pipe.kv_cache1 is kv and pipe.crossattn_cache is cross
+    assert all(a is b for old, d in zip(tensors, kv + cross) for a, b in zip(old, (d, d["k"], d["v"])))
+    assert not any(d["is_init"] for d in cross) and kvcache.read_indices(kv) == (0, 0)
+    assert all(int(d["global_end_index"]) == 0 and int(d["local_end_index"]) == 0 for d in kv)
+    gen.calls.clear()
+    assert [k for k, lat, pixels in session] == [0, 1] and gen.calls[0][0] == 0 and kvcache.read_indices(kv) == (2 * FS, 2 * FS)
+    session = pipe.open_session(["p", "q"], (8, 12), batch_size=2, noise_feed=[])
+    assert pipe.kv_cache1 is not kv and pipe.crossattn_cache is not cross and pipe.kv_cache1[0]["k"].shape[0] == 2
+    assert not any(d["is_init"] for d in pipe.crossattn_cache) and kvcache.read_indices(pipe.kv_cache1) == (0, 0)
+
+
 # ============================================================================================== the pose buffer
 class FakeStream:
     """Stand-in for `PoseStream` that follows the plan and writes the latent frame's index into the rows it is told to fill."""
